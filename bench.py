@@ -7,14 +7,17 @@ own N ranks (torch.distributed.run, RCCL) when it was not started by a launcher;
 
   --scaling weak    (default) every rank processes --proofs proofs (256 = BASELINE configs[3]'s batch); no data-path collective
   --scaling strong  --proofs proofs in total, split over the ranks (configs[3] as written: 256 proofs sharded across 8);
-                    --gather adds the all-gather of the witness rows (RCCL over xGMI) to the step and times it separately
+                    --gather adds the all-gather of the witness rows (RCCL over xGMI) to the step (--full: and times it separately)
   --mode c5         BASELINE configs[4]: ONE proof at N = 512, validator lanes sharded across the ranks, one all-gather of the
                     448-byte EdDSA lane records, replicated finish (tendermintx_amd/sharding.py)
   --workload survey8d (default) SURVEY 8(d)'s measured workload: 100 validators in 128 lanes, four distinct validator sets per batch,
                     Bernoulli(0.9) signing re-drawn until > 2/3, rounds {0,0,0,3}; `best_case` (one set, 128 of 128, everybody signs --
-                    round 1's headline) is timed beside it and reported in the same line
+                    round 1's headline) is timed beside it with --full and reported in the same line
 
-Prints ONE JSON line on rank 0 (contract: task description "bench.py").  Beside the contract's fields:
+Prints ONE JSON line on rank 0 (contract: task description "bench.py").  A plain run sets up, warms up (--warmup steps), times --steps
+steps, writes the last step's outputs when --dump-outputs DIR is given, and prints the line: the contract's fields, the kernel times and the
+step's roofline from the HIP events of the timed region, the key-cache state of the timed steps.  With --full, after that, rank 0 of a
+one-GPU run also measures (extras()) and the full record goes to bench_extras.json and an earlier, prefixed stdout line:
   single_proof   BASELINE configs[2]: device-resident latency of one proof and its host-to-host time (SURVEY 8(d)'s metric definition)
   host_to_host   the batch through the host-buffer entry point (H2D + step + D2H), full rows and hint-only rows
   key_cache      the timed steps run with a WARM per-key table cache (the same validator sets step after step: what a light client does);
@@ -54,8 +57,14 @@ def parse_args(argv=None):
     ap.add_argument("--gather", action="store_true", help="strong scaling: all-gather the witness rows on every rank inside the step")
     ap.add_argument("--mode", choices=("batch", "c5"), default="batch")
     ap.add_argument("--workload", choices=("survey8d", "one_set"), default="survey8d")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything beside the headline (extras(): other workload, batch sizes, single "
+                         "proof, host-to-host, typed value, kernel-alone figures, rocprofv3 counter passes, CPU baseline and parity against the "
+                         "oracle) and write the full record to bench_extras.json.  Off by default: a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step handed its caller to DIR/<name>.npy (float64, < 64 MB): see dump_outputs()")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: still only the timed region (profiling runs)")
     ap.add_argument("--other-scaling", action="store_true",
                     help="more than one GPU: after the timed region also run the scaling mode the command line did not ask for (strong: one batch sharded "
                          "through tmx_witness_batch_sharded_device without / with the row exchange, the sharded Level-2 rows).  Off by default: these are "
@@ -187,9 +196,11 @@ def main():
         ms_per_step = 1e3 * max_over_ranks(time.perf_counter() - t0) / args.steps
         gather_ms = None
         ok = int(rep.cpu().numpy()[32:36].view(np.uint32)[0])
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, elems.view(1, -1), rep.cpu().numpy().reshape(1, 64))
         if rank == 0:
             out_bytes = ctx.elem_stride(KIND_SKIP) * 8
-            emit({
+            record(args, {
                 "metric": "skip-circuit witness-gen ms at VALIDATOR_SET_SIZE_MAX=512, one proof, validator-sharded", "value": round(ms_per_step, 5),
                 "unit": "ms", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
                 "higher_is_better": False, "scaling": "strong", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
@@ -268,9 +279,12 @@ def main():
     kms = ctx.kernel_ms_mean(min(args.steps, 128))  # HIP events recorded on the launch stream inside the timed region
     n_unique, used_tables = ctx.last_dedup()
     kc = ctx.key_cache_stats()
+    row0 = lo if (args.scaling == "strong" and comm_world > 1) else 0   # (strong: this rank's rows sit at their place in the full-size buffer)
+    if rank == 0 and args.dump_outputs:   # the last timed step's rows and reports, before anything below runs the step again
+        dump_outputs(args.dump_outputs, d_out[row0:row0 + P, :count], d_rep.cpu().numpy().reshape(-1, 64)[row0:row0 + P])
 
     gather_ms = None
-    if gather:   # the same step without the exchange, for the difference
+    if gather and args.full:   # the same step without the exchange, for the difference
         for _ in range(3):
             sharding.proof_sharded_batch(ctx, KIND_SKIP, P_total, d_proofs, d_targets, d_trusteds, d_out, d_rep, gather=False, stream=stream.cuda_stream)
         barrier()
@@ -281,7 +295,6 @@ def main():
         gather_ms = ms_per_step - 1e3 * max_over_ranks(time.perf_counter() - t0) / 10
 
     # every proof of this rank must have verified (synthetic inputs are well-formed)
-    row0 = lo if (args.scaling == "strong" and comm_world > 1) else 0   # (strong: this rank's rows sit at their place in the full-size buffer)
     rep = d_rep.cpu().numpy().reshape(-1, 64)[row0:row0 + P]
     all_ok = int(rep[:, 32:36].copy().view(np.uint32).sum())
     ok_flag = torch.tensor([1 if all_ok == P else 0], device="cpu" if control_cpu else dev)
@@ -345,7 +358,7 @@ def main():
                           "control_backend": (dist.get_backend() if use_dist and dist.is_initialized() else None),
                           "note": "the data-path exchange (strong scaling with --gather, --mode c5) is RCCL inside libtmx (tmx_comm_create); torch.distributed "
                                   "carries the unique id, the barriers and the max over ranks"}
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             extras(args, result, roofline, ctx, run, wl_all, n, P, stride, count, dev, stream, d_out, d_rep, dev_bytes, kms, ms_per_step, alg_bytes)
     # ---- more than one GPU: the OTHER scaling of the same record (a SCALE run of the default command then carries both the weak-scaled value
     # and BASELINE configs[3] as written: 256 proofs sharded over the ranks, without and with the row exchange)
@@ -354,7 +367,7 @@ def main():
         if rank == 0:
             result["other_scaling"] = other
     if rank == 0:
-        emit(result)
+        record(args, result)
     barrier()
     if use_dist:
         dist.destroy_process_group()
@@ -473,6 +486,55 @@ def emit(full):
     line = json.dumps(compact_line(full))
     assert len(line) <= LINE_CAP, len(line)
     print(line, flush=True)
+
+
+def record(args, full):
+    """--full: emit() (bench_extras.json, the full record on an earlier line, the record line last).  A plain run prints the record line
+    alone and writes no file: its record holds nothing that the line would shed."""
+    if args.full:
+        emit(full)
+        return
+    c = compact_line(full)
+    c.pop("extras", None)
+    line = json.dumps(c)
+    assert len(line) <= LINE_CAP, len(line)
+    print(line, flush=True)
+
+
+DUMP_SEED = 0x544D58        # the sample of elements below, fixed for every run
+DUMP_SAMPLE = 1 << 20       # elements sampled from the rows (16 MB + 8 MB of index)
+DUMP_CAP = 64 << 20         # bytes of all files together
+
+
+def dump_outputs(out_dir, rows, reps):
+    """--dump-outputs DIR: what the timed path handed its caller in the last step, as float64 .npy files that two builds can be compared by.
+    rows: int64 device tensor [proofs, elem_count] (the witness rows: Goldilocks elements as u64); reps: uint8 [proofs, 64] (tmx_report).
+    A u64 does not fit a float64, and a 256-proof batch is 1.1 GB of rows, so the rows go out as
+      elems_sample.npy        [K, 2]  high and low 32-bit halves of K = 2^20 elements at
+      elems_sample_index.npy  [K]     their flat indices into [proofs, elem_count], drawn with numpy's default_rng(DUMP_SEED), sorted
+      elems_row_sums.npy      [proofs, 4]  per row, the exact sums of the element's four 16-bit limbs (low limb first) over the whole row
+    and the reports as
+      report_header.npy       [proofs, 32] the header bytes
+      report_verdict.npy      [proofs, 7]  all_ok, fail_mask, first_bad_sig, gt_target, gt_trusted, dist_ok, precond"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_rows, count = rows.shape
+    total = n_rows * count
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=min(DUMP_SAMPLE, total), dtype=np.int64))
+    d_idx = torch.from_numpy(idx).to(rows.device)
+    v = rows[d_idx // count, d_idx % count].cpu().numpy().view(np.uint64)
+    sums = torch.stack([((rows >> (16 * k)) & 0xFFFF).sum(dim=1) for k in range(4)], dim=1).cpu().numpy()   # < 2^16 x count: exact
+    words = np.ascontiguousarray(reps[:, 32:60]).view(np.uint32).astype(np.float64)
+    words[:, 2] = np.ascontiguousarray(reps[:, 40:44]).view(np.int32)[:, 0]   # first_bad_sig is signed (-1: none)
+    out = {"elems_sample": np.stack([(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1),
+           "elems_sample_index": idx.astype(np.float64),
+           "elems_row_sums": sums.astype(np.float64),
+           "report_header": reps[:, :32].astype(np.float64),
+           "report_verdict": words}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_CAP, {k: a.nbytes for k, a in out.items()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def both_scalings(args, strong_ctx, n, world, rank, local_rank, dev, stream, dev_bytes, barrier, max_over_ranks):

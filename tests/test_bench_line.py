@@ -75,3 +75,43 @@ def test_emit_prints_the_record_last_and_caps_it(tmp_path, monkeypatch):
     assert lines[0].startswith("# bench_extras ") and len(lines) == 2
     assert len(lines[-1]) <= bench.LINE_CAP and json.loads(lines[-1])["roofline"]["frac"] == full["roofline"]["frac"]
     assert json.load(open(tmp_path / "bench_extras.json"))["metric"] == full["metric"]
+
+
+def test_plain_run_options():
+    """A plain run times the steps and nothing else; everything beside the headline needs --full."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "3", "--full", "--dump-outputs", "out"])
+    assert a.steps == 3 and a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_is_exact_and_small(tmp_path):
+    """--dump-outputs: float64 files that carry the u64 elements exactly (sampled), exact per-row limb sums and the reports."""
+    import numpy as np
+    import torch
+    import bench
+    rng = np.random.default_rng(5)
+    P, stride, count = 6, 1200, 1100
+    u = rng.integers(0, 2**64 - 2**32 + 1, size=(P, stride), dtype=np.uint64)
+    rows = torch.from_numpy(u.view(np.int64).copy())
+    reps = rng.integers(0, 256, size=(P, 64), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path), rows[:, :count], reps)
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["elems_row_sums.npy", "elems_sample.npy", "elems_sample_index.npy", "report_header.npy", "report_verdict.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= bench.DUMP_CAP
+    got = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype == np.float64 for a in got.values())
+    idx = got["elems_sample_index"].astype(np.int64)
+    assert idx.size == P * count and np.all(np.diff(idx) >= 0)
+    s = got["elems_sample"]
+    back = (s[:, 0].astype(np.uint64) << np.uint64(32)) | s[:, 1].astype(np.uint64)
+    assert np.array_equal(back, u[:, :count].reshape(-1)[idx])
+    want = np.stack([((u[:, :count] >> np.uint64(16 * k)) & np.uint64(0xFFFF)).sum(axis=1) for k in range(4)], axis=1)
+    assert np.array_equal(got["elems_row_sums"], want.astype(np.float64))
+    assert np.array_equal(got["report_header"], reps[:, :32].astype(np.float64))
+    assert np.array_equal(got["report_verdict"][:, 2], reps[:, 40:44].copy().view(np.int32)[:, 0].astype(np.float64))
+    # the same rows give the same files (the sample is seeded)
+    again = tmp_path / "again"
+    bench.dump_outputs(str(again), rows[:, :count], reps)
+    assert all(np.array_equal(np.load(again / f), got[f[:-4]]) for f in files)

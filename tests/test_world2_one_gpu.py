@@ -131,7 +131,7 @@ def test_bench_py_at_world_2_on_one_gpu(built_lib, fake_rccl, tmp_path):
     o = weak["other_scaling"]
     assert o["strong"]["libtmx_comm_world"] == 2 and o["strong"]["proofs_per_gpu"] == 8 and o["strong_with_row_exchange"]["ms_per_step"] > 0
     assert "error" not in o.get("level2_trace_rows", {}) and o["level2_trace_rows_with_exchange"]["ms_per_step"] > 0
-    strong = run("--scaling", "strong", "--gather", "--other-scaling")  # BASELINE configs[3] as written, the row exchange inside the step
+    strong = run("--scaling", "strong", "--gather", "--other-scaling", "--full")  # BASELINE configs[3] as written, the row exchange inside the step
     assert strong["scaling"] == "strong" and strong["config"]["proofs_per_gpu"] == 8 and strong["gather_rows"]["bytes_per_rank_out"] > 0
     assert strong["other_scaling"]["weak"]["proofs_total"] == 32
     c5 = run("--mode", "c5", "--n-max", "128")     # BASELINE configs[4]'s code path (one proof, lanes sharded), at a size that is quick
