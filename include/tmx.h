@@ -399,7 +399,9 @@ int32_t tmx_witness_validator_sharded_device(tmx_ctx* ctx, int32_t kind, uint32_
  *                                            by lane slab (one proof: one all-gather per section); the small per-proof sections (leaf / tree /
  *                                            header SHA-256, N x N) are computed on every rank.  All rows on every rank afterwards.
  *   tmx_trace_commit_sharded_device          tmx_trace_commit_device over this rank's own proofs (no row crosses a link), its cap into slot
- *                                            `rank` of d_caps[world][4 << cap_height], then ONE all-gather of the caps. */
+ *                                            `rank` of d_caps[world][4 << cap_height], then ONE all-gather of the caps.
+ *                                            tmx_trace_commit_open_device then opens this rank's tree (cap slot `rank`); an empty shard
+ *                                            leaves nothing to open. */
 int32_t tmx_trace_rows_sharded_device(tmx_ctx* ctx, int32_t kind, uint32_t n_total, const void* d_targets, const void* d_trusteds, void* d_trace_out,
                                       uint32_t sections, uint32_t gather, void* hip_stream);
 int32_t tmx_trace_rows_validator_sharded_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proofs, const void* d_targets, const void* d_trusteds,
@@ -569,6 +571,44 @@ int32_t tmx_poseidon_merkle_device(tmx_ctx* ctx, uint32_t log_n, uint32_t n_cols
                                    void* hip_stream);
 /* n permutations of caller-provided states (host buffers, 12 u64 each, blocking): test hook and micro-benchmark */
 int32_t tmx_poseidon_permute(tmx_ctx* ctx, uint32_t n, const uint64_t* states_in, uint64_t* states_out);
+
+/* ---- openings of a Poseidon Merkle tree: the query phase of a FRI-style consumer of a cap.  An opening of leaf i of a tree of 2^log_n rows
+ * over n_cols columns (column-major as for tmx_poseidon_merkle_device) is
+ *   row   n_cols u64: element i of every column, the stored words as they are (no reduction mod p);
+ *   path  tmx_poseidon_merkle_path_len(log_n, cap_height) = log_n - cap_height digests of 4 u64, bottom-up: the sibling of the leaf first,
+ *         then the sibling of its parent, ... (plonky2's MerkleProof.siblings order); path[l] = levels[off_l + ((i >> l) ^ 1)] in the layout
+ *         of tmx_poseidon_merkle_device's d_levels (off_l: the start of level l).
+ * It is checked as the tree was built: leaf = the row itself, canonical and zero padded, if n_cols <= 4, else hash_no_pad(row) (overwrite
+ * mode: the unused rate words of a short last chunk keep their values); then for l = 0 .. path_len - 1 cur = bit l of i ? two_to_one(path[l],
+ * cur) : two_to_one(cur, path[l]); accepted iff cur == cap[i >> path_len] word for word.
+ * Indices are a HOST array of uint64_t, validated before anything is enqueued (n_queries >= 1 and at most 2^22, every index < 2^log_n: else
+ * TMX_ERR_BAD_ARG and nothing is written), then copied to the device on hip_stream through the context's own staging: the caller may reuse
+ * its array when the call returns.  Outputs are device pointers; every call is asynchronous on hip_stream.  d_paths may be NULL when the
+ * paths are empty (cap_height == log_n).
+ *   tmx_poseidon_merkle_open_device    openings of caller columns and their d_levels (what tmx_poseidon_merkle_device wrote for them).
+ *                                      d_rows[n_queries][n_cols], d_paths[n_queries][path_len][4].
+ *   tmx_trace_commit_last_shape        (log_rows + log_blowup, n_proofs * width, cap_height) of the context's most recent commit.
+ *   tmx_trace_commit_open_device       openings of the context's most recent tmx_trace_commit_device: its extended columns and levels are still
+ *                                      in the context's scratch.  Order it after that commit on the same stream (the rule of
+ *                                      tmx_trace_rows_device), and before the next commit call overwrites the scratch.  A commit call that
+ *                                      fails anywhere leaves nothing to open, and so does tmx_trace_commit_sharded_device on a rank with an
+ *                                      empty shard: these two calls then return TMX_ERR_BAD_ARG (tmx_last_error says why), as on a fresh
+ *                                      context.  After tmx_trace_commit_sharded_device, rank r opens the tree of ITS proofs, the one behind
+ *                                      cap slot r (no collective: gathering openings across ranks is the caller's).
+ *   tmx_poseidon_merkle_verify_device  d_ok[q] = 1 if opening q leads to d_cap[4 << cap_height], else 0; one thread per query (sequential:
+ *                                      one permutation per 8 columns and per level).  It hashes with the context's CURRENT constants: an
+ *                                      opening is checked against the caller's tables, and fails under any other.
+ * The caveats of the commit hold: natural row order, no salt, injectable constants -- parity unpinned against plonky2. */
+uint32_t tmx_poseidon_merkle_path_len(uint32_t log_n, uint32_t cap_height); /* log_n - cap_height; 0 if cap_height > log_n or log_n > 30 */
+int32_t tmx_poseidon_merkle_open_device(tmx_ctx* ctx, uint32_t log_n, uint32_t n_cols, const uint64_t* d_cols, uint32_t cap_height,
+                                        const uint64_t* d_levels, uint32_t n_queries, const uint64_t* h_indices, uint64_t* d_rows,
+                                        uint64_t* d_paths, void* hip_stream);
+int32_t tmx_trace_commit_last_shape(const tmx_ctx* ctx, uint32_t* log_rows_ext, uint32_t* n_cols, uint32_t* cap_height);
+int32_t tmx_trace_commit_open_device(tmx_ctx* ctx, uint32_t n_queries, const uint64_t* h_indices, uint64_t* d_rows, uint64_t* d_paths,
+                                     void* hip_stream);
+int32_t tmx_poseidon_merkle_verify_device(tmx_ctx* ctx, uint32_t log_n, uint32_t n_cols, uint32_t cap_height, const uint64_t* d_cap,
+                                          uint32_t n_queries, const uint64_t* h_indices, const uint64_t* d_rows, const uint64_t* d_paths,
+                                          uint32_t* d_ok, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

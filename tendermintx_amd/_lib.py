@@ -228,6 +228,18 @@ def lib():
     L.tmx_poseidon_merkle_digests.argtypes = [C.c_uint32, C.c_uint32]
     L.tmx_poseidon_merkle_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.tmx_poseidon_permute.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    try:
+        L.tmx_poseidon_merkle_path_len.restype = C.c_uint32
+        L.tmx_poseidon_merkle_path_len.argtypes = [C.c_uint32, C.c_uint32]
+        L.tmx_poseidon_merkle_open_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_last_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.tmx_trace_commit_open_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_poseidon_merkle_verify_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
     L.tmx_selftest_fe_invert.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.tmx_selftest_f16.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.tmx_eddsa_lanes_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -7,6 +7,13 @@ from . import _lib
 from ._lib import KIND_SKIP, KIND_STEP, Config, Report, check
 
 
+def _indices(indices):
+    """query indices (a sequence or a numpy array) as the contiguous uint64 host buffer the opening calls take"""
+    if isinstance(indices, np.ndarray):
+        return np.ascontiguousarray(indices.reshape(-1), dtype=np.uint64)
+    return np.array([int(i) for i in indices], dtype=np.uint64)
+
+
 class Context:
     """One tmx_ctx: a HIP stream, device scratch for `max_batch` proofs and the serializer programs for a fixed
     (VALIDATOR_SET_SIZE_MAX, chain id, SKIP_MAX) -- the const generics / TendermintConfig of the reference's
@@ -235,6 +242,22 @@ class Context:
     def poseidon_merkle_device(self, log_n, n_cols, d_cols, cap_height, d_levels, stream=None):
         check(self._L.tmx_poseidon_merkle_device(self._h, log_n, n_cols, d_cols, cap_height, d_levels, self._stream(stream)), self._h)
 
+    # ---- openings of a Poseidon Merkle tree (rows + paths) and their verification; indices: a sequence or numpy array, host side
+    def poseidon_merkle_path_len(self, log_n, cap_height):
+        return int(self._L.tmx_poseidon_merkle_path_len(log_n, cap_height))
+
+    def poseidon_merkle_open_device(self, log_n, n_cols, d_cols, cap_height, d_levels, indices, d_rows, d_paths, stream=None):
+        """d_rows: [n_queries][n_cols] u64, d_paths: [n_queries][path_len][4] u64 (device pointers)"""
+        idx = _indices(indices)
+        check(self._L.tmx_poseidon_merkle_open_device(self._h, log_n, n_cols, d_cols, cap_height, d_levels, idx.size, idx.ctypes.data, d_rows, d_paths,
+                                                      self._stream(stream)), self._h)
+
+    def poseidon_merkle_verify_device(self, log_n, n_cols, cap_height, d_cap, indices, d_rows, d_paths, d_ok, stream=None):
+        """d_ok: [n_queries] u32, 1 where the opening leads to the cap"""
+        idx = _indices(indices)
+        check(self._L.tmx_poseidon_merkle_verify_device(self._h, log_n, n_cols, cap_height, d_cap, idx.size, idx.ctypes.data, d_rows, d_paths, d_ok,
+                                                        self._stream(stream)), self._h)
+
     def eddsa_lanes_device(self, n_lanes, d_lanes, d_ed_out, stream=None):
         check(self._L.tmx_eddsa_lanes_device(self._h, n_lanes, d_lanes, d_ed_out, self._stream(stream)), self._h)
 
@@ -255,6 +278,17 @@ class Context:
         ms = (C.c_float * 3)()
         check(self._L.tmx_trace_commit_last_ms(self._h, ms), self._h)
         return {"columns": ms[0], "lde": ms[1], "merkle": ms[2]}
+
+    def trace_commit_last_shape(self):
+        """(log_rows + log_blowup, n_proofs * width, cap_height) of the context's most recent commit; TmxError if there is none to open"""
+        lg, nc, ch = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(self._L.tmx_trace_commit_last_shape(self._h, C.byref(lg), C.byref(nc), C.byref(ch)), self._h)
+        return lg.value, nc.value, ch.value
+
+    def trace_commit_open_device(self, indices, d_rows, d_paths, stream=None):
+        """openings of the most recent trace_commit_device (same stream, after it): rows [n_queries][n_cols], paths [n_queries][path_len][4]"""
+        idx = _indices(indices)
+        check(self._L.tmx_trace_commit_open_device(self._h, idx.size, idx.ctypes.data, d_rows, d_paths, self._stream(stream)), self._h)
 
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):

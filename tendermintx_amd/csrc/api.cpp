@@ -397,6 +397,15 @@ struct tmx_ctx {
   void* d_commit = nullptr;    // scratch of tmx_trace_commit_device: columns | extended columns | tree levels (grows on demand)
   size_t commit_bytes = 0;
   hipEvent_t ev_commit[4] = {};
+  // the last tmx_trace_commit_device (what tmx_trace_commit_open_device opens): its shape and where its extended columns and levels sit in
+  // d_commit.  valid: that call finished enqueueing (any failure of a later commit call, or an empty shard, clears it)
+  struct CommitRec { bool valid; uint32_t log_m, n_cols, cap_height; size_t lde_off, lev_off; } last_commit = {};
+  // staging of the host query indices of the opening / verifying calls: a ring of page-locked + device buffers, each slot reused only once
+  // the event behind the launch that read it has completed
+  struct IdxSlot { uint64_t* h = nullptr; uint64_t* d = nullptr; uint64_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+  static constexpr int IDX_RING = 4;
+  IdxSlot idx_ring[IDX_RING];
+  uint32_t idx_next = 0;
   void* comm = nullptr;        // ncclComm_t of this context's device (tmx_comm_create), or null
   bool comm_aborted = false;   // a local failure (or a peer's) in front of a collective aborted the communicator: tmx_comm_create again
   uint32_t comm_rank = 0, comm_world = 1;
@@ -1370,6 +1379,11 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
   for (hipEvent_t e : c->ev_commit)
     if (e) (void)hipEventDestroy(e);
+  for (auto& sl : c->idx_ring) {
+    if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
+    if (sl.d) (void)hipFree(sl.d);
+    if (sl.h) (void)hipHostFree(sl.h);
+  }
   if (c->have_streams) release_streams(c->cfg.device);
   delete c;
 }
@@ -2886,7 +2900,9 @@ int32_t tmx_trace_commit_shape(int32_t kind, uint32_t n, uint32_t section, uint3
 
 int32_t tmx_trace_commit_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uint32_t section, uint32_t log_blowup, uint32_t cap_height,
                                 const void* d_trace_rows, uint64_t* d_cap, void* hip_stream) {
-  if (!c || !d_trace_rows || !d_cap || n_proofs == 0) return TMX_ERR_BAD_ARG;
+  if (!c) return TMX_ERR_BAD_ARG;
+  c->last_commit.valid = false;  // (set again at the end: a call that fails anywhere leaves nothing to open)
+  if (!d_trace_rows || !d_cap || n_proofs == 0) return TMX_ERR_BAD_ARG;
   uint32_t log_n = 0, width = 0;
   if (tmx_trace_commit_shape(kind, c->cfg.n_max, section, &log_n, &width)) return fail(c, TMX_ERR_BAD_ARG, "section must be one row table of the trace block");
   const uint32_t log_m = log_n + log_blowup;
@@ -2929,6 +2945,7 @@ int32_t tmx_trace_commit_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uin
   const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, cap_height), n_cap = (uint64_t)1 << cap_height;
   HIPCK(c, hipMemcpyAsync(d_cap, levels + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
   HIPCK(c, hipEventRecord(c->ev_commit[3], s));
+  c->last_commit = {true, log_m, n_cols, cap_height, cols_b, cols_b + lde_b};
   return TMX_OK;
 }
 
@@ -2937,7 +2954,9 @@ int32_t tmx_trace_commit_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uin
 // them on every rank -- the batch's commitment is the `world` caps, each over n_shard * width columns
 int32_t tmx_trace_commit_sharded_device(tmx_ctx* c, int32_t kind, uint32_t n_total, uint32_t section, uint32_t log_blowup, uint32_t cap_height,
                                         const void* d_trace_rows, uint64_t* d_caps, void* hip_stream) {
-  if (!c || !d_trace_rows || !d_caps || n_total == 0) return TMX_ERR_BAD_ARG;
+  if (!c) return TMX_ERR_BAD_ARG;
+  c->last_commit.valid = false;
+  if (!d_trace_rows || !d_caps || n_total == 0) return TMX_ERR_BAD_ARG;
   uint64_t lo, hi;
   tmx_shard_range(n_total, c->comm_rank, c->comm_world, &lo, &hi);
   const size_t row_bytes = (size_t)trace_elems((uint32_t)kind, c->cfg.n_max) * 8, cap_bytes = ((size_t)4 << cap_height) * 8;
@@ -2950,9 +2969,11 @@ int32_t tmx_trace_commit_sharded_device(tmx_ctx* c, int32_t kind, uint32_t n_tot
                                  mine, hip_stream);
     if (st) return shard_fail(c, st);
   } else {
-    HIPCK(c, hipMemsetAsync(mine, 0, cap_bytes, s));  // an empty shard commits to nothing: a zero cap
+    HIPCK(c, hipMemsetAsync(mine, 0, cap_bytes, s));  // an empty shard commits to nothing: a zero cap (and leaves nothing to open)
   }
-  return exchange_slices(c, d_caps, c->comm_world, cap_bytes, s);
+  const int32_t st = exchange_slices(c, d_caps, c->comm_world, cap_bytes, s);
+  if (st) c->last_commit.valid = false;
+  return st;
 }
 
 int32_t tmx_trace_commit_last_ms(tmx_ctx* c, float ms[3]) {
@@ -2961,6 +2982,132 @@ int32_t tmx_trace_commit_last_ms(tmx_ctx* c, float ms[3]) {
   HIPCK(c, hipEventSynchronize(c->ev_commit[3]));
   for (int k = 0; k < 3; k++) HIPCK(c, hipEventElapsedTime(&ms[k], c->ev_commit[k], c->ev_commit[k + 1]));
   return TMX_OK;
+}
+
+}  // extern "C"
+
+// ---- openings of a Poseidon Merkle tree: rows + paths, and their verification on the device (include/tmx.h) -------------------------------
+constexpr uint32_t OPEN_MAX_QUERIES = 1u << 22;  // (one workgroup per query in k_merkle_open's first grid dimension)
+
+static int32_t check_indices(tmx_ctx* c, uint32_t log_n, uint32_t n_queries, const uint64_t* h_idx) {
+  if (n_queries == 0) return fail(c, TMX_ERR_BAD_ARG, "n_queries must be at least 1");
+  if (n_queries > OPEN_MAX_QUERIES) return fail(c, TMX_ERR_BAD_ARG, "n_queries exceeds " + std::to_string(OPEN_MAX_QUERIES) + " per call");
+  if (!h_idx) return fail(c, TMX_ERR_BAD_ARG, "h_indices is null");
+  for (uint32_t q = 0; q < n_queries; q++)
+    if (h_idx[q] >> log_n)
+      return fail(c, TMX_ERR_BAD_ARG, "query " + std::to_string(q) + ": index " + std::to_string(h_idx[q]) + " is not below 2^" + std::to_string(log_n));
+  return TMX_OK;
+}
+
+// the next slot of the index ring, holding a device copy of h_idx enqueued on s.  The caller records slot->ev on s behind the launch that
+// reads it (index_release), whatever became of the launch: the slot is not written again before that event has completed.
+static int32_t index_stage(tmx_ctx* c, uint32_t n, const uint64_t* h_idx, hipStream_t s, tmx_ctx::IdxSlot** out) {
+  tmx_ctx::IdxSlot& sl = c->idx_ring[c->idx_next];
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if (!sl.ev) HIPCK(c, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+  if (sl.used) HIPCK(c, hipEventSynchronize(sl.ev));
+  sl.used = false;
+  if (sl.cap < n) {
+    if (sl.d) { HIPCK(c, hipFree(sl.d)); sl.d = nullptr; }
+    if (sl.h) { HIPCK(c, hipHostFree(sl.h)); sl.h = nullptr; }
+    sl.cap = 0;
+    const uint64_t want = std::max<uint64_t>(n, 1024);
+    HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&sl.h), want * 8, hipHostMallocDefault));
+    HIPCK(c, hipMalloc(reinterpret_cast<void**>(&sl.d), want * 8));
+    sl.cap = want;
+  }
+  std::memcpy(sl.h, h_idx, (size_t)n * 8);
+  HIPCK(c, hipMemcpyAsync(sl.d, sl.h, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  sl.used = true;  // (from here on the copy may be pending: index_release records the event)
+  c->idx_next = (c->idx_next + 1) % tmx_ctx::IDX_RING;
+  *out = &sl;
+  return TMX_OK;
+}
+static int32_t index_release(tmx_ctx* c, tmx_ctx::IdxSlot* sl, hipStream_t s, int launch_rc, const char* what) {
+  const hipError_t e = hipEventRecord(sl->ev, s);
+  if (e != hipSuccess) {  // (no event to wait for: drain the stream so that the slot is free when it comes round again)
+    (void)hipStreamSynchronize(s);
+    sl->used = false;
+  }
+  if (launch_rc) return fail(c, TMX_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)launch_rc));
+  if (e != hipSuccess) return fail(c, TMX_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+  return TMX_OK;
+}
+
+static int32_t merkle_open(tmx_ctx* c, uint32_t log_n, uint32_t n_cols, const uint64_t* d_cols, uint32_t cap_height, const uint64_t* d_levels,
+                           uint32_t n_queries, const uint64_t* h_idx, uint64_t* d_rows, uint64_t* d_paths, void* hip_stream) {
+  const uint32_t path_len = log_n - cap_height;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  tmx_ctx::IdxSlot* sl = nullptr;
+  int32_t st = index_stage(c, n_queries, h_idx, s, &sl);
+  if (st) return st;
+  const char* split = std::getenv("TMX_OPEN_SPLIT");  // TMX_OPEN_SPLIT=1: rows and paths as two launches (times the one-launch form against it)
+  const int rc = launch_merkle_open(log_n, n_cols, d_cols, path_len, d_levels, n_queries, sl->d, d_rows, d_paths, split && split[0] == '1', s);
+  return index_release(c, sl, s, rc, "k_merkle_open");
+}
+
+extern "C" {
+
+uint32_t tmx_poseidon_merkle_path_len(uint32_t log_n, uint32_t cap_height) {
+  if (log_n > 30 || cap_height > log_n) return 0;
+  return log_n - cap_height;
+}
+
+int32_t tmx_poseidon_merkle_open_device(tmx_ctx* c, uint32_t log_n, uint32_t n_cols, const uint64_t* d_cols, uint32_t cap_height,
+                                        const uint64_t* d_levels, uint32_t n_queries, const uint64_t* h_indices, uint64_t* d_rows,
+                                        uint64_t* d_paths, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (log_n > 30 || cap_height > log_n) return fail(c, TMX_ERR_BAD_ARG, "cap_height must not exceed log_n (<= 30)");
+  if (!d_cols || !d_levels || !d_rows || n_cols == 0) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_levels and d_rows must be set and n_cols >= 1");
+  if (!d_paths && log_n > cap_height) return fail(c, TMX_ERR_BAD_ARG, "d_paths is null but the paths are not empty");
+  int32_t st = check_indices(c, log_n, n_queries, h_indices);
+  if (st) return st;
+  return merkle_open(c, log_n, n_cols, d_cols, cap_height, d_levels, n_queries, h_indices, d_rows, d_paths, hip_stream);
+}
+
+int32_t tmx_trace_commit_last_shape(const tmx_ctx* c, uint32_t* log_rows_ext, uint32_t* n_cols, uint32_t* cap_height) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (!c->last_commit.valid)
+    return fail(const_cast<tmx_ctx*>(c), TMX_ERR_BAD_ARG, "no commit to open: no tmx_trace_commit_device call has completed since the context was created or since the last failed or empty-shard commit");
+  if (log_rows_ext) *log_rows_ext = c->last_commit.log_m;
+  if (n_cols) *n_cols = c->last_commit.n_cols;
+  if (cap_height) *cap_height = c->last_commit.cap_height;
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_open_device(tmx_ctx* c, uint32_t n_queries, const uint64_t* h_indices, uint64_t* d_rows, uint64_t* d_paths,
+                                     void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = tmx_trace_commit_last_shape(c, nullptr, nullptr, nullptr);
+  if (st) return st;
+  const tmx_ctx::CommitRec r = c->last_commit;
+  if (!d_rows) return fail(c, TMX_ERR_BAD_ARG, "d_rows is null");
+  if (!d_paths && r.log_m > r.cap_height) return fail(c, TMX_ERR_BAD_ARG, "d_paths is null but the paths are not empty");
+  st = check_indices(c, r.log_m, n_queries, h_indices);
+  if (st) return st;
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_commit);
+  return merkle_open(c, r.log_m, r.n_cols, reinterpret_cast<const uint64_t*>(base + r.lde_off), r.cap_height,
+                     reinterpret_cast<const uint64_t*>(base + r.lev_off), n_queries, h_indices, d_rows, d_paths, hip_stream);
+}
+
+int32_t tmx_poseidon_merkle_verify_device(tmx_ctx* c, uint32_t log_n, uint32_t n_cols, uint32_t cap_height, const uint64_t* d_cap,
+                                          uint32_t n_queries, const uint64_t* h_indices, const uint64_t* d_rows, const uint64_t* d_paths,
+                                          uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (log_n > 30 || cap_height > log_n) return fail(c, TMX_ERR_BAD_ARG, "cap_height must not exceed log_n (<= 30)");
+  if (!d_cap || !d_rows || !d_ok || n_cols == 0) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_rows and d_ok must be set and n_cols >= 1");
+  if (!d_paths && log_n > cap_height) return fail(c, TMX_ERR_BAD_ARG, "d_paths is null but the paths are not empty");
+  int32_t st = check_indices(c, log_n, n_queries, h_indices);
+  if (st) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  st = poseidon_ready(c, s);
+  if (st) return st;
+  tmx_ctx::IdxSlot* sl = nullptr;
+  st = index_stage(c, n_queries, h_indices, s, &sl);
+  if (st) return st;
+  const int rc = launch_merkle_verify(c->d_pos_consts, c->pos_mode, n_cols, log_n - cap_height, n_queries, d_cap, sl->d, d_rows, d_paths, d_ok, s);
+  return index_release(c, sl, s, rc, "k_merkle_verify");
 }
 
 }  // extern "C"

@@ -30,4 +30,13 @@ int launch_poseidon_leaves(const void* d_consts, int mode, uint32_t log_n, uint3
 // one tree level: out[i] = two_to_one(in[2 i], in[2 i + 1]), i < n_out
 int launch_poseidon_level(const void* d_consts, int mode, uint64_t n_out, const void* d_in, void* d_out, void* stream);
 
+// openings of n_queries leaves (d_idx: device u64, each < 2^log_n, checked by the caller): d_rows[q][n_cols] = row idx[q] of the columns as
+// stored, d_paths[q][path_len][4] = the siblings from the leaf level up (d_levels: the layout of the Merkle levels above).  split: the rows
+// and the paths as two launches instead of one.
+int launch_merkle_open(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint32_t path_len, const void* d_levels, uint32_t n_queries,
+                       const void* d_idx, void* d_rows, void* d_paths, bool split, void* stream);
+// d_ok[q] = 1 if row q and path q lead to d_cap[idx[q] >> path_len], else 0
+int launch_merkle_verify(const void* d_consts, int mode, uint32_t n_cols, uint32_t path_len, uint32_t n_queries, const void* d_cap, const void* d_idx,
+                         const void* d_rows, const void* d_paths, void* d_ok, void* stream);
+
 }  // namespace tmx

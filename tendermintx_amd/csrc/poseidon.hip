@@ -13,6 +13,7 @@
 //   24 v_mad_u64_u32 and ONE reduction (2^32 (h_lo + 2^32 h_hi) = 2^32 h_lo + (2^32 - 1) h_hi) instead of 12 field products.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "goldilocks.hpp"
@@ -223,6 +224,81 @@ __global__ __launch_bounds__(256) void k_poseidon_level(const uint64_t* __restri
   o[0] = a; o[1] = b;
 }
 
+// ---- openings of a tree (the query phase of a FRI-style consumer) ----------------------------------------------------------------------
+// Query q opens leaf i = idx[q] (validated on the host: i < 2^log_n).  Rows: rows[q][c] = cols[(c << log_n) + i], the stored word as it is
+// (no reduction).  Block (q, y) copies columns y * 256 + t, y * 256 + t + gridDim.y * 256, ...: consecutive threads write consecutive words
+// of one row, and each read is the one word of a different column that sits 2^log_n * 8 B from its neighbour -- a cache line per (query,
+// column), so the grid is sized to keep many of them in flight.  Paths: block (q, 0) also writes paths[q][l] = levels[off_l + ((i >> l) ^ 1)]
+// for l < path_len (bottom-up, the leaf's sibling first), off_l = 2^(log_n + 1) - 2^(log_n + 1 - l) digests (the leaves, then each level).
+// Either pointer may be null: the split form runs the rows and the paths as two launches.
+__global__ __launch_bounds__(256) void k_merkle_open(uint32_t log_n, uint32_t n_cols, const uint64_t* __restrict__ cols, uint32_t path_len,
+                                                     const uint64_t* __restrict__ levels, const uint64_t* __restrict__ idx,
+                                                     uint64_t* __restrict__ rows, uint64_t* __restrict__ paths) {
+  const uint32_t q = blockIdx.x;
+  const uint64_t i = idx[q];
+  if (rows) {
+    uint64_t* row = rows + (uint64_t)q * n_cols;
+    for (uint64_t c = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; c < n_cols; c += (uint64_t)gridDim.y * blockDim.x)
+      row[c] = cols[(c << log_n) + i];
+  }
+  if (paths && blockIdx.y == 0 && threadIdx.x < 4 * path_len) {
+    const uint32_t l = threadIdx.x >> 2, w = threadIdx.x & 3;
+    const uint64_t off = (2ull << log_n) - (2ull << (log_n - l));
+    paths[((uint64_t)q * path_len + l) * 4 + w] = levels[(off + ((i >> l) ^ 1ull)) * 4 + w];
+  }
+}
+
+__device__ __forceinline__ void pos_digest_out(const uint64_t (&s)[12], uint64_t (&d)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) d[k] = gl_canon(s[k]);
+}
+
+// One thread per query: the leaf digest of rows[q] formed exactly as k_poseidon_leaves forms it (rows of <= 4 words: their own canonical,
+// zero-padded digest; else the overwrite-mode sponge, whose short last chunk leaves the unused rate words as they were), then the path
+// (bit l of i set: cur = two_to_one(sib, cur), else two_to_one(cur, sib)), then cur == cap[i >> path_len] word for word.  Latency-bound:
+// one permutation per 8 columns plus one per level, in sequence; blocks of one wave spread the queries over the CUs.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_merkle_verify(const uint64_t* __restrict__ consts, uint32_t n_cols, uint32_t path_len, uint32_t n_queries,
+                                                      const uint64_t* __restrict__ cap, const uint64_t* __restrict__ idx,
+                                                      const uint64_t* __restrict__ rows, const uint64_t* __restrict__ paths, uint32_t* __restrict__ ok) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_queries) return;
+  const PosConsts K = pos_consts(consts);
+  const uint64_t i = idx[q];
+  const uint64_t* row = rows + (uint64_t)q * n_cols;
+  uint64_t s[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) s[k] = 0;
+  if (n_cols <= 4) {
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) s[c] = c < n_cols ? gl_canon(row[c]) : 0;
+  } else {
+    for (uint32_t c0 = 0; c0 < n_cols; c0 += 8) {
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++)
+        if (c0 + k < n_cols) s[k] = row[c0 + k];
+      pos_permute<MODE>(s, K);
+    }
+  }
+  uint64_t cur[4];
+  pos_digest_out(s, cur);
+  const uint64_t* path = paths + (uint64_t)q * path_len * 4;
+  for (uint32_t l = 0; l < path_len; l++) {
+    const bool right = (i >> l) & 1ull;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint64_t sib = path[4 * l + k];
+      s[k] = right ? sib : cur[k];
+      s[4 + k] = right ? cur[k] : sib;
+      s[8 + k] = 0;
+    }
+    pos_permute<MODE>(s, K);
+    pos_digest_out(s, cur);
+  }
+  const uint64_t* want = cap + 4 * (i >> path_len);
+  ok[q] = (cur[0] == want[0] && cur[1] == want[1] && cur[2] == want[2] && cur[3] == want[3]) ? 1u : 0u;
+}
+
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 int launch_poseidon_permute(const void* d_consts, int mode, uint32_t n, const void* d_in, void* d_out, void* stream) {
@@ -265,6 +341,43 @@ int launch_poseidon_level(const void* d_consts, int mode, uint64_t n_out, const 
   else
     hipLaunchKernelGGL(k_poseidon_level<POS_MODE_GENERAL>, grid, dim3(256), 0, S_(stream), reinterpret_cast<const uint64_t*>(d_consts), n_out,
                        reinterpret_cast<const uint64_t*>(d_in), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+
+int launch_merkle_open(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint32_t path_len, const void* d_levels, uint32_t n_queries,
+                       const void* d_idx, void* d_rows, void* d_paths, bool split, void* stream) {
+  if (n_queries == 0) return 0;
+  // column blocks per query: all of the row's columns at once up to 64 blocks (16 k columns), then a grid-stride loop
+  const uint32_t col_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_cols + 255) / 256, 64);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* lv = reinterpret_cast<const uint64_t*>(d_levels);
+  const uint64_t* idx = reinterpret_cast<const uint64_t*>(d_idx);
+  uint64_t* rows = reinterpret_cast<uint64_t*>(d_rows);
+  uint64_t* paths = path_len ? reinterpret_cast<uint64_t*>(d_paths) : nullptr;
+  if (!split || !paths) {
+    hipLaunchKernelGGL(k_merkle_open, dim3(n_queries, col_blocks), dim3(256), 0, S_(stream), log_n, n_cols, cols, path_len, lv, idx, rows, paths);
+  } else {
+    hipLaunchKernelGGL(k_merkle_open, dim3(n_queries, col_blocks), dim3(256), 0, S_(stream), log_n, n_cols, cols, 0u, lv, idx, rows, nullptr);
+    hipLaunchKernelGGL(k_merkle_open, dim3(n_queries, 1), dim3(256), 0, S_(stream), log_n, n_cols, cols, path_len, lv, idx, nullptr, paths);
+  }
+  return (int)hipGetLastError();
+}
+int launch_merkle_verify(const void* d_consts, int mode, uint32_t n_cols, uint32_t path_len, uint32_t n_queries, const void* d_cap, const void* d_idx,
+                         const void* d_rows, const void* d_paths, void* d_ok, void* stream) {
+  if (n_queries == 0) return 0;
+  const dim3 grid((n_queries + 63) / 64);
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* cap = reinterpret_cast<const uint64_t*>(d_cap);
+  const uint64_t* idx = reinterpret_cast<const uint64_t*>(d_idx);
+  const uint64_t* rows = reinterpret_cast<const uint64_t*>(d_rows);
+  const uint64_t* paths = reinterpret_cast<const uint64_t*>(d_paths);
+  uint32_t* ok = reinterpret_cast<uint32_t*>(d_ok);
+  if (mode == POS_MODE_MERGE3)
+    hipLaunchKernelGGL(k_merkle_verify<POS_MODE_MERGE3>, grid, dim3(64), 0, S_(stream), K, n_cols, path_len, n_queries, cap, idx, rows, paths, ok);
+  else if (mode == POS_MODE_SMALL)
+    hipLaunchKernelGGL(k_merkle_verify<POS_MODE_SMALL>, grid, dim3(64), 0, S_(stream), K, n_cols, path_len, n_queries, cap, idx, rows, paths, ok);
+  else
+    hipLaunchKernelGGL(k_merkle_verify<POS_MODE_GENERAL>, grid, dim3(64), 0, S_(stream), K, n_cols, path_len, n_queries, cap, idx, rows, paths, ok);
   return (int)hipGetLastError();
 }
 
