@@ -610,6 +610,73 @@ int32_t tmx_poseidon_merkle_verify_device(tmx_ctx* ctx, uint32_t log_n, uint32_t
                                           uint32_t n_queries, const uint64_t* h_indices, const uint64_t* d_rows, const uint64_t* d_paths,
                                           uint32_t* d_ok, void* hip_stream);
 
+/* ---- a batched FRI low-degree proof over committed columns: the consumer of the cap and its openings.  PARITY UNPINNED against plonky2
+ * (natural row order, no salt, injectable Poseidon constants, this project's own transcript below); everything is over the Goldilocks
+ * field p = 2^64 - 2^32 + 1 and its extension F_p^2 = F_p[X] / (X^2 - 7), values (c0, c1).
+ * Input: n_cols columns of M = 2^log_n u64 (column-major, words taken mod p), their evaluations on D_0 = { s w^i : i < M } with (w, s) the
+ * NTT domain (tmx_ntt_set_domain) -- what tmx_lde_goldilocks_device writes -- and d_levels, tmx_poseidon_merkle_device's tree of them.  The
+ * claim: every column has degree < 2^(log_n - log_blowup).
+ *   batching   f_0(x_i) = sum_c alpha^c col_c[i], alpha in F_p^2.
+ *   schedule   d = log_n - log_blowup; while d > final_log_max: b = min(arity_bits, d - final_log_max), append b, d -= b.  final_log = the d
+ *              left (2^final_log final coefficients); zero layers if d <= final_log_max from the start.  Layer l has arity a_l = 2^b_l.
+ *   domains    D_(l+1) = { y^a_l : y in D_l }: s_(l+1) = s_l^a_l, w_(l+1) = w_l^a_l, M_(l+1) = M_l / a_l, natural order.
+ *   layer tree layer l is stored planar (all c0, then all c1); leaf r < M_(l+1) is the coset { r + j M_(l+1) : j < a_l }, its row (c0 of those
+ *              a_l points, c1 of them): the planar buffer IS the column-major matrix of 2 a_l columns over M_(l+1) rows, and the tree is
+ *              tmx_poseidon_merkle_device's tree of it (rows of <= 4 words are their own leaf), cap height h_l = min(cap_height, log M_(l+1)).
+ *   fold       f(x) = sum_(j < a) x^j f_j(x^a) -> f_(l+1)(y) = sum_j beta_l^j f_j(y): b_l radix-2 folds with beta, beta^2, beta^4, ..., each
+ *              g(x^2) = (f(x) + f(-x)) / 2 + beta (f(x) - f(-x)) / (2 x), x = point i, -x = point i + M / 2 (a fold stays inside a leaf).
+ *   final      the last layer interpolated on its coset (inverse NTT of both planes, coefficient k times s_L^-k), the low 2^final_log
+ *              coefficients kept; whether the dropped ones were all zero is recorded (tmx_fri_last_degree_ok).
+ *   transcript a Poseidon duplex modelled on plonky2's Challenger, with the context's CURRENT width-12 permutation: state[12] = 0, an input
+ *              and an output buffer.  observe(x): clear the output buffer, append x mod p to the input buffer, duplex when it holds 8.
+ *              duplex: state[0..k) = the input buffer, clear it, permute, output buffer = state[0..8).  challenge(): duplex if the input
+ *              buffer is non-empty or the output buffer empty, then pop the LAST output word.  An extension challenge = (challenge(),
+ *              challenge()).  Order: observe the seven parameters (log_n, n_cols, cap_height, log_blowup, arity_bits, final_log_max,
+ *              n_queries); observe the commit cap (4 << cap_height words), draw alpha; per layer observe its cap, draw beta_l; observe the
+ *              final coefficients (c0, c1 of coefficient 0, then 1, ...); per query idx_q = challenge() mod 2^log_n.
+ *   query q    the commit's opening of row idx_q (as tmx_trace_commit_open_device), and per layer the opening of leaf r_l = i_l mod M_(l+1)
+ *              (i_0 = idx_q, i_(l+1) = r_l); the value sits at entry j_l = i_l >> log M_(l+1) of that leaf.  Checked: the commit opening
+ *              against the commit cap; v = sum alpha^c row_c; per layer leaf entry j_l == v, the leaf's path against layer cap l, v = the
+ *              leaf folded with beta_l; at the end v == the final polynomial at point i_L of D_L.  Any other transcript (a wrong idx_q in the
+ *              proof included) rejects the query.
+ * The proof is one flat buffer of u64 words (tmx_fri_layout_of gives every offset): each layer's cap; the final coefficients interleaved
+ * (c0, c1); the n_queries indices; the initial rows [n_queries][n_cols] and paths [n_queries][log_n - cap_height][4]; then per layer its rows
+ * [n_queries][2 a_l] (planar, as hashed) and paths [n_queries][log M_(l+1) - h_l][4].
+ * Validation (every call, before anything is enqueued; TMX_ERR_BAD_ARG, nothing written, tmx_last_error says why): 1 <= log_blowup <= 6,
+ * log_blowup < log_n <= 28, n_cols >= 1, cap_height <= log_n, 1 <= arity_bits <= 4, final_log_max <= 8, final_log_max + log_blowup <= 12,
+ * 1 <= n_queries <= 256, reserved == 0.
+ *   tmx_fri_layout_of            host only: the schedule and the offsets of the proof for these parameters.
+ *   tmx_fri_prove_device         a proof over caller columns d_cols and their d_levels, under the context's CURRENT NTT domain.
+ *   tmx_trace_commit_fri_device  a proof over the context's last tmx_trace_commit_device (its extended columns and tree, still in the
+ *                                commit's scratch, under the domain in use at commit time).  The parameters must match that commit
+ *                                (log_n = log_rows + log_blowup, n_cols, cap_height, log_blowup); with no commit to open (fresh context,
+ *                                failed commit, empty shard) TMX_ERR_BAD_ARG, as for the openings.  Proving leaves the commit's scratch
+ *                                untouched: its openings still work afterwards.
+ *   tmx_fri_verify_device        d_ok[q] = 1 if query q of the proof checks against the commit cap d_cap[4 << cap_height], else 0.  One
+ *                                workgroup: one lane re-derives the transcript from the proof, then one thread per query (latency-bound).
+ *   tmx_fri_last_degree_ok       blocks until the last prove of this context finished: 1 if the dropped coefficients were zero, else 0.
+ *   tmx_fri_last_ms              HIP-event times of the last prove's stages: combine, layers (trees + folds), final + transcript, openings.
+ * Both provers and the verifier hash with the context's CURRENT Poseidon constants.  Prove and verify are asynchronous on hip_stream, with
+ * no host synchronisation and no device-to-host copy inside (alpha, the beta_l and the query indices are drawn on the device); the prover's
+ * scratch is the context's own (separate from the commit's; it grows on demand, which waits for the device once), so proves of one context
+ * are ordered on one stream. */
+typedef struct { uint32_t log_n, n_cols, cap_height, log_blowup, arity_bits, final_log_max, n_queries, reserved; } tmx_fri_params;
+#define TMX_FRI_MAX_LAYERS 28
+typedef struct {
+  uint32_t n_layers, final_log;
+  uint32_t layer_bits[TMX_FRI_MAX_LAYERS], layer_cap_height[TMX_FRI_MAX_LAYERS];
+  uint64_t off_caps[TMX_FRI_MAX_LAYERS], off_final, off_indices, off_init_rows, off_init_paths;
+  uint64_t off_rows[TMX_FRI_MAX_LAYERS], off_paths[TMX_FRI_MAX_LAYERS], words;  /* u64 offsets into the proof; words = total */
+} tmx_fri_layout;
+int32_t tmx_fri_layout_of(const tmx_fri_params* p, tmx_fri_layout* out);  /* host only: TMX_OK or TMX_ERR_BAD_ARG */
+int32_t tmx_fri_prove_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof,
+                             void* hip_stream);
+int32_t tmx_trace_commit_fri_device(tmx_ctx* ctx, const tmx_fri_params* p, uint64_t* d_proof, void* hip_stream);
+int32_t tmx_fri_verify_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok,
+                              void* hip_stream);
+int32_t tmx_fri_last_degree_ok(tmx_ctx* ctx);                  /* blocks; 1 / 0 for the last prove, TMX_ERR_BAD_ARG if none */
+int32_t tmx_fri_last_ms(tmx_ctx* ctx, float ms[4]);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

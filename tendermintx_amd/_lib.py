@@ -133,10 +133,25 @@ class ValueLayout(C.Structure):
                 ("off_nodes_trusted", C.c_uint32), ("off_proof_derived", C.c_uint32), ("tree_nodes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+
+FRI_MAX_LAYERS = 28
+
+
+class FriParams(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("log_n", "n_cols", "cap_height", "log_blowup", "arity_bits", "final_log_max", "n_queries", "reserved")]
+
+
+class FriLayout(C.Structure):
+    _fields_ = [("n_layers", C.c_uint32), ("final_log", C.c_uint32), ("layer_bits", C.c_uint32 * FRI_MAX_LAYERS),
+                ("layer_cap_height", C.c_uint32 * FRI_MAX_LAYERS), ("off_caps", C.c_uint64 * FRI_MAX_LAYERS), ("off_final", C.c_uint64),
+                ("off_indices", C.c_uint64), ("off_init_rows", C.c_uint64), ("off_init_paths", C.c_uint64),
+                ("off_rows", C.c_uint64 * FRI_MAX_LAYERS), ("off_paths", C.c_uint64 * FRI_MAX_LAYERS), ("words", C.c_uint64)]
+
 assert (C.sizeof(ValidatorValue), C.sizeof(HashFieldValue), C.sizeof(SkipInputsFixed), C.sizeof(StepInputsFixed)) == (240, 48, 832, 1008)
 assert (C.sizeof(TargetLaneDerived), C.sizeof(TrustedLaneDerived), C.sizeof(ProofDerived)) == (560, 112, 976)
 assert C.sizeof(ValidatorRec) == 256 and C.sizeof(HashFieldRec) == 48 and C.sizeof(ProofRec) == 2336
 assert C.sizeof(Report) == 64 and C.sizeof(AddrRec) == 32
+assert C.sizeof(FriParams) == 32 and C.sizeof(FriLayout) == 8 + 8 * 28 + 8 * 28 * 3 + 8 * 5
 
 _lib = None
 _hip = None
@@ -237,6 +252,12 @@ def lib():
         L.tmx_trace_commit_open_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_poseidon_merkle_verify_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_fri_layout_of.argtypes = [C.POINTER(FriParams), C.POINTER(FriLayout)]
+        L.tmx_fri_prove_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_fri_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p]
+        L.tmx_fri_verify_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_fri_last_degree_ok.argtypes = [C.c_void_p]
+        L.tmx_fri_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

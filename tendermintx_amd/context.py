@@ -290,6 +290,42 @@ class Context:
         idx = _indices(indices)
         check(self._L.tmx_trace_commit_open_device(self._h, idx.size, idx.ctypes.data, d_rows, d_paths, self._stream(stream)), self._h)
 
+    # ---- a batched FRI low-degree proof over committed columns (include/tmx.h "a batched FRI low-degree proof"); params: a dict or
+    # _lib.FriParams with log_n, n_cols, cap_height, log_blowup, arity_bits, final_log_max, n_queries
+    @staticmethod
+    def _fri_params(params):
+        if isinstance(params, _lib.FriParams):
+            return params
+        return _lib.FriParams(**{k: int(v) for k, v in params.items()})
+
+    def fri_layout(self, params):
+        """the schedule and every u64 offset of the proof (host only): a dict; TmxError on parameters the ABI refuses"""
+        return fri_layout(params, self._L)
+
+    def fri_prove_device(self, params, d_cols, d_levels, d_proof, stream=None):
+        """a proof over caller columns (d_cols, d_levels: what lde_goldilocks_device / poseidon_merkle_device wrote) into d_proof[words]"""
+        check(self._L.tmx_fri_prove_device(self._h, C.byref(self._fri_params(params)), d_cols, d_levels, d_proof, self._stream(stream)), self._h)
+
+    def trace_commit_fri_device(self, params, d_proof, stream=None):
+        """a proof over the most recent trace_commit_device (same stream, after it); the parameters must match that commit"""
+        check(self._L.tmx_trace_commit_fri_device(self._h, C.byref(self._fri_params(params)), d_proof, self._stream(stream)), self._h)
+
+    def fri_verify_device(self, params, d_cap, d_proof, d_ok, stream=None):
+        """d_ok[n_queries] u32: 1 where the query checks against the commit cap d_cap"""
+        check(self._L.tmx_fri_verify_device(self._h, C.byref(self._fri_params(params)), d_cap, d_proof, d_ok, self._stream(stream)), self._h)
+
+    def fri_last_degree_ok(self):
+        """(blocks) True if the last prove's dropped final coefficients were all zero"""
+        st = self._L.tmx_fri_last_degree_ok(self._h)
+        if st < 0:
+            check(st, self._h)
+        return st == 1
+
+    def fri_last_ms(self):
+        ms = (C.c_float * 4)()
+        check(self._L.tmx_fri_last_ms(self._h, ms), self._h)
+        return {"combine": ms[0], "layers": ms[1], "final": ms[2], "openings": ms[3]}
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -367,3 +403,15 @@ class Context:
 
     def sync(self):
         check(self._L.tmx_sync(self._h), self._h)
+
+
+def fri_layout(params, L=None):
+    """tmx_fri_layout_of as a dict (no context, no device): n_layers, final_log, layer_bits, layer_cap_height, off_caps, off_final,
+    off_indices, off_init_rows, off_init_paths, off_rows, off_paths, words"""
+    L = L or _lib.lib()
+    out = _lib.FriLayout()
+    check(L.tmx_fri_layout_of(C.byref(Context._fri_params(params)), C.byref(out)))
+    n = out.n_layers
+    return {"n_layers": n, "final_log": out.final_log, "layer_bits": list(out.layer_bits[:n]), "layer_cap_height": list(out.layer_cap_height[:n]),
+            "off_caps": list(out.off_caps[:n]), "off_final": out.off_final, "off_indices": out.off_indices, "off_init_rows": out.off_init_rows,
+            "off_init_paths": out.off_init_paths, "off_rows": list(out.off_rows[:n]), "off_paths": list(out.off_paths[:n]), "words": out.words}

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "fri.h"
 #include "ntt.h"
 #include "poseidon.h"
 #include "trace.h"
@@ -399,7 +400,14 @@ struct tmx_ctx {
   hipEvent_t ev_commit[4] = {};
   // the last tmx_trace_commit_device (what tmx_trace_commit_open_device opens): its shape and where its extended columns and levels sit in
   // d_commit.  valid: that call finished enqueueing (any failure of a later commit call, or an empty shard, clears it)
-  struct CommitRec { bool valid; uint32_t log_m, n_cols, cap_height; size_t lde_off, lev_off; } last_commit = {};
+  // (and the log_blowup and NTT domain it was extended with: what tmx_trace_commit_fri_device proves under)
+  struct CommitRec { bool valid; uint32_t log_m, n_cols, cap_height; size_t lde_off, lev_off; uint32_t log_blowup; uint64_t root, shift; } last_commit = {};
+  // scratch of the FRI provers (transcript state, challenges, degree flag, alpha powers, leaf indices, layers, layer trees; grows on demand)
+  // and the events around the stages of the last prove.  fri_valid: a prove finished enqueueing (tmx_fri_last_degree_ok / _ms read it)
+  void* d_fri = nullptr;
+  size_t fri_bytes = 0, fri_flag_off = 0;
+  hipEvent_t ev_fri[5] = {};
+  bool fri_valid = false;
   // staging of the host query indices of the opening / verifying calls: a ring of page-locked + device buffers, each slot reused only once
   // the event behind the launch that read it has completed
   struct IdxSlot { uint64_t* h = nullptr; uint64_t* d = nullptr; uint64_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -1379,6 +1387,9 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
   for (hipEvent_t e : c->ev_commit)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_fri)
+    if (e) (void)hipEventDestroy(e);
+  if (c->d_fri) (void)hipFree(c->d_fri);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
     if (sl.d) (void)hipFree(sl.d);
@@ -2945,7 +2956,7 @@ int32_t tmx_trace_commit_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uin
   const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, cap_height), n_cap = (uint64_t)1 << cap_height;
   HIPCK(c, hipMemcpyAsync(d_cap, levels + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
   HIPCK(c, hipEventRecord(c->ev_commit[3], s));
-  c->last_commit = {true, log_m, n_cols, cap_height, cols_b, cols_b + lde_b};
+  c->last_commit = {true, log_m, n_cols, cap_height, cols_b, cols_b + lde_b, log_blowup, c->ntt_root, c->ntt_shift};
   return TMX_OK;
 }
 
@@ -3108,6 +3119,221 @@ int32_t tmx_poseidon_merkle_verify_device(tmx_ctx* c, uint32_t log_n, uint32_t n
   if (st) return st;
   const int rc = launch_merkle_verify(c->d_pos_consts, c->pos_mode, n_cols, log_n - cap_height, n_queries, d_cap, sl->d, d_rows, d_paths, d_ok, s);
   return index_release(c, sl, s, rc, "k_merkle_verify");
+}
+
+}  // extern "C"
+
+// ---- a batched FRI low-degree proof over committed columns (include/tmx.h "a batched FRI low-degree proof") ---------------------------------
+static int32_t fri_check(tmx_ctx* c, const tmx_fri_params* p) {
+  auto bad = [&](const char* why) { return c ? fail(c, TMX_ERR_BAD_ARG, why) : TMX_ERR_BAD_ARG; };
+  if (!p) return bad("params is null");
+  if (p->log_blowup < 1 || p->log_blowup > 6) return bad("log_blowup must be 1 .. 6");
+  if (p->log_n <= p->log_blowup || p->log_n > 28) return bad("log_n must exceed log_blowup and be at most 28");
+  if (p->n_cols < 1) return bad("n_cols must be at least 1");
+  if (p->cap_height > p->log_n) return bad("cap_height must not exceed log_n");
+  if (p->arity_bits < 1 || p->arity_bits > 4) return bad("arity_bits must be 1 .. 4");
+  if (p->final_log_max > 8 || p->final_log_max + p->log_blowup > 12) return bad("final_log_max must be at most 8 and final_log_max + log_blowup at most 12");
+  if (p->n_queries < 1 || p->n_queries > FRI_MAX_QUERIES) return bad("n_queries must be 1 .. 256");
+  if (p->reserved) return bad("reserved must be 0");
+  return TMX_OK;
+}
+
+static void fri_layout(const tmx_fri_params& p, tmx_fri_layout& L) {
+  std::memset(&L, 0, sizeof L);
+  uint32_t d = p.log_n - p.log_blowup;
+  while (d > p.final_log_max) {
+    const uint32_t b = std::min(p.arity_bits, d - p.final_log_max);
+    L.layer_bits[L.n_layers++] = b;
+    d -= b;
+  }
+  L.final_log = d;
+  uint64_t w = 0;
+  uint32_t lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    L.layer_cap_height[l] = std::min(p.cap_height, lg);
+    L.off_caps[l] = w;
+    w += 4ull << L.layer_cap_height[l];
+  }
+  L.off_final = w; w += 2ull << L.final_log;
+  L.off_indices = w; w += p.n_queries;
+  L.off_init_rows = w; w += (uint64_t)p.n_queries * p.n_cols;
+  L.off_init_paths = w; w += (uint64_t)p.n_queries * (p.log_n - p.cap_height) * 4;
+  lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    L.off_rows[l] = w; w += (uint64_t)p.n_queries * (2ull << L.layer_bits[l]);
+    L.off_paths[l] = w; w += (uint64_t)p.n_queries * (lg - L.layer_cap_height[l]) * 4;
+  }
+  L.words = w;
+}
+
+static FriGeom fri_geom(const tmx_fri_params& p, const tmx_fri_layout& L, uint64_t root_2_32, uint64_t shift) {
+  const uint64_t P = 0xffffffff00000001ull;
+  auto inv = [&](uint64_t x) { return gl_pow_host(x, P - 2); };
+  FriGeom G;
+  std::memset(&G, 0, sizeof G);
+  const uint32_t obs[8] = {p.log_n, p.n_cols, p.cap_height, p.log_blowup, p.arity_bits, p.final_log_max, p.n_queries, 0};
+  std::memcpy(G.params, obs, sizeof obs);
+  G.log_n = p.log_n; G.n_cols = p.n_cols; G.cap_height = p.cap_height; G.n_queries = p.n_queries;
+  G.n_layers = L.n_layers; G.final_log = L.final_log;
+  uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - p.log_n));
+  uint32_t lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    G.bits[l] = L.layer_bits[l]; G.cap_h[l] = L.layer_cap_height[l];
+    G.s_inv[l] = inv(s); G.w_inv[l] = inv(w); G.g[l] = gl_pow_host(G.w_inv[l], 1ull << lg);
+    s = gl_pow_host(s, 1ull << L.layer_bits[l]); w = gl_pow_host(w, 1ull << L.layer_bits[l]);
+    G.off_caps[l] = L.off_caps[l]; G.off_rows[l] = L.off_rows[l]; G.off_paths[l] = L.off_paths[l];
+  }
+  G.s_fin = s; G.w_fin = w; G.s_fin_inv = inv(s); G.w_fin_inv = inv(w); G.m_fin_inv = inv(1ull << lg);
+  G.off_final = L.off_final; G.off_indices = L.off_indices; G.off_init_rows = L.off_init_rows; G.off_init_paths = L.off_init_paths;
+  return G;
+}
+
+// cols / levels: the committed columns and their tree; (root_2_32, shift): the domain they were extended on.  Validated by the caller.
+static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* cols, const uint64_t* levels, uint64_t root_2_32, uint64_t shift,
+                         uint64_t* proof, void* hip_stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  tmx_fri_layout L;
+  fri_layout(p, L);
+  const FriGeom G = fri_geom(p, L, root_2_32, shift);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  int32_t st = poseidon_ready(c, s);
+  if (st) return st;
+  // scratch (u64 words): transcript state 32 | challenges 64 | degree flag 8 | alpha powers | leaf indices | layers 0 .. L | layer trees
+  const uint64_t nq = p.n_queries;
+  uint64_t at = 104;
+  const uint64_t o_apow = at; at += 2ull * p.n_cols;
+  const uint64_t o_qidx = at; at += L.n_layers * nq;
+  uint64_t o_layer[FRI_MAX_LAYERS + 1], o_lev[FRI_MAX_LAYERS];
+  uint32_t lg = p.log_n;
+  for (uint32_t l = 0; l <= L.n_layers; l++) {
+    o_layer[l] = at; at += 2ull << lg;
+    if (l < L.n_layers) lg -= L.layer_bits[l];
+  }
+  lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    o_lev[l] = at; at += 4 * tmx_poseidon_merkle_digests(lg, L.layer_cap_height[l]);
+  }
+  if (c->fri_bytes < at * 8) {
+    if (c->d_fri) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_fri)); c->d_fri = nullptr; c->fri_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_fri, at * 8));
+    c->fri_bytes = at * 8;
+  }
+  for (auto& e : c->ev_fri)
+    if (!e) HIPCK(c, hipEventCreate(&e));
+  c->fri_valid = false;
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_fri);
+  uint64_t *state = W, *chal = W + 32, *apow = W + o_apow, *qidx = W + o_qidx;
+  c->fri_flag_off = 96 * 8;
+  const uint64_t* commit_cap = levels + 4 * (tmx_poseidon_merkle_digests(p.log_n, p.cap_height) - (1ull << p.cap_height));
+  auto launched = [&](int rc, const char* what) { return rc ? fail(c, TMX_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc)) : TMX_OK; };
+
+  HIPCK(c, hipEventRecord(c->ev_fri[0], s));
+  if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 0, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+  if ((st = launched(launch_fri_alpha_powers(p.n_cols, chal, apow, s), "k_fri_alpha_powers"))) return st;
+  if ((st = launched(launch_fri_combine(p.log_n, p.n_cols, cols, apow, W + o_layer[0], s), "k_fri_combine"))) return st;
+  HIPCK(c, hipEventRecord(c->ev_fri[1], s));
+  lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    const uint32_t b = L.layer_bits[l], h = L.layer_cap_height[l];
+    lg -= b;
+    st = tmx_poseidon_merkle_device(c, lg, 2u << b, W + o_layer[l], h, W + o_lev[l], hip_stream);
+    if (st) return st;
+    const uint64_t nd = tmx_poseidon_merkle_digests(lg, h);
+    HIPCK(c, hipMemcpyAsync(proof + L.off_caps[l], W + o_lev[l] + 4 * (nd - (1ull << h)), 32ull << h, hipMemcpyDeviceToDevice, s));
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 1, l, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+    if ((st = launched(launch_fri_fold(lg, b, G.s_inv[l], G.w_inv[l], G.g[l], chal + 2 + 2 * l, W + o_layer[l], W + o_layer[l + 1], s), "k_fri_fold")))
+      return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[2], s));
+  if ((st = launched(launch_fri_final(lg, L.final_log, G.w_fin_inv, G.s_fin_inv, G.m_fin_inv, W + o_layer[L.n_layers], proof + L.off_final, W + 96, s),
+                     "k_fri_final")))
+    return st;
+  if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 2, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+  HIPCK(c, hipEventRecord(c->ev_fri[3], s));
+  // the openings, with the indices the transcript drew (device side): the commit's rows and paths, then every layer's leaf
+  if ((st = launched(launch_merkle_open(p.log_n, p.n_cols, cols, p.log_n - p.cap_height, levels, p.n_queries, proof + L.off_indices,
+                                        proof + L.off_init_rows, proof + L.off_init_paths, false, s), "k_merkle_open")))
+    return st;
+  lg = p.log_n;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    if ((st = launched(launch_merkle_open(lg, 2u << L.layer_bits[l], W + o_layer[l], lg - L.layer_cap_height[l], W + o_lev[l], p.n_queries,
+                                          qidx + l * nq, proof + L.off_rows[l], proof + L.off_paths[l], false, s), "k_merkle_open")))
+      return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[4], s));
+  c->fri_valid = true;
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_fri_layout_of(const tmx_fri_params* p, tmx_fri_layout* out) {
+  if (!out || fri_check(nullptr, p)) return TMX_ERR_BAD_ARG;
+  fri_layout(*p, *out);
+  return TMX_OK;
+}
+
+int32_t tmx_fri_prove_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = fri_check(c, p);
+  if (st) return st;
+  if (!d_cols || !d_levels || !d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_levels and d_proof must be set");
+  return fri_prove(c, *p, d_cols, d_levels, c->ntt_root, c->ntt_shift, d_proof, hip_stream);
+}
+
+int32_t tmx_trace_commit_fri_device(tmx_ctx* c, const tmx_fri_params* p, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = fri_check(c, p);
+  if (st) return st;
+  st = tmx_trace_commit_last_shape(c, nullptr, nullptr, nullptr);
+  if (st) return st;
+  const tmx_ctx::CommitRec r = c->last_commit;
+  if (p->log_n != r.log_m || p->n_cols != r.n_cols || p->cap_height != r.cap_height || p->log_blowup != r.log_blowup)
+    return fail(c, TMX_ERR_BAD_ARG, "FRI parameters do not match the last commit: log_n " + std::to_string(r.log_m) + ", n_cols " + std::to_string(r.n_cols) +
+                                        ", cap_height " + std::to_string(r.cap_height) + ", log_blowup " + std::to_string(r.log_blowup));
+  if (!d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_proof is null");
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_commit);
+  return fri_prove(c, *p, reinterpret_cast<const uint64_t*>(base + r.lde_off), reinterpret_cast<const uint64_t*>(base + r.lev_off), r.root, r.shift,
+                   d_proof, hip_stream);
+}
+
+int32_t tmx_fri_verify_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = fri_check(c, p);
+  if (st) return st;
+  if (!d_cap || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_proof and d_ok must be set");
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  st = poseidon_ready(c, s);
+  if (st) return st;
+  tmx_fri_layout L;
+  fri_layout(*p, L);
+  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, fri_geom(*p, L, c->ntt_root, c->ntt_shift), d_cap, d_proof, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_fri_last_degree_ok(tmx_ctx* c) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (!c->fri_valid) return fail(c, TMX_ERR_BAD_ARG, "no FRI prove has completed on this context");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
+  uint32_t flag = 0;
+  HIPCK(c, hipMemcpy(&flag, reinterpret_cast<uint8_t*>(c->d_fri) + c->fri_flag_off, 4, hipMemcpyDeviceToHost));
+  return flag ? 1 : 0;
+}
+
+int32_t tmx_fri_last_ms(tmx_ctx* c, float ms[4]) {
+  if (!c || !ms) return TMX_ERR_BAD_ARG;
+  if (!c->fri_valid) return fail(c, TMX_ERR_BAD_ARG, "no FRI prove has completed on this context");
+  HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
+  for (int k = 0; k < 4; k++) HIPCK(c, hipEventElapsedTime(&ms[k], c->ev_fri[k], c->ev_fri[k + 1]));
+  return TMX_OK;
 }
 
 }  // extern "C"

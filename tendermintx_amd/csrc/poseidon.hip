@@ -16,7 +16,8 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "goldilocks.hpp"
+#include "fri.h"
+#include "goldilocks_ext.hpp"
 #include "poseidon.h"
 
 namespace tmx {
@@ -253,19 +254,13 @@ __device__ __forceinline__ void pos_digest_out(const uint64_t (&s)[12], uint64_t
   for (int k = 0; k < 4; k++) d[k] = gl_canon(s[k]);
 }
 
-// One thread per query: the leaf digest of rows[q] formed exactly as k_poseidon_leaves forms it (rows of <= 4 words: their own canonical,
-// zero-padded digest; else the overwrite-mode sponge, whose short last chunk leaves the unused rate words as they were), then the path
-// (bit l of i set: cur = two_to_one(sib, cur), else two_to_one(cur, sib)), then cur == cap[i >> path_len] word for word.  Latency-bound:
-// one permutation per 8 columns plus one per level, in sequence; blocks of one wave spread the queries over the CUs.
+// Does row (n_cols words) with its path (path_len digests, bottom-up) lead to cap[i >> path_len]?  The leaf digest is formed exactly as
+// k_poseidon_leaves forms it (rows of <= 4 words: their own canonical, zero-padded digest; else the overwrite-mode sponge, whose short last
+// chunk leaves the unused rate words as they were), then the path (bit l of i set: cur = two_to_one(sib, cur), else two_to_one(cur, sib)),
+// then cur == the cap digest word for word.  Sequential: one permutation per 8 columns plus one per level.
 template <int MODE>
-__global__ __launch_bounds__(64) void k_merkle_verify(const uint64_t* __restrict__ consts, uint32_t n_cols, uint32_t path_len, uint32_t n_queries,
-                                                      const uint64_t* __restrict__ cap, const uint64_t* __restrict__ idx,
-                                                      const uint64_t* __restrict__ rows, const uint64_t* __restrict__ paths, uint32_t* __restrict__ ok) {
-  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n_queries) return;
-  const PosConsts K = pos_consts(consts);
-  const uint64_t i = idx[q];
-  const uint64_t* row = rows + (uint64_t)q * n_cols;
+__device__ bool merkle_leads_to_cap(const PosConsts& K, const uint64_t* __restrict__ row, uint32_t n_cols, const uint64_t* __restrict__ path,
+                                    uint32_t path_len, uint64_t i, const uint64_t* __restrict__ cap) {
   uint64_t s[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) s[k] = 0;
@@ -282,7 +277,6 @@ __global__ __launch_bounds__(64) void k_merkle_verify(const uint64_t* __restrict
   }
   uint64_t cur[4];
   pos_digest_out(s, cur);
-  const uint64_t* path = paths + (uint64_t)q * path_len * 4;
   for (uint32_t l = 0; l < path_len; l++) {
     const bool right = (i >> l) & 1ull;
 #pragma unroll
@@ -296,7 +290,192 @@ __global__ __launch_bounds__(64) void k_merkle_verify(const uint64_t* __restrict
     pos_digest_out(s, cur);
   }
   const uint64_t* want = cap + 4 * (i >> path_len);
-  ok[q] = (cur[0] == want[0] && cur[1] == want[1] && cur[2] == want[2] && cur[3] == want[3]) ? 1u : 0u;
+  return cur[0] == want[0] && cur[1] == want[1] && cur[2] == want[2] && cur[3] == want[3];
+}
+
+// One thread per query (merkle_leads_to_cap); blocks of one wave spread the queries over the CUs.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_merkle_verify(const uint64_t* __restrict__ consts, uint32_t n_cols, uint32_t path_len, uint32_t n_queries,
+                                                      const uint64_t* __restrict__ cap, const uint64_t* __restrict__ idx,
+                                                      const uint64_t* __restrict__ rows, const uint64_t* __restrict__ paths, uint32_t* __restrict__ ok) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_queries) return;
+  const PosConsts K = pos_consts(consts);
+  ok[q] = merkle_leads_to_cap<MODE>(K, rows + (uint64_t)q * n_cols, n_cols, paths + (uint64_t)q * path_len * 4, path_len, idx[q], cap) ? 1u : 0u;
+}
+
+// ---- the FRI transcript (include/tmx.h "transcript"): a Poseidon duplex modelled on plonky2's Challenger ---------------------------------
+// The buffers are indexed by selects over unrolled loops (no dynamic register indexing: the whole duplex stays in VGPRs).
+struct FriChal {
+  uint64_t st[12], in[8], out[8];
+  uint32_t n_in, n_out;
+};
+__device__ __forceinline__ void chal_init(FriChal& c) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) c.st[k] = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) c.in[k] = c.out[k] = 0;
+  c.n_in = c.n_out = 0;
+}
+template <int MODE>
+__device__ __forceinline__ void chal_duplex(FriChal& c, const PosConsts& K) {
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++)
+    if (k < c.n_in) c.st[k] = c.in[k];
+  c.n_in = 0;
+  pos_permute<MODE>(c.st, K);
+#pragma unroll
+  for (int k = 0; k < 12; k++) c.st[k] = gl_canon(c.st[k]);
+#pragma unroll
+  for (int k = 0; k < 8; k++) c.out[k] = c.st[k];
+  c.n_out = 8;
+}
+template <int MODE>
+__device__ __forceinline__ void chal_observe(FriChal& c, const PosConsts& K, uint64_t x) {
+  c.n_out = 0;
+  x = gl_canon(x);
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++)
+    if (k == c.n_in) c.in[k] = x;
+  if (++c.n_in == 8) chal_duplex<MODE>(c, K);
+}
+template <int MODE>
+__device__ __forceinline__ uint64_t chal_challenge(FriChal& c, const PosConsts& K) {
+  if (c.n_in || !c.n_out) chal_duplex<MODE>(c, K);
+  const uint32_t at = --c.n_out;
+  uint64_t x = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++)
+    if (k == at) x = c.out[k];
+  return x;
+}
+template <int MODE>
+__device__ void chal_observe_span(FriChal& c, const PosConsts& K, const uint64_t* __restrict__ p, uint64_t n) {
+  for (uint64_t k = 0; k < n; k++) chal_observe<MODE>(c, K, p[k]);
+}
+// the duplex between the prover's launches: st | in | out | n_in, n_out (32 u64)
+__device__ __forceinline__ void chal_load(FriChal& c, const uint64_t* __restrict__ m) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) c.st[k] = m[k];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { c.in[k] = m[12 + k]; c.out[k] = m[20 + k]; }
+  c.n_in = (uint32_t)m[28]; c.n_out = (uint32_t)m[29];
+}
+__device__ __forceinline__ void chal_store(const FriChal& c, uint64_t* __restrict__ m) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) m[k] = c.st[k];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { m[12 + k] = c.in[k]; m[20 + k] = c.out[k]; }
+  m[28] = c.n_in; m[29] = c.n_out;
+}
+template <int MODE>
+__device__ __forceinline__ void chal_start(FriChal& c, const PosConsts& K, const FriGeom& G, const uint64_t* __restrict__ commit_cap) {
+  chal_init(c);
+  for (int k = 0; k < 7; k++) chal_observe<MODE>(c, K, G.params[k]);
+  chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
+}
+
+// One lane, between the prover's stages (fri.h launch_fri_transcript): the parameters and the commit cap -> alpha (phase 0), the cap of
+// `layer` -> beta_layer (phase 1), the final coefficients -> the query indices and every layer's leaf indices (phase 2).
+template <int MODE>
+__global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
+                                                       const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
+                                                       uint64_t* __restrict__ chal, uint64_t* __restrict__ qidx) {
+  if (threadIdx.x) return;
+  const PosConsts K = pos_consts(consts);
+  FriChal c;
+  if (phase == 0) {
+    chal_start<MODE>(c, K, G, commit_cap);
+    chal[0] = chal_challenge<MODE>(c, K);
+    chal[1] = chal_challenge<MODE>(c, K);
+  } else if (phase == 1) {
+    chal_load(c, state);
+    chal_observe_span<MODE>(c, K, proof + G.off_caps[layer], 4ull << G.cap_h[layer]);
+    chal[2 + 2 * layer] = chal_challenge<MODE>(c, K);
+    chal[3 + 2 * layer] = chal_challenge<MODE>(c, K);
+  } else {
+    chal_load(c, state);
+    chal_observe_span<MODE>(c, K, proof + G.off_final, 2ull << G.final_log);
+    const uint64_t mask = (1ull << G.log_n) - 1;
+    for (uint32_t q = 0; q < G.n_queries; q++) {
+      uint64_t i = chal_challenge<MODE>(c, K) & mask;
+      proof[G.off_indices + q] = i;
+      uint32_t lg = G.log_n;
+      for (uint32_t l = 0; l < G.n_layers; l++) {
+        lg -= G.bits[l];
+        i &= (1ull << lg) - 1;
+        qidx[(uint64_t)l * G.n_queries + q] = i;
+      }
+    }
+  }
+  chal_store(c, state);
+}
+
+template <int B>
+__device__ __forceinline__ gl2 fri_fold_row(const uint64_t* __restrict__ row, uint64_t xinv0, uint64_t g, gl2 beta) {
+  gl2 v[1 << B];
+#pragma unroll
+  for (int j = 0; j < (1 << B); j++) v[j] = {gl_canon(row[j]), gl_canon(row[(1 << B) + j])};
+  return fri_fold_leaf<B>(v, xinv0, g, beta);
+}
+
+// The verifier: one workgroup, lane 0 re-derives the transcript from the proof and the caller's commit cap (alpha, every beta_l, the
+// expected indices), then one thread per query walks its openings (include/tmx.h "query q").  Latency-bound like k_merkle_verify.
+template <int MODE>
+__global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* __restrict__ consts, FriGeom G, const uint64_t* __restrict__ cap,
+                                                                const uint64_t* __restrict__ proof, uint32_t* __restrict__ ok) {
+  __shared__ uint64_t s_chal[2 + 2 * FRI_MAX_LAYERS], s_idx[FRI_MAX_QUERIES];
+  const PosConsts K = pos_consts(consts);
+  if (threadIdx.x == 0) {
+    FriChal c;
+    chal_start<MODE>(c, K, G, cap);
+    s_chal[0] = chal_challenge<MODE>(c, K);
+    s_chal[1] = chal_challenge<MODE>(c, K);
+    for (uint32_t l = 0; l < G.n_layers; l++) {
+      chal_observe_span<MODE>(c, K, proof + G.off_caps[l], 4ull << G.cap_h[l]);
+      s_chal[2 + 2 * l] = chal_challenge<MODE>(c, K);
+      s_chal[3 + 2 * l] = chal_challenge<MODE>(c, K);
+    }
+    chal_observe_span<MODE>(c, K, proof + G.off_final, 2ull << G.final_log);
+    for (uint32_t q = 0; q < G.n_queries; q++) s_idx[q] = chal_challenge<MODE>(c, K) & ((1ull << G.log_n) - 1);
+  }
+  __syncthreads();
+  const uint32_t q = threadIdx.x;
+  if (q >= G.n_queries) return;
+  uint64_t i = s_idx[q];
+  bool good = proof[G.off_indices + q] == i;
+  const uint32_t pl0 = G.log_n - G.cap_height;
+  const uint64_t* row = proof + G.off_init_rows + (uint64_t)q * G.n_cols;
+  good = merkle_leads_to_cap<MODE>(K, row, G.n_cols, proof + G.off_init_paths + (uint64_t)q * pl0 * 4, pl0, i, cap) && good;
+  const gl2 alpha = {s_chal[0], s_chal[1]};
+  gl2 v = {0, 0}, ap = {1, 0};
+  for (uint32_t c = 0; c < G.n_cols; c++) {
+    v = gl2_add(v, gl2_scale(ap, gl_canon(row[c])));
+    ap = gl2_mul(ap, alpha);
+  }
+  uint32_t lg = G.log_n;
+  for (uint32_t l = 0; l < G.n_layers; l++) {
+    const uint32_t b = G.bits[l], a = 1u << b, lgn = lg - b, pl = lgn - G.cap_h[l];
+    const uint64_t r = i & ((1ull << lgn) - 1), j = i >> lgn;
+    const uint64_t* lr = proof + G.off_rows[l] + (uint64_t)q * 2 * a;
+    good = good && gl_canon(lr[j]) == v.c0 && gl_canon(lr[a + j]) == v.c1;
+    good = merkle_leads_to_cap<MODE>(K, lr, 2 * a, proof + G.off_paths[l] + (uint64_t)q * pl * 4, pl, r, proof + G.off_caps[l]) && good;
+    const uint64_t xinv0 = gl_mul(G.s_inv[l], gl_pow(G.w_inv[l], r));
+    const gl2 beta = {s_chal[2 + 2 * l], s_chal[3 + 2 * l]};
+    switch (b) {
+      case 1: v = fri_fold_row<1>(lr, xinv0, G.g[l], beta); break;
+      case 2: v = fri_fold_row<2>(lr, xinv0, G.g[l], beta); break;
+      case 3: v = fri_fold_row<3>(lr, xinv0, G.g[l], beta); break;
+      default: v = fri_fold_row<4>(lr, xinv0, G.g[l], beta); break;
+    }
+    i = r;
+    lg = lgn;
+  }
+  const uint64_t x = gl_mul(G.s_fin, gl_pow(G.w_fin, i));
+  const uint64_t* coef = proof + G.off_final;
+  gl2 e = {0, 0};
+  for (int k = (1 << G.final_log) - 1; k >= 0; k--) e = gl2_add(gl2_scale(e, x), {gl_canon(coef[2 * k]), gl_canon(coef[2 * k + 1])});
+  ok[q] = (good && gl2_eq(e, v)) ? 1u : 0u;
 }
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -378,6 +557,36 @@ int launch_merkle_verify(const void* d_consts, int mode, uint32_t n_cols, uint32
     hipLaunchKernelGGL(k_merkle_verify<POS_MODE_SMALL>, grid, dim3(64), 0, S_(stream), K, n_cols, path_len, n_queries, cap, idx, rows, paths, ok);
   else
     hipLaunchKernelGGL(k_merkle_verify<POS_MODE_GENERAL>, grid, dim3(64), 0, S_(stream), K, n_cols, path_len, n_queries, cap, idx, rows, paths, ok);
+  return (int)hipGetLastError();
+}
+
+template <int MODE>
+static void fri_transcript_launch(const uint64_t* K, const FriGeom& G, int phase, uint32_t layer, const uint64_t* commit_cap, uint64_t* proof,
+                                  uint64_t* state, uint64_t* chal, uint64_t* qidx, hipStream_t s) {
+  hipLaunchKernelGGL(k_fri_transcript<MODE>, dim3(1), dim3(64), 0, s, K, G, phase, layer, commit_cap, proof, state, chal, qidx);
+}
+int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
+                          void* d_state, void* d_chal, void* d_qidx, void* stream) {
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* cap = reinterpret_cast<const uint64_t*>(d_commit_cap);
+  uint64_t* proof = reinterpret_cast<uint64_t*>(d_proof);
+  uint64_t* st = reinterpret_cast<uint64_t*>(d_state);
+  uint64_t* ch = reinterpret_cast<uint64_t*>(d_chal);
+  uint64_t* qi = reinterpret_cast<uint64_t*>(d_qidx);
+  if (mode == POS_MODE_MERGE3) fri_transcript_launch<POS_MODE_MERGE3>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
+  else if (mode == POS_MODE_SMALL) fri_transcript_launch<POS_MODE_SMALL>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
+  else fri_transcript_launch<POS_MODE_GENERAL>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
+  return (int)hipGetLastError();
+}
+int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, void* d_ok, void* stream) {
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* cap = reinterpret_cast<const uint64_t*>(d_cap);
+  const uint64_t* proof = reinterpret_cast<const uint64_t*>(d_proof);
+  uint32_t* ok = reinterpret_cast<uint32_t*>(d_ok);
+  const dim3 grid(1), block(FRI_MAX_QUERIES);
+  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL(k_fri_verify<POS_MODE_MERGE3>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
+  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL(k_fri_verify<POS_MODE_SMALL>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
+  else hipLaunchKernelGGL(k_fri_verify<POS_MODE_GENERAL>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
   return (int)hipGetLastError();
 }
 
