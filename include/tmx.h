@@ -677,6 +677,48 @@ int32_t tmx_fri_verify_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint6
 int32_t tmx_fri_last_degree_ok(tmx_ctx* ctx);                  /* blocks; 1 / 0 for the last prove, TMX_ERR_BAD_ARG if none */
 int32_t tmx_fri_last_ms(tmx_ctx* ctx, float ms[4]);
 
+/* ---- out-of-domain openings (DEEP-FRI): the committed columns opened at a point the transcript picks, and at the next row.  The FRI proof
+ * above then runs over the DEEP quotients instead of the raw columns, so the commitment serves as a polynomial commitment.  Same field,
+ * extension, parameters, validation (plus n_cols <= 2^24), transcript duplex and caveats as the FRI block (parity unpinned against plonky2).
+ * Notation: M = 2^log_n, B = 2^log_blowup, N = M / B; D_0 = { s w^i } the NTT domain as for FRI; omega_N = w^B generates the trace domain.
+ *   points     the transcript observes the seven parameters as FRI does, then the word 2 (the number of points: a FRI transcript and a DEEP
+ *              transcript never coincide), then the commit cap; it draws zeta = (challenge(), challenge()), again while zeta.c1 == 0, so zeta
+ *              is not in F_p.  z_0 = zeta, z_1 = zeta omega_N: neither lies in F_p, so no x - z_k is zero on D_0.
+ *   openings   y_(c,k) = the value at z_k of the unique polynomial of degree < N that agrees with column c (words mod p) on the points
+ *              x_(jB) = s omega_N^j (j < N) of D_0.  For an honest LDE that is f_c(z_k); the definition holds for any input.
+ *   digest     the openings section is planar with R = 2^ceil(log2 n_cols) rows per plane: y_(.,0).c0, y_(.,0).c1, y_(.,1).c0, y_(.,1).c1, rows
+ *              n_cols and above zero.  That buffer IS the column-major 4-column matrix tmx_poseidon_merkle_device(log2 R, 4, cap_height 0)
+ *              hashes (each 4-word row its own leaf); the transcript observes its root (4 words) and draws alpha.
+ *   after      everything is the FRI above (layers, betas, final coefficients, query indices: the same draws in the same order), with layer 0
+ *              f_0(x_i) = (F(x_i) - Y_0) / (x_i - z_0) + alpha^n_cols (F(x_i) - Y_1) / (x_i - z_1), F(x_i) = sum_c alpha^c col_c[i] and
+ *              Y_k = sum_c alpha^c y_(c,k): degree < N - 1 for honest columns; schedule, layers and degree flag as for FRI.
+ *   proof      the openings section (tmx_deep_openings_words(n_cols) = 4 R words), then a FRI proof laid out exactly as tmx_fri_layout_of
+ *              gives it, every offset shifted by 4 R.
+ *   verifier   every query is rejected if a padding word of the openings section is non-zero; opening words are taken mod p (the leaves hash
+ *              canonically: y + p verifies as y); per query v_0 is the layer-0 formula at x_idx from the opened row and the Y_k the
+ *              verifier forms from the openings; every other check is FRI's.  A changed opening changes the root, hence alpha, the betas
+ *              and the indices: every query is rejected.
+ *   tmx_deep_openings_words       host only: 4 R, or 0 if n_cols is 0 or above 2^24.
+ *   tmx_deep_prove_device         a proof over caller columns d_cols (extended: the openings read the strided subset x_(jB)) and their d_levels,
+ *                                 under the context's CURRENT NTT domain.
+ *   tmx_trace_commit_deep_device  a proof over the context's last commit, under the rules of tmx_trace_commit_fri_device (matching parameters;
+ *                                 TMX_ERR_BAD_ARG with no commit).  The openings read the commit's pre-LDE columns (1/B of the bytes, the same
+ *                                 openings bit for bit); the commit's scratch is left untouched.
+ *   tmx_deep_verify_device        d_ok[q] as tmx_fri_verify_device: enqueues the openings tree into a verifier scratch of the context, then the
+ *                                 verifier.  Verifies of one context are ordered on one stream, as proves are.
+ *   tmx_deep_last_zeta            blocks, then zeta of the last prove; TMX_ERR_BAD_ARG if there was none or it was a plain FRI prove.
+ * tmx_fri_last_degree_ok and tmx_fri_last_ms report on DEEP proves too; ms[0] ("combine") then covers everything before the first layer:
+ * transcript start, evaluation, openings tree, combine and quotient.  Asynchronous, no host synchronisation and no device-to-host copy
+ * inside; validation before anything is enqueued (TMX_ERR_BAD_ARG: nothing written). */
+#define TMX_DEEP_MAX_COLS (1u << 24)
+uint64_t tmx_deep_openings_words(uint32_t n_cols);
+int32_t tmx_deep_prove_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof,
+                              void* hip_stream);
+int32_t tmx_trace_commit_deep_device(tmx_ctx* ctx, const tmx_fri_params* p, uint64_t* d_proof, void* hip_stream);
+int32_t tmx_deep_verify_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok,
+                               void* hip_stream);
+int32_t tmx_deep_last_zeta(tmx_ctx* ctx, uint64_t z[2]);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

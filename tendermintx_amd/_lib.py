@@ -258,6 +258,12 @@ def lib():
         L.tmx_fri_verify_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_fri_last_degree_ok.argtypes = [C.c_void_p]
         L.tmx_fri_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.tmx_deep_openings_words.argtypes = [C.c_uint32]
+        L.tmx_deep_openings_words.restype = C.c_uint64
+        L.tmx_deep_prove_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_deep_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p]
+        L.tmx_deep_verify_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_deep_last_zeta.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

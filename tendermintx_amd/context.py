@@ -326,6 +326,26 @@ class Context:
         check(self._L.tmx_fri_last_ms(self._h, ms), self._h)
         return {"combine": ms[0], "layers": ms[1], "final": ms[2], "openings": ms[3]}
 
+    # ---- out-of-domain openings (DEEP-FRI; include/tmx.h "out-of-domain openings"): the same params as the FRI calls; a proof is
+    # deep_proof_words(params) words: the openings section, then the FRI part
+    def deep_prove_device(self, params, d_cols, d_levels, d_proof, stream=None):
+        """a DEEP proof over caller columns (extended, with their tree) into d_proof"""
+        check(self._L.tmx_deep_prove_device(self._h, C.byref(self._fri_params(params)), d_cols, d_levels, d_proof, self._stream(stream)), self._h)
+
+    def trace_commit_deep_device(self, params, d_proof, stream=None):
+        """a DEEP proof over the most recent trace_commit_device (same stream, after it); the parameters must match that commit"""
+        check(self._L.tmx_trace_commit_deep_device(self._h, C.byref(self._fri_params(params)), d_proof, self._stream(stream)), self._h)
+
+    def deep_verify_device(self, params, d_cap, d_proof, d_ok, stream=None):
+        """d_ok[n_queries] u32: 1 where the query of the DEEP proof checks against the commit cap d_cap"""
+        check(self._L.tmx_deep_verify_device(self._h, C.byref(self._fri_params(params)), d_cap, d_proof, d_ok, self._stream(stream)), self._h)
+
+    def deep_last_zeta(self):
+        """(blocks) zeta of the last DEEP prove as (c0, c1); TmxError if the last prove was a plain FRI prove or there was none"""
+        z = (C.c_uint64 * 2)()
+        check(self._L.tmx_deep_last_zeta(self._h, z), self._h)
+        return int(z[0]), int(z[1])
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -415,3 +435,20 @@ def fri_layout(params, L=None):
     return {"n_layers": n, "final_log": out.final_log, "layer_bits": list(out.layer_bits[:n]), "layer_cap_height": list(out.layer_cap_height[:n]),
             "off_caps": list(out.off_caps[:n]), "off_final": out.off_final, "off_indices": out.off_indices, "off_init_rows": out.off_init_rows,
             "off_init_paths": out.off_init_paths, "off_rows": list(out.off_rows[:n]), "off_paths": list(out.off_paths[:n]), "words": out.words}
+
+
+def deep_openings_words(n_cols, L=None):
+    """tmx_deep_openings_words: 4 R words (R = n_cols rounded up to a power of two), 0 for n_cols 0 or above 2^24"""
+    L = L or _lib.lib()
+    return int(L.tmx_deep_openings_words(int(n_cols)))
+
+
+def deep_proof_words(params, L=None):
+    """the words of a DEEP proof: the openings section, then the FRI proof of the same parameters; TmxError on parameters the DEEP calls
+    refuse (FRI's rules and n_cols <= 2^24)"""
+    p = Context._fri_params(params)
+    fri_words = fri_layout(p, L)["words"]
+    open_words = deep_openings_words(p.n_cols, L)
+    if not open_words:
+        raise _lib.TmxError(-1, "n_cols must be at most 2^24 for a DEEP proof")
+    return open_words + fri_words

@@ -408,6 +408,10 @@ struct tmx_ctx {
   size_t fri_bytes = 0, fri_flag_off = 0;
   hipEvent_t ev_fri[5] = {};
   bool fri_valid = false;
+  bool fri_deep = false;  // the last prove was a DEEP prove (its zeta sits in d_fri: tmx_deep_last_zeta)
+  // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
+  void* d_deepv = nullptr;
+  size_t deepv_bytes = 0;
   // staging of the host query indices of the opening / verifying calls: a ring of page-locked + device buffers, each slot reused only once
   // the event behind the launch that read it has completed
   struct IdxSlot { uint64_t* h = nullptr; uint64_t* d = nullptr; uint64_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
@@ -1390,6 +1394,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   for (hipEvent_t e : c->ev_fri)
     if (e) (void)hipEventDestroy(e);
   if (c->d_fri) (void)hipFree(c->d_fri);
+  if (c->d_deepv) (void)hipFree(c->d_deepv);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
     if (sl.d) (void)hipFree(sl.d);
@@ -3178,6 +3183,7 @@ static FriGeom fri_geom(const tmx_fri_params& p, const tmx_fri_layout& L, uint64
   G.log_n = p.log_n; G.n_cols = p.n_cols; G.cap_height = p.cap_height; G.n_queries = p.n_queries;
   G.n_layers = L.n_layers; G.final_log = L.final_log;
   uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - p.log_n));
+  G.s0 = s; G.w0 = w; G.omega_n = gl_pow_host(w, 1ull << p.log_blowup);
   uint32_t lg = p.log_n;
   for (uint32_t l = 0; l < L.n_layers; l++) {
     lg -= L.layer_bits[l];
@@ -3191,13 +3197,33 @@ static FriGeom fri_geom(const tmx_fri_params& p, const tmx_fri_layout& L, uint64
   return G;
 }
 
+// The columns a DEEP prove evaluates at zeta and zeta omega_N: N = 2^(log_n - log_blowup) words per column, word j of column c at
+// cols[(c << log_col) + (j << stride_log)], on the coset s <omega_N>.  The extended columns themselves (stride B, s = the domain's shift)
+// or the commit's pre-LDE columns (stride 1, s = 1).
+struct DeepSrc { const uint64_t* cols; uint32_t log_col, stride_log; uint64_t s; };
+
+static uint32_t deep_log_r(uint32_t n_cols) {
+  uint32_t lr = 0;
+  while ((1ull << lr) < n_cols) lr++;
+  return lr;
+}
+
 // cols / levels: the committed columns and their tree; (root_2_32, shift): the domain they were extended on.  Validated by the caller.
+// deep: null for a plain FRI prove; else the DEEP prove: the openings section first, then the FRI proof of the DEEP quotients.  Everything
+// after layer 0 is the same for both.
 static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* cols, const uint64_t* levels, uint64_t root_2_32, uint64_t shift,
-                         uint64_t* proof, void* hip_stream) {
+                         uint64_t* proof, void* hip_stream, const DeepSrc* deep = nullptr) {
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   tmx_fri_layout L;
   fri_layout(p, L);
-  const FriGeom G = fri_geom(p, L, root_2_32, shift);
+  FriGeom G = fri_geom(p, L, root_2_32, shift);
+  const uint32_t log_r = deep ? deep_log_r(p.n_cols) : 0, log_sub = p.log_n - p.log_blowup;
+  uint64_t* open = proof;
+  if (deep) {
+    G.deep = 1;
+    G.log_r = log_r;
+    proof += 4ull << log_r;  // (the FRI part: every offset of the layout shifted by the openings section)
+  }
   HIPCK(c, hipSetDevice(c->cfg.device));
   int32_t st = poseidon_ready(c, s);
   if (st) return st;
@@ -3217,6 +3243,14 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
     lg -= L.layer_bits[l];
     o_lev[l] = at; at += 4 * tmx_poseidon_merkle_digests(lg, L.layer_cap_height[l]);
   }
+  // DEEP: weights [N][2] | partial sums [tiles][n_cols][4] | openings tree | Y_0, Y_1, alpha^n
+  uint64_t o_wt = 0, o_part = 0, o_olev = 0, o_y = 0;
+  if (deep) {
+    o_wt = at; at += 2ull << log_sub;
+    o_part = at; at += deep_eval_tiles(log_sub) * p.n_cols * 4;
+    o_olev = at; at += 4 * tmx_poseidon_merkle_digests(log_r, 0);
+    o_y = at; at += 8;
+  }
   if (c->fri_bytes < at * 8) {
     if (c->d_fri) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_fri)); c->d_fri = nullptr; c->fri_bytes = 0; }
     HIPCK(c, hipMalloc(&c->d_fri, at * 8));
@@ -3225,6 +3259,7 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
   for (auto& e : c->ev_fri)
     if (!e) HIPCK(c, hipEventCreate(&e));
   c->fri_valid = false;
+  c->fri_deep = deep != nullptr;
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_fri);
   uint64_t *state = W, *chal = W + 32, *apow = W + o_apow, *qidx = W + o_qidx;
   c->fri_flag_off = 96 * 8;
@@ -3232,9 +3267,28 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
   auto launched = [&](int rc, const char* what) { return rc ? fail(c, TMX_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc)) : TMX_OK; };
 
   HIPCK(c, hipEventRecord(c->ev_fri[0], s));
-  if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 0, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
-  if ((st = launched(launch_fri_alpha_powers(p.n_cols, chal, apow, s), "k_fri_alpha_powers"))) return st;
-  if ((st = launched(launch_fri_combine(p.log_n, p.n_cols, cols, apow, W + o_layer[0], s), "k_fri_combine"))) return st;
+  if (!deep) {
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 0, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+    if ((st = launched(launch_fri_alpha_powers(p.n_cols, chal, apow, s), "k_fri_alpha_powers"))) return st;
+    if ((st = launched(launch_fri_combine(p.log_n, p.n_cols, cols, apow, W + o_layer[0], s), "k_fri_combine"))) return st;
+  } else {
+    // zeta; the openings (weights, the pass over the columns, the tiles added into the proof's planes); their root -> alpha; layer 0 as
+    // for FRI, then rewritten into the DEEP quotient
+    const uint64_t P = 0xffffffff00000001ull, s_n = gl_pow_host(deep->s, 1ull << log_sub);
+    const uint64_t k_inv = gl_pow_host((uint64_t)(((unsigned __int128)(1ull << log_sub) * s_n) % P), P - 2);
+    const uint64_t* zeta = chal + FRI_ZETA_AT;
+    const uint64_t* root = W + o_olev + 4 * (tmx_poseidon_merkle_digests(log_r, 0) - 1);
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 3, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+    if ((st = launched(launch_deep_weights(log_sub, deep->s, G.omega_n, s_n, k_inv, zeta, W + o_wt, s), "k_deep_weights"))) return st;
+    if ((st = launched(launch_deep_eval(log_sub, deep->log_col, deep->stride_log, p.n_cols, deep->cols, W + o_wt, W + o_part, s), "k_deep_eval"))) return st;
+    if ((st = launched(launch_deep_open(log_sub, p.n_cols, log_r, W + o_part, open, s), "k_deep_open"))) return st;
+    if ((st = tmx_poseidon_merkle_device(c, log_r, 4, open, 0, W + o_olev, hip_stream))) return st;
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 4, 0, root, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+    if ((st = launched(launch_fri_alpha_powers(p.n_cols, chal, apow, s), "k_fri_alpha_powers"))) return st;
+    if ((st = launched(launch_fri_combine(p.log_n, p.n_cols, cols, apow, W + o_layer[0], s), "k_fri_combine"))) return st;
+    if ((st = launched(launch_deep_y(p.n_cols, log_r, open, apow, chal, W + o_y, s), "k_deep_y"))) return st;
+    if ((st = launched(launch_deep_quotient(p.log_n, G.s0, G.w0, G.omega_n, zeta, W + o_y, W + o_layer[0], s), "k_deep_quotient"))) return st;
+  }
   HIPCK(c, hipEventRecord(c->ev_fri[1], s));
   lg = p.log_n;
   for (uint32_t l = 0; l < L.n_layers; l++) {
@@ -3313,7 +3367,7 @@ int32_t tmx_fri_verify_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_
   if (st) return st;
   tmx_fri_layout L;
   fri_layout(*p, L);
-  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, fri_geom(*p, L, c->ntt_root, c->ntt_shift), d_cap, d_proof, d_ok, s);
+  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, fri_geom(*p, L, c->ntt_root, c->ntt_shift), d_cap, d_proof, nullptr, nullptr, d_ok, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
   return TMX_OK;
 }
@@ -3333,6 +3387,83 @@ int32_t tmx_fri_last_ms(tmx_ctx* c, float ms[4]) {
   if (!c->fri_valid) return fail(c, TMX_ERR_BAD_ARG, "no FRI prove has completed on this context");
   HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
   for (int k = 0; k < 4; k++) HIPCK(c, hipEventElapsedTime(&ms[k], c->ev_fri[k], c->ev_fri[k + 1]));
+  return TMX_OK;
+}
+
+// ---- DEEP: the committed columns opened at zeta and zeta omega_N (include/tmx.h "out-of-domain openings") --------------------------------
+uint64_t tmx_deep_openings_words(uint32_t n_cols) {
+  if (n_cols == 0 || n_cols > TMX_DEEP_MAX_COLS) return 0;
+  return 4ull << deep_log_r(n_cols);
+}
+
+static int32_t deep_check(tmx_ctx* c, const tmx_fri_params* p) {
+  int32_t st = fri_check(c, p);
+  if (st) return st;
+  if (p->n_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "n_cols must be at most 2^24 for a DEEP proof");
+  return TMX_OK;
+}
+
+int32_t tmx_deep_prove_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = deep_check(c, p);
+  if (st) return st;
+  if (!d_cols || !d_levels || !d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_levels and d_proof must be set");
+  const DeepSrc src = {d_cols, p->log_n, p->log_blowup, c->ntt_shift % 0xffffffff00000001ull};
+  return fri_prove(c, *p, d_cols, d_levels, c->ntt_root, c->ntt_shift, d_proof, hip_stream, &src);
+}
+
+int32_t tmx_trace_commit_deep_device(tmx_ctx* c, const tmx_fri_params* p, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = deep_check(c, p);
+  if (st) return st;
+  st = tmx_trace_commit_last_shape(c, nullptr, nullptr, nullptr);
+  if (st) return st;
+  const tmx_ctx::CommitRec r = c->last_commit;
+  if (p->log_n != r.log_m || p->n_cols != r.n_cols || p->cap_height != r.cap_height || p->log_blowup != r.log_blowup)
+    return fail(c, TMX_ERR_BAD_ARG, "DEEP parameters do not match the last commit: log_n " + std::to_string(r.log_m) + ", n_cols " + std::to_string(r.n_cols) +
+                                        ", cap_height " + std::to_string(r.cap_height) + ", log_blowup " + std::to_string(r.log_blowup));
+  if (!d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_proof is null");
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_commit);
+  // the openings read the pre-LDE columns at offset 0 of the commit scratch (k_trace_to_columns: n_cols x N, on the subgroup itself)
+  const DeepSrc src = {reinterpret_cast<const uint64_t*>(base), r.log_m - r.log_blowup, 0, 1};
+  return fri_prove(c, *p, reinterpret_cast<const uint64_t*>(base + r.lde_off), reinterpret_cast<const uint64_t*>(base + r.lev_off), r.root, r.shift,
+                   d_proof, hip_stream, &src);
+}
+
+int32_t tmx_deep_verify_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = deep_check(c, p);
+  if (st) return st;
+  if (!d_cap || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_proof and d_ok must be set");
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  st = poseidon_ready(c, s);
+  if (st) return st;
+  const uint32_t log_r = deep_log_r(p->n_cols);
+  const uint64_t nd = tmx_poseidon_merkle_digests(log_r, 0);
+  if (c->deepv_bytes < nd * 32) {
+    if (c->d_deepv) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_deepv)); c->d_deepv = nullptr; c->deepv_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_deepv, nd * 32));
+    c->deepv_bytes = nd * 32;
+  }
+  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_deepv);
+  if ((st = tmx_poseidon_merkle_device(c, log_r, 4, d_proof, 0, lev, hip_stream))) return st;
+  tmx_fri_layout L;
+  fri_layout(*p, L);
+  FriGeom G = fri_geom(*p, L, c->ntt_root, c->ntt_shift);
+  G.deep = 1;
+  G.log_r = log_r;
+  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, G, d_cap, d_proof + (4ull << log_r), d_proof, lev + 4 * (nd - 1), d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_deep_last_zeta(tmx_ctx* c, uint64_t z[2]) {
+  if (!c || !z) return TMX_ERR_BAD_ARG;
+  if (!c->fri_valid || !c->fri_deep) return fail(c, TMX_ERR_BAD_ARG, "the last prove of this context was not a DEEP prove");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
+  HIPCK(c, hipMemcpy(z, reinterpret_cast<uint64_t*>(c->d_fri) + 32 + FRI_ZETA_AT, 16, hipMemcpyDeviceToHost));
   return TMX_OK;
 }
 

@@ -15,7 +15,14 @@ struct FriGeom {
   uint64_t s_inv[FRI_MAX_LAYERS], w_inv[FRI_MAX_LAYERS], g[FRI_MAX_LAYERS];
   uint64_t s_fin, w_fin, s_fin_inv, w_fin_inv, m_fin_inv;  // the last domain (D_L), its inverses, 1 / M_L
   uint64_t off_caps[FRI_MAX_LAYERS], off_final, off_indices, off_init_rows, off_init_paths, off_rows[FRI_MAX_LAYERS], off_paths[FRI_MAX_LAYERS];
+  // DEEP (include/tmx.h "out-of-domain openings"): deep = 1 for a DEEP transcript / verifier; log_r = log2 of the rows per openings plane;
+  // s0, w0: layer 0's domain D_0; omega_n = w0^B, the trace domain's generator (z_1 = zeta omega_n)
+  uint32_t deep, log_r;
+  uint64_t s0, w0, omega_n;
 };
+
+// where the DEEP scratch keeps zeta between launches: chal[FRI_ZETA_AT], chal[FRI_ZETA_AT + 1] (after alpha and the betas)
+constexpr uint32_t FRI_ZETA_AT = 2 + 2 * FRI_MAX_LAYERS + 2;
 
 // apow[c] = alpha^c (c < n_cols, pairs of u64), alpha at d_alpha
 int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, void* stream);
@@ -29,12 +36,30 @@ int launch_fri_fold(uint32_t log_m_next, uint32_t bits, uint64_t s_inv, uint64_t
 int launch_fri_final(uint32_t log_m, uint32_t final_log, uint64_t w_inv, uint64_t s_inv, uint64_t m_inv, const void* d_in, void* d_coef,
                      void* d_flag, void* stream);
 
+// DEEP, the openings of the columns at zeta and zeta omega_N (barycentric on the subset x_j = s omega_N^j, j < N = 2^log_sub).
+// wt[j] (interleaved c0, c1) = K x_j / (zeta - x_j), K = (zeta^N - s^N) k_inv with k_inv = 1 / (N s^N); zeta at d_zeta.
+int launch_deep_weights(uint32_t log_sub, uint64_t s, uint64_t omega_n, uint64_t s_n, uint64_t k_inv, const void* d_zeta, void* d_wt, void* stream);
+// The partial sums of sum_j v_j wt[j] and sum_j v_j wt[j - 1 mod N] of every column over row tiles: column c's word j is
+// cols[(c << log_col) + (j << stride_log)].  d_part[tiles][n_cols][4] (y0.c0, y0.c1, y1.c0, y1.c1), tiles = deep_eval_tiles(log_sub).
+uint64_t deep_eval_tiles(uint32_t log_sub);
+int launch_deep_eval(uint32_t log_sub, uint32_t log_col, uint32_t stride_log, uint32_t n_cols, const void* d_cols, const void* d_wt, void* d_part,
+                     void* stream);
+// The openings section (planar, 2^log_r rows per plane, zero padding) from the partial sums
+int launch_deep_open(uint32_t log_sub, uint32_t n_cols, uint32_t log_r, const void* d_part, void* d_open, void* stream);
+// Y_0, Y_1 = sum_c alpha^c y_(c,k) (apow: k_fri_alpha_powers' table) and alpha^n_cols into d_y[6], alpha at d_alpha
+int launch_deep_y(uint32_t n_cols, uint32_t log_r, const void* d_open, const void* d_apow, const void* d_alpha, void* d_y, void* stream);
+// layer 0 (planar, 2^log_m points of s w^i) in place: f_0 = (F - Y_0) / (x - z_0) + alpha^n (F - Y_1) / (x - z_1)
+int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const void* d_zeta, const void* d_y, void* d_layer, void* stream);
+
 // The single-lane transcript between the prover's stages (poseidon.hip).  d_state: the duplex state between launches (32 u64); d_chal:
 // alpha (2 u64) then beta_l (2 u64 each).  phase 0: parameters + commit cap -> alpha; phase 1: cap of `layer` (in the proof) -> beta_layer;
-// phase 2: final coefficients -> query indices into the proof and each layer's leaf indices into d_qidx[n_layers][n_queries].
+// phase 2: final coefficients -> query indices into the proof and each layer's leaf indices into d_qidx[n_layers][n_queries];
+// DEEP: phase 3: parameters, the word 2, commit cap -> zeta (chal[FRI_ZETA_AT]); phase 4: the openings root at d_commit_cap -> alpha.
 int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
                           void* d_state, void* d_chal, void* d_qidx, void* stream);
-// d_ok[q] for every query of the proof against d_cap (one workgroup)
-int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, void* d_ok, void* stream);
+// d_ok[q] for every query of the proof against d_cap (one workgroup).  G.deep: d_proof is the FRI part of a DEEP proof, d_open its
+// openings section and d_root the root of the openings tree; otherwise both are unused.
+int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, const void* d_open, const void* d_root,
+                      void* d_ok, void* stream);
 
 }  // namespace tmx

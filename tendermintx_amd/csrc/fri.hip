@@ -3,6 +3,7 @@
 // beside it in poseidon.hip.  Goldilocks words, F_p^2 = F_p[X] / (X^2 - 7) values (goldilocks_ext.hpp); no MFMA (nothing is a contraction).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "fri.h"
@@ -125,6 +126,130 @@ __global__ __launch_bounds__(FINAL_THREADS) void k_fri_final(uint32_t log_m, uin
   if (t == 0) flag[0] = nonzero ? 0u : 1u;
 }
 
+// ---- DEEP: the openings at zeta and zeta omega_N (include/tmx.h "out-of-domain openings") ----------------------------------------------
+// Barycentric weights on the subset x_j = s omega_N^j: one thread per j, one Fermat inversion in F_p^2 each.  K is folded in, so an opening is
+// the plain dot product of a column with the table (and with the table rotated by one for zeta omega_N).
+__global__ __launch_bounds__(256) void k_deep_weights(uint32_t log_sub, uint64_t s, uint64_t omega_n, uint64_t s_n, uint64_t k_inv,
+                                                      const uint64_t* __restrict__ zeta, uint64_t* __restrict__ wt) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >> log_sub) return;
+  const gl2 z = {zeta[0], zeta[1]};
+  gl2 zn = z;
+  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
+  const gl2 K = gl2_scale({gl_sub(zn.c0, s_n), zn.c1}, k_inv);
+  const uint64_t x = gl_mul(s, gl_pow(omega_n, j));
+  const gl2 w = gl2_mul(gl2_scale(gl2_inv({gl_sub(z.c0, x), z.c1}), x), K);
+  wt[2 * j] = w.c0;
+  wt[2 * j + 1] = w.c1;
+}
+
+// The hot pass: every word of the subset is read once.  A block is one wave and owns a row tile of 64 R rows (lane + 64 k, k < R: each load
+// is 64 consecutive rows of one column) and a chunk of columns.  The tile's weights sit in registers for the whole chunk -- w[j] and w[j - 1]
+// (the rotation that gives zeta omega_N), 4 words per row -- so the 0.5-MB table is read once per wave, not once per column.  Per column: R
+// loads in flight, 4 R reduced products (a base word times an F_p^2 weight, twice), lazy sums, then one butterfly reduction over the wave;
+// lane 0 writes the tile's four partial sums (k_deep_open adds the tiles).
+constexpr int DEEP_ROWS = 8;
+template <int R>
+__global__ __launch_bounds__(64) void k_deep_eval(uint32_t log_sub, uint32_t log_col, uint32_t stride_log, uint32_t n_cols, uint32_t cols_per_chunk,
+                                                  const uint64_t* __restrict__ cols, const uint64_t* __restrict__ wt, uint64_t* __restrict__ part) {
+  const uint32_t lane = threadIdx.x, tile = blockIdx.x;
+  const uint64_t N = 1ull << log_sub, mask = N - 1;
+  uint64_t w0[R][2], w1[R][2];
+  bool live[R];
+#pragma unroll
+  for (int k = 0; k < R; k++) {
+    const uint64_t j = ((uint64_t)tile * R + k) * 64 + lane;
+    live[k] = j < N;
+    const uint64_t jm = (j - 1) & mask;
+    w0[k][0] = live[k] ? wt[2 * j] : 0;
+    w0[k][1] = live[k] ? wt[2 * j + 1] : 0;
+    w1[k][0] = live[k] ? wt[2 * jm] : 0;
+    w1[k][1] = live[k] ? wt[2 * jm + 1] : 0;
+  }
+  const uint32_t c_lo = blockIdx.y * cols_per_chunk, c_hi = min(n_cols, c_lo + cols_per_chunk);
+  for (uint32_t c = c_lo; c < c_hi; c++) {
+    const uint64_t* p = cols + ((uint64_t)c << log_col);
+    uint64_t v[R];
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      const uint64_t j = ((uint64_t)tile * R + k) * 64 + lane;
+      v[k] = live[k] ? __builtin_nontemporal_load(p + (j << stride_log)) : 0;
+    }
+    uint64_t a[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      a[0] = gl_add_lazy(a[0], gl_mul(w0[k][0], v[k]));
+      a[1] = gl_add_lazy(a[1], gl_mul(w0[k][1], v[k]));
+      a[2] = gl_add_lazy(a[2], gl_mul(w1[k][0], v[k]));
+      a[3] = gl_add_lazy(a[3], gl_mul(w1[k][1], v[k]));
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1)
+#pragma unroll
+      for (int t = 0; t < 4; t++) a[t] = gl_add_lazy(a[t], gl_canon(__shfl_xor(a[t], off)));
+    if (lane == 0) {
+      uint64_t* o = part + ((uint64_t)tile * n_cols + c) * 4;
+#pragma unroll
+      for (int t = 0; t < 4; t++) o[t] = gl_canon(a[t]);
+    }
+  }
+}
+
+// One thread per row r of a plane: the tiles' partial sums of column r added, or zero at r >= n_cols.  Writes the four planes.
+__global__ __launch_bounds__(256) void k_deep_open(uint32_t tiles, uint32_t n_cols, uint32_t log_r, const uint64_t* __restrict__ part,
+                                                   uint64_t* __restrict__ open) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, Rr = 1ull << log_r;
+  if (r >= Rr) return;
+  uint64_t y[4] = {0, 0, 0, 0};
+  if (r < n_cols)
+    for (uint32_t t = 0; t < tiles; t++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) y[k] = gl_add(y[k], part[((uint64_t)t * n_cols + r) * 4 + k]);
+#pragma unroll
+  for (int k = 0; k < 4; k++) open[k * Rr + r] = y[k];
+}
+
+// One workgroup: Y_k = sum_c alpha^c y_(c,k) (opening words taken mod p), and alpha^n_cols.  y[6] = Y_0, Y_1, alpha^n.
+constexpr int DEEP_Y_THREADS = 256;
+__global__ __launch_bounds__(DEEP_Y_THREADS) void k_deep_y(uint32_t n_cols, uint32_t log_r, const uint64_t* __restrict__ open,
+                                                           const uint64_t* __restrict__ apow, const uint64_t* __restrict__ alpha, uint64_t* __restrict__ y) {
+  __shared__ uint64_t red[4][DEEP_Y_THREADS];
+  const uint32_t t = threadIdx.x;
+  const uint64_t Rr = 1ull << log_r;
+  gl2 s0 = {0, 0}, s1 = {0, 0};
+  for (uint32_t c = t; c < n_cols; c += DEEP_Y_THREADS) {
+    const gl2 a = {apow[2 * c], apow[2 * c + 1]};
+    s0 = gl2_add(s0, gl2_mul(a, {gl_canon(open[c]), gl_canon(open[Rr + c])}));
+    s1 = gl2_add(s1, gl2_mul(a, {gl_canon(open[2 * Rr + c]), gl_canon(open[3 * Rr + c])}));
+  }
+  red[0][t] = s0.c0; red[1][t] = s0.c1; red[2][t] = s1.c0; red[3][t] = s1.c1;
+  for (uint32_t h = DEEP_Y_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h)
+#pragma unroll
+      for (int k = 0; k < 4; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+  }
+  __syncthreads();
+  if (t == 0) {
+    const gl2 an = gl2_pow({alpha[0], alpha[1]}, n_cols);
+#pragma unroll
+    for (int k = 0; k < 4; k++) y[k] = red[k][0];
+    y[4] = an.c0;
+    y[5] = an.c1;
+  }
+}
+
+// One thread per point of D_0: layer 0 (k_fri_combine's output, canonical) rewritten in place into the DEEP quotient.
+__global__ __launch_bounds__(256) void k_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const uint64_t* __restrict__ zeta,
+                                                       const uint64_t* __restrict__ y, uint64_t* __restrict__ layer) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, M = 1ull << log_m;
+  if (i >= M) return;
+  const gl2 z0 = {zeta[0], zeta[1]}, z1 = gl2_scale(z0, omega_n);
+  const gl2 f = deep_layer0({layer[i], layer[M + i]}, gl_mul(s, gl_pow(w, i)), z0, z1, {y[0], y[1]}, {y[2], y[3]}, {y[4], y[5]});
+  layer[i] = f.c0;
+  layer[M + i] = f.c1;
+}
+
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, void* stream) {
@@ -158,6 +283,39 @@ int launch_fri_final(uint32_t log_m, uint32_t final_log, uint64_t w_inv, uint64_
   if (log_m > (uint32_t)FINAL_MAX_LOG || final_log > log_m) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_fri_final, dim3(1), dim3(FINAL_THREADS), 0, S_(stream), log_m, final_log, w_inv, s_inv, m_inv,
                      reinterpret_cast<const uint64_t*>(d_in), reinterpret_cast<uint64_t*>(d_coef), reinterpret_cast<uint32_t*>(d_flag));
+  return (int)hipGetLastError();
+}
+
+int launch_deep_weights(uint32_t log_sub, uint64_t s, uint64_t omega_n, uint64_t s_n, uint64_t k_inv, const void* d_zeta, void* d_wt, void* stream) {
+  hipLaunchKernelGGL(k_deep_weights, dim3((uint32_t)(((1ull << log_sub) + 255) / 256)), dim3(256), 0, S_(stream), log_sub, s, omega_n, s_n, k_inv,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_wt));
+  return (int)hipGetLastError();
+}
+uint64_t deep_eval_tiles(uint32_t log_sub) { return ((1ull << log_sub) + 64 * DEEP_ROWS - 1) / (64 * DEEP_ROWS); }
+int launch_deep_eval(uint32_t log_sub, uint32_t log_col, uint32_t stride_log, uint32_t n_cols, const void* d_cols, const void* d_wt, void* d_part,
+                     void* stream) {
+  // about 4096 waves in all (16 per CU): the columns are split into as many chunks as the row tiles leave room for
+  const uint64_t tiles = deep_eval_tiles(log_sub);
+  uint64_t chunks = std::min<uint64_t>(n_cols, std::max<uint64_t>(1, 4096 / tiles));
+  const uint32_t per = (uint32_t)((n_cols + chunks - 1) / chunks);
+  chunks = (n_cols + per - 1) / per;
+  hipLaunchKernelGGL(k_deep_eval<DEEP_ROWS>, dim3((uint32_t)tiles, (uint32_t)chunks), dim3(64), 0, S_(stream), log_sub, log_col, stride_log, n_cols, per,
+                     reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_wt), reinterpret_cast<uint64_t*>(d_part));
+  return (int)hipGetLastError();
+}
+int launch_deep_open(uint32_t log_sub, uint32_t n_cols, uint32_t log_r, const void* d_part, void* d_open, void* stream) {
+  hipLaunchKernelGGL(k_deep_open, dim3((uint32_t)(((1ull << log_r) + 255) / 256)), dim3(256), 0, S_(stream), (uint32_t)deep_eval_tiles(log_sub), n_cols,
+                     log_r, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<uint64_t*>(d_open));
+  return (int)hipGetLastError();
+}
+int launch_deep_y(uint32_t n_cols, uint32_t log_r, const void* d_open, const void* d_apow, const void* d_alpha, void* d_y, void* stream) {
+  hipLaunchKernelGGL(k_deep_y, dim3(1), dim3(DEEP_Y_THREADS), 0, S_(stream), n_cols, log_r, reinterpret_cast<const uint64_t*>(d_open),
+                     reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<const uint64_t*>(d_alpha), reinterpret_cast<uint64_t*>(d_y));
+  return (int)hipGetLastError();
+}
+int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const void* d_zeta, const void* d_y, void* d_layer, void* stream) {
+  hipLaunchKernelGGL(k_deep_quotient, dim3((uint32_t)(((1ull << log_m) + 255) / 256)), dim3(256), 0, S_(stream), log_m, s, w, omega_n,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_y), reinterpret_cast<uint64_t*>(d_layer));
   return (int)hipGetLastError();
 }
 

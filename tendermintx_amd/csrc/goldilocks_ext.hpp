@@ -25,6 +25,19 @@ __device__ __forceinline__ gl2 gl2_pow(gl2 b, uint64_t e) {
   }
   return r;
 }
+// a^-1 = conj(a) / norm(a), norm = a0^2 - 7 a1^2 in F_p: never zero for a != 0 (7 is not a square mod p); one Fermat chain
+__device__ __forceinline__ gl2 gl2_inv(gl2 a) {
+  const uint64_t n = gl_sub(gl_mul(a.c0, a.c0), gl_mul(gl_mul(a.c1, a.c1), 7));
+  const uint64_t ni = gl_pow(n, GL_P - 2);
+  return {gl_mul(a.c0, ni), gl_mul(gl_neg(a.c1), ni)};
+}
+// DEEP layer 0 at a point x of D_0 (include/tmx.h "out-of-domain openings"): (F - Y_0) / (x - z_0) + alpha^n (F - Y_1) / (x - z_1);
+// z_0, z_1 lie outside F_p, so x - z_k is never zero.  Shared by k_deep_quotient and the verifier.
+__device__ __forceinline__ gl2 deep_layer0(gl2 F, uint64_t x, gl2 z0, gl2 z1, gl2 Y0, gl2 Y1, gl2 alpha_n) {
+  const gl2 q0 = gl2_mul(gl2_sub(F, Y0), gl2_inv({gl_sub(x, z0.c0), gl_neg(z0.c1)}));
+  const gl2 q1 = gl2_mul(gl2_sub(F, Y1), gl2_inv({gl_sub(x, z1.c0), gl_neg(z1.c1)}));
+  return gl2_add(q0, gl2_mul(alpha_n, q1));
+}
 
 // One leaf of a FRI layer: v[j] = f(x_j) at the a = 2^B points x_j = s w^(r + j M'), M' = M / a, of a domain of M points (canonical values).
 // On return v[0] = f_next(x_0^a) after B radix-2 folds with beta, beta^2, ...: fold t pairs j with j + h (h = a >> (t + 1): x_(j + h) = -x_j)

@@ -374,9 +374,25 @@ __device__ __forceinline__ void chal_start(FriChal& c, const PosConsts& K, const
   for (int k = 0; k < 7; k++) chal_observe<MODE>(c, K, G.params[k]);
   chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
 }
+// DEEP: the same start with the word 2 (the number of opening points) between the parameters and the cap, then zeta = (challenge(),
+// challenge()), drawn again while zeta.c1 == 0 (zeta outside F_p)
+template <int MODE>
+__device__ __forceinline__ gl2 chal_start_deep(FriChal& c, const PosConsts& K, const FriGeom& G, const uint64_t* __restrict__ commit_cap) {
+  chal_init(c);
+  for (int k = 0; k < 7; k++) chal_observe<MODE>(c, K, G.params[k]);
+  chal_observe<MODE>(c, K, 2);
+  chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
+  gl2 z;
+  do {
+    z.c0 = chal_challenge<MODE>(c, K);
+    z.c1 = chal_challenge<MODE>(c, K);
+  } while (z.c1 == 0);
+  return z;
+}
 
 // One lane, between the prover's stages (fri.h launch_fri_transcript): the parameters and the commit cap -> alpha (phase 0), the cap of
-// `layer` -> beta_layer (phase 1), the final coefficients -> the query indices and every layer's leaf indices (phase 2).
+// `layer` -> beta_layer (phase 1), the final coefficients -> the query indices and every layer's leaf indices (phase 2).  DEEP: the start
+// with its point count and the commit cap -> zeta (phase 3), the openings root at commit_cap -> alpha (phase 4).
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
                                                        const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
@@ -386,6 +402,15 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
   FriChal c;
   if (phase == 0) {
     chal_start<MODE>(c, K, G, commit_cap);
+    chal[0] = chal_challenge<MODE>(c, K);
+    chal[1] = chal_challenge<MODE>(c, K);
+  } else if (phase == 3) {
+    const gl2 z = chal_start_deep<MODE>(c, K, G, commit_cap);
+    chal[FRI_ZETA_AT] = z.c0;
+    chal[FRI_ZETA_AT + 1] = z.c1;
+  } else if (phase == 4) {
+    chal_load(c, state);
+    chal_observe_span<MODE>(c, K, commit_cap, 4);
     chal[0] = chal_challenge<MODE>(c, K);
     chal[1] = chal_challenge<MODE>(c, K);
   } else if (phase == 1) {
@@ -421,14 +446,26 @@ __device__ __forceinline__ gl2 fri_fold_row(const uint64_t* __restrict__ row, ui
 
 // The verifier: one workgroup, lane 0 re-derives the transcript from the proof and the caller's commit cap (alpha, every beta_l, the
 // expected indices), then one thread per query walks its openings (include/tmx.h "query q").  Latency-bound like k_merkle_verify.
-template <int MODE>
+// DEEP: `proof` is the FRI part of a DEEP proof, `open` its openings section and `root` the root of the openings tree (enqueued before);
+// the transcript starts with zeta and the root, the whole workgroup forms Y_0, Y_1 from the openings and checks their padding, and a
+// query's v_0 is the DEEP layer 0 at its point instead of the plain combination.
+template <int MODE, bool DEEP>
 __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* __restrict__ consts, FriGeom G, const uint64_t* __restrict__ cap,
-                                                                const uint64_t* __restrict__ proof, uint32_t* __restrict__ ok) {
+                                                                const uint64_t* __restrict__ proof, const uint64_t* __restrict__ open,
+                                                                const uint64_t* __restrict__ root, uint32_t* __restrict__ ok) {
   __shared__ uint64_t s_chal[2 + 2 * FRI_MAX_LAYERS], s_idx[FRI_MAX_QUERIES];
+  __shared__ uint64_t s_deep[DEEP ? 4 : 1][DEEP ? FRI_MAX_QUERIES : 1], s_z[DEEP ? 4 : 1];
   const PosConsts K = pos_consts(consts);
   if (threadIdx.x == 0) {
     FriChal c;
-    chal_start<MODE>(c, K, G, cap);
+    if constexpr (DEEP) {
+      const gl2 z = chal_start_deep<MODE>(c, K, G, cap);
+      s_z[0] = z.c0;
+      s_z[1] = z.c1;
+      chal_observe_span<MODE>(c, K, root, 4);
+    } else {
+      chal_start<MODE>(c, K, G, cap);
+    }
     s_chal[0] = chal_challenge<MODE>(c, K);
     s_chal[1] = chal_challenge<MODE>(c, K);
     for (uint32_t l = 0; l < G.n_layers; l++) {
@@ -440,10 +477,38 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
     for (uint32_t q = 0; q < G.n_queries; q++) s_idx[q] = chal_challenge<MODE>(c, K) & ((1ull << G.log_n) - 1);
   }
   __syncthreads();
+  gl2 Y0 = {0, 0}, Y1 = {0, 0};
+  bool pad_ok = true;
+  if constexpr (DEEP) {
+    // every thread: its share of Y_k = sum_c alpha^c y_(c,k) (c = t mod the block), a tree sum in LDS; and the padding rows must be zero
+    const uint32_t t = threadIdx.x;
+    const uint64_t Rr = 1ull << G.log_r;
+    const gl2 alpha = {s_chal[0], s_chal[1]};
+    gl2 ap = gl2_pow(alpha, t);
+    const gl2 step = gl2_pow(alpha, FRI_MAX_QUERIES);
+    for (uint32_t c = t; c < G.n_cols; c += FRI_MAX_QUERIES) {
+      Y0 = gl2_add(Y0, gl2_mul(ap, {gl_canon(open[c]), gl_canon(open[Rr + c])}));
+      Y1 = gl2_add(Y1, gl2_mul(ap, {gl_canon(open[2 * Rr + c]), gl_canon(open[3 * Rr + c])}));
+      ap = gl2_mul(ap, step);
+    }
+    bool pad_bad = false;
+    for (uint64_t r = G.n_cols + t; r < Rr; r += FRI_MAX_QUERIES)
+      pad_bad = pad_bad || open[r] || open[Rr + r] || open[2 * Rr + r] || open[3 * Rr + r];
+    s_deep[0][t] = Y0.c0; s_deep[1][t] = Y0.c1; s_deep[2][t] = Y1.c0; s_deep[3][t] = Y1.c1;
+    pad_ok = !__syncthreads_or(pad_bad);
+    for (uint32_t h = FRI_MAX_QUERIES / 2; h; h >>= 1) {
+      if (t < h)
+#pragma unroll
+        for (int k = 0; k < 4; k++) s_deep[k][t] = gl_add(s_deep[k][t], s_deep[k][t + h]);
+      __syncthreads();
+    }
+    Y0 = {s_deep[0][0], s_deep[1][0]};
+    Y1 = {s_deep[2][0], s_deep[3][0]};
+  }
   const uint32_t q = threadIdx.x;
   if (q >= G.n_queries) return;
   uint64_t i = s_idx[q];
-  bool good = proof[G.off_indices + q] == i;
+  bool good = proof[G.off_indices + q] == i && pad_ok;
   const uint32_t pl0 = G.log_n - G.cap_height;
   const uint64_t* row = proof + G.off_init_rows + (uint64_t)q * G.n_cols;
   good = merkle_leads_to_cap<MODE>(K, row, G.n_cols, proof + G.off_init_paths + (uint64_t)q * pl0 * 4, pl0, i, cap) && good;
@@ -452,6 +517,10 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
   for (uint32_t c = 0; c < G.n_cols; c++) {
     v = gl2_add(v, gl2_scale(ap, gl_canon(row[c])));
     ap = gl2_mul(ap, alpha);
+  }
+  if constexpr (DEEP) {  // (ap = alpha^n_cols here)
+    const gl2 z0 = {s_z[0], s_z[1]};
+    v = deep_layer0(v, gl_mul(G.s0, gl_pow(G.w0, i)), z0, gl2_scale(z0, G.omega_n), Y0, Y1, ap);
   }
   uint32_t lg = G.log_n;
   for (uint32_t l = 0; l < G.n_layers; l++) {
@@ -578,15 +647,24 @@ int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int 
   else fri_transcript_launch<POS_MODE_GENERAL>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
   return (int)hipGetLastError();
 }
-int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, void* d_ok, void* stream) {
+template <bool DEEP>
+static void fri_verify_launch(const uint64_t* K, int mode, const FriGeom& G, const uint64_t* cap, const uint64_t* proof, const uint64_t* open,
+                              const uint64_t* root, uint32_t* ok, hipStream_t s) {
+  const dim3 grid(1), block(FRI_MAX_QUERIES);
+  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL((k_fri_verify<POS_MODE_MERGE3, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL((k_fri_verify<POS_MODE_SMALL, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+  else hipLaunchKernelGGL((k_fri_verify<POS_MODE_GENERAL, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+}
+int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, const void* d_open, const void* d_root,
+                      void* d_ok, void* stream) {
   const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
   const uint64_t* cap = reinterpret_cast<const uint64_t*>(d_cap);
   const uint64_t* proof = reinterpret_cast<const uint64_t*>(d_proof);
+  const uint64_t* open = reinterpret_cast<const uint64_t*>(d_open);
+  const uint64_t* root = reinterpret_cast<const uint64_t*>(d_root);
   uint32_t* ok = reinterpret_cast<uint32_t*>(d_ok);
-  const dim3 grid(1), block(FRI_MAX_QUERIES);
-  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL(k_fri_verify<POS_MODE_MERGE3>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
-  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL(k_fri_verify<POS_MODE_SMALL>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
-  else hipLaunchKernelGGL(k_fri_verify<POS_MODE_GENERAL>, grid, block, 0, S_(stream), K, G, cap, proof, ok);
+  if (G.deep) fri_verify_launch<true>(K, mode, G, cap, proof, open, root, ok, S_(stream));
+  else fri_verify_launch<false>(K, mode, G, cap, proof, open, root, ok, S_(stream));
   return (int)hipGetLastError();
 }
 
