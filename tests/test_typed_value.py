@@ -176,6 +176,82 @@ def test_oracle_value_expands_to_the_row(built_lib, oracle, cases):
         assert bytes(f.target_header if kind == 0 else f.next_header).hex() == c["header"]
 
 
+def _value_is_the_row(built_lib, oracle, kind, n, proof, target, trusted, chain_id, skip_max, what, prefix=False):
+    """one proof: the oracle's typed value (with the derived part) expands to the oracle's row, and both sinks report the same"""
+    from tendermintx_amd import _lib
+    row, rep = oracle.witness(kind, proof, target, trusted, chain_id, skip_max)
+    val, vrep = oracle.witness_value(kind, proof, target, trusted, chain_id, skip_max, True)
+    assert vrep == rep, what
+    lay = _lib.ValueLayout()
+    assert built_lib.tmx_value_layout_of(kind, n, _lib.SEC_ALL, C.byref(lay)) == 0 and lay.bytes == val.size
+    hint = int(built_lib.tmx_hint_elem_count(kind, n))
+    h = expand_hint(_lib, kind, n, val, lay)
+    if not (h.size == hint and np.array_equal(h, row[:hint])):
+        raise AssertionError(f"{what}: hint elements differ at {np.argwhere(h != row[:hint])[:8].ravel().tolist()} (of {hint})")
+    d = expand_derived(_lib, kind, n, val, lay)
+    if not np.array_equal(d, row[hint:]):
+        raise AssertionError(f"{what}: derived elements differ at {(hint + np.argwhere(d != row[hint:])[:8].ravel()).tolist()}")
+    f = (_lib.SkipInputsFixed if kind == 0 else _lib.StepInputsFixed).from_buffer_copy(bytes(val[:lay.fixed_bytes]))
+    assert f.report.as_dict() == rep, what                                  # the report the value carries is the one returned beside it
+    if prefix:
+        vh, _ = oracle.witness_value(kind, proof, target, trusted, chain_id, skip_max, False)
+        assert np.array_equal(vh, val[:vh.size]), what
+    return rep
+
+
+VALUE_CPU_SEEDS = int(os.environ.get("TMX_VALUE_CPU_SEEDS", "48"))
+
+
+def test_oracle_value_is_its_row_on_hostile_inputs(built_lib, oracle):
+    """The two sinks of the oracle (the typed value, the element row) agree on what the GPU tier feeds the HIP path: every proof of
+    TMX_VALUE_CPU_SEEDS mutated batches of test_fuzz_extended.py (random and extreme bytes, lengths, flags, powers, keys, signatures), then
+    hand-made lanes at the edges k_pack_value masks and repacks (value.hip: message_byte_length beside the 124 message bytes, the length
+    and flag bytes of a record word, u64 powers, the trusted record's length and flag bytes), every header field length at 0 / 79 / 80 / 255, and
+    nb = 1 / nb = N at N = 1, 3, 100.  A disagreement here would make the GPU tier's expected values wrong before any GPU run."""
+    import struct
+
+    from test_fuzz_extended import _mutated_batch
+    from tendermintx_amd.synth import Workload
+    checked = 0
+    for seed in range(VALUE_CPU_SEEDS):
+        kind, n, proofs, targets, trusteds, chain_id, skip_max = _mutated_batch(seed)
+        for p in range(len(proofs) // 2336):
+            _value_is_the_row(built_lib, oracle, kind, n, proofs[2336 * p:2336 * (p + 1)], targets[256 * n * p:256 * n * (p + 1)],
+                              trusteds[48 * n * p:48 * n * (p + 1)] if kind == 0 else None, chain_id, skip_max, f"seed {seed} proof {p}")
+            checked += 1
+    assert checked >= VALUE_CPU_SEEDS
+    # hand-made lanes: one edge per proof, on lane p % 7 of an N = 8 set of 7 validators (lane 7 is a dummy lane)
+    lane_edges = ([(220, struct.pack("<H", v)) for v in (0, 124, 125, 300, 65535)] + [(222, bytes([v])) for v in (0, 46, 47, 255)]
+                  + [(223, bytes([v])) for v in (0x00, 0x01, 0x02, 0xFE, 0xFF)] + [(224, struct.pack("<Q", v)) for v in (2**63 - 1, 2**63 + 5, 2**64 - 1)])
+    trusted_edges = ([(40, bytes([v])) for v in (0, 46, 47, 255)] + [(41, bytes([v])) for v in (0x00, 0x01, 0xFE, 0xFF)]
+                     + [(32, struct.pack("<Q", v)) for v in (2**63 - 1, 2**63 + 5, 2**64 - 1)])
+    header_edges = [(64 + hdr * 1136 + field, v) for hdr in range(2) for field in range(14) for v in (0, 79, 80, 255)]
+    n = 8
+    for kind in (0, 1):
+        edges = [("target", e) for e in lane_edges] + ([("trusted", e) for e in trusted_edges] if kind == 0 else []) + [("header", e) for e in header_edges]
+        wl = Workload(kind, n, len(edges), 7, chain_id=b"celestia", seed=909 + kind, signed_permille=1000, rounds=(0, 2))
+        for p, (where, (off, v)) in enumerate(edges):
+            proof, target = bytearray(wl.proofs[2336 * p:2336 * (p + 1)]), bytearray(wl.targets[256 * n * p:256 * n * (p + 1)])
+            trusted = bytearray(wl.trusteds[48 * n * p:48 * n * (p + 1)]) if kind == 0 else None
+            lane = p % 7
+            if where == "target":
+                target[256 * lane + off:256 * lane + off + len(v)] = v
+            elif where == "trusted":
+                trusted[48 * lane + off:48 * lane + off + len(v)] = v
+            else:
+                proof[off] = v
+            _value_is_the_row(built_lib, oracle, kind, n, bytes(proof), bytes(target), bytes(trusted) if kind == 0 else None, b"celestia", 100800,
+                              f"kind {kind} {where} byte {off} := {v if isinstance(v, int) else v.hex()}", prefix=True)
+    # the validator set at its smallest and its largest: nb = 1 and nb = N
+    for kind in (0, 1):
+        for N in (1, 3, 100):
+            for nb in sorted({1, N}):
+                wl = Workload(kind, N, 1, nb, chain_id=b"celestia", seed=31 + N + nb, signed_permille=1000, rounds=(1,))
+                rep = _value_is_the_row(built_lib, oracle, kind, N, wl.proofs, wl.targets, wl.trusteds if kind == 0 else None, b"celestia", 100800,
+                                        f"kind {kind} N {N} nb {nb}", prefix=True)
+                assert rep["all_ok"], (kind, N, nb)
+
+
 # ------------------------------------------------------------------------------------------------ GPU tier
 @pytest.fixture(scope="module")
 def tmx(built_lib):
