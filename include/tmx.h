@@ -719,6 +719,53 @@ int32_t tmx_deep_verify_device(tmx_ctx* ctx, const tmx_fri_params* p, const uint
                                void* hip_stream);
 int32_t tmx_deep_last_zeta(tmx_ctx* ctx, uint64_t z[2]);
 
+/* ---- proof of work (grinding): a variant of the FRI proof and of the DEEP proof above whose transcript ends with a nonce the prover has to
+ * search for, so that pow_bits bits of soundness come from one word of proof and one permutation of the verifier instead of from more
+ * queries.  The plain entry points, proof layouts and transcripts above are unchanged (tmx_fri_params.reserved stays refused when non-zero);
+ * the new parameter has a struct of its own.  Same field, duplex, caveats (parity unpinned against plonky2) as the blocks above.
+ *   parameters tmx_pow_params { fri, pow_bits, deep }: deep = 0 the FRI proof, 1 the DEEP proof.  Validation is that of the underlying proof
+ *              (FRI's rules; n_cols <= 2^24 when deep), plus 1 <= pow_bits <= TMX_POW_MAX_BITS (24) and deep <= 1: TMX_ERR_BAD_ARG, nothing
+ *              written, tmx_last_error says why, before anything is enqueued.  The bound 24 keeps the longest possible search short on a
+ *              shared device (see "bound").
+ *   transcript exactly the FRI (deep: the DEEP) transcript up to and including the final coefficients.  Then
+ *              1. observe(pow_bits): a proof made for one pow_bits does not verify under another, and no grinding transcript coincides with
+ *                 a plain one (which draws the indices right after the final coefficients);
+ *              2. the nonce is the SMALLEST n in 0, 1, 2, ... such that, on a copy of the duplex at this point, observe(n) followed by
+ *                 r = challenge() gives r < 2^(64 - pow_bits) (r is canonical: its top pow_bits bits are zero).  Whatever the input buffer
+ *                 holds after step 1, a candidate costs one permutation (if step 1 filled the buffer, that duplex happens once, before the
+ *                 search).  Smallest, not any: the proof is a function of its inputs;
+ *              3. the real transcript does observe(nonce), challenge() (the same r, consumed), and goes on with the query indices from the
+ *                 remaining output words, as the plain transcript does.
+ *   proof      the FRI (deep: the DEEP) proof laid out as above, then one more word, the nonce.  tmx_pow_proof_words gives the total:
+ *              tmx_fri_layout_of(...).words + 1, plus tmx_deep_openings_words(n_cols) when deep; 0 for parameters that do not validate.
+ *   verifier   as above, plus: every query is rejected if the nonce word is >= p, or if r has fewer than pow_bits leading zero bits.  A
+ *              changed nonce that still satisfies the condition changes the indices, so the index check rejects every query, as it does
+ *              for any other change of the transcript.
+ *   bound      the search gives up after 2^(pow_bits + 6) candidates (an honest search fails with probability about e^-64).  Then the nonce
+ *              word is written as 2^64 - 1 (which the verifier rejects), the rest of the proof is still written, and tmx_pow_last reports
+ *              it.  This makes the search's running time finite by construction: at most 2^30 permutations, under half a second at the
+ *              bulk Poseidon rate.  It cannot be reached with honest inputs, so no test reaches it.
+ *   tmx_pow_proof_words          host only.
+ *   tmx_pow_prove_device         a proof over caller columns, as tmx_fri_prove_device / tmx_deep_prove_device.
+ *   tmx_trace_commit_pow_device  a proof over the context's last commit, under the rules of tmx_trace_commit_fri_device.
+ *   tmx_pow_verify_device        d_ok[q] as tmx_fri_verify_device / tmx_deep_verify_device.
+ *   tmx_pow_last                 blocks like tmx_fri_last_degree_ok, then the nonce of the last prove and the number of candidates the search
+ *                                evaluated (either pointer may be null; the count depends on timing: rounds in flight finish).
+ *                                TMX_ERR_BAD_ARG if there was no prove or the last one was not a grinding prove; TMX_ERR_CAPACITY, with both
+ *                                values still written (nonce = 2^64 - 1), if the search gave up.
+ * tmx_fri_last_degree_ok, tmx_fri_last_ms and (deep) tmx_deep_last_zeta report on grinding proves too; the search's time is part of ms[2]
+ * ("final + transcript").  Prove and verify are asynchronous on hip_stream, no host synchronisation and no device-to-host copy inside: the
+ * search is one launch that ends itself. */
+#define TMX_POW_MAX_BITS 24
+typedef struct { tmx_fri_params fri; uint32_t pow_bits, deep; } tmx_pow_params;
+uint64_t tmx_pow_proof_words(const tmx_pow_params* pp);
+int32_t tmx_pow_prove_device(tmx_ctx* ctx, const tmx_pow_params* pp, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof,
+                             void* hip_stream);
+int32_t tmx_trace_commit_pow_device(tmx_ctx* ctx, const tmx_pow_params* pp, uint64_t* d_proof, void* hip_stream);
+int32_t tmx_pow_verify_device(tmx_ctx* ctx, const tmx_pow_params* pp, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok,
+                              void* hip_stream);
+int32_t tmx_pow_last(tmx_ctx* ctx, uint64_t* nonce, uint64_t* tried);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

@@ -141,6 +141,10 @@ class FriParams(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("log_n", "n_cols", "cap_height", "log_blowup", "arity_bits", "final_log_max", "n_queries", "reserved")]
 
 
+class PowParams(C.Structure):
+    _fields_ = [("fri", FriParams), ("pow_bits", C.c_uint32), ("deep", C.c_uint32)]
+
+
 class FriLayout(C.Structure):
     _fields_ = [("n_layers", C.c_uint32), ("final_log", C.c_uint32), ("layer_bits", C.c_uint32 * FRI_MAX_LAYERS),
                 ("layer_cap_height", C.c_uint32 * FRI_MAX_LAYERS), ("off_caps", C.c_uint64 * FRI_MAX_LAYERS), ("off_final", C.c_uint64),
@@ -264,6 +268,12 @@ def lib():
         L.tmx_trace_commit_deep_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p]
         L.tmx_deep_verify_device.argtypes = [C.c_void_p, C.POINTER(FriParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_deep_last_zeta.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.tmx_pow_proof_words.argtypes = [C.POINTER(PowParams)]
+        L.tmx_pow_proof_words.restype = C.c_uint64
+        L.tmx_pow_prove_device.argtypes = [C.c_void_p, C.POINTER(PowParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_pow_device.argtypes = [C.c_void_p, C.POINTER(PowParams), C.c_void_p, C.c_void_p]
+        L.tmx_pow_verify_device.argtypes = [C.c_void_p, C.POINTER(PowParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_pow_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

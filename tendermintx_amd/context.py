@@ -346,6 +346,36 @@ class Context:
         check(self._L.tmx_deep_last_zeta(self._h, z), self._h)
         return int(z[0]), int(z[1])
 
+    # ---- proof of work (include/tmx.h "proof of work"): the grinding variants of both proofs; params: the FRI params, pow_bits (1 .. 24)
+    # and deep (False: the FRI proof, True: the DEEP proof); a proof is pow_proof_words(params, pow_bits, deep) words, the nonce last
+    @staticmethod
+    def _pow_params(params, pow_bits, deep):
+        return _lib.PowParams(fri=Context._fri_params(params), pow_bits=int(pow_bits), deep=int(deep))
+
+    def pow_proof_words(self, params, pow_bits, deep=False):
+        return pow_proof_words(params, pow_bits, deep, self._L)
+
+    def pow_prove_device(self, params, pow_bits, deep, d_cols, d_levels, d_proof, stream=None):
+        """a grinding proof over caller columns (as fri_prove_device / deep_prove_device) into d_proof"""
+        check(self._L.tmx_pow_prove_device(self._h, C.byref(self._pow_params(params, pow_bits, deep)), d_cols, d_levels, d_proof,
+                                           self._stream(stream)), self._h)
+
+    def trace_commit_pow_device(self, params, pow_bits, deep, d_proof, stream=None):
+        """a grinding proof over the most recent trace_commit_device (same stream, after it); the parameters must match that commit"""
+        check(self._L.tmx_trace_commit_pow_device(self._h, C.byref(self._pow_params(params, pow_bits, deep)), d_proof, self._stream(stream)), self._h)
+
+    def pow_verify_device(self, params, pow_bits, deep, d_cap, d_proof, d_ok, stream=None):
+        """d_ok[n_queries] u32: 1 where the query of the grinding proof checks against the commit cap d_cap"""
+        check(self._L.tmx_pow_verify_device(self._h, C.byref(self._pow_params(params, pow_bits, deep)), d_cap, d_proof, d_ok,
+                                            self._stream(stream)), self._h)
+
+    def pow_last(self):
+        """(blocks) (nonce, candidates evaluated) of the last grinding prove; TmxError if the last prove was not one, or (status -4) if
+        its search gave up"""
+        nonce, tried = C.c_uint64(), C.c_uint64()
+        check(self._L.tmx_pow_last(self._h, C.byref(nonce), C.byref(tried)), self._h)
+        return int(nonce.value), int(tried.value)
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -452,3 +482,12 @@ def deep_proof_words(params, L=None):
     if not open_words:
         raise _lib.TmxError(-1, "n_cols must be at most 2^24 for a DEEP proof")
     return open_words + fri_words
+
+
+def pow_proof_words(params, pow_bits, deep=False, L=None):
+    """tmx_pow_proof_words: the words of a grinding proof (the FRI or DEEP proof, then the nonce); TmxError on parameters the calls refuse"""
+    L = L or _lib.lib()
+    words = int(L.tmx_pow_proof_words(C.byref(Context._pow_params(params, pow_bits, deep))))
+    if not words:
+        raise _lib.TmxError(-1, "parameters refused: the rules of the underlying proof, 1 <= pow_bits <= 24, deep 0 or 1")
+    return words

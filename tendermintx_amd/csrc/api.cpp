@@ -409,6 +409,7 @@ struct tmx_ctx {
   hipEvent_t ev_fri[5] = {};
   bool fri_valid = false;
   bool fri_deep = false;  // the last prove was a DEEP prove (its zeta sits in d_fri: tmx_deep_last_zeta)
+  uint32_t fri_pow_bits = 0;  // non-zero: the last prove was a grinding prove (the search's two words sit in d_fri: tmx_pow_last)
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -3210,9 +3211,10 @@ static uint32_t deep_log_r(uint32_t n_cols) {
 
 // cols / levels: the committed columns and their tree; (root_2_32, shift): the domain they were extended on.  Validated by the caller.
 // deep: null for a plain FRI prove; else the DEEP prove: the openings section first, then the FRI proof of the DEEP quotients.  Everything
-// after layer 0 is the same for both.
+// after layer 0 is the same for both.  pow_bits: 0, or the grinding variant of either: the transcript's last phase in two halves around the
+// search, and the nonce word behind the FRI part.
 static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* cols, const uint64_t* levels, uint64_t root_2_32, uint64_t shift,
-                         uint64_t* proof, void* hip_stream, const DeepSrc* deep = nullptr) {
+                         uint64_t* proof, void* hip_stream, const DeepSrc* deep = nullptr, uint32_t pow_bits = 0) {
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   tmx_fri_layout L;
   fri_layout(p, L);
@@ -3224,6 +3226,8 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
     G.log_r = log_r;
     proof += 4ull << log_r;  // (the FRI part: every offset of the layout shifted by the openings section)
   }
+  G.pow_bits = pow_bits;
+  G.off_nonce = L.words;
   HIPCK(c, hipSetDevice(c->cfg.device));
   int32_t st = poseidon_ready(c, s);
   if (st) return st;
@@ -3260,6 +3264,7 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
     if (!e) HIPCK(c, hipEventCreate(&e));
   c->fri_valid = false;
   c->fri_deep = deep != nullptr;
+  c->fri_pow_bits = pow_bits;
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_fri);
   uint64_t *state = W, *chal = W + 32, *apow = W + o_apow, *qidx = W + o_qidx;
   c->fri_flag_off = 96 * 8;
@@ -3306,7 +3311,13 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
   if ((st = launched(launch_fri_final(lg, L.final_log, G.w_fin_inv, G.s_fin_inv, G.m_fin_inv, W + o_layer[L.n_layers], proof + L.off_final, W + 96, s),
                      "k_fri_final")))
     return st;
-  if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 2, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+  if (!pow_bits) {
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 2, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+  } else {
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 5, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+    if ((st = launched(launch_fri_grind(c->d_pos_consts, c->pos_mode, pow_bits, state, chal + FRI_POW_AT, s), "k_fri_grind"))) return st;
+    if ((st = launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 6, 0, commit_cap, proof, state, chal, qidx, s), "k_fri_transcript"))) return st;
+  }
   HIPCK(c, hipEventRecord(c->ev_fri[3], s));
   // the openings, with the indices the transcript drew (device side): the commit's rows and paths, then every layer's leaf
   if ((st = launched(launch_merkle_open(p.log_n, p.n_cols, cols, p.log_n - p.cap_height, levels, p.n_queries, proof + L.off_indices,
@@ -3321,6 +3332,42 @@ static int32_t fri_prove(tmx_ctx* c, const tmx_fri_params& p, const uint64_t* co
   }
   HIPCK(c, hipEventRecord(c->ev_fri[4], s));
   c->fri_valid = true;
+  return TMX_OK;
+}
+
+// The verifier of all four proofs (parameters validated by the caller).  deep: the openings tree goes into the context's verifier scratch
+// first and the FRI part sits behind the openings section; pow_bits: the nonce word sits behind the FRI part.
+static int32_t fri_verify(tmx_ctx* c, const tmx_fri_params& p, bool deep, uint32_t pow_bits, const uint64_t* d_cap, const uint64_t* d_proof,
+                          uint32_t* d_ok, void* hip_stream) {
+  if (!d_cap || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_proof and d_ok must be set");
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  int32_t st = poseidon_ready(c, s);
+  if (st) return st;
+  tmx_fri_layout L;
+  fri_layout(p, L);
+  FriGeom G = fri_geom(p, L, c->ntt_root, c->ntt_shift);
+  G.pow_bits = pow_bits;
+  G.off_nonce = L.words;
+  const uint64_t *open = nullptr, *root = nullptr;
+  if (deep) {
+    const uint32_t log_r = deep_log_r(p.n_cols);
+    const uint64_t nd = tmx_poseidon_merkle_digests(log_r, 0);
+    if (c->deepv_bytes < nd * 32) {
+      if (c->d_deepv) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_deepv)); c->d_deepv = nullptr; c->deepv_bytes = 0; }
+      HIPCK(c, hipMalloc(&c->d_deepv, nd * 32));
+      c->deepv_bytes = nd * 32;
+    }
+    uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_deepv);
+    if ((st = tmx_poseidon_merkle_device(c, log_r, 4, d_proof, 0, lev, hip_stream))) return st;
+    G.deep = 1;
+    G.log_r = log_r;
+    open = d_proof;
+    root = lev + 4 * (nd - 1);
+    d_proof += 4ull << log_r;
+  }
+  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, G, d_cap, d_proof, open, root, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
   return TMX_OK;
 }
 
@@ -3360,16 +3407,7 @@ int32_t tmx_fri_verify_device(tmx_ctx* c, const tmx_fri_params* p, const uint64_
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = fri_check(c, p);
   if (st) return st;
-  if (!d_cap || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_proof and d_ok must be set");
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  st = poseidon_ready(c, s);
-  if (st) return st;
-  tmx_fri_layout L;
-  fri_layout(*p, L);
-  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, fri_geom(*p, L, c->ntt_root, c->ntt_shift), d_cap, d_proof, nullptr, nullptr, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return fri_verify(c, *p, false, 0, d_cap, d_proof, d_ok, hip_stream);
 }
 
 int32_t tmx_fri_last_degree_ok(tmx_ctx* c) {
@@ -3434,28 +3472,7 @@ int32_t tmx_deep_verify_device(tmx_ctx* c, const tmx_fri_params* p, const uint64
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = deep_check(c, p);
   if (st) return st;
-  if (!d_cap || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_cap, d_proof and d_ok must be set");
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  st = poseidon_ready(c, s);
-  if (st) return st;
-  const uint32_t log_r = deep_log_r(p->n_cols);
-  const uint64_t nd = tmx_poseidon_merkle_digests(log_r, 0);
-  if (c->deepv_bytes < nd * 32) {
-    if (c->d_deepv) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_deepv)); c->d_deepv = nullptr; c->deepv_bytes = 0; }
-    HIPCK(c, hipMalloc(&c->d_deepv, nd * 32));
-    c->deepv_bytes = nd * 32;
-  }
-  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_deepv);
-  if ((st = tmx_poseidon_merkle_device(c, log_r, 4, d_proof, 0, lev, hip_stream))) return st;
-  tmx_fri_layout L;
-  fri_layout(*p, L);
-  FriGeom G = fri_geom(*p, L, c->ntt_root, c->ntt_shift);
-  G.deep = 1;
-  G.log_r = log_r;
-  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, G, d_cap, d_proof + (4ull << log_r), d_proof, lev + 4 * (nd - 1), d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return fri_verify(c, *p, true, 0, d_cap, d_proof, d_ok, hip_stream);
 }
 
 int32_t tmx_deep_last_zeta(tmx_ctx* c, uint64_t z[2]) {
@@ -3464,6 +3481,75 @@ int32_t tmx_deep_last_zeta(tmx_ctx* c, uint64_t z[2]) {
   HIPCK(c, hipSetDevice(c->cfg.device));
   HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
   HIPCK(c, hipMemcpy(z, reinterpret_cast<uint64_t*>(c->d_fri) + 32 + FRI_ZETA_AT, 16, hipMemcpyDeviceToHost));
+  return TMX_OK;
+}
+
+// ---- proof of work: the grinding variants of both proofs (include/tmx.h "proof of work") ---------------------------------------------------
+static int32_t pow_check(tmx_ctx* c, const tmx_pow_params* pp) {
+  auto bad = [&](const char* why) { return c ? fail(c, TMX_ERR_BAD_ARG, why) : TMX_ERR_BAD_ARG; };
+  if (!pp) return bad("params is null");
+  int32_t st = fri_check(c, &pp->fri);
+  if (st) return st;
+  if (pp->deep > 1) return bad("deep must be 0 or 1");
+  if (pp->deep && pp->fri.n_cols > TMX_DEEP_MAX_COLS) return bad("n_cols must be at most 2^24 for a DEEP proof");
+  if (pp->pow_bits < 1 || pp->pow_bits > FRI_POW_MAX_BITS) return bad("pow_bits must be 1 .. 24");
+  return TMX_OK;
+}
+
+uint64_t tmx_pow_proof_words(const tmx_pow_params* pp) {
+  if (pow_check(nullptr, pp)) return 0;
+  tmx_fri_layout L;
+  fri_layout(pp->fri, L);
+  return L.words + 1 + (pp->deep ? tmx_deep_openings_words(pp->fri.n_cols) : 0);
+}
+
+int32_t tmx_pow_prove_device(tmx_ctx* c, const tmx_pow_params* pp, const uint64_t* d_cols, const uint64_t* d_levels, uint64_t* d_proof,
+                             void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = pow_check(c, pp);
+  if (st) return st;
+  if (!d_cols || !d_levels || !d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_levels and d_proof must be set");
+  const tmx_fri_params& p = pp->fri;
+  const DeepSrc src = {d_cols, p.log_n, p.log_blowup, c->ntt_shift % 0xffffffff00000001ull};
+  return fri_prove(c, p, d_cols, d_levels, c->ntt_root, c->ntt_shift, d_proof, hip_stream, pp->deep ? &src : nullptr, pp->pow_bits);
+}
+
+int32_t tmx_trace_commit_pow_device(tmx_ctx* c, const tmx_pow_params* pp, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = pow_check(c, pp);
+  if (st) return st;
+  st = tmx_trace_commit_last_shape(c, nullptr, nullptr, nullptr);
+  if (st) return st;
+  const tmx_fri_params& p = pp->fri;
+  const tmx_ctx::CommitRec r = c->last_commit;
+  if (p.log_n != r.log_m || p.n_cols != r.n_cols || p.cap_height != r.cap_height || p.log_blowup != r.log_blowup)
+    return fail(c, TMX_ERR_BAD_ARG, "proof parameters do not match the last commit: log_n " + std::to_string(r.log_m) + ", n_cols " + std::to_string(r.n_cols) +
+                                        ", cap_height " + std::to_string(r.cap_height) + ", log_blowup " + std::to_string(r.log_blowup));
+  if (!d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_proof is null");
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_commit);
+  const DeepSrc src = {reinterpret_cast<const uint64_t*>(base), r.log_m - r.log_blowup, 0, 1};  // (as tmx_trace_commit_deep_device)
+  return fri_prove(c, p, reinterpret_cast<const uint64_t*>(base + r.lde_off), reinterpret_cast<const uint64_t*>(base + r.lev_off), r.root, r.shift,
+                   d_proof, hip_stream, pp->deep ? &src : nullptr, pp->pow_bits);
+}
+
+int32_t tmx_pow_verify_device(tmx_ctx* c, const tmx_pow_params* pp, const uint64_t* d_cap, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = pow_check(c, pp);
+  if (st) return st;
+  return fri_verify(c, pp->fri, pp->deep != 0, pp->pow_bits, d_cap, d_proof, d_ok, hip_stream);
+}
+
+int32_t tmx_pow_last(tmx_ctx* c, uint64_t* nonce, uint64_t* tried) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (!c->fri_valid || !c->fri_pow_bits) return fail(c, TMX_ERR_BAD_ARG, "the last prove of this context was not a grinding prove");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  HIPCK(c, hipEventSynchronize(c->ev_fri[4]));
+  uint64_t w[2] = {0, 0};
+  HIPCK(c, hipMemcpy(w, reinterpret_cast<uint64_t*>(c->d_fri) + 32 + FRI_POW_AT, 16, hipMemcpyDeviceToHost));
+  if (nonce) *nonce = w[0];
+  if (tried) *tried = w[1];
+  if (w[0] == ~0ull)
+    return fail(c, TMX_ERR_CAPACITY, "the proof-of-work search gave up after 2^(pow_bits + 6) candidates: the proof's nonce word is 2^64 - 1 and does not verify");
   return TMX_OK;
 }
 

@@ -19,10 +19,17 @@ struct FriGeom {
   // s0, w0: layer 0's domain D_0; omega_n = w0^B, the trace domain's generator (z_1 = zeta omega_n)
   uint32_t deep, log_r;
   uint64_t s0, w0, omega_n;
+  // proof of work (include/tmx.h "proof of work"): pow_bits = 0 for a plain transcript / verifier; off_nonce: the nonce word, behind the
+  // FRI part
+  uint32_t pow_bits;
+  uint64_t off_nonce;
 };
 
 // where the DEEP scratch keeps zeta between launches: chal[FRI_ZETA_AT], chal[FRI_ZETA_AT + 1] (after alpha and the betas)
 constexpr uint32_t FRI_ZETA_AT = 2 + 2 * FRI_MAX_LAYERS + 2;
+// where the grinding prover keeps the search's two words: chal[FRI_POW_AT] = the smallest satisfying nonce so far (2^64 - 1: none),
+// chal[FRI_POW_AT + 1] = the candidates evaluated.  The search gives up after 2^(pow_bits + FRI_POW_SLACK_BITS) candidates.
+constexpr uint32_t FRI_POW_AT = FRI_ZETA_AT + 2, FRI_POW_SLACK_BITS = 6, FRI_POW_MAX_BITS = 24;
 
 // apow[c] = alpha^c (c < n_cols, pairs of u64), alpha at d_alpha
 int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, void* stream);
@@ -55,8 +62,13 @@ int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_
 // alpha (2 u64) then beta_l (2 u64 each).  phase 0: parameters + commit cap -> alpha; phase 1: cap of `layer` (in the proof) -> beta_layer;
 // phase 2: final coefficients -> query indices into the proof and each layer's leaf indices into d_qidx[n_layers][n_queries];
 // DEEP: phase 3: parameters, the word 2, commit cap -> zeta (chal[FRI_ZETA_AT]); phase 4: the openings root at d_commit_cap -> alpha.
+// Grinding splits phase 2: phase 5 (2a): final coefficients and pow_bits observed, the duplex left in d_state, the search's words reset;
+// phase 6 (2b): the nonce the search left -> the proof, observed, r drawn, then the indices as phase 2.
 int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
                           void* d_state, void* d_chal, void* d_qidx, void* stream);
+// The search between phases 5 and 6: the smallest nonce whose challenge has pow_bits leading zero bits, from the duplex in d_state, into
+// d_pow[0] (atomic minimum), the candidates evaluated added to d_pow[1].  One launch that ends itself; the grid is sized from pow_bits.
+int launch_fri_grind(const void* d_consts, int mode, uint32_t pow_bits, const void* d_state, void* d_pow, void* stream);
 // d_ok[q] for every query of the proof against d_cap (one workgroup).  G.deep: d_proof is the FRI part of a DEEP proof, d_open its
 // openings section and d_root the root of the openings tree; otherwise both are unused.
 int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, const void* d_open, const void* d_root,

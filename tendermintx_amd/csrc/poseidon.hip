@@ -392,7 +392,8 @@ __device__ __forceinline__ gl2 chal_start_deep(FriChal& c, const PosConsts& K, c
 
 // One lane, between the prover's stages (fri.h launch_fri_transcript): the parameters and the commit cap -> alpha (phase 0), the cap of
 // `layer` -> beta_layer (phase 1), the final coefficients -> the query indices and every layer's leaf indices (phase 2).  DEEP: the start
-// with its point count and the commit cap -> zeta (phase 3), the openings root at commit_cap -> alpha (phase 4).
+// with its point count and the commit cap -> zeta (phase 3), the openings root at commit_cap -> alpha (phase 4).  Grinding: phase 2 in two
+// halves around k_fri_grind: the final coefficients and pow_bits observed (phase 5), the nonce observed and r drawn -> the indices (phase 6).
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
                                                        const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
@@ -418,9 +419,22 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
     chal_observe_span<MODE>(c, K, proof + G.off_caps[layer], 4ull << G.cap_h[layer]);
     chal[2 + 2 * layer] = chal_challenge<MODE>(c, K);
     chal[3 + 2 * layer] = chal_challenge<MODE>(c, K);
-  } else {
+  } else if (phase == 5) {
     chal_load(c, state);
     chal_observe_span<MODE>(c, K, proof + G.off_final, 2ull << G.final_log);
+    chal_observe<MODE>(c, K, G.pow_bits);  // (a buffer this fills is duplexed here, once: a candidate is one permutation either way)
+    chal[FRI_POW_AT] = ~0ull;              // the search's minimum and its counter start here, not in a launch of their own
+    chal[FRI_POW_AT + 1] = 0;
+  } else {
+    chal_load(c, state);
+    if (phase == 6) {
+      const uint64_t nonce = chal[FRI_POW_AT];  // (2^64 - 1 if the search gave up: the verifier rejects it)
+      proof[G.off_nonce] = nonce;
+      chal_observe<MODE>(c, K, nonce);
+      (void)chal_challenge<MODE>(c, K);  // r, consumed: the indices come from the remaining output words
+    } else {
+      chal_observe_span<MODE>(c, K, proof + G.off_final, 2ull << G.final_log);
+    }
     const uint64_t mask = (1ull << G.log_n) - 1;
     for (uint32_t q = 0; q < G.n_queries; q++) {
       uint64_t i = chal_challenge<MODE>(c, K) & mask;
@@ -436,6 +450,41 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
   chal_store(c, state);
 }
 
+// The proof-of-work search (include/tmx.h "proof of work"), the one wide piece of the transcript: every candidate is one permutation of the
+// duplex phase 5 left in `state` (12 words and the n_in <= 7 pending input words, uniform across the grid: scalar loads) with the
+// candidate as the next input word; it satisfies the condition if output word 7, the one challenge() pops, has pow_bits leading zero bits.
+// Lane t of a grid of G lanes tries t, t + G, t + 2 G, ...; a hit is a 64-bit atomic minimum on pow[0], and a lane stops when its next
+// candidate lies above the current minimum (one relaxed load per round) or at the bound 2^(pow_bits + FRI_POW_SLACK_BITS) <= 2^30.  The
+// minimum over all hits is the smallest satisfying nonce whatever order the workgroups run in: every candidate below it is evaluated by
+// its lane before that lane stops, and no workgroup waits for another.  pow[1] += the candidates evaluated, one add per wave (it depends
+// on timing: rounds in flight finish).
+template <int MODE>
+__global__ __launch_bounds__(256, 4) void k_fri_grind(const uint64_t* __restrict__ consts, uint32_t pow_bits, const uint64_t* __restrict__ state,
+                                                   uint64_t* __restrict__ pow) {
+  const PosConsts K = pos_consts(consts);
+  const uint32_t n_in = (uint32_t)state[28];
+  uint64_t base[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) base[k] = state[k];
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++)
+    if (k < n_in) base[k] = state[12 + k];
+  const uint64_t lanes = (uint64_t)gridDim.x * blockDim.x, bound = 1ull << (pow_bits + FRI_POW_SLACK_BITS);
+  uint32_t evaluated = 0;
+  for (uint64_t cand = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; cand < bound; cand += lanes) {
+    if (cand > __hip_atomic_load(pow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+    uint64_t s[12];
+#pragma unroll
+    for (uint32_t k = 0; k < 12; k++) s[k] = k == n_in ? cand : base[k];
+    pos_permute<MODE>(s, K);
+    evaluated++;
+    if ((gl_canon(s[7]) >> (64 - pow_bits)) == 0) __hip_atomic_fetch_min(pow, cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) evaluated += __shfl_down(evaluated, off);
+  if ((threadIdx.x & 63) == 0 && evaluated) __hip_atomic_fetch_add(pow + 1, (uint64_t)evaluated, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int B>
 __device__ __forceinline__ gl2 fri_fold_row(const uint64_t* __restrict__ row, uint64_t xinv0, uint64_t g, gl2 beta) {
   gl2 v[1 << B];
@@ -449,12 +498,15 @@ __device__ __forceinline__ gl2 fri_fold_row(const uint64_t* __restrict__ row, ui
 // DEEP: `proof` is the FRI part of a DEEP proof, `open` its openings section and `root` the root of the openings tree (enqueued before);
 // the transcript starts with zeta and the root, the whole workgroup forms Y_0, Y_1 from the openings and checks their padding, and a
 // query's v_0 is the DEEP layer 0 at its point instead of the plain combination.
+// G.pow_bits != 0 (a grinding proof): lane 0 also observes pow_bits and the nonce word and draws r in front of the indices; every query is
+// rejected if the nonce is not canonical or r has fewer than pow_bits leading zero bits.
 template <int MODE, bool DEEP>
 __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* __restrict__ consts, FriGeom G, const uint64_t* __restrict__ cap,
                                                                 const uint64_t* __restrict__ proof, const uint64_t* __restrict__ open,
                                                                 const uint64_t* __restrict__ root, uint32_t* __restrict__ ok) {
   __shared__ uint64_t s_chal[2 + 2 * FRI_MAX_LAYERS], s_idx[FRI_MAX_QUERIES];
   __shared__ uint64_t s_deep[DEEP ? 4 : 1][DEEP ? FRI_MAX_QUERIES : 1], s_z[DEEP ? 4 : 1];
+  __shared__ uint32_t s_pow_ok;
   const PosConsts K = pos_consts(consts);
   if (threadIdx.x == 0) {
     FriChal c;
@@ -474,6 +526,14 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
       s_chal[3 + 2 * l] = chal_challenge<MODE>(c, K);
     }
     chal_observe_span<MODE>(c, K, proof + G.off_final, 2ull << G.final_log);
+    bool pow_ok = true;
+    if (G.pow_bits) {
+      chal_observe<MODE>(c, K, G.pow_bits);
+      const uint64_t nonce = proof[G.off_nonce];
+      chal_observe<MODE>(c, K, nonce);
+      pow_ok = nonce < GL_P && (chal_challenge<MODE>(c, K) >> (64 - G.pow_bits)) == 0;
+    }
+    s_pow_ok = pow_ok ? 1u : 0u;
     for (uint32_t q = 0; q < G.n_queries; q++) s_idx[q] = chal_challenge<MODE>(c, K) & ((1ull << G.log_n) - 1);
   }
   __syncthreads();
@@ -508,7 +568,7 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
   const uint32_t q = threadIdx.x;
   if (q >= G.n_queries) return;
   uint64_t i = s_idx[q];
-  bool good = proof[G.off_indices + q] == i && pad_ok;
+  bool good = proof[G.off_indices + q] == i && pad_ok && s_pow_ok;
   const uint32_t pl0 = G.log_n - G.cap_height;
   const uint64_t* row = proof + G.off_init_rows + (uint64_t)q * G.n_cols;
   good = merkle_leads_to_cap<MODE>(K, row, G.n_cols, proof + G.off_init_paths + (uint64_t)q * pl0 * 4, pl0, i, cap) && good;
@@ -645,6 +705,22 @@ int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int 
   if (mode == POS_MODE_MERGE3) fri_transcript_launch<POS_MODE_MERGE3>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
   else if (mode == POS_MODE_SMALL) fri_transcript_launch<POS_MODE_SMALL>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
   else fri_transcript_launch<POS_MODE_GENERAL>(K, G, phase, layer, cap, proof, st, ch, qi, S_(stream));
+  return (int)hipGetLastError();
+}
+// The grid of the search: one lane per expected candidate (2^pow_bits: a 4-bit search is one workgroup), at most four 256-thread workgroups
+// per compute unit: the four waves per SIMD the kernel's launch bounds keep its registers within (docs/kernels.md).
+int launch_fri_grind(const void* d_consts, int mode, uint32_t pow_bits, const void* d_state, void* d_pow, void* stream) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+    return (int)hipErrorInvalidDevice;
+  const uint64_t want = std::max<uint64_t>(1, (1ull << pow_bits) / 256);
+  const dim3 grid((uint32_t)std::min<uint64_t>(want, 4ull * (uint64_t)cus)), block(256);
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* st = reinterpret_cast<const uint64_t*>(d_state);
+  uint64_t* pw = reinterpret_cast<uint64_t*>(d_pow);
+  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL(k_fri_grind<POS_MODE_MERGE3>, grid, block, 0, S_(stream), K, pow_bits, st, pw);
+  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL(k_fri_grind<POS_MODE_SMALL>, grid, block, 0, S_(stream), K, pow_bits, st, pw);
+  else hipLaunchKernelGGL(k_fri_grind<POS_MODE_GENERAL>, grid, block, 0, S_(stream), K, pow_bits, st, pw);
   return (int)hipGetLastError();
 }
 template <bool DEEP>

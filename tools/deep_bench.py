@@ -4,6 +4,8 @@ parameters) and its device check (tmx_deep_verify_device), on the tools/fri_benc
 events around REPS back-to-back calls), the DEEP prove split by tmx_fri_last_ms (its "combine" holds everything before the first layer:
 transcript start, evaluation, openings tree, combine, quotient), verify time per call, the bytes the evaluation reads (n_cols x N x 8),
 all-queries-accept, and a spot check: the openings of 8 columns against the CPU oracle (interpolation + Horner, tests/deep_model.py).
+POW_BITS=b (1 .. 24) adds the grinding DEEP prove of the same commit (tmx_trace_commit_pow_device), back to back with the plain one: its
+time, stages, nonce, candidates evaluated, and the search's time as the difference of the two "final" stages, hence candidates per second.
    P=256 N=128 python tools/deep_bench.py   (SECTION=sha512 BLOWUP=3 CAP=4 ARITY=4 FINAL=5 QUERIES=28 by default)"""
 import json
 import os
@@ -24,6 +26,7 @@ SEC = {"ladders": _lib.TRACE_LADDERS, "sha512": _lib.TRACE_SHA512, "sha256": _li
 name = os.environ.get("SECTION", "sha512")
 log_blowup, cap_h, reps = int(os.environ.get("BLOWUP", "3")), int(os.environ.get("CAP", "4")), int(os.environ.get("REPS", "20"))
 arity, final_max, nq = int(os.environ.get("ARITY", "4")), int(os.environ.get("FINAL", "5")), int(os.environ.get("QUERIES", "28"))
+pow_bits = int(os.environ.get("POW_BITS", "0"))
 w = bench_workload("survey8d", n, P, seed=0x544D58)
 dev = torch.device("cuda:0")
 d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
@@ -66,6 +69,20 @@ degree_ok = ctx.fri_last_degree_ok()
 zeta = ctx.deep_last_zeta()
 verify_ms = timed(lambda: ctx.deep_verify_device(params, cap.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3)
 all_ok = bool((ok.cpu().numpy() == 1).all())
+grind = {}
+if pow_bits:
+    pproof = torch.empty(ctx.pow_proof_words(params, pow_bits, True), dtype=torch.int64, device=dev)
+    pow_ms = timed(lambda: ctx.trace_commit_pow_device(params, pow_bits, True, pproof.data_ptr(), 0), reps)
+    pstages = ctx.fri_last_ms()
+    nonce, tried = ctx.pow_last()
+    plain_again_ms = timed(lambda: ctx.trace_commit_deep_device(params, proof.data_ptr(), 0), reps)
+    ctx.pow_verify_device(params, pow_bits, True, cap.data_ptr(), pproof.data_ptr(), ok.data_ptr(), 0)
+    pow_ok = bool((ok.cpu().numpy() == 1).all())
+    search_ms = pstages["final"] - stages["final"]
+    grind = {"pow_bits": pow_bits, "pow_prove_ms": round(pow_ms, 4), "plain_prove_again_ms": round(plain_again_ms, 4),
+             "pow_extra_ms": round(pow_ms - (deep_ms + plain_again_ms) / 2, 4), "pow_stage_ms": {k: round(v, 4) for k, v in pstages.items()},
+             "nonce": nonce, "tried": tried, "search_ms_by_stage_difference": round(search_ms, 4),
+             "candidates_per_s": round(tried / (search_ms * 1e-3)) if search_ms > 0 else None, "pow_all_ok": pow_ok}
 # spot check: 8 columns' openings against interpolation + Horner of the trace columns on the CPU (tests/deep_model.py over the oracle's NTT;
 # a column is one (proof, cell) of the section's rows, natural order, zero padded -- tmx_trace_commit_device's first stage)
 import deep_model as dm  # noqa: E402
@@ -82,7 +99,7 @@ for k, c in enumerate(pick):
 ys = dm.evaluate(oracle_c, cols, 1, dm.points(oracle_c, params, zeta))
 got = dm.openings_of(params, proof.cpu().numpy().view(np.uint64))
 spot_ok = all(tuple(ys[k]) == got[c] for k, c in enumerate(pick))
-print(json.dumps({"section": name, "proofs": P, "n": n, "log_rows_ext": log_m, "columns": n_cols, "cap_height": ch, "arity_bits": arity,
+print(json.dumps({**grind, "section": name, "proofs": P, "n": n, "log_rows_ext": log_m, "columns": n_cols, "cap_height": ch, "arity_bits": arity,
                   "final_log_max": final_max, "queries": nq, "layer_bits": layout["layer_bits"], "final_log": layout["final_log"],
                   "proof_words": proof.numel(), "commit_ms_total": round(sum(commit_ms.values()), 4), "fri_prove_ms": round(fri_ms, 4),
                   "fri_stage_ms": {k: round(v, 4) for k, v in fri_stages.items()}, "deep_prove_ms": round(deep_ms, 4),
