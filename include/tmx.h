@@ -766,6 +766,100 @@ int32_t tmx_pow_verify_device(tmx_ctx* ctx, const tmx_pow_params* pp, const uint
                               void* hip_stream);
 int32_t tmx_pow_last(tmx_ctx* ctx, uint64_t* nonce, uint64_t* tried);
 
+/* ---- one DEEP-FRI proof over several oracles of different sizes, and the commit set it consumes.  The entry points above work on ONE
+ * committed section; a batch's trace is five row tables of different heights, and a consumer needs all of them opened at the SAME
+ * out-of-domain point.  This block adds a commit set (several sections committed and kept resident side by side) and one proof over a list
+ * of committed oracles: ONE zeta, one set of layers, one final polynomial, one query set.  plonky2's `prove` (what the reference calls,
+ * circuits/skip.rs:119-133) opens several oracles in one FRI proof; this is that capability in the project's own format.  Nothing above
+ * changes: the single-commit entry points, proofs, layouts, transcripts and scratch are what they were.  Same field, extension
+ * F_p^2 = F_p[X] / (X^2 - 7), Poseidon duplex, NTT domain convention and caveats as the FRI and DEEP blocks (natural order, no salt,
+ * injectable constants, the project's own transcript: PARITY UNPINNED against plonky2).
+ *   oracles    K oracles, 1 <= K <= TMX_BATCH_MAX_ORACLES (8).  Oracle k is n_cols_k columns of M_k = 2^log_n_k words (column-major, taken
+ *              mod p): evaluations on D^(k) = { s w_k^i }, w_k the 2^log_n_k-th root of the NTT domain and THE SAME coset shift s for every
+ *              size (what tmx_lde_goldilocks_device writes), with its own Poseidon tree (tmx_poseidon_merkle_device) of cap height
+ *              h_k = min(cap_height, log_n_k).  One log_blowup B for all; N_k = M_k / 2^B; the claim is degree < N_k for every column of
+ *              oracle k.  The list is ordered by non-increasing log_n_k; equal sizes are allowed.  off_k = n_cols_0 + ... + n_cols_(k-1),
+ *              C = sum n_cols_k (C <= 2^24).  A group g is the set of oracles of one size; the distinct sizes are m^(0) > ... > m^(G-1).
+ *   parameters tmx_batch_params.  TMX_ERR_BAD_ARG before anything is enqueued (nothing written, tmx_last_error says which rule): the FRI
+ *              rules on every oracle (1 <= log_blowup <= 6, log_blowup < log_n_k <= 28, n_cols_k >= 1, 1 <= arity_bits <= 4,
+ *              final_log_max <= 8, final_log_max + log_blowup <= 12, 1 <= n_queries <= 256, reserved == 0), cap_height <= log_n_0,
+ *              pow_bits <= TMX_POW_MAX_BITS (0 = no grinding), the ordering rule, C <= 2^24, unused array entries zero.
+ *   schedule   d = m^(0) - B.  For g = 0 .. G - 2: gap = m^(g) - m^(g+1); while gap > 0: b = min(arity_bits, gap), append b, gap -= b,
+ *              d -= b.  Then FRI's rule on what is left: while d > final_log_max: b = min(arity_bits, d - final_log_max), append b, d -= b.
+ *              final_log = d.  So a layer boundary falls on every distinct oracle size whatever arity_bits is.  Layer domains, layer trees,
+ *              leaves, cap heights, final polynomial and degree flag are FRI's, unchanged.
+ *   transcript observe 2^32 + K (no FRI / DEEP / grinding transcript starts with a word >= 2^32, so none coincides), then log_blowup,
+ *              cap_height, arity_bits, final_log_max, n_queries, pow_bits, then (log_n_k, n_cols_k) for each k, then the word 2, then the K
+ *              commit caps in order (4 << h_k words each).  zeta as DEEP draws it (again while zeta.c1 == 0).  Points of oracle k:
+ *              z_(k,0) = zeta, z_(k,1) = zeta omega_(N_k), omega_(N_k) = w_k^(2^B).  Openings y_(k,c,j) as DEEP defines them, on oracle k's own
+ *              subset x_(i 2^B).  Openings section: K blocks in order, block k exactly DEEP's planar section for n_cols_k (4 R_k words,
+ *              R_k = 2^ceil(log2 n_cols_k), zero padding), each hashed as DEEP hashes its section; the transcript observes the K roots in
+ *              order (4 words each) and draws ONE alpha.  After that: per layer its cap -> beta_l; the final coefficients; if pow_bits > 0
+ *              the grinding steps 1 - 3 exactly as the proof-of-work block defines them; indices idx_q = challenge() mod 2^(m^(0)).
+ *   layers     for oracle k and i < M_k, x = s w_k^i:  F_k(x) = sum_c alpha^(off_k + c) col_(k,c)[i],  Y_(k,j) = sum_c alpha^(off_k + c) y_(k,c,j),
+ *              Q_k[i] = (F_k(x) - Y_(k,0)) / (x - z_(k,0)) + alpha^C (F_k(x) - Y_(k,1)) / (x - z_(k,1));  Q^(g)[i] = sum of Q_k[i] over group g.
+ *              Layer 0 = Q^(0).  The fold from layer l (arity a_l) is FRI's, and when the new layer has 2^(m^(g)) points for some g >= 1 the
+ *              group enters it INDEX FOR INDEX, scaled by the first power of beta_l the fold did not use:
+ *              f_(l+1)[i] = sum_(j < a_l) beta_l^j f_j(...) + beta_l^(a_l) Q^(g)[i].
+ *              The one non-obvious step: layer l + 1's nominal domain has shift s^(a_0 ... a_l), the group's has shift s.  Reading a vector of
+ *              evaluations on one coset as evaluations on another coset of the same subgroup substitutes x -> c x in the polynomial: its
+ *              degree is the same, so the low-degree claim carries over, and the sum of the two vectors is low-degree exactly if (up to the
+ *              random beta_l) both are.  The verifier therefore uses each oracle's OWN x for Q_k and the layer's own x for the folds.
+ *   query q    i_0 = idx_q, i_(l+1) = i_l mod M_(l+1) as in FRI.  Oracle k is opened at row idx_q mod M_k (a row of n_cols_k words and a path
+ *              of log_n_k - h_k digests, as tmx_poseidon_merkle_open_device); layers as in FRI.  Checks: each oracle opening against its
+ *              cap; v_0 = Q^(0) from the opened rows of group 0 and the Y sums the verifier forms from the openings section; per layer: leaf
+ *              entry == v, path against the layer cap, v = leaf folded with beta_l, plus beta_l^(a_l) Q^(g) from the opened rows of group g
+ *              when that layer takes one in; at the end v == the final polynomial at point i_L.  A non-zero padding word in any openings
+ *              block, a nonce >= p or a failed grinding condition rejects every query.
+ *   proof      one flat u64 buffer, every offset in tmx_batch_layout: the K openings blocks; the layer caps; the final coefficients
+ *              (c0, c1); the indices; for k = 0 .. K - 1 the oracle rows [n_queries][n_cols_k] and paths [n_queries][log_n_k - h_k][4]; per
+ *              layer its rows and paths as FRI; one nonce word if pow_bits > 0 (off_nonce; == words without grinding).
+ *              layer_enter[l] = g >= 1: the fold of layer l takes group g in; 0: a plain fold.
+ * A K = 1 batch proof is a different transcript from a DEEP proof of the same oracle and does not equal it.
+ *   tmx_batch_layout_of                host only.
+ *   tmx_batch_prove_device             caller oracles (d_cols[k], d_levels[k]: what tmx_lde_goldilocks_device / tmx_poseidon_merkle_device
+ *                                      wrote for oracle k; host arrays of K device pointers), under the context's CURRENT NTT domain.
+ *   tmx_batch_verify_device            d_caps: the K caps concatenated in order; d_ok[q] as tmx_fri_verify_device.
+ *   tmx_trace_commit_set_device        commits every section of the mask `sections` (row tables only: TMX_TRACE_MATCH refused) through the
+ *                                      stages of tmx_trace_commit_device into a scratch of the SET'S OWN, where the pre-LDE columns, extended
+ *                                      columns and tree levels of every section stay resident together.  Oracle order: by decreasing
+ *                                      log_rows, ties by ascending section bit; d_caps receives the caps in that order (4 << h_k words each),
+ *                                      each word for word what tmx_trace_commit_device writes for that section alone.  It does not touch the
+ *                                      last single commit or its scratch, and tmx_trace_commit_device does not touch the set: both can be
+ *                                      open at once.  A call that fails anywhere leaves no set.  The scratch is checked against free memory
+ *                                      before allocation (the rule of tmx_trace_commit_device summed over the sections): TMX_ERR_CAPACITY.  At
+ *                                      256 proofs x N = 128 and blow-up 8 the ladders section alone needs > 200 GB, so a full-size set holds
+ *                                      the other four (about 55 GB + the LDE's scratch; derived from that formula, not measured).
+ *   tmx_trace_commit_set_shape         the set's oracle list into out (n_oracles, log_blowup, cap_height, log_n[], n_cols[]; the other
+ *                                      fields zero, for the caller to fill) and each oracle's section bit; TMX_ERR_BAD_ARG with no set.
+ *   tmx_trace_commit_set_prove_device  a proof over the set; the oracle list, log_blowup and cap_height must match it (TMX_ERR_BAD_ARG).  The
+ *                                      openings read the set's pre-LDE columns, as tmx_trace_commit_deep_device does; the set stays intact.
+ * tmx_fri_last_degree_ok, tmx_fri_last_ms, tmx_deep_last_zeta and (pow_bits > 0) tmx_pow_last report on batch proves too; ms[0] covers
+ * everything before the first layer, over all oracles.  Asynchronous on hip_stream, no host synchronisation and no device-to-host copy
+ * inside; the prover's scratch is the FRI provers' (grows on demand). */
+#define TMX_BATCH_MAX_ORACLES 8
+typedef struct {
+  uint32_t n_oracles, log_blowup, cap_height, arity_bits, final_log_max, n_queries, pow_bits, reserved;
+  uint32_t log_n[TMX_BATCH_MAX_ORACLES], n_cols[TMX_BATCH_MAX_ORACLES];
+} tmx_batch_params;
+typedef struct {
+  uint32_t n_layers, final_log, n_groups, reserved;
+  uint32_t layer_bits[TMX_FRI_MAX_LAYERS], layer_cap_height[TMX_FRI_MAX_LAYERS], layer_enter[TMX_FRI_MAX_LAYERS];
+  uint32_t group_of[TMX_BATCH_MAX_ORACLES], cap_height_of[TMX_BATCH_MAX_ORACLES];
+  uint64_t off_open[TMX_BATCH_MAX_ORACLES], off_caps[TMX_FRI_MAX_LAYERS], off_final, off_indices;
+  uint64_t off_init_rows[TMX_BATCH_MAX_ORACLES], off_init_paths[TMX_BATCH_MAX_ORACLES];
+  uint64_t off_rows[TMX_FRI_MAX_LAYERS], off_paths[TMX_FRI_MAX_LAYERS], off_nonce, words;  /* u64 offsets into the proof; words = total */
+} tmx_batch_layout;
+int32_t tmx_batch_layout_of(const tmx_batch_params* p, tmx_batch_layout* out);  /* host only: TMX_OK or TMX_ERR_BAD_ARG */
+int32_t tmx_batch_prove_device(tmx_ctx* ctx, const tmx_batch_params* p, const uint64_t* const d_cols[], const uint64_t* const d_levels[],
+                               uint64_t* d_proof, void* hip_stream);
+int32_t tmx_batch_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok,
+                                void* hip_stream);
+int32_t tmx_trace_commit_set_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t log_blowup, uint32_t cap_height,
+                                    const void* d_trace_rows, uint64_t* d_caps, void* hip_stream);
+int32_t tmx_trace_commit_set_shape(const tmx_ctx* ctx, tmx_batch_params* out, uint32_t section_of[TMX_BATCH_MAX_ORACLES]);
+int32_t tmx_trace_commit_set_prove_device(tmx_ctx* ctx, const tmx_batch_params* p, uint64_t* d_proof, void* hip_stream);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

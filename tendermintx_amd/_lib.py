@@ -151,11 +151,30 @@ class FriLayout(C.Structure):
                 ("off_indices", C.c_uint64), ("off_init_rows", C.c_uint64), ("off_init_paths", C.c_uint64),
                 ("off_rows", C.c_uint64 * FRI_MAX_LAYERS), ("off_paths", C.c_uint64 * FRI_MAX_LAYERS), ("words", C.c_uint64)]
 
+BATCH_MAX_ORACLES = 8
+
+
+class BatchParams(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_oracles", "log_blowup", "cap_height", "arity_bits", "final_log_max", "n_queries", "pow_bits", "reserved")] + [
+        ("log_n", C.c_uint32 * BATCH_MAX_ORACLES), ("n_cols", C.c_uint32 * BATCH_MAX_ORACLES)]
+
+
+class BatchLayout(C.Structure):
+    _fields_ = [("n_layers", C.c_uint32), ("final_log", C.c_uint32), ("n_groups", C.c_uint32), ("reserved", C.c_uint32),
+                ("layer_bits", C.c_uint32 * FRI_MAX_LAYERS), ("layer_cap_height", C.c_uint32 * FRI_MAX_LAYERS),
+                ("layer_enter", C.c_uint32 * FRI_MAX_LAYERS), ("group_of", C.c_uint32 * BATCH_MAX_ORACLES),
+                ("cap_height_of", C.c_uint32 * BATCH_MAX_ORACLES), ("off_open", C.c_uint64 * BATCH_MAX_ORACLES),
+                ("off_caps", C.c_uint64 * FRI_MAX_LAYERS), ("off_final", C.c_uint64), ("off_indices", C.c_uint64),
+                ("off_init_rows", C.c_uint64 * BATCH_MAX_ORACLES), ("off_init_paths", C.c_uint64 * BATCH_MAX_ORACLES),
+                ("off_rows", C.c_uint64 * FRI_MAX_LAYERS), ("off_paths", C.c_uint64 * FRI_MAX_LAYERS), ("off_nonce", C.c_uint64),
+                ("words", C.c_uint64)]
+
 assert (C.sizeof(ValidatorValue), C.sizeof(HashFieldValue), C.sizeof(SkipInputsFixed), C.sizeof(StepInputsFixed)) == (240, 48, 832, 1008)
 assert (C.sizeof(TargetLaneDerived), C.sizeof(TrustedLaneDerived), C.sizeof(ProofDerived)) == (560, 112, 976)
 assert C.sizeof(ValidatorRec) == 256 and C.sizeof(HashFieldRec) == 48 and C.sizeof(ProofRec) == 2336
 assert C.sizeof(Report) == 64 and C.sizeof(AddrRec) == 32
 assert C.sizeof(FriParams) == 32 and C.sizeof(FriLayout) == 8 + 8 * 28 + 8 * 28 * 3 + 8 * 5
+assert C.sizeof(BatchParams) == 96 and C.sizeof(BatchLayout) == 16 + 4 * 28 * 3 + 4 * 8 * 2 + 8 * (8 * 3 + 28 * 3 + 4)
 
 _lib = None
 _hip = None
@@ -274,6 +293,13 @@ def lib():
         L.tmx_trace_commit_pow_device.argtypes = [C.c_void_p, C.POINTER(PowParams), C.c_void_p, C.c_void_p]
         L.tmx_pow_verify_device.argtypes = [C.c_void_p, C.POINTER(PowParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_pow_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.tmx_batch_layout_of.argtypes = [C.POINTER(BatchParams), C.POINTER(BatchLayout)]
+        L.tmx_batch_prove_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+        L.tmx_batch_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        L.tmx_trace_commit_set_shape.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.POINTER(C.c_uint32)]
+        L.tmx_trace_commit_set_prove_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -376,6 +376,51 @@ class Context:
         check(self._L.tmx_pow_last(self._h, C.byref(nonce), C.byref(tried)), self._h)
         return int(nonce.value), int(tried.value)
 
+    # ---- one DEEP-FRI proof over several oracles of different sizes, and the commit set (include/tmx.h "one DEEP-FRI proof over several
+    # oracles"); params: a dict with log_blowup, cap_height, arity_bits, final_log_max, n_queries, pow_bits (0: no grinding) and the oracle
+    # list log_n, n_cols (sequences of equal length, by non-increasing log_n), or a _lib.BatchParams
+    @staticmethod
+    def _batch_params(params):
+        if isinstance(params, _lib.BatchParams):
+            return params
+        p = dict(params)
+        log_n, n_cols = [int(x) for x in p.pop("log_n")], [int(x) for x in p.pop("n_cols")]
+        n = int(p.pop("n_oracles", len(log_n)))
+        if len(log_n) != len(n_cols) or len(log_n) > _lib.BATCH_MAX_ORACLES:
+            raise _lib.TmxError(-1, "log_n and n_cols must have the same length, at most 8")
+        return _lib.BatchParams(n_oracles=n, log_n=(C.c_uint32 * _lib.BATCH_MAX_ORACLES)(*log_n),
+                                n_cols=(C.c_uint32 * _lib.BATCH_MAX_ORACLES)(*n_cols), **{k: int(v) for k, v in p.items()})
+
+    def batch_layout(self, params):
+        return batch_layout(params, self._L)
+
+    def batch_prove_device(self, params, d_cols, d_levels, d_proof, stream=None):
+        """one proof over caller oracles: d_cols[k], d_levels[k] device pointers of oracle k's extended columns and tree"""
+        p = self._batch_params(params)
+        cols, levels = (C.c_void_p * p.n_oracles)(*d_cols), (C.c_void_p * p.n_oracles)(*d_levels)
+        check(self._L.tmx_batch_prove_device(self._h, C.byref(p), cols, levels, d_proof, self._stream(stream)), self._h)
+
+    def batch_verify_device(self, params, d_caps, d_proof, d_ok, stream=None):
+        """d_ok[n_queries] u32: 1 where the query checks against the K caps concatenated at d_caps"""
+        check(self._L.tmx_batch_verify_device(self._h, C.byref(self._batch_params(params)), d_caps, d_proof, d_ok, self._stream(stream)), self._h)
+
+    def trace_commit_set_device(self, kind, n_proofs, sections, log_blowup, cap_height, d_trace_rows, d_caps, stream=None):
+        """commits every row table of the mask `sections` side by side; d_caps receives the caps in the set's oracle order"""
+        check(self._L.tmx_trace_commit_set_device(self._h, kind, n_proofs, sections, log_blowup, cap_height, d_trace_rows, d_caps,
+                                                  self._stream(stream)), self._h)
+
+    def trace_commit_set_shape(self):
+        """(params dict with the set's n_oracles, log_blowup, cap_height, log_n, n_cols and the other fields zero, [section bit per oracle])"""
+        p, sec = _lib.BatchParams(), (C.c_uint32 * _lib.BATCH_MAX_ORACLES)()
+        check(self._L.tmx_trace_commit_set_shape(self._h, C.byref(p), sec), self._h)
+        K = p.n_oracles
+        return (dict(log_blowup=p.log_blowup, cap_height=p.cap_height, arity_bits=0, final_log_max=0, n_queries=0, pow_bits=0,
+                     log_n=list(p.log_n[:K]), n_cols=list(p.n_cols[:K])), list(sec[:K]))
+
+    def trace_commit_set_prove_device(self, params, d_proof, stream=None):
+        """one proof over the commit set (same stream, after it); the oracle list, log_blowup and cap_height must match the set"""
+        check(self._L.tmx_trace_commit_set_prove_device(self._h, C.byref(self._batch_params(params)), d_proof, self._stream(stream)), self._h)
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -491,3 +536,18 @@ def pow_proof_words(params, pow_bits, deep=False, L=None):
     if not words:
         raise _lib.TmxError(-1, "parameters refused: the rules of the underlying proof, 1 <= pow_bits <= 24, deep 0 or 1")
     return words
+
+
+def batch_layout(params, L=None):
+    """tmx_batch_layout_of as a dict (no context, no device); TmxError on parameters the ABI refuses"""
+    L = L or _lib.lib()
+    p = Context._batch_params(params)
+    out = _lib.BatchLayout()
+    check(L.tmx_batch_layout_of(C.byref(p), C.byref(out)))
+    n, K = out.n_layers, p.n_oracles
+    return {"n_layers": n, "final_log": out.final_log, "n_groups": out.n_groups, "layer_bits": list(out.layer_bits[:n]),
+            "layer_cap_height": list(out.layer_cap_height[:n]), "layer_enter": list(out.layer_enter[:n]), "group_of": list(out.group_of[:K]),
+            "cap_height_of": list(out.cap_height_of[:K]), "off_open": list(out.off_open[:K]), "off_caps": list(out.off_caps[:n]),
+            "off_final": out.off_final, "off_indices": out.off_indices, "off_init_rows": list(out.off_init_rows[:K]),
+            "off_init_paths": list(out.off_init_paths[:K]), "off_rows": list(out.off_rows[:n]), "off_paths": list(out.off_paths[:n]),
+            "off_nonce": out.off_nonce, "words": out.words}

@@ -410,6 +410,14 @@ struct tmx_ctx {
   bool fri_valid = false;
   bool fri_deep = false;  // the last prove was a DEEP prove (its zeta sits in d_fri: tmx_deep_last_zeta)
   uint32_t fri_pow_bits = 0;  // non-zero: the last prove was a grinding prove (the search's two words sit in d_fri: tmx_pow_last)
+  // the commit set (tmx_trace_commit_set_device): several sections committed side by side in a scratch of its own -- per oracle its pre-LDE
+  // columns | extended columns | tree levels -- in the oracle order of the batch proof.  Independent of last_commit and d_commit.
+  void* d_set = nullptr;
+  size_t set_bytes = 0;
+  struct SetRec {
+    bool valid; uint32_t n_oracles, log_blowup, cap_height; uint64_t root, shift;
+    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; } o[8];
+  } set = {};
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1396,6 +1404,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->d_fri) (void)hipFree(c->d_fri);
   if (c->d_deepv) (void)hipFree(c->d_deepv);
+  if (c->d_set) (void)hipFree(c->d_set);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
     if (sl.d) (void)hipFree(sl.d);
@@ -3551,6 +3560,436 @@ int32_t tmx_pow_last(tmx_ctx* c, uint64_t* nonce, uint64_t* tried) {
   if (w[0] == ~0ull)
     return fail(c, TMX_ERR_CAPACITY, "the proof-of-work search gave up after 2^(pow_bits + 6) candidates: the proof's nonce word is 2^64 - 1 and does not verify");
   return TMX_OK;
+}
+
+}  // extern "C"
+
+// ---- one DEEP-FRI proof over several oracles of different sizes, and the commit set (include/tmx.h "one DEEP-FRI proof over several oracles")
+static int32_t batch_check(tmx_ctx* c, const tmx_batch_params* p) {
+  auto bad = [&](const std::string& why) { return c ? fail(c, TMX_ERR_BAD_ARG, why) : TMX_ERR_BAD_ARG; };
+  if (!p) return bad("params is null");
+  if (p->n_oracles < 1 || p->n_oracles > TMX_BATCH_MAX_ORACLES) return bad("n_oracles must be 1 .. 8");
+  if (p->log_blowup < 1 || p->log_blowup > 6) return bad("log_blowup must be 1 .. 6");
+  if (p->arity_bits < 1 || p->arity_bits > 4) return bad("arity_bits must be 1 .. 4");
+  if (p->final_log_max > 8 || p->final_log_max + p->log_blowup > 12) return bad("final_log_max must be at most 8 and final_log_max + log_blowup at most 12");
+  if (p->n_queries < 1 || p->n_queries > FRI_MAX_QUERIES) return bad("n_queries must be 1 .. 256");
+  if (p->pow_bits > FRI_POW_MAX_BITS) return bad("pow_bits must be at most 24");
+  if (p->reserved) return bad("reserved must be 0");
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < TMX_BATCH_MAX_ORACLES; k++) {
+    const std::string who = "oracle " + std::to_string(k) + ": ";
+    if (k >= p->n_oracles) {
+      if (p->log_n[k] || p->n_cols[k]) return bad(who + "unused array entries must be zero");
+      continue;
+    }
+    if (p->log_n[k] <= p->log_blowup || p->log_n[k] > 28) return bad(who + "log_n must exceed log_blowup and be at most 28");
+    if (p->n_cols[k] < 1) return bad(who + "n_cols must be at least 1");
+    if (k && p->log_n[k] > p->log_n[k - 1]) return bad(who + "the oracles must be ordered by non-increasing log_n");
+    total += p->n_cols[k];
+  }
+  if (p->cap_height > p->log_n[0]) return bad("cap_height must not exceed log_n of the first oracle");
+  if (total > TMX_DEEP_MAX_COLS) return bad("the oracles must have at most 2^24 columns in all");
+  return TMX_OK;
+}
+
+static void batch_layout(const tmx_batch_params& p, tmx_batch_layout& L) {
+  std::memset(&L, 0, sizeof L);
+  const uint32_t K = p.n_oracles;
+  uint32_t sizes[TMX_BATCH_MAX_ORACLES];
+  for (uint32_t k = 0; k < K; k++) {
+    if (k && p.log_n[k] != p.log_n[k - 1]) L.n_groups++;
+    L.group_of[k] = L.n_groups;
+    sizes[L.n_groups] = p.log_n[k];
+    L.cap_height_of[k] = std::min(p.cap_height, p.log_n[k]);
+  }
+  L.n_groups++;
+  uint32_t d = p.log_n[0] - p.log_blowup;
+  for (uint32_t g = 0; g + 1 < L.n_groups; g++) {
+    uint32_t gap = sizes[g] - sizes[g + 1];
+    while (gap > 0) {
+      const uint32_t b = std::min(p.arity_bits, gap);
+      L.layer_bits[L.n_layers++] = b;
+      gap -= b;
+      d -= b;
+    }
+    L.layer_enter[L.n_layers - 1] = g + 1;  // (the fold of this layer produces the layer of group g + 1's size)
+  }
+  while (d > p.final_log_max) {
+    const uint32_t b = std::min(p.arity_bits, d - p.final_log_max);
+    L.layer_bits[L.n_layers++] = b;
+    d -= b;
+  }
+  L.final_log = d;
+  uint64_t w = 0;
+  for (uint32_t k = 0; k < K; k++) {
+    L.off_open[k] = w;
+    w += 4ull << deep_log_r(p.n_cols[k]);
+  }
+  uint32_t lg = p.log_n[0];
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    L.layer_cap_height[l] = std::min(p.cap_height, lg);
+    L.off_caps[l] = w;
+    w += 4ull << L.layer_cap_height[l];
+  }
+  L.off_final = w; w += 2ull << L.final_log;
+  L.off_indices = w; w += p.n_queries;
+  for (uint32_t k = 0; k < K; k++) {
+    L.off_init_rows[k] = w; w += (uint64_t)p.n_queries * p.n_cols[k];
+    L.off_init_paths[k] = w; w += (uint64_t)p.n_queries * (p.log_n[k] - L.cap_height_of[k]) * 4;
+  }
+  lg = p.log_n[0];
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    L.off_rows[l] = w; w += (uint64_t)p.n_queries * (2ull << L.layer_bits[l]);
+    L.off_paths[l] = w; w += (uint64_t)p.n_queries * (lg - L.layer_cap_height[l]) * 4;
+  }
+  L.off_nonce = w;
+  if (p.pow_bits) w++;
+  L.words = w;
+}
+
+// The geometry of a batch proof: FRI's (over the largest oracle's domain and the batch schedule; offsets absolute in the proof) and the
+// oracle table
+static FriGeom batch_geom(const tmx_batch_params& p, const tmx_batch_layout& L, uint64_t root_2_32, uint64_t shift) {
+  tmx_fri_params fp = {p.log_n[0], p.n_cols[0], p.cap_height, p.log_blowup, p.arity_bits, p.final_log_max, p.n_queries, 0};
+  tmx_fri_layout FL;
+  std::memset(&FL, 0, sizeof FL);
+  FL.n_layers = L.n_layers; FL.final_log = L.final_log;
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    FL.layer_bits[l] = L.layer_bits[l]; FL.layer_cap_height[l] = L.layer_cap_height[l];
+    FL.off_caps[l] = L.off_caps[l]; FL.off_rows[l] = L.off_rows[l]; FL.off_paths[l] = L.off_paths[l];
+  }
+  FL.off_final = L.off_final; FL.off_indices = L.off_indices;
+  FriGeom G = fri_geom(fp, FL, root_2_32, shift);
+  G.pow_bits = p.pow_bits;
+  G.off_nonce = L.off_nonce;
+  G.n_oracles = p.n_oracles; G.n_groups = L.n_groups;
+  const uint64_t head[7] = {(1ull << 32) + p.n_oracles, p.log_blowup, p.cap_height, p.arity_bits, p.final_log_max, p.n_queries, p.pow_bits};
+  std::memcpy(G.batch_head, head, sizeof head);
+  uint32_t off = 0, cap_at = 0;
+  for (uint32_t k = 0; k < p.n_oracles; k++) {
+    G.o_log_n[k] = p.log_n[k]; G.o_n_cols[k] = p.n_cols[k]; G.o_cap_h[k] = L.cap_height_of[k]; G.o_log_r[k] = deep_log_r(p.n_cols[k]);
+    G.o_group[k] = L.group_of[k]; G.o_alpha_off[k] = off; G.o_cap_at[k] = cap_at;
+    G.o_w[k] = gl_pow_host(root_2_32, 1ull << (32 - p.log_n[k]));
+    G.o_omega[k] = gl_pow_host(G.o_w[k], 1ull << p.log_blowup);
+    G.o_off_open[k] = L.off_open[k]; G.o_off_rows[k] = L.off_init_rows[k]; G.o_off_paths[k] = L.off_init_paths[k];
+    off += p.n_cols[k];
+    cap_at += 4u << L.cap_height_of[k];
+  }
+  G.total_cols = off;
+  for (uint32_t l = 0; l < L.n_layers; l++) G.enter[l] = L.layer_enter[l];
+  return G;
+}
+
+// What a batch prove reads: per oracle its extended columns, its tree, and the columns its openings are evaluated from (DeepSrc)
+struct BatchSrc { const uint64_t* cols[TMX_BATCH_MAX_ORACLES]; const uint64_t* levels[TMX_BATCH_MAX_ORACLES]; DeepSrc deep[TMX_BATCH_MAX_ORACLES]; };
+
+// Validated by the caller.  The stages are DEEP's, run per oracle (evaluation, openings block and its tree) and per group (combine of every
+// oracle of the group into ONE buffer, the Y sums, one quotient pass), then ONE set of layers whose folds take the smaller groups in.
+static int32_t batch_prove(tmx_ctx* c, const tmx_batch_params& p, const BatchSrc& src, uint64_t root_2_32, uint64_t shift, uint64_t* proof,
+                           void* hip_stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  tmx_batch_layout L;
+  batch_layout(p, L);
+  const FriGeom G = batch_geom(p, L, root_2_32, shift);
+  const uint32_t K = p.n_oracles;
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  int32_t st = poseidon_ready(c, s);
+  if (st) return st;
+  // scratch (u64 words): transcript state 32 | challenges 64 | degree flag 8 | the K caps | the K openings roots | alpha powers (C + 1) |
+  // leaf indices | Y sums [G][8] | layers 0 .. L | Q^(g) of groups 1 .. G - 1 | layer trees | weights | partial sums | an openings tree
+  const uint64_t nq = p.n_queries;
+  uint64_t at = 104;
+  const uint64_t o_caps = at; at += G.o_cap_at[K - 1] + (4ull << G.o_cap_h[K - 1]);
+  const uint64_t o_roots = at; at += 4ull * K;
+  const uint64_t o_apow = at; at += 2ull * (G.total_cols + 1);
+  const uint64_t o_qidx = at; at += L.n_layers * nq;
+  const uint64_t o_y = at; at += 8ull * L.n_groups;
+  uint64_t o_layer[FRI_MAX_LAYERS + 1], o_lev[FRI_MAX_LAYERS], o_q[TMX_BATCH_MAX_ORACLES] = {};
+  uint32_t g_log[TMX_BATCH_MAX_ORACLES] = {}, g_enter_layer[TMX_BATCH_MAX_ORACLES] = {};
+  uint32_t lg = p.log_n[0];
+  for (uint32_t l = 0; l <= L.n_layers; l++) {
+    o_layer[l] = at; at += 2ull << lg;
+    if (l < L.n_layers) lg -= L.layer_bits[l];
+  }
+  for (uint32_t k = 0; k < K; k++) g_log[L.group_of[k]] = p.log_n[k];
+  o_q[0] = o_layer[0];
+  for (uint32_t g = 1; g < L.n_groups; g++) { o_q[g] = at; at += 2ull << g_log[g]; }
+  for (uint32_t l = 0; l < L.n_layers; l++)
+    if (L.layer_enter[l]) g_enter_layer[L.layer_enter[l]] = l;
+  lg = p.log_n[0];
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    o_lev[l] = at; at += 4 * tmx_poseidon_merkle_digests(lg, L.layer_cap_height[l]);
+  }
+  uint64_t part_words = 0, olev_words = 0;
+  for (uint32_t k = 0; k < K; k++) {
+    part_words = std::max<uint64_t>(part_words, deep_eval_tiles(p.log_n[k] - p.log_blowup) * p.n_cols[k] * 4);
+    olev_words = std::max<uint64_t>(olev_words, 4 * tmx_poseidon_merkle_digests(G.o_log_r[k], 0));
+  }
+  const uint64_t o_wt = at; at += 2ull << (p.log_n[0] - p.log_blowup);
+  const uint64_t o_part = at; at += part_words;
+  const uint64_t o_olev = at; at += olev_words;
+  if (c->fri_bytes < at * 8) {
+    if (c->d_fri) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_fri)); c->d_fri = nullptr; c->fri_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_fri, at * 8));
+    c->fri_bytes = at * 8;
+  }
+  for (auto& e : c->ev_fri)
+    if (!e) HIPCK(c, hipEventCreate(&e));
+  c->fri_valid = false;
+  c->fri_deep = true;
+  c->fri_pow_bits = p.pow_bits;
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_fri);
+  uint64_t *state = W, *chal = W + 32, *apow = W + o_apow, *qidx = W + o_qidx;
+  c->fri_flag_off = 96 * 8;
+  auto launched = [&](int rc, const char* what) { return rc ? fail(c, TMX_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc)) : TMX_OK; };
+  auto transcript = [&](int phase, uint32_t layer, const uint64_t* in) {
+    return launched(launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, phase, layer, in, proof, state, chal, qidx, s), "k_fri_transcript");
+  };
+
+  HIPCK(c, hipEventRecord(c->ev_fri[0], s));
+  for (uint32_t k = 0; k < K; k++) {
+    const uint64_t nd = tmx_poseidon_merkle_digests(p.log_n[k], G.o_cap_h[k]), nc = 1ull << G.o_cap_h[k];
+    HIPCK(c, hipMemcpyAsync(W + o_caps + G.o_cap_at[k], src.levels[k] + 4 * (nd - nc), nc * 32, hipMemcpyDeviceToDevice, s));
+  }
+  if ((st = transcript(7, 0, W + o_caps))) return st;
+  const uint64_t P = 0xffffffff00000001ull;
+  const uint64_t* zeta = chal + FRI_ZETA_AT;
+  // the openings, oracle by oracle: one weights table per distinct size (equal sizes are adjacent), the pass over the oracle's columns, its
+  // block of the openings section, that block's tree and its root
+  for (uint32_t k = 0; k < K; k++) {
+    const DeepSrc& d = src.deep[k];
+    const uint32_t log_sub = p.log_n[k] - p.log_blowup, log_r = G.o_log_r[k];
+    if (k == 0 || p.log_n[k] != p.log_n[k - 1] || d.s != src.deep[k - 1].s) {
+      const uint64_t s_n = gl_pow_host(d.s, 1ull << log_sub);
+      const uint64_t k_inv = gl_pow_host((uint64_t)(((unsigned __int128)(1ull << log_sub) * s_n) % P), P - 2);
+      if ((st = launched(launch_deep_weights(log_sub, d.s, G.o_omega[k], s_n, k_inv, zeta, W + o_wt, s), "k_deep_weights"))) return st;
+    }
+    uint64_t* open = proof + L.off_open[k];
+    if ((st = launched(launch_deep_eval(log_sub, d.log_col, d.stride_log, p.n_cols[k], d.cols, W + o_wt, W + o_part, s), "k_deep_eval"))) return st;
+    if ((st = launched(launch_deep_open(log_sub, p.n_cols[k], log_r, W + o_part, open, s), "k_deep_open"))) return st;
+    if ((st = tmx_poseidon_merkle_device(c, log_r, 4, open, 0, W + o_olev, hip_stream))) return st;
+    HIPCK(c, hipMemcpyAsync(W + o_roots + 4 * k, W + o_olev + 4 * (tmx_poseidon_merkle_digests(log_r, 0) - 1), 32, hipMemcpyDeviceToDevice, s));
+  }
+  if ((st = transcript(8, 0, W + o_roots))) return st;
+  if ((st = launched(launch_fri_alpha_powers(G.total_cols + 1, chal, apow, s), "k_fri_alpha_powers"))) return st;
+  // every oracle's columns into its group's buffer (the first of a group writes, the others add), the alpha offset in the table pointer
+  for (uint32_t k = 0; k < K; k++) {
+    uint64_t* q = W + o_q[L.group_of[k]];
+    const bool first = k == 0 || L.group_of[k] != L.group_of[k - 1];
+    const int rc = first ? launch_fri_combine(p.log_n[k], p.n_cols[k], src.cols[k], apow + 2ull * G.o_alpha_off[k], q, s)
+                         : launch_fri_combine_add(p.log_n[k], p.n_cols[k], src.cols[k], apow + 2ull * G.o_alpha_off[k], q, s);
+    if ((st = launched(rc, "k_fri_combine"))) return st;
+  }
+  if ((st = launched(launch_batch_y(G, proof, apow, W + o_y, s), "k_batch_y"))) return st;
+  for (uint32_t k = 0; k < K; k++) {
+    if (k && L.group_of[k] == L.group_of[k - 1]) continue;
+    const uint32_t g = L.group_of[k];
+    if ((st = launched(launch_deep_quotient(p.log_n[k], G.s0, G.o_w[k], G.o_omega[k], zeta, W + o_y + 6 * g, W + o_q[g], s), "k_deep_quotient"))) return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[1], s));
+  lg = p.log_n[0];
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    const uint32_t b = L.layer_bits[l], h = L.layer_cap_height[l];
+    lg -= b;
+    st = tmx_poseidon_merkle_device(c, lg, 2u << b, W + o_layer[l], h, W + o_lev[l], hip_stream);
+    if (st) return st;
+    const uint64_t nd = tmx_poseidon_merkle_digests(lg, h);
+    HIPCK(c, hipMemcpyAsync(proof + L.off_caps[l], W + o_lev[l] + 4 * (nd - (1ull << h)), 32ull << h, hipMemcpyDeviceToDevice, s));
+    if ((st = transcript(1, l, W + o_caps))) return st;
+    const int rc = L.layer_enter[l] ? launch_fri_fold_add(lg, b, G.s_inv[l], G.w_inv[l], G.g[l], chal + 2 + 2 * l, W + o_layer[l], W + o_q[L.layer_enter[l]],
+                                                          W + o_layer[l + 1], s)
+                                    : launch_fri_fold(lg, b, G.s_inv[l], G.w_inv[l], G.g[l], chal + 2 + 2 * l, W + o_layer[l], W + o_layer[l + 1], s);
+    if ((st = launched(rc, "k_fri_fold"))) return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[2], s));
+  if ((st = launched(launch_fri_final(lg, L.final_log, G.w_fin_inv, G.s_fin_inv, G.m_fin_inv, W + o_layer[L.n_layers], proof + L.off_final, W + 96, s),
+                     "k_fri_final")))
+    return st;
+  if (!p.pow_bits) {
+    if ((st = transcript(2, 0, W + o_caps))) return st;
+  } else {
+    if ((st = transcript(5, 0, W + o_caps))) return st;
+    if ((st = launched(launch_fri_grind(c->d_pos_consts, c->pos_mode, p.pow_bits, state, chal + FRI_POW_AT, s), "k_fri_grind"))) return st;
+    if ((st = transcript(6, 0, W + o_caps))) return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[3], s));
+  // the openings: oracle k at idx mod M_k -- the drawn indices for group 0, the leaf indices of the layer it entered for a later group
+  for (uint32_t k = 0; k < K; k++) {
+    const uint32_t g = L.group_of[k];
+    const uint64_t* idx = g ? qidx + g_enter_layer[g] * nq : proof + L.off_indices;
+    if ((st = launched(launch_merkle_open(p.log_n[k], p.n_cols[k], src.cols[k], p.log_n[k] - G.o_cap_h[k], src.levels[k], p.n_queries, idx,
+                                          proof + L.off_init_rows[k], proof + L.off_init_paths[k], false, s), "k_merkle_open")))
+      return st;
+  }
+  lg = p.log_n[0];
+  for (uint32_t l = 0; l < L.n_layers; l++) {
+    lg -= L.layer_bits[l];
+    if ((st = launched(launch_merkle_open(lg, 2u << L.layer_bits[l], W + o_layer[l], lg - L.layer_cap_height[l], W + o_lev[l], p.n_queries,
+                                          qidx + l * nq, proof + L.off_rows[l], proof + L.off_paths[l], false, s), "k_merkle_open")))
+      return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_fri[4], s));
+  c->fri_valid = true;
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_batch_layout_of(const tmx_batch_params* p, tmx_batch_layout* out) {
+  if (!out || batch_check(nullptr, p)) return TMX_ERR_BAD_ARG;
+  batch_layout(*p, *out);
+  return TMX_OK;
+}
+
+int32_t tmx_batch_prove_device(tmx_ctx* c, const tmx_batch_params* p, const uint64_t* const d_cols[], const uint64_t* const d_levels[], uint64_t* d_proof,
+                               void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (!d_cols || !d_levels || !d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_levels and d_proof must be set");
+  BatchSrc src = {};
+  for (uint32_t k = 0; k < p->n_oracles; k++) {
+    if (!d_cols[k] || !d_levels[k]) return fail(c, TMX_ERR_BAD_ARG, "oracle " + std::to_string(k) + ": d_cols and d_levels must be set");
+    src.cols[k] = d_cols[k];
+    src.levels[k] = d_levels[k];
+    src.deep[k] = {d_cols[k], p->log_n[k], p->log_blowup, c->ntt_shift % 0xffffffff00000001ull};
+  }
+  return batch_prove(c, *p, src, c->ntt_root, c->ntt_shift, d_proof, hip_stream);
+}
+
+int32_t tmx_batch_verify_device(tmx_ctx* c, const tmx_batch_params* p, const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (!d_caps || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_caps, d_proof and d_ok must be set");
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // the verifier scratch: the K roots, then one openings tree at a time (its root copied out before the next one is built)
+  uint64_t tree = 0;
+  for (uint32_t k = 0; k < p->n_oracles; k++) tree = std::max<uint64_t>(tree, tmx_poseidon_merkle_digests(G.o_log_r[k], 0));
+  const size_t want = (4ull * TMX_BATCH_MAX_ORACLES + 4 * tree) * 8;
+  if (c->deepv_bytes < want) {
+    if (c->d_deepv) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_deepv)); c->d_deepv = nullptr; c->deepv_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_deepv, want));
+    c->deepv_bytes = want;
+  }
+  uint64_t* roots = reinterpret_cast<uint64_t*>(c->d_deepv);
+  uint64_t* lev = roots + 4 * TMX_BATCH_MAX_ORACLES;
+  for (uint32_t k = 0; k < p->n_oracles; k++) {
+    if ((st = tmx_poseidon_merkle_device(c, G.o_log_r[k], 4, d_proof + L.off_open[k], 0, lev, hip_stream))) return st;
+    HIPCK(c, hipMemcpyAsync(roots + 4 * k, lev + 4 * (tmx_poseidon_merkle_digests(G.o_log_r[k], 0) - 1), 32, hipMemcpyDeviceToDevice, s));
+  }
+  const int rc = launch_fri_verify(c->d_pos_consts, c->pos_mode, G, d_caps, d_proof, nullptr, roots, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_verify launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t log_blowup, uint32_t cap_height,
+                                    const void* d_trace_rows, uint64_t* d_caps, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  c->set.valid = false;  // (set again at the end: a call that fails anywhere leaves no set)
+  if (!d_trace_rows || !d_caps || n_proofs == 0) return TMX_ERR_BAD_ARG;
+  const uint32_t tables = TMX_TRACE_LADDERS | TMX_TRACE_SHA512 | TMX_TRACE_SHA256 | TMX_TRACE_TREE | TMX_TRACE_HEADER;
+  if (sections == 0 || (sections & ~tables)) return fail(c, TMX_ERR_BAD_ARG, "sections must be a non-empty mask of row tables of the trace block");
+  tmx_ctx::SetRec r = {};
+  struct Geo { uint64_t off, rows; uint32_t width, log_n; } geo[8];
+  for (uint32_t bit = 1; bit <= TMX_TRACE_HEADER; bit <<= 1) {
+    if (!(sections & bit)) continue;
+    uint32_t log_n = 0, width = 0;
+    if (tmx_trace_commit_shape(kind, c->cfg.n_max, bit, &log_n, &width)) return fail(c, TMX_ERR_BAD_ARG, "section must be one row table of the trace block");
+    if (log_n + log_blowup > TMX_NTT_MAX_LOG) return fail(c, TMX_ERR_CAPACITY, "log_rows + log_blowup exceeds TMX_NTT_MAX_LOG");
+    if ((uint64_t)n_proofs * width > 0xffffffffull) return fail(c, TMX_ERR_CAPACITY, "too many columns");
+    // insertion by decreasing log_rows; the bits come in ascending order, so ties keep ascending section bits
+    uint32_t at = r.n_oracles++;
+    while (at && r.o[at - 1].log_m < log_n + log_blowup) { r.o[at] = r.o[at - 1]; geo[at] = geo[at - 1]; at--; }
+    r.o[at] = {bit, log_n + log_blowup, n_proofs * width, 0, 0, 0};
+    geo[at].width = width; geo[at].log_n = log_n;
+    (void)trace_section_geom((uint32_t)kind, c->cfg.n_max, bit, &geo[at].off, &geo[at].rows, &width);
+  }
+  if (cap_height > r.o[0].log_m) return fail(c, TMX_ERR_BAD_ARG, "cap_height exceeds the height of the largest tree");
+  size_t want = 0, lde_max = 0;
+  for (uint32_t k = 0; k < r.n_oracles; k++) {
+    auto& o = r.o[k];
+    const size_t cols_b = ((size_t)o.n_cols << geo[k].log_n) * 8, lde_b = ((size_t)o.n_cols << o.log_m) * 8;
+    o.cols_off = want; o.lde_off = want + cols_b; o.lev_off = want + cols_b + lde_b;
+    want = o.lev_off + (size_t)tmx_poseidon_merkle_digests(o.log_m, std::min(cap_height, o.log_m)) * 32;
+    lde_max = std::max(lde_max, lde_b);
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if (c->set_bytes < want) {
+    if (c->d_set) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set)); c->d_set = nullptr; c->set_bytes = 0; }
+    size_t free_b = 0, total_b = 0;
+    // (the rule of tmx_trace_commit_device summed over the sections; the LDE's own scratch is twice the largest extended section)
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + 2 * lde_max > free_b + c->ntt_tmp_bytes)
+      return fail(c, TMX_ERR_CAPACITY, "commit set needs " + std::to_string((want + 2 * lde_max) >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
+    HIPCK(c, hipMalloc(&c->d_set, want));
+    c->set_bytes = want;
+  }
+  uint8_t* base = reinterpret_cast<uint8_t*>(c->d_set);
+  uint64_t cap_at = 0;
+  for (uint32_t k = 0; k < r.n_oracles; k++) {
+    const auto& o = r.o[k];
+    uint64_t* cols = reinterpret_cast<uint64_t*>(base + o.cols_off);
+    uint64_t* lde = reinterpret_cast<uint64_t*>(base + o.lde_off);
+    uint64_t* levels = reinterpret_cast<uint64_t*>(base + o.lev_off);
+    const uint32_t h = std::min(cap_height, o.log_m);
+    const int rc = launch_trace_to_columns(d_trace_rows, trace_elems((uint32_t)kind, c->cfg.n_max), geo[k].off, geo[k].rows, geo[k].width, geo[k].log_n, n_proofs, cols, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_trace_to_columns launch: ") + hipGetErrorString((hipError_t)rc));
+    int32_t st = tmx_lde_goldilocks_device(c, geo[k].log_n, log_blowup, o.n_cols, cols, lde, hip_stream);
+    if (st) return st;
+    if ((st = tmx_poseidon_merkle_device(c, o.log_m, o.n_cols, lde, h, levels, hip_stream))) return st;
+    const uint64_t n_dig = tmx_poseidon_merkle_digests(o.log_m, h), n_cap = (uint64_t)1 << h;
+    HIPCK(c, hipMemcpyAsync(d_caps + cap_at, levels + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+    cap_at += 4 * n_cap;
+  }
+  r.valid = true; r.log_blowup = log_blowup; r.cap_height = cap_height; r.root = c->ntt_root; r.shift = c->ntt_shift;
+  c->set = r;
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_shape(const tmx_ctx* c, tmx_batch_params* out, uint32_t section_of[TMX_BATCH_MAX_ORACLES]) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (!c->set.valid)
+    return fail(const_cast<tmx_ctx*>(c), TMX_ERR_BAD_ARG, "no commit set: no tmx_trace_commit_set_device call has completed since the context was created or since the last failed one");
+  if (out) {
+    std::memset(out, 0, sizeof *out);
+    out->n_oracles = c->set.n_oracles; out->log_blowup = c->set.log_blowup; out->cap_height = c->set.cap_height;
+  }
+  for (uint32_t k = 0; k < TMX_BATCH_MAX_ORACLES; k++) {
+    const bool live = k < c->set.n_oracles;
+    if (out && live) { out->log_n[k] = c->set.o[k].log_m; out->n_cols[k] = c->set.o[k].n_cols; }
+    if (section_of) section_of[k] = live ? c->set.o[k].section : 0;
+  }
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p, uint64_t* d_proof, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if ((st = tmx_trace_commit_set_shape(c, nullptr, nullptr))) return st;
+  const tmx_ctx::SetRec& r = c->set;
+  bool same = p->n_oracles == r.n_oracles && p->log_blowup == r.log_blowup && p->cap_height == r.cap_height;
+  for (uint32_t k = 0; same && k < r.n_oracles; k++) same = p->log_n[k] == r.o[k].log_m && p->n_cols[k] == r.o[k].n_cols;
+  if (!same) return fail(c, TMX_ERR_BAD_ARG, "batch parameters do not match the commit set (tmx_trace_commit_set_shape gives its oracle list, log_blowup and cap_height)");
+  if (!d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_proof is null");
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
+  BatchSrc src = {};
+  for (uint32_t k = 0; k < r.n_oracles; k++) {
+    src.cols[k] = reinterpret_cast<const uint64_t*>(base + r.o[k].lde_off);
+    src.levels[k] = reinterpret_cast<const uint64_t*>(base + r.o[k].lev_off);
+    // the openings read the pre-LDE columns (n_cols x N_k, on the subgroup itself), as tmx_trace_commit_deep_device does
+    src.deep[k] = {reinterpret_cast<const uint64_t*>(base + r.o[k].cols_off), r.o[k].log_m - r.log_blowup, 0, 1};
+  }
+  return batch_prove(c, *p, src, r.root, r.shift, d_proof, hip_stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 
 namespace tmx {
 
-constexpr uint32_t FRI_MAX_LAYERS = 28, FRI_MAX_QUERIES = 256;
+constexpr uint32_t FRI_MAX_LAYERS = 28, FRI_MAX_QUERIES = 256, FRI_MAX_ORACLES = 8;
 
 // Everything a FRI kernel needs to know about one proof, built on the host from the parameters, their schedule and the domain (passed
 // by value: no upload).  Layer l's domain: s_l, w_l; the fold needs s_l^-1, w_l^-1 and g_l = w_l^-M_(l+1).  Offsets in u64 words.
@@ -23,6 +23,17 @@ struct FriGeom {
   // FRI part
   uint32_t pow_bits;
   uint64_t off_nonce;
+  // the mixed-size batch proof (include/tmx.h "one DEEP-FRI proof over several oracles"): n_oracles = 0 for the single-oracle proofs above.
+  // Oracle k: its shape, its group (the oracles of one size), alpha_off = n_cols_0 + ... + n_cols_(k-1), its own domain generator w and
+  // trace generator omega (the coset shift s0 is common), and where its openings block, rows and paths sit in the proof.  total_cols = C.
+  // enter[l] = g >= 1: the fold of layer l adds beta_l^(a_l) Q^(g) (layer l + 1 has the size of group g); 0: a plain fold.
+  // batch_head: the words the transcript starts with (2^32 + K, the six scalars); the (log_n_k, n_cols_k) pairs come from the table.
+  uint32_t n_oracles, n_groups, total_cols;
+  uint64_t batch_head[7];
+  uint32_t o_log_n[FRI_MAX_ORACLES], o_n_cols[FRI_MAX_ORACLES], o_cap_h[FRI_MAX_ORACLES], o_log_r[FRI_MAX_ORACLES], o_group[FRI_MAX_ORACLES],
+      o_alpha_off[FRI_MAX_ORACLES], o_cap_at[FRI_MAX_ORACLES];  // (o_cap_at: word offset of oracle k's cap in the concatenated caps)
+  uint64_t o_w[FRI_MAX_ORACLES], o_omega[FRI_MAX_ORACLES], o_off_open[FRI_MAX_ORACLES], o_off_rows[FRI_MAX_ORACLES], o_off_paths[FRI_MAX_ORACLES];
+  uint32_t enter[FRI_MAX_LAYERS];
 };
 
 // where the DEEP scratch keeps zeta between launches: chal[FRI_ZETA_AT], chal[FRI_ZETA_AT + 1] (after alpha and the betas)
@@ -35,9 +46,14 @@ constexpr uint32_t FRI_POW_AT = FRI_ZETA_AT + 2, FRI_POW_SLACK_BITS = 6, FRI_POW
 int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, void* stream);
 // layer 0, planar: out[i] = sum_c apow[c].c0 cols[c][i], out[M + i] = sum_c apow[c].c1 cols[c][i]  (M = 2^log_m, canonical)
 int launch_fri_combine(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream);
+// the same pass ADDED to what d_out holds (canonical): the second and later oracles of a group, d_apow already offset to alpha^off_k
+int launch_fri_combine_add(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream);
 // layer l (planar, M_l points) -> layer l + 1 (planar, M_l >> bits), with beta at d_beta
 int launch_fri_fold(uint32_t log_m_next, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in,
                     void* d_out, void* stream);
+// the fold that takes a group in: as launch_fri_fold, plus beta^(2^bits) d_add[i] at every output index i (d_add planar, 2^log_m_next points)
+int launch_fri_fold_add(uint32_t log_m_next, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in,
+                        const void* d_add, void* d_out, void* stream);
 // the final polynomial of the last layer (planar, 2^log_m points, log_m <= 12): coefficients into d_coef interleaved (c0, c1), the low
 // 2^final_log of them; d_flag[0] = 1 if the others are all zero, else 0
 int launch_fri_final(uint32_t log_m, uint32_t final_log, uint64_t w_inv, uint64_t s_inv, uint64_t m_inv, const void* d_in, void* d_coef,
@@ -55,6 +71,9 @@ int launch_deep_eval(uint32_t log_sub, uint32_t log_col, uint32_t stride_log, ui
 int launch_deep_open(uint32_t log_sub, uint32_t n_cols, uint32_t log_r, const void* d_part, void* d_open, void* stream);
 // Y_0, Y_1 = sum_c alpha^c y_(c,k) (apow: k_fri_alpha_powers' table) and alpha^n_cols into d_y[6], alpha at d_alpha
 int launch_deep_y(uint32_t n_cols, uint32_t log_r, const void* d_open, const void* d_apow, const void* d_alpha, void* d_y, void* stream);
+// the batch proof's Y sums, one workgroup per group g: d_y[6 g ..] = sum over the group's oracles k of sum_c alpha^(off_k + c) y_(k,c,j)
+// (j = 0, 1; the openings blocks sit in d_proof at G.o_off_open[k]), then alpha^C.  d_apow: the table of C + 1 powers.
+int launch_batch_y(const FriGeom& G, const void* d_proof, const void* d_apow, void* d_y, void* stream);
 // layer 0 (planar, 2^log_m points of s w^i) in place: f_0 = (F - Y_0) / (x - z_0) + alpha^n (F - Y_1) / (x - z_1)
 int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const void* d_zeta, const void* d_y, void* d_layer, void* stream);
 
@@ -62,6 +81,8 @@ int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_
 // alpha (2 u64) then beta_l (2 u64 each).  phase 0: parameters + commit cap -> alpha; phase 1: cap of `layer` (in the proof) -> beta_layer;
 // phase 2: final coefficients -> query indices into the proof and each layer's leaf indices into d_qidx[n_layers][n_queries];
 // DEEP: phase 3: parameters, the word 2, commit cap -> zeta (chal[FRI_ZETA_AT]); phase 4: the openings root at d_commit_cap -> alpha.
+// The batch proof: phase 7: the batch start over the K caps concatenated at d_commit_cap -> zeta; phase 8: the K openings roots (4 K words
+// at d_commit_cap) -> alpha.  The other phases serve it unchanged (G.log_n = the largest oracle's).
 // Grinding splits phase 2: phase 5 (2a): final coefficients and pow_bits observed, the duplex left in d_state, the search's words reset;
 // phase 6 (2b): the nonce the search left -> the proof, observed, r drawn, then the indices as phase 2.
 int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
@@ -70,7 +91,8 @@ int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int 
 // d_pow[0] (atomic minimum), the candidates evaluated added to d_pow[1].  One launch that ends itself; the grid is sized from pow_bits.
 int launch_fri_grind(const void* d_consts, int mode, uint32_t pow_bits, const void* d_state, void* d_pow, void* stream);
 // d_ok[q] for every query of the proof against d_cap (one workgroup).  G.deep: d_proof is the FRI part of a DEEP proof, d_open its
-// openings section and d_root the root of the openings tree; otherwise both are unused.
+// openings section and d_root the root of the openings tree; otherwise both are unused.  G.n_oracles: the batch proof: d_cap the K caps
+// concatenated, d_proof the whole proof, d_root the K roots (4 words each); d_open unused.
 int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, const void* d_open, const void* d_root,
                       void* d_ok, void* stream);
 

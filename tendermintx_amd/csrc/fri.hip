@@ -24,7 +24,10 @@ __global__ __launch_bounds__(256) void k_fri_alpha_powers(uint32_t n_cols, const
 // alpha^c comes through the scalar cache (s_load of the wave-uniform table entry) instead of an LDS tile.  Eight columns are loaded
 // before they are accumulated (eight loads in flight per wave).  The products are reduced (gl_mul), the sums are lazy (any representative:
 // gl_add_lazy with a canonical second operand), and the four partial sums meet in LDS -- no atomics.  Writes layer 0 planar, canonical.
+// ACC (the batch proof: the second and later oracles of a group): the row's sum is added to what `out` holds -- one more read of the
+// output per ROW, nothing per word; the oracle's alpha offset is in the table pointer, not in the loop.
 constexpr int COMBINE_WAVES = 4, COMBINE_UNROLL = 8;
+template <bool ACC>
 __global__ __launch_bounds__(64 * COMBINE_WAVES) void k_fri_combine(uint32_t log_m, uint32_t n_cols, const uint64_t* __restrict__ cols,
                                                                     const uint64_t* __restrict__ apow, uint64_t* __restrict__ out) {
   __shared__ uint64_t part[COMBINE_WAVES - 1][2][64];
@@ -33,7 +36,11 @@ __global__ __launch_bounds__(64 * COMBINE_WAVES) void k_fri_combine(uint32_t log
   const uint64_t M = 1ull << log_m, row = (uint64_t)blockIdx.x * 64 + lane;
   const uint32_t chunk = (n_cols + COMBINE_WAVES - 1) / COMBINE_WAVES;
   const uint32_t c_lo = min(n_cols, wave * chunk), c_hi = min(n_cols, c_lo + chunk);
-  uint64_t a0 = 0, a1 = 0;
+  uint64_t a0 = 0, a1 = 0, h0 = 0, h1 = 0;
+  if (ACC && wave == 0 && row < M) {  // (what the buffer holds, requested before the pass: its latency hides behind the column loop)
+    h0 = out[row];
+    h1 = out[M + row];
+  }
   if (row < M) {
     const uint64_t* p = cols + ((uint64_t)c_lo << log_m) + row;
     uint32_t c = c_lo;
@@ -66,6 +73,10 @@ __global__ __launch_bounds__(64 * COMBINE_WAVES) void k_fri_combine(uint32_t log
       a0 = gl_add(a0, gl_canon(part[w][0][lane]));
       a1 = gl_add(a1, gl_canon(part[w][1][lane]));
     }
+    if (ACC) {
+      a0 = gl_add(a0, h0);
+      a1 = gl_add(a1, h1);
+    }
     out[row] = a0;
     out[M + row] = a1;
   }
@@ -73,15 +84,23 @@ __global__ __launch_bounds__(64 * COMBINE_WAVES) void k_fri_combine(uint32_t log
 
 // One thread per leaf coset r < M' of layer l (M' = M_(l+1)): its 2^B values in registers, B radix-2 folds (fri_fold_leaf), one value of
 // layer l + 1 out.  x_0^-1 = s^-1 (w^-1)^r: one exponentiation per thread.
-template <int B>
+// ADD (the batch proof: a group of smaller oracles enters layer l + 1): the group's quotient sum at the OUTPUT index r joins the value
+// scaled by beta^(2^B), the first power the fold did not use -- one extra read of M_(l+1) values, no pass of its own.
+template <int B, bool ADD>
 __global__ __launch_bounds__(256) void k_fri_fold(uint32_t log_mn, uint64_t s_inv, uint64_t w_inv, uint64_t g, const uint64_t* __restrict__ beta,
-                                                  const uint64_t* __restrict__ in, uint64_t* __restrict__ out) {
+                                                  const uint64_t* __restrict__ in, const uint64_t* __restrict__ add, uint64_t* __restrict__ out) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, Mn = 1ull << log_mn, M = Mn << B;
   if (r >= Mn) return;
   gl2 v[1 << B];
 #pragma unroll
   for (int j = 0; j < (1 << B); j++) v[j] = {in[r + j * Mn], in[M + r + j * Mn]};
-  const gl2 f = fri_fold_leaf<B>(v, gl_mul(s_inv, gl_pow(w_inv, r)), g, {beta[0], beta[1]});
+  gl2 f = fri_fold_leaf<B>(v, gl_mul(s_inv, gl_pow(w_inv, r)), g, {beta[0], beta[1]});
+  if (ADD) {
+    gl2 bp = {beta[0], beta[1]};
+#pragma unroll
+    for (int k = 0; k < B; k++) bp = gl2_mul(bp, bp);
+    f = gl2_add(f, gl2_mul(bp, {add[r], add[Mn + r]}));
+  }
   out[r] = f.c0;
   out[Mn + r] = f.c1;
 }
@@ -239,6 +258,40 @@ __global__ __launch_bounds__(DEEP_Y_THREADS) void k_deep_y(uint32_t n_cols, uint
   }
 }
 
+// The batch proof's Y sums: workgroup g adds, over the oracles k of group g, sum_c alpha^(off_k + c) y_(k,c,j) (opening words taken mod p,
+// oracle k's planar block at proof + o_off_open[k]); y[6 g ..] = Y_0, Y_1 of the group, then alpha^C (the last entry of the table).
+__global__ __launch_bounds__(DEEP_Y_THREADS) void k_batch_y(FriGeom G, const uint64_t* __restrict__ proof, const uint64_t* __restrict__ apow,
+                                                            uint64_t* __restrict__ y) {
+  __shared__ uint64_t red[4][DEEP_Y_THREADS];
+  const uint32_t t = threadIdx.x, g = blockIdx.x;
+  gl2 s0 = {0, 0}, s1 = {0, 0};
+  for (uint32_t k = 0; k < G.n_oracles; k++) {
+    if (G.o_group[k] != g) continue;
+    const uint64_t Rr = 1ull << G.o_log_r[k];
+    const uint64_t* open = proof + G.o_off_open[k];
+    const uint64_t* ap = apow + 2ull * G.o_alpha_off[k];
+    for (uint32_t c = t; c < G.o_n_cols[k]; c += DEEP_Y_THREADS) {
+      const gl2 a = {ap[2 * c], ap[2 * c + 1]};
+      s0 = gl2_add(s0, gl2_mul(a, {gl_canon(open[c]), gl_canon(open[Rr + c])}));
+      s1 = gl2_add(s1, gl2_mul(a, {gl_canon(open[2 * Rr + c]), gl_canon(open[3 * Rr + c])}));
+    }
+  }
+  red[0][t] = s0.c0; red[1][t] = s0.c1; red[2][t] = s1.c0; red[3][t] = s1.c1;
+  for (uint32_t h = DEEP_Y_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h)
+#pragma unroll
+      for (int k = 0; k < 4; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+  }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) y[6 * g + k] = red[k][0];
+    y[6 * g + 4] = apow[2ull * G.total_cols];
+    y[6 * g + 5] = apow[2ull * G.total_cols + 1];
+  }
+}
+
 // One thread per point of D_0: layer 0 (k_fri_combine's output, canonical) rewritten in place into the DEEP quotient.
 __global__ __launch_bounds__(256) void k_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const uint64_t* __restrict__ zeta,
                                                        const uint64_t* __restrict__ y, uint64_t* __restrict__ layer) {
@@ -259,24 +312,40 @@ int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, 
 }
 int launch_fri_combine(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream) {
   const uint64_t blocks = ((1ull << log_m) + 63) / 64;
-  hipLaunchKernelGGL(k_fri_combine, dim3((uint32_t)blocks), dim3(64 * COMBINE_WAVES), 0, S_(stream), log_m, n_cols,
+  hipLaunchKernelGGL(k_fri_combine<false>, dim3((uint32_t)blocks), dim3(64 * COMBINE_WAVES), 0, S_(stream), log_m, n_cols,
                      reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_fri_combine_add(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream) {
+  const uint64_t blocks = ((1ull << log_m) + 63) / 64;
+  hipLaunchKernelGGL(k_fri_combine<true>, dim3((uint32_t)blocks), dim3(64 * COMBINE_WAVES), 0, S_(stream), log_m, n_cols,
+                     reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+template <bool ADD>
+static int fri_fold_launch(uint32_t log_mn, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in,
+                           const void* d_add, void* d_out, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_mn) + 255) / 256));
+  const uint64_t* beta = reinterpret_cast<const uint64_t*>(d_beta);
+  const uint64_t* in = reinterpret_cast<const uint64_t*>(d_in);
+  const uint64_t* add = reinterpret_cast<const uint64_t*>(d_add);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_out);
+  switch (bits) {
+    case 1: hipLaunchKernelGGL((k_fri_fold<1, ADD>), grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, add, out); break;
+    case 2: hipLaunchKernelGGL((k_fri_fold<2, ADD>), grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, add, out); break;
+    case 3: hipLaunchKernelGGL((k_fri_fold<3, ADD>), grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, add, out); break;
+    case 4: hipLaunchKernelGGL((k_fri_fold<4, ADD>), grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, add, out); break;
+    default: return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }
 int launch_fri_fold(uint32_t log_mn, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in, void* d_out,
                     void* stream) {
-  const dim3 grid((uint32_t)(((1ull << log_mn) + 255) / 256));
-  const uint64_t* beta = reinterpret_cast<const uint64_t*>(d_beta);
-  const uint64_t* in = reinterpret_cast<const uint64_t*>(d_in);
-  uint64_t* out = reinterpret_cast<uint64_t*>(d_out);
-  switch (bits) {
-    case 1: hipLaunchKernelGGL(k_fri_fold<1>, grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, out); break;
-    case 2: hipLaunchKernelGGL(k_fri_fold<2>, grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, out); break;
-    case 3: hipLaunchKernelGGL(k_fri_fold<3>, grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, out); break;
-    case 4: hipLaunchKernelGGL(k_fri_fold<4>, grid, dim3(256), 0, S_(stream), log_mn, s_inv, w_inv, g, beta, in, out); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  return fri_fold_launch<false>(log_mn, bits, s_inv, w_inv, g, d_beta, d_in, nullptr, d_out, stream);
+}
+int launch_fri_fold_add(uint32_t log_mn, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in,
+                        const void* d_add, void* d_out, void* stream) {
+  return fri_fold_launch<true>(log_mn, bits, s_inv, w_inv, g, d_beta, d_in, d_add, d_out, stream);
 }
 int launch_fri_final(uint32_t log_m, uint32_t final_log, uint64_t w_inv, uint64_t s_inv, uint64_t m_inv, const void* d_in, void* d_coef, void* d_flag,
                      void* stream) {
@@ -311,6 +380,11 @@ int launch_deep_open(uint32_t log_sub, uint32_t n_cols, uint32_t log_r, const vo
 int launch_deep_y(uint32_t n_cols, uint32_t log_r, const void* d_open, const void* d_apow, const void* d_alpha, void* d_y, void* stream) {
   hipLaunchKernelGGL(k_deep_y, dim3(1), dim3(DEEP_Y_THREADS), 0, S_(stream), n_cols, log_r, reinterpret_cast<const uint64_t*>(d_open),
                      reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<const uint64_t*>(d_alpha), reinterpret_cast<uint64_t*>(d_y));
+  return (int)hipGetLastError();
+}
+int launch_batch_y(const FriGeom& G, const void* d_proof, const void* d_apow, void* d_y, void* stream) {
+  hipLaunchKernelGGL(k_batch_y, dim3(G.n_groups), dim3(DEEP_Y_THREADS), 0, S_(stream), G, reinterpret_cast<const uint64_t*>(d_proof),
+                     reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<uint64_t*>(d_y));
   return (int)hipGetLastError();
 }
 int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_n, const void* d_zeta, const void* d_y, void* d_layer, void* stream) {

@@ -389,11 +389,29 @@ __device__ __forceinline__ gl2 chal_start_deep(FriChal& c, const PosConsts& K, c
   } while (z.c1 == 0);
   return z;
 }
+// The batch proof (include/tmx.h "one DEEP-FRI proof over several oracles"): 2^32 + K and the six scalars, the (log_n_k, n_cols_k) pairs,
+// the word 2, the K caps (concatenated at `caps`), then zeta as DEEP draws it
+template <int MODE>
+__device__ __forceinline__ gl2 chal_start_batch(FriChal& c, const PosConsts& K, const FriGeom& G, const uint64_t* __restrict__ caps) {
+  chal_init(c);
+  for (int k = 0; k < 7; k++) chal_observe<MODE>(c, K, G.batch_head[k]);
+  for (uint32_t k = 0; k < 2 * G.n_oracles; k++) chal_observe<MODE>(c, K, (k & 1) ? G.o_n_cols[k >> 1] : G.o_log_n[k >> 1]);
+  chal_observe<MODE>(c, K, 2);
+  const uint32_t last = G.n_oracles - 1;
+  chal_observe_span<MODE>(c, K, caps, G.o_cap_at[last] + (4ull << G.o_cap_h[last]));
+  gl2 z;
+  do {
+    z.c0 = chal_challenge<MODE>(c, K);
+    z.c1 = chal_challenge<MODE>(c, K);
+  } while (z.c1 == 0);
+  return z;
+}
 
 // One lane, between the prover's stages (fri.h launch_fri_transcript): the parameters and the commit cap -> alpha (phase 0), the cap of
 // `layer` -> beta_layer (phase 1), the final coefficients -> the query indices and every layer's leaf indices (phase 2).  DEEP: the start
 // with its point count and the commit cap -> zeta (phase 3), the openings root at commit_cap -> alpha (phase 4).  Grinding: phase 2 in two
 // halves around k_fri_grind: the final coefficients and pow_bits observed (phase 5), the nonce observed and r drawn -> the indices (phase 6).
+// The batch proof: its start over the K caps at commit_cap -> zeta (phase 7), the K openings roots at commit_cap -> alpha (phase 8).
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
                                                        const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
@@ -409,9 +427,13 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
     const gl2 z = chal_start_deep<MODE>(c, K, G, commit_cap);
     chal[FRI_ZETA_AT] = z.c0;
     chal[FRI_ZETA_AT + 1] = z.c1;
-  } else if (phase == 4) {
+  } else if (phase == 7) {
+    const gl2 z = chal_start_batch<MODE>(c, K, G, commit_cap);
+    chal[FRI_ZETA_AT] = z.c0;
+    chal[FRI_ZETA_AT + 1] = z.c1;
+  } else if (phase == 4 || phase == 8) {
     chal_load(c, state);
-    chal_observe_span<MODE>(c, K, commit_cap, 4);
+    chal_observe_span<MODE>(c, K, commit_cap, phase == 4 ? 4 : 4 * G.n_oracles);
     chal[0] = chal_challenge<MODE>(c, K);
     chal[1] = chal_challenge<MODE>(c, K);
   } else if (phase == 1) {
@@ -500,17 +522,27 @@ __device__ __forceinline__ gl2 fri_fold_row(const uint64_t* __restrict__ row, ui
 // query's v_0 is the DEEP layer 0 at its point instead of the plain combination.
 // G.pow_bits != 0 (a grinding proof): lane 0 also observes pow_bits and the nonce word and draws r in front of the indices; every query is
 // rejected if the nonce is not canonical or r has fewer than pow_bits leading zero bits.
-template <int MODE, bool DEEP>
+// BATCH (the mixed-size batch proof): `cap` is the K caps concatenated, `proof` the whole proof (its offsets are absolute), `root` the K
+// openings roots.  The workgroup forms the Y sums group by group; a query checks every oracle's row at idx mod M_k against its cap, forms
+// Q^(g) of every group from the opened rows at the oracle's OWN point s w_k^(idx mod M_k), starts from Q^(0) and adds beta_l^(a_l) Q^(g)
+// behind the fold of the layer that group g enters.
+template <int MODE, bool DEEP, bool BATCH>
 __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* __restrict__ consts, FriGeom G, const uint64_t* __restrict__ cap,
                                                                 const uint64_t* __restrict__ proof, const uint64_t* __restrict__ open,
                                                                 const uint64_t* __restrict__ root, uint32_t* __restrict__ ok) {
   __shared__ uint64_t s_chal[2 + 2 * FRI_MAX_LAYERS], s_idx[FRI_MAX_QUERIES];
-  __shared__ uint64_t s_deep[DEEP ? 4 : 1][DEEP ? FRI_MAX_QUERIES : 1], s_z[DEEP ? 4 : 1];
+  __shared__ uint64_t s_deep[DEEP || BATCH ? 4 : 1][DEEP || BATCH ? FRI_MAX_QUERIES : 1], s_z[DEEP || BATCH ? 4 : 1];
+  __shared__ uint64_t s_y[BATCH ? FRI_MAX_ORACLES : 1][4];
   __shared__ uint32_t s_pow_ok;
   const PosConsts K = pos_consts(consts);
   if (threadIdx.x == 0) {
     FriChal c;
-    if constexpr (DEEP) {
+    if constexpr (BATCH) {
+      const gl2 z = chal_start_batch<MODE>(c, K, G, cap);
+      s_z[0] = z.c0;
+      s_z[1] = z.c1;
+      chal_observe_span<MODE>(c, K, root, 4 * G.n_oracles);
+    } else if constexpr (DEEP) {
       const gl2 z = chal_start_deep<MODE>(c, K, G, cap);
       s_z[0] = z.c0;
       s_z[1] = z.c1;
@@ -565,22 +597,82 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
     Y0 = {s_deep[0][0], s_deep[1][0]};
     Y1 = {s_deep[2][0], s_deep[3][0]};
   }
+  if constexpr (BATCH) {
+    // group by group: every thread's share of the group's Y sums (alpha^(off_k + c) y_(k,c,j)) and the padding rows of its blocks
+    const uint32_t t = threadIdx.x;
+    const gl2 alpha = {s_chal[0], s_chal[1]};
+    const gl2 step = gl2_pow(alpha, FRI_MAX_QUERIES);
+    bool pad_bad = false;
+    for (uint32_t g = 0; g < G.n_groups; g++) {
+      gl2 y0 = {0, 0}, y1 = {0, 0};
+      for (uint32_t k = 0; k < G.n_oracles; k++) {
+        if (G.o_group[k] != g) continue;
+        const uint64_t Rr = 1ull << G.o_log_r[k];
+        const uint64_t* ob = proof + G.o_off_open[k];
+        gl2 ap = gl2_pow(alpha, (uint64_t)G.o_alpha_off[k] + t);
+        for (uint32_t c = t; c < G.o_n_cols[k]; c += FRI_MAX_QUERIES) {
+          y0 = gl2_add(y0, gl2_mul(ap, {gl_canon(ob[c]), gl_canon(ob[Rr + c])}));
+          y1 = gl2_add(y1, gl2_mul(ap, {gl_canon(ob[2 * Rr + c]), gl_canon(ob[3 * Rr + c])}));
+          ap = gl2_mul(ap, step);
+        }
+        for (uint64_t r = G.o_n_cols[k] + t; r < Rr; r += FRI_MAX_QUERIES)
+          pad_bad = pad_bad || ob[r] || ob[Rr + r] || ob[2 * Rr + r] || ob[3 * Rr + r];
+      }
+      s_deep[0][t] = y0.c0; s_deep[1][t] = y0.c1; s_deep[2][t] = y1.c0; s_deep[3][t] = y1.c1;
+      __syncthreads();
+      for (uint32_t h = FRI_MAX_QUERIES / 2; h; h >>= 1) {
+        if (t < h)
+#pragma unroll
+          for (int k = 0; k < 4; k++) s_deep[k][t] = gl_add(s_deep[k][t], s_deep[k][t + h]);
+        __syncthreads();
+      }
+      if (t < 4) s_y[g][t] = s_deep[t][0];
+      __syncthreads();
+    }
+    pad_ok = !__syncthreads_or(pad_bad);
+  }
   const uint32_t q = threadIdx.x;
   if (q >= G.n_queries) return;
   uint64_t i = s_idx[q];
   bool good = proof[G.off_indices + q] == i && pad_ok && s_pow_ok;
-  const uint32_t pl0 = G.log_n - G.cap_height;
-  const uint64_t* row = proof + G.off_init_rows + (uint64_t)q * G.n_cols;
-  good = merkle_leads_to_cap<MODE>(K, row, G.n_cols, proof + G.off_init_paths + (uint64_t)q * pl0 * 4, pl0, i, cap) && good;
   const gl2 alpha = {s_chal[0], s_chal[1]};
   gl2 v = {0, 0}, ap = {1, 0};
-  for (uint32_t c = 0; c < G.n_cols; c++) {
-    v = gl2_add(v, gl2_scale(ap, gl_canon(row[c])));
-    ap = gl2_mul(ap, alpha);
-  }
-  if constexpr (DEEP) {  // (ap = alpha^n_cols here)
+  gl2 Qg[BATCH ? FRI_MAX_ORACLES : 1];
+  if constexpr (BATCH) {
+    // every oracle's row against its own cap; F of every group (the alpha powers run on across the oracles: alpha^(off_k + c))
+    for (uint32_t k = 0; k < G.n_oracles; k++) {
+      const uint32_t lgk = G.o_log_n[k], nck = G.o_n_cols[k], plk = lgk - G.o_cap_h[k];
+      const uint64_t ik = i & ((1ull << lgk) - 1);
+      const uint64_t* row = proof + G.o_off_rows[k] + (uint64_t)q * nck;
+      good = merkle_leads_to_cap<MODE>(K, row, nck, proof + G.o_off_paths[k] + (uint64_t)q * plk * 4, plk, ik, cap + G.o_cap_at[k]) && good;
+      if (k == 0 || G.o_group[k] != G.o_group[k - 1]) v = {0, 0};
+      for (uint32_t c = 0; c < nck; c++) {
+        v = gl2_add(v, gl2_scale(ap, gl_canon(row[c])));
+        ap = gl2_mul(ap, alpha);
+      }
+      Qg[G.o_group[k]] = v;
+    }
+    // (ap = alpha^C here) the quotients, each at its group's own point s w_k^(idx mod M_k) and with its own omega_(N_k)
     const gl2 z0 = {s_z[0], s_z[1]};
-    v = deep_layer0(v, gl_mul(G.s0, gl_pow(G.w0, i)), z0, gl2_scale(z0, G.omega_n), Y0, Y1, ap);
+    for (uint32_t k = 0; k < G.n_oracles; k++) {
+      if (k && G.o_group[k] == G.o_group[k - 1]) continue;
+      const uint32_t g = G.o_group[k];
+      const uint64_t ik = i & ((1ull << G.o_log_n[k]) - 1);
+      Qg[g] = deep_layer0(Qg[g], gl_mul(G.s0, gl_pow(G.o_w[k], ik)), z0, gl2_scale(z0, G.o_omega[k]), {s_y[g][0], s_y[g][1]}, {s_y[g][2], s_y[g][3]}, ap);
+    }
+    v = Qg[0];
+  } else {
+    const uint32_t pl0 = G.log_n - G.cap_height;
+    const uint64_t* row = proof + G.off_init_rows + (uint64_t)q * G.n_cols;
+    good = merkle_leads_to_cap<MODE>(K, row, G.n_cols, proof + G.off_init_paths + (uint64_t)q * pl0 * 4, pl0, i, cap) && good;
+    for (uint32_t c = 0; c < G.n_cols; c++) {
+      v = gl2_add(v, gl2_scale(ap, gl_canon(row[c])));
+      ap = gl2_mul(ap, alpha);
+    }
+    if constexpr (DEEP) {  // (ap = alpha^n_cols here)
+      const gl2 z0 = {s_z[0], s_z[1]};
+      v = deep_layer0(v, gl_mul(G.s0, gl_pow(G.w0, i)), z0, gl2_scale(z0, G.omega_n), Y0, Y1, ap);
+    }
   }
   uint32_t lg = G.log_n;
   for (uint32_t l = 0; l < G.n_layers; l++) {
@@ -596,6 +688,13 @@ __global__ __launch_bounds__(FRI_MAX_QUERIES) void k_fri_verify(const uint64_t* 
       case 2: v = fri_fold_row<2>(lr, xinv0, G.g[l], beta); break;
       case 3: v = fri_fold_row<3>(lr, xinv0, G.g[l], beta); break;
       default: v = fri_fold_row<4>(lr, xinv0, G.g[l], beta); break;
+    }
+    if constexpr (BATCH) {
+      if (G.enter[l]) {  // the group that has layer l + 1's size joins, scaled by beta^(2^b)
+        gl2 bp = beta;
+        for (uint32_t k = 0; k < b; k++) bp = gl2_mul(bp, bp);
+        v = gl2_add(v, gl2_mul(bp, Qg[G.enter[l]]));
+      }
     }
     i = r;
     lg = lgn;
@@ -723,13 +822,13 @@ int launch_fri_grind(const void* d_consts, int mode, uint32_t pow_bits, const vo
   else hipLaunchKernelGGL(k_fri_grind<POS_MODE_GENERAL>, grid, block, 0, S_(stream), K, pow_bits, st, pw);
   return (int)hipGetLastError();
 }
-template <bool DEEP>
+template <bool DEEP, bool BATCH = false>
 static void fri_verify_launch(const uint64_t* K, int mode, const FriGeom& G, const uint64_t* cap, const uint64_t* proof, const uint64_t* open,
                               const uint64_t* root, uint32_t* ok, hipStream_t s) {
   const dim3 grid(1), block(FRI_MAX_QUERIES);
-  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL((k_fri_verify<POS_MODE_MERGE3, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
-  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL((k_fri_verify<POS_MODE_SMALL, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
-  else hipLaunchKernelGGL((k_fri_verify<POS_MODE_GENERAL, DEEP>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL((k_fri_verify<POS_MODE_MERGE3, DEEP, BATCH>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL((k_fri_verify<POS_MODE_SMALL, DEEP, BATCH>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
+  else hipLaunchKernelGGL((k_fri_verify<POS_MODE_GENERAL, DEEP, BATCH>), grid, block, 0, s, K, G, cap, proof, open, root, ok);
 }
 int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const void* d_cap, const void* d_proof, const void* d_open, const void* d_root,
                       void* d_ok, void* stream) {
@@ -739,7 +838,8 @@ int launch_fri_verify(const void* d_consts, int mode, const FriGeom& G, const vo
   const uint64_t* open = reinterpret_cast<const uint64_t*>(d_open);
   const uint64_t* root = reinterpret_cast<const uint64_t*>(d_root);
   uint32_t* ok = reinterpret_cast<uint32_t*>(d_ok);
-  if (G.deep) fri_verify_launch<true>(K, mode, G, cap, proof, open, root, ok, S_(stream));
+  if (G.n_oracles) fri_verify_launch<false, true>(K, mode, G, cap, proof, open, root, ok, S_(stream));
+  else if (G.deep) fri_verify_launch<true>(K, mode, G, cap, proof, open, root, ok, S_(stream));
   else fri_verify_launch<false>(K, mode, G, cap, proof, open, root, ok, S_(stream));
   return (int)hipGetLastError();
 }
