@@ -11,7 +11,9 @@ import pytest
 
 P = 2**64 - 2**32 + 1
 BAD_ARG = -1
-MERKLE_SHAPES = [(3, 3, 0), (4, 4, 2), (6, 5, 1), (8, 8, 4), (10, 9, 0), (9, 20, 3), (12, 135, 4), (5, 300, 5)]
+# (3, 16389, 1): above the 64 blocks x 256 threads that launch_merkle_open gives a query's columns (poseidon.hip), so k_merkle_open's
+# grid-stride loop runs a second time for columns 16384 .. 16388
+MERKLE_SHAPES = [(3, 3, 0), (4, 4, 2), (6, 5, 1), (8, 8, 4), (10, 9, 0), (9, 20, 3), (12, 135, 4), (5, 300, 5), (3, 16389, 1)]
 
 
 # ---- the host-side reference verifier (the yardstick of every device result below)
@@ -179,7 +181,7 @@ def test_standalone_openings_are_oracle_slices_and_verify(ctx, oracle, log_n, n_
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("log_n,n_cols,cap", [(9, 20, 3), (4, 4, 2), (6, 5, 1), (8, 300, 2)])
+@pytest.mark.parametrize("log_n,n_cols,cap", [(9, 20, 3), (4, 4, 2), (6, 5, 1), (8, 300, 2), (4, 16389, 1)])
 def test_verifier_rejects_query_by_query(ctx, oracle, log_n, n_cols, cap):
     """(3) in one mixed batch, only the tampered queries report 0: a row element to another residue, one word of one sibling, the indices
     of two queries with different rows swapped, one word of the cap (every query under that cap digest)"""
@@ -207,6 +209,9 @@ def test_verifier_rejects_query_by_query(ctx, oracle, log_n, n_cols, cap):
     r = rows.copy()
     r[3, n_cols // 2] = (int(r[3, n_cols // 2]) % P + 12345) % P
     run(r, paths, idx, cap_h, {3})
+    last = rows.copy()  # the last column: above 16384 columns, one that k_merkle_open copies in a later pass of its loop
+    last[9, n_cols - 1] = (int(last[9, n_cols - 1]) % P + 1) % P
+    run(last, paths, idx, cap_h, {9})
     p_ = paths.copy()
     p_[7, pl // 2, 2] = (int(p_[7, pl // 2, 2]) + 1) % P
     run(rows, p_, idx, cap_h, {7})
