@@ -860,6 +860,43 @@ int32_t tmx_trace_commit_set_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proof
 int32_t tmx_trace_commit_set_shape(const tmx_ctx* ctx, tmx_batch_params* out, uint32_t section_of[TMX_BATCH_MAX_ORACLES]);
 int32_t tmx_trace_commit_set_prove_device(tmx_ctx* ctx, const tmx_batch_params* p, uint64_t* d_proof, void* hip_stream);
 
+/* ---- streamed members of a commit set ----------------------------------------------------------------------------------------------
+ * A resident member of a commit set keeps its extended columns (n_cols << log_n words) and the LDE wants twice that again as scratch: at 256
+ * proofs x N = 128 and blow-up 8 the ladders section alone would ask for about 218 GB.  None of those words has to stay:
+ *   - the leaf sponge absorbs a row eight columns at a time and can stop after any multiple of eight and go on from its 12-word state;
+ *   - the openings at zeta, zeta omega read the pre-LDE columns;
+ *   - F_k = sum alpha^c col_c is F_p-linear in the columns and so is the LDE: combining the pre-LDE columns and extending the two planes of
+ *     the result gives the same canonical words as combining the extended columns;
+ *   - the queried rows are produced after the indices are drawn, by extending the columns once more, a chunk at a time.
+ * A STREAMED member therefore keeps in the set's scratch its pre-LDE columns and its tree levels, nothing else of its own.  All streamed
+ * members share one sponge-state buffer ([12][2^log_n] words, planar) and one chunk buffer (chunk_cols << log_n words), sized by the tallest.
+ * The chunk rule: chunk_cols is a multiple of 8, at least 8, so every chunk but a member's last ends on a block boundary of the sponge.  A
+ * member of `streamed` whose n_cols <= chunk_cols fits one chunk and is kept resident.
+ * THE EQUALITY PROMISE: the caps, tmx_trace_commit_set_shape, and every word of tmx_trace_commit_set_prove_device's proof (and so the
+ * transcript, zeta, the layout and the verifier) are those of the resident set of the same sections, whatever `streamed` and chunk_cols.
+ *   tmx_trace_commit_set_bytes            host only: the bytes tmx_trace_commit_set_streamed_device checks against free memory before it
+ *                                         allocates -- the set's scratch (per member: pre-LDE columns + extended columns unless streamed +
+ *                                         levels; then the state and chunk buffers if any member is streamed) plus the LDE's own scratch,
+ *                                         twice the largest thing extended at once (a resident member's extended columns, or the chunk
+ *                                         buffer).  0 for arguments the commit would refuse.
+ *   tmx_trace_commit_set_streamed_device  tmx_trace_commit_set_device with the members of the mask `streamed` (a subset of `sections`)
+ *                                         streamed in chunks of chunk_cols columns; chunk_cols is checked even when nothing is streamed.
+ *                                         Anything else -> TMX_ERR_BAD_ARG before anything is enqueued; a failed call leaves no set.
+ *                                         streamed == 0 is tmx_trace_commit_set_device exactly.  TMX_COMMIT_SET_CHUNK_COLS is the smallest
+ *                                         chunk of the measured sweep (256 .. 2048) within spread of the fastest commit: the
+ *                                         state round trip, 192 B per row and chunk, is 9 % of the column traffic there and hides.
+ * tmx_trace_commit_set_prove_device works on a set with streamed members unchanged.  It extends a streamed member's two planes of F_k (into
+ * the group's buffer if the member opens its size group, else next to it and added in) and, after the indices are drawn, every chunk once
+ * more to gather the queried rows: that second LDE pass is the price of streaming.  These LDEs run under the domain the set was committed
+ * with: if tmx_ntt_set_domain has changed the context's since, the prove puts the set's domain back for its own duration and restores the
+ * caller's before it returns -- the one case in which this call waits for the device. */
+#define TMX_COMMIT_SET_CHUNK_COLS 256
+uint64_t tmx_trace_commit_set_bytes(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t sections, uint32_t streamed, uint32_t chunk_cols,
+                                    uint32_t log_blowup, uint32_t cap_height);
+int32_t tmx_trace_commit_set_streamed_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t streamed,
+                                             uint32_t chunk_cols, uint32_t log_blowup, uint32_t cap_height, const void* d_trace_rows,
+                                             uint64_t* d_caps, void* hip_stream);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

@@ -300,6 +300,10 @@ def lib():
                                                   C.c_void_p]
         L.tmx_trace_commit_set_shape.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.POINTER(C.c_uint32)]
         L.tmx_trace_commit_set_prove_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_bytes.argtypes = [C.c_int32] + [C.c_uint32] * 7
+        L.tmx_trace_commit_set_bytes.restype = C.c_uint64
+        L.tmx_trace_commit_set_streamed_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -409,6 +409,18 @@ class Context:
         check(self._L.tmx_trace_commit_set_device(self._h, kind, n_proofs, sections, log_blowup, cap_height, d_trace_rows, d_caps,
                                                   self._stream(stream)), self._h)
 
+    def trace_commit_set_streamed_device(self, kind, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height, d_trace_rows, d_caps,
+                                         stream=None):
+        """trace_commit_set_device with the members of the mask `streamed` kept as pre-LDE columns + tree levels only and extended
+        chunk_cols columns (a multiple of 8) at a time; caps, shape and proofs are the resident set's word for word"""
+        check(self._L.tmx_trace_commit_set_streamed_device(self._h, kind, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height,
+                                                           d_trace_rows, d_caps, self._stream(stream)), self._h)
+
+    def trace_commit_set_bytes(self, kind, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height):
+        """(host only) the bytes trace_commit_set_streamed_device checks against free memory: set scratch + the LDE's scratch; 0 for
+        arguments it would refuse"""
+        return trace_commit_set_bytes(kind, self.n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height, self._L)
+
     def trace_commit_set_shape(self):
         """(params dict with the set's n_oracles, log_blowup, cap_height, log_n, n_cols and the other fields zero, [section bit per oracle])"""
         p, sec = _lib.BatchParams(), (C.c_uint32 * _lib.BATCH_MAX_ORACLES)()
@@ -551,3 +563,10 @@ def batch_layout(params, L=None):
             "off_final": out.off_final, "off_indices": out.off_indices, "off_init_rows": list(out.off_init_rows[:K]),
             "off_init_paths": list(out.off_init_paths[:K]), "off_rows": list(out.off_rows[:n]), "off_paths": list(out.off_paths[:n]),
             "off_nonce": out.off_nonce, "words": out.words}
+
+
+def trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height, L=None):
+    """tmx_trace_commit_set_bytes (no context, no device): set scratch + LDE scratch of a commit set in bytes; 0 for arguments the commit
+    would refuse"""
+    L = L or _lib.lib()
+    return int(L.tmx_trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height))

@@ -412,11 +412,15 @@ struct tmx_ctx {
   uint32_t fri_pow_bits = 0;  // non-zero: the last prove was a grinding prove (the search's two words sit in d_fri: tmx_pow_last)
   // the commit set (tmx_trace_commit_set_device): several sections committed side by side in a scratch of its own -- per oracle its pre-LDE
   // columns | extended columns | tree levels -- in the oracle order of the batch proof.  Independent of last_commit and d_commit.
+  // A streamed member (tmx_trace_commit_set_streamed_device) keeps no extended columns (lde_off unused); behind the last member sit the two
+  // buffers all streamed members share: the sponge states [12][2^log_m] and one chunk of extended columns [chunk_cols][2^log_m], both sized
+  // by the tallest streamed member.
   void* d_set = nullptr;
   size_t set_bytes = 0;
   struct SetRec {
     bool valid; uint32_t n_oracles, log_blowup, cap_height; uint64_t root, shift;
-    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; } o[8];
+    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed; } o[8];
+    uint32_t chunk_cols; size_t state_off, chunk_off;
   } set = {};
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
@@ -3683,7 +3687,13 @@ static FriGeom batch_geom(const tmx_batch_params& p, const tmx_batch_layout& L, 
 }
 
 // What a batch prove reads: per oracle its extended columns, its tree, and the columns its openings are evaluated from (DeepSrc)
-struct BatchSrc { const uint64_t* cols[TMX_BATCH_MAX_ORACLES]; const uint64_t* levels[TMX_BATCH_MAX_ORACLES]; DeepSrc deep[TMX_BATCH_MAX_ORACLES]; };
+// A streamed oracle (chunk_cols[k] != 0, a member of a commit set) has no extended columns (cols[k] == nullptr): its deep[k] columns are the
+// set's pre-LDE columns, extended chunk_cols[k] at a time into chunk_buf (chunk_cols << log_n words for the tallest of them) when the
+// queried rows are gathered.
+struct BatchSrc {
+  const uint64_t* cols[TMX_BATCH_MAX_ORACLES]; const uint64_t* levels[TMX_BATCH_MAX_ORACLES]; DeepSrc deep[TMX_BATCH_MAX_ORACLES];
+  uint32_t chunk_cols[TMX_BATCH_MAX_ORACLES]; uint64_t* chunk_buf;
+};
 
 // Validated by the caller.  The stages are DEEP's, run per oracle (evaluation, openings block and its tree) and per group (combine of every
 // oracle of the group into ONE buffer, the Y sums, one quotient pass), then ONE set of layers whose folds take the smaller groups in.
@@ -3731,6 +3741,16 @@ static int32_t batch_prove(tmx_ctx* c, const tmx_batch_params& p, const BatchSrc
   const uint64_t o_wt = at; at += 2ull << (p.log_n[0] - p.log_blowup);
   const uint64_t o_part = at; at += part_words;
   const uint64_t o_olev = at; at += olev_words;
+  // streamed oracles: F_k on the trace domain (two planes of N_k words), and its extension (two planes of M_k words) for one that does not
+  // open its group
+  uint64_t sc_words = 0, sx_words = 0;
+  for (uint32_t k = 0; k < K; k++) {
+    if (!src.chunk_cols[k]) continue;
+    sc_words = std::max<uint64_t>(sc_words, 2ull << (p.log_n[k] - p.log_blowup));
+    if (k && L.group_of[k] == L.group_of[k - 1]) sx_words = std::max<uint64_t>(sx_words, 2ull << p.log_n[k]);
+  }
+  const uint64_t o_sc = at; at += sc_words;
+  const uint64_t o_sx = at; at += sx_words;
   if (c->fri_bytes < at * 8) {
     if (c->d_fri) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_fri)); c->d_fri = nullptr; c->fri_bytes = 0; }
     HIPCK(c, hipMalloc(&c->d_fri, at * 8));
@@ -3779,6 +3799,16 @@ static int32_t batch_prove(tmx_ctx* c, const tmx_batch_params& p, const BatchSrc
   for (uint32_t k = 0; k < K; k++) {
     uint64_t* q = W + o_q[L.group_of[k]];
     const bool first = k == 0 || L.group_of[k] != L.group_of[k - 1];
+    if (src.chunk_cols[k]) {
+      // a streamed oracle: the combination is F_p-linear in the columns and so is the LDE, so combining the pre-LDE columns and extending
+      // the two planes gives the words combining the extended columns gives.  The LDE writes into the group's buffer when the oracle opens
+      // the group, else next to it, and k_fri_add adds it in.
+      const uint32_t log_sub = p.log_n[k] - p.log_blowup;
+      if ((st = launched(launch_fri_combine(log_sub, p.n_cols[k], src.deep[k].cols, apow + 2ull * G.o_alpha_off[k], W + o_sc, s), "k_fri_combine"))) return st;
+      if ((st = tmx_lde_goldilocks_device(c, log_sub, p.log_blowup, 2, W + o_sc, first ? q : W + o_sx, hip_stream))) return st;
+      if (!first && (st = launched(launch_fri_add(2ull << p.log_n[k], W + o_sx, q, s), "k_fri_add"))) return st;
+      continue;
+    }
     const int rc = first ? launch_fri_combine(p.log_n[k], p.n_cols[k], src.cols[k], apow + 2ull * G.o_alpha_off[k], q, s)
                          : launch_fri_combine_add(p.log_n[k], p.n_cols[k], src.cols[k], apow + 2ull * G.o_alpha_off[k], q, s);
     if ((st = launched(rc, "k_fri_combine"))) return st;
@@ -3820,6 +3850,20 @@ static int32_t batch_prove(tmx_ctx* c, const tmx_batch_params& p, const BatchSrc
   for (uint32_t k = 0; k < K; k++) {
     const uint32_t g = L.group_of[k];
     const uint64_t* idx = g ? qidx + g_enter_layer[g] * nq : proof + L.off_indices;
+    if (src.chunk_cols[k]) {  // a streamed oracle: every chunk extended once more, its part of the queried rows gathered; the paths as ever
+      const uint32_t log_sub = p.log_n[k] - p.log_blowup;
+      for (uint32_t c0 = 0; c0 < p.n_cols[k]; c0 += src.chunk_cols[k]) {
+        const uint32_t n = std::min(src.chunk_cols[k], p.n_cols[k] - c0);
+        if ((st = tmx_lde_goldilocks_device(c, log_sub, p.log_blowup, n, src.deep[k].cols + ((uint64_t)c0 << log_sub), src.chunk_buf, hip_stream))) return st;
+        if ((st = launched(launch_merkle_open_chunk(p.log_n[k], n, src.chunk_buf, p.n_queries, idx, proof + L.off_init_rows[k] + c0, p.n_cols[k], s),
+                           "k_merkle_open_chunk")))
+          return st;
+      }
+      if ((st = launched(launch_merkle_open(p.log_n[k], 1, src.levels[k], p.log_n[k] - G.o_cap_h[k], src.levels[k], p.n_queries, idx, nullptr,
+                                            proof + L.off_init_paths[k], false, s), "k_merkle_open")))
+        return st;
+      continue;
+    }
     if ((st = launched(launch_merkle_open(p.log_n[k], p.n_cols[k], src.cols[k], p.log_n[k] - G.o_cap_h[k], src.levels[k], p.n_queries, idx,
                                           proof + L.off_init_rows[k], proof + L.off_init_paths[k], false, s), "k_merkle_open")))
       return st;
@@ -3891,45 +3935,87 @@ int32_t tmx_batch_verify_device(tmx_ctx* c, const tmx_batch_params* p, const uin
   return TMX_OK;
 }
 
-int32_t tmx_trace_commit_set_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t log_blowup, uint32_t cap_height,
-                                    const void* d_trace_rows, uint64_t* d_caps, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  c->set.valid = false;  // (set again at the end: a call that fails anywhere leaves no set)
-  if (!d_trace_rows || !d_caps || n_proofs == 0) return TMX_ERR_BAD_ARG;
-  const uint32_t tables = TMX_TRACE_LADDERS | TMX_TRACE_SHA512 | TMX_TRACE_SHA256 | TMX_TRACE_TREE | TMX_TRACE_HEADER;
-  if (sections == 0 || (sections & ~tables)) return fail(c, TMX_ERR_BAD_ARG, "sections must be a non-empty mask of row tables of the trace block");
-  tmx_ctx::SetRec r = {};
+// The plan of a commit set: the oracle list in proof order, where every member's parts sit in the set's scratch, the scratch's size and the
+// size of the LDE's own scratch (twice the largest thing it extends at once: a resident member's columns, or one chunk).  Host only; on
+// refusal the status and `err`.
+struct SetPlan {
+  tmx_ctx::SetRec r;
   struct Geo { uint64_t off, rows; uint32_t width, log_n; } geo[8];
+  size_t want, lde_scratch;
+};
+static int32_t set_plan(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t sections, uint32_t streamed, uint32_t chunk_cols, uint32_t log_blowup,
+                        uint32_t cap_height, SetPlan& P, std::string& err) {
+  const uint32_t tables = TMX_TRACE_LADDERS | TMX_TRACE_SHA512 | TMX_TRACE_SHA256 | TMX_TRACE_TREE | TMX_TRACE_HEADER;
+  if (n_proofs == 0) { err = "n_proofs must not be zero"; return TMX_ERR_BAD_ARG; }
+  if (sections == 0 || (sections & ~tables)) { err = "sections must be a non-empty mask of row tables of the trace block"; return TMX_ERR_BAD_ARG; }
+  if (streamed & ~sections) { err = "streamed must be a subset of sections"; return TMX_ERR_BAD_ARG; }
+  if (chunk_cols < 8 || chunk_cols % 8) { err = "chunk_cols must be a multiple of 8, at least 8 (the sponge absorbs eight columns at a time)"; return TMX_ERR_BAD_ARG; }
+  tmx_ctx::SetRec& r = P.r;
+  r = {};
   for (uint32_t bit = 1; bit <= TMX_TRACE_HEADER; bit <<= 1) {
     if (!(sections & bit)) continue;
     uint32_t log_n = 0, width = 0;
-    if (tmx_trace_commit_shape(kind, c->cfg.n_max, bit, &log_n, &width)) return fail(c, TMX_ERR_BAD_ARG, "section must be one row table of the trace block");
-    if (log_n + log_blowup > TMX_NTT_MAX_LOG) return fail(c, TMX_ERR_CAPACITY, "log_rows + log_blowup exceeds TMX_NTT_MAX_LOG");
-    if ((uint64_t)n_proofs * width > 0xffffffffull) return fail(c, TMX_ERR_CAPACITY, "too many columns");
+    if (tmx_trace_commit_shape(kind, n_max, bit, &log_n, &width)) { err = "section must be one row table of the trace block"; return TMX_ERR_BAD_ARG; }
+    if (log_n + log_blowup > TMX_NTT_MAX_LOG) { err = "log_rows + log_blowup exceeds TMX_NTT_MAX_LOG"; return TMX_ERR_CAPACITY; }
+    if ((uint64_t)n_proofs * width > 0xffffffffull) { err = "too many columns"; return TMX_ERR_CAPACITY; }
     // insertion by decreasing log_rows; the bits come in ascending order, so ties keep ascending section bits
     uint32_t at = r.n_oracles++;
-    while (at && r.o[at - 1].log_m < log_n + log_blowup) { r.o[at] = r.o[at - 1]; geo[at] = geo[at - 1]; at--; }
-    r.o[at] = {bit, log_n + log_blowup, n_proofs * width, 0, 0, 0};
-    geo[at].width = width; geo[at].log_n = log_n;
-    (void)trace_section_geom((uint32_t)kind, c->cfg.n_max, bit, &geo[at].off, &geo[at].rows, &width);
+    while (at && r.o[at - 1].log_m < log_n + log_blowup) { r.o[at] = r.o[at - 1]; P.geo[at] = P.geo[at - 1]; at--; }
+    // (a member that fits one chunk takes the resident path: nothing to carry between chunks)
+    r.o[at] = {bit, log_n + log_blowup, n_proofs * width, 0, 0, 0, (streamed & bit) != 0 && n_proofs * width > chunk_cols};
+    P.geo[at].width = width; P.geo[at].log_n = log_n;
+    (void)trace_section_geom((uint32_t)kind, n_max, bit, &P.geo[at].off, &P.geo[at].rows, &width);
   }
-  if (cap_height > r.o[0].log_m) return fail(c, TMX_ERR_BAD_ARG, "cap_height exceeds the height of the largest tree");
+  if (cap_height > r.o[0].log_m) { err = "cap_height exceeds the height of the largest tree"; return TMX_ERR_BAD_ARG; }
   size_t want = 0, lde_max = 0;
+  uint32_t st_log_m = 0;
+  bool any = false;
   for (uint32_t k = 0; k < r.n_oracles; k++) {
     auto& o = r.o[k];
-    const size_t cols_b = ((size_t)o.n_cols << geo[k].log_n) * 8, lde_b = ((size_t)o.n_cols << o.log_m) * 8;
+    const size_t cols_b = ((size_t)o.n_cols << P.geo[k].log_n) * 8, lde_b = o.streamed ? 0 : ((size_t)o.n_cols << o.log_m) * 8;
     o.cols_off = want; o.lde_off = want + cols_b; o.lev_off = want + cols_b + lde_b;
     want = o.lev_off + (size_t)tmx_poseidon_merkle_digests(o.log_m, std::min(cap_height, o.log_m)) * 32;
     lde_max = std::max(lde_max, lde_b);
+    if (o.streamed) { any = true; st_log_m = std::max(st_log_m, o.log_m); }
   }
+  r.chunk_cols = chunk_cols;
+  if (any) {
+    r.state_off = want; want += ((size_t)12 << st_log_m) * 8;
+    r.chunk_off = want; want += ((size_t)chunk_cols << st_log_m) * 8;
+    lde_max = std::max(lde_max, ((size_t)chunk_cols << st_log_m) * 8);
+  }
+  P.want = want; P.lde_scratch = 2 * lde_max;
+  r.log_blowup = log_blowup; r.cap_height = cap_height;
+  return TMX_OK;
+}
+
+uint64_t tmx_trace_commit_set_bytes(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t sections, uint32_t streamed, uint32_t chunk_cols,
+                                    uint32_t log_blowup, uint32_t cap_height) {
+  SetPlan P;
+  std::string err;
+  if (set_plan(kind, n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height, P, err)) return 0;
+  return (uint64_t)P.want + P.lde_scratch;
+}
+
+int32_t tmx_trace_commit_set_streamed_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t streamed, uint32_t chunk_cols,
+                                             uint32_t log_blowup, uint32_t cap_height, const void* d_trace_rows, uint64_t* d_caps, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  c->set.valid = false;  // (set again at the end: a call that fails anywhere leaves no set)
+  if (!d_trace_rows || !d_caps || n_proofs == 0) return TMX_ERR_BAD_ARG;
+  SetPlan P;
+  std::string err;
+  int32_t st = set_plan(kind, c->cfg.n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height, P, err);
+  if (st) return fail(c, st, err);
+  tmx_ctx::SetRec& r = P.r;
+  const size_t want = P.want;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCK(c, hipSetDevice(c->cfg.device));
   if (c->set_bytes < want) {
     if (c->d_set) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set)); c->d_set = nullptr; c->set_bytes = 0; }
     size_t free_b = 0, total_b = 0;
-    // (the rule of tmx_trace_commit_device summed over the sections; the LDE's own scratch is twice the largest extended section)
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + 2 * lde_max > free_b + c->ntt_tmp_bytes)
-      return fail(c, TMX_ERR_CAPACITY, "commit set needs " + std::to_string((want + 2 * lde_max) >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
+    // (the rule of tmx_trace_commit_device summed over the sections; the LDE's own scratch is twice the largest thing extended at once)
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + P.lde_scratch > free_b + c->ntt_tmp_bytes)
+      return fail(c, TMX_ERR_CAPACITY, "commit set needs " + std::to_string((want + P.lde_scratch) >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
     HIPCK(c, hipMalloc(&c->d_set, want));
     c->set_bytes = want;
   }
@@ -3937,22 +4023,48 @@ int32_t tmx_trace_commit_set_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs,
   uint64_t cap_at = 0;
   for (uint32_t k = 0; k < r.n_oracles; k++) {
     const auto& o = r.o[k];
+    const auto& g = P.geo[k];
     uint64_t* cols = reinterpret_cast<uint64_t*>(base + o.cols_off);
-    uint64_t* lde = reinterpret_cast<uint64_t*>(base + o.lde_off);
     uint64_t* levels = reinterpret_cast<uint64_t*>(base + o.lev_off);
     const uint32_t h = std::min(cap_height, o.log_m);
-    const int rc = launch_trace_to_columns(d_trace_rows, trace_elems((uint32_t)kind, c->cfg.n_max), geo[k].off, geo[k].rows, geo[k].width, geo[k].log_n, n_proofs, cols, s);
+    int rc = launch_trace_to_columns(d_trace_rows, trace_elems((uint32_t)kind, c->cfg.n_max), g.off, g.rows, g.width, g.log_n, n_proofs, cols, s);
     if (rc) return fail(c, TMX_ERR_HIP, std::string("k_trace_to_columns launch: ") + hipGetErrorString((hipError_t)rc));
-    int32_t st = tmx_lde_goldilocks_device(c, geo[k].log_n, log_blowup, o.n_cols, cols, lde, hip_stream);
-    if (st) return st;
-    if ((st = tmx_poseidon_merkle_device(c, o.log_m, o.n_cols, lde, h, levels, hip_stream))) return st;
+    if (!o.streamed) {
+      uint64_t* lde = reinterpret_cast<uint64_t*>(base + o.lde_off);
+      if ((st = tmx_lde_goldilocks_device(c, g.log_n, log_blowup, o.n_cols, cols, lde, hip_stream))) return st;
+      if ((st = tmx_poseidon_merkle_device(c, o.log_m, o.n_cols, lde, h, levels, hip_stream))) return st;
+    } else {
+      // chunk by chunk: extend chunk_cols columns into the shared chunk buffer, absorb them into the rows' sponge states; the last chunk
+      // leaves the leaf digests where k_poseidon_leaves would, and the levels above them are the resident path's
+      uint64_t* state = reinterpret_cast<uint64_t*>(base + r.state_off);
+      uint64_t* chunk = reinterpret_cast<uint64_t*>(base + r.chunk_off);
+      if ((st = poseidon_ready(c, s))) return st;
+      for (uint32_t c0 = 0; c0 < o.n_cols; c0 += chunk_cols) {
+        const uint32_t n = std::min(chunk_cols, o.n_cols - c0);
+        if ((st = tmx_lde_goldilocks_device(c, g.log_n, log_blowup, n, cols + ((uint64_t)c0 << g.log_n), chunk, hip_stream))) return st;
+        rc = launch_poseidon_leaves_chunk(c->d_pos_consts, c->pos_mode, o.log_m, n, chunk, c0 == 0, c0 + n == o.n_cols, state, levels, s);
+        if (rc) return fail(c, TMX_ERR_HIP, std::string("k_poseidon_leaves_chunk launch: ") + hipGetErrorString((hipError_t)rc));
+      }
+      uint64_t* cur = levels;
+      for (uint32_t l = 0; l + h < o.log_m; l++) {
+        const uint64_t cnt = 1ull << (o.log_m - l);
+        rc = launch_poseidon_level(c->d_pos_consts, c->pos_mode, cnt / 2, cur, cur + 4 * cnt, s);
+        if (rc) return fail(c, TMX_ERR_HIP, std::string("k_poseidon_level launch: ") + hipGetErrorString((hipError_t)rc));
+        cur += 4 * cnt;
+      }
+    }
     const uint64_t n_dig = tmx_poseidon_merkle_digests(o.log_m, h), n_cap = (uint64_t)1 << h;
     HIPCK(c, hipMemcpyAsync(d_caps + cap_at, levels + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
     cap_at += 4 * n_cap;
   }
-  r.valid = true; r.log_blowup = log_blowup; r.cap_height = cap_height; r.root = c->ntt_root; r.shift = c->ntt_shift;
+  r.valid = true; r.root = c->ntt_root; r.shift = c->ntt_shift;
   c->set = r;
   return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, uint32_t sections, uint32_t log_blowup, uint32_t cap_height,
+                                    const void* d_trace_rows, uint64_t* d_caps, void* hip_stream) {
+  return tmx_trace_commit_set_streamed_device(c, kind, n_proofs, sections, 0, 8, log_blowup, cap_height, d_trace_rows, d_caps, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_shape(const tmx_ctx* c, tmx_batch_params* out, uint32_t section_of[TMX_BATCH_MAX_ORACLES]) {
@@ -3983,13 +4095,28 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
   if (!d_proof) return fail(c, TMX_ERR_BAD_ARG, "d_proof is null");
   const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
   BatchSrc src = {};
+  bool any = false;
   for (uint32_t k = 0; k < r.n_oracles; k++) {
-    src.cols[k] = reinterpret_cast<const uint64_t*>(base + r.o[k].lde_off);
+    if (r.o[k].streamed) { any = true; src.chunk_cols[k] = r.chunk_cols; }
+    src.cols[k] = r.o[k].streamed ? nullptr : reinterpret_cast<const uint64_t*>(base + r.o[k].lde_off);
     src.levels[k] = reinterpret_cast<const uint64_t*>(base + r.o[k].lev_off);
     // the openings read the pre-LDE columns (n_cols x N_k, on the subgroup itself), as tmx_trace_commit_deep_device does
     src.deep[k] = {reinterpret_cast<const uint64_t*>(base + r.o[k].cols_off), r.o[k].log_m - r.log_blowup, 0, 1};
   }
-  return batch_prove(c, *p, src, r.root, r.shift, d_proof, hip_stream);
+  if (!any) return batch_prove(c, *p, src, r.root, r.shift, d_proof, hip_stream);
+  src.chunk_buf = reinterpret_cast<uint64_t*>(c->d_set) + r.chunk_off / 8;
+  // the streamed members are extended again inside the prove, under the domain the set was committed with.  If tmx_ntt_set_domain has
+  // changed the context's since, it is put back for the prove and restored after it (each change waits for the device: the tables of the
+  // other domain are dropped)
+  const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+  const bool moved = root != r.root || shift != r.shift;
+  if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+  st = batch_prove(c, *p, src, r.root, r.shift, d_proof, hip_stream);
+  if (moved) {
+    const int32_t back = tmx_ntt_set_domain(c, root, shift);
+    if (!st) st = back;
+  }
+  return st;
 }
 
 }  // extern "C"

@@ -48,6 +48,8 @@ int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, 
 int launch_fri_combine(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream);
 // the same pass ADDED to what d_out holds (canonical): the second and later oracles of a group, d_apow already offset to alpha^off_k
 int launch_fri_combine_add(uint32_t log_m, uint32_t n_cols, const void* d_cols, const void* d_apow, void* d_out, void* stream);
+// d_dst[i] = d_dst[i] + d_src[i] mod p over n_words words (d_dst canonical, and canonical after)
+int launch_fri_add(uint64_t n_words, const void* d_src, void* d_dst, void* stream);
 // layer l (planar, M_l points) -> layer l + 1 (planar, M_l >> bits), with beta at d_beta
 int launch_fri_fold(uint32_t log_m_next, uint32_t bits, uint64_t s_inv, uint64_t w_inv, uint64_t g, const void* d_beta, const void* d_in,
                     void* d_out, void* stream);

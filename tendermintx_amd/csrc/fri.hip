@@ -82,6 +82,13 @@ __global__ __launch_bounds__(64 * COMBINE_WAVES) void k_fri_combine(uint32_t log
   }
 }
 
+// dst[i] += src[i] over n canonical words (both planes of a group's buffer at once): a streamed oracle that does not open its group is
+// combined on the trace domain, extended next to the buffer and added here -- what k_fri_combine<true> does in its last step.
+__global__ __launch_bounds__(256) void k_fri_add(uint64_t n, const uint64_t* __restrict__ src, uint64_t* __restrict__ dst) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = gl_add(gl_canon(src[i]), dst[i]);
+}
+
 // One thread per leaf coset r < M' of layer l (M' = M_(l+1)): its 2^B values in registers, B radix-2 folds (fri_fold_leaf), one value of
 // layer l + 1 out.  x_0^-1 = s^-1 (w^-1)^r: one exponentiation per thread.
 // ADD (the batch proof: a group of smaller oracles enters layer l + 1): the group's quotient sum at the OUTPUT index r joins the value
@@ -320,6 +327,11 @@ int launch_fri_combine_add(uint32_t log_m, uint32_t n_cols, const void* d_cols, 
   const uint64_t blocks = ((1ull << log_m) + 63) / 64;
   hipLaunchKernelGGL(k_fri_combine<true>, dim3((uint32_t)blocks), dim3(64 * COMBINE_WAVES), 0, S_(stream), log_m, n_cols,
                      reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_apow), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_fri_add(uint64_t n_words, const void* d_src, void* d_dst, void* stream) {
+  hipLaunchKernelGGL(k_fri_add, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, S_(stream), n_words, reinterpret_cast<const uint64_t*>(d_src),
+                     reinterpret_cast<uint64_t*>(d_dst));
   return (int)hipGetLastError();
 }
 template <bool ADD>

@@ -27,6 +27,11 @@ enum : int { POS_MODE_GENERAL = 0, POS_MODE_SMALL = 1, POS_MODE_MERGE3 = 2 };
 int launch_poseidon_permute(const void* d_consts, int mode, uint32_t n, const void* d_in, void* d_out, void* stream);
 // leaf digests of the 2^log_n rows of n_cols column-major columns -> d_digests[2^log_n][4]
 int launch_poseidon_leaves(const void* d_consts, int mode, uint32_t log_n, uint32_t n_cols, const void* d_cols, void* d_digests, void* stream);
+// the same sponge over one chunk of n_cols of a row's columns (d_cols: the chunk alone, column-major): first = from the zero state, else from
+// d_state ([12][2^log_n] u64, planar); last = the digests into d_digests, else the 12 state words back into d_state.  Every chunk but the
+// last of a row has a multiple of eight columns.
+int launch_poseidon_leaves_chunk(const void* d_consts, int mode, uint32_t log_n, uint32_t n_cols, const void* d_cols, bool first, bool last,
+                                 void* d_state, void* d_digests, void* stream);
 // one tree level: out[i] = two_to_one(in[2 i], in[2 i + 1]), i < n_out
 int launch_poseidon_level(const void* d_consts, int mode, uint64_t n_out, const void* d_in, void* d_out, void* stream);
 
@@ -35,6 +40,10 @@ int launch_poseidon_level(const void* d_consts, int mode, uint64_t n_out, const 
 // and the paths as two launches instead of one.
 int launch_merkle_open(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint32_t path_len, const void* d_levels, uint32_t n_queries,
                        const void* d_idx, void* d_rows, void* d_paths, bool split, void* stream);
+// the rows alone for a chunk of n_cols columns of a wider row: d_rows[q * row_stride + c] = d_cols[(c << log_n) + idx[q]], c < n_cols (d_rows
+// already points at the chunk's first column of query 0)
+int launch_merkle_open_chunk(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint32_t n_queries, const void* d_idx, void* d_rows,
+                             uint64_t row_stride, void* stream);
 // d_ok[q] = 1 if row q and path q lead to d_cap[idx[q] >> path_len], else 0
 int launch_merkle_verify(const void* d_consts, int mode, uint32_t n_cols, uint32_t path_len, uint32_t n_queries, const void* d_cap, const void* d_idx,
                          const void* d_rows, const void* d_paths, void* d_ok, void* stream);

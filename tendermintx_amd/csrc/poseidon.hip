@@ -208,6 +208,46 @@ __global__ __launch_bounds__(256) void k_poseidon_leaves(const uint64_t* __restr
   o[0] = a; o[1] = b;
 }
 
+// The same sponge over ONE CHUNK of a row's columns (the streamed members of a commit set: the extended columns exist a chunk at a time).
+// `first`: start from the zero state, else load the row's 12 state words; absorb the chunk's n_cols columns eight at a time exactly as
+// k_poseidon_leaves does; `last`: write the canonical digest, else store the 12 words as they are (lazy representatives: the next chunk
+// goes on with the very words the one-pass kernel would hold).  All 12 travel: overwrite mode keeps the rate words of a short block.
+// state is planar, word k of row r at state[(k << log_n) + r], so consecutive lanes load and store consecutive addresses.  A chunk that is
+// not the last has a multiple of eight columns (the caller's rule), so a short block only ever ends the row; rows of <= 4 columns are
+// never streamed.  first and last are wave-uniform (scalar branches).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_poseidon_leaves_chunk(const uint64_t* __restrict__ consts, uint32_t log_n, uint32_t n_cols,
+                                                               const uint64_t* __restrict__ cols, uint32_t first, uint32_t last,
+                                                               uint64_t* __restrict__ state, uint64_t* __restrict__ digests) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >> log_n) return;
+  const PosConsts K = pos_consts(consts);
+  uint64_t s[12];
+  if (first) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = 0;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = state[((uint64_t)k << log_n) + r];
+  }
+  for (uint32_t c0 = 0; c0 < n_cols; c0 += 8) {
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++)
+      if (c0 + k < n_cols) s[k] = cols[((uint64_t)(c0 + k) << log_n) + r];
+    pos_permute<MODE>(s, K);
+  }
+  if (last) {
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    u64x2 a, b;
+    a.x = gl_canon(s[0]); a.y = gl_canon(s[1]); b.x = gl_canon(s[2]); b.y = gl_canon(s[3]);
+    u64x2* o = reinterpret_cast<u64x2*>(digests + 4 * r);
+    o[0] = a; o[1] = b;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; k++) state[((uint64_t)k << log_n) + r] = s[k];
+  }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_poseidon_level(const uint64_t* __restrict__ consts, uint64_t n_out, const uint64_t* __restrict__ in,
                                                         uint64_t* __restrict__ out) {
@@ -247,6 +287,17 @@ __global__ __launch_bounds__(256) void k_merkle_open(uint32_t log_n, uint32_t n_
     const uint64_t off = (2ull << log_n) - (2ull << (log_n - l));
     paths[((uint64_t)q * path_len + l) * 4 + w] = levels[(off + ((i >> l) ^ 1ull)) * 4 + w];
   }
+}
+
+// The rows of k_merkle_open for one chunk of a wider row (a streamed member: `cols` holds n_cols of the row's row_stride columns, `rows`
+// points at the chunk's first column inside row 0): rows[q * row_stride + c] = cols[(c << log_n) + idx[q]], c < n_cols.
+__global__ __launch_bounds__(256) void k_merkle_open_chunk(uint32_t log_n, uint32_t n_cols, const uint64_t* __restrict__ cols,
+                                                           const uint64_t* __restrict__ idx, uint64_t* __restrict__ rows, uint64_t row_stride) {
+  const uint32_t q = blockIdx.x;
+  const uint64_t i = idx[q];
+  uint64_t* row = rows + (uint64_t)q * row_stride;
+  for (uint64_t c = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; c < n_cols; c += (uint64_t)gridDim.y * blockDim.x)
+    row[c] = cols[(c << log_n) + i];
 }
 
 __device__ __forceinline__ void pos_digest_out(const uint64_t (&s)[12], uint64_t (&d)[4]) {
@@ -736,6 +787,23 @@ int launch_poseidon_leaves(const void* d_consts, int mode, uint32_t log_n, uint3
                        reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<uint64_t*>(d_digests));
   return (int)hipGetLastError();
 }
+int launch_poseidon_leaves_chunk(const void* d_consts, int mode, uint32_t log_n, uint32_t n_cols, const void* d_cols, bool first, bool last,
+                                 void* d_state, void* d_digests, void* stream) {
+  const uint64_t n = 1ull << log_n;
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  uint64_t* state = reinterpret_cast<uint64_t*>(d_state);
+  uint64_t* dig = reinterpret_cast<uint64_t*>(d_digests);
+  const uint32_t f = first ? 1u : 0u, l = last ? 1u : 0u;
+  if (mode == POS_MODE_MERGE3)
+    hipLaunchKernelGGL(k_poseidon_leaves_chunk<POS_MODE_MERGE3>, grid, dim3(256), 0, S_(stream), K, log_n, n_cols, cols, f, l, state, dig);
+  else if (mode == POS_MODE_SMALL)
+    hipLaunchKernelGGL(k_poseidon_leaves_chunk<POS_MODE_SMALL>, grid, dim3(256), 0, S_(stream), K, log_n, n_cols, cols, f, l, state, dig);
+  else
+    hipLaunchKernelGGL(k_poseidon_leaves_chunk<POS_MODE_GENERAL>, grid, dim3(256), 0, S_(stream), K, log_n, n_cols, cols, f, l, state, dig);
+  return (int)hipGetLastError();
+}
 int launch_poseidon_level(const void* d_consts, int mode, uint64_t n_out, const void* d_in, void* d_out, void* stream) {
   if (n_out == 0) return 0;
   const dim3 grid((uint32_t)((n_out + 255) / 256));
@@ -767,6 +835,14 @@ int launch_merkle_open(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint
     hipLaunchKernelGGL(k_merkle_open, dim3(n_queries, col_blocks), dim3(256), 0, S_(stream), log_n, n_cols, cols, 0u, lv, idx, rows, nullptr);
     hipLaunchKernelGGL(k_merkle_open, dim3(n_queries, 1), dim3(256), 0, S_(stream), log_n, n_cols, cols, path_len, lv, idx, nullptr, paths);
   }
+  return (int)hipGetLastError();
+}
+int launch_merkle_open_chunk(uint32_t log_n, uint32_t n_cols, const void* d_cols, uint32_t n_queries, const void* d_idx, void* d_rows,
+                             uint64_t row_stride, void* stream) {
+  if (n_queries == 0 || n_cols == 0) return 0;
+  const uint32_t col_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_cols + 255) / 256, 64);
+  hipLaunchKernelGGL(k_merkle_open_chunk, dim3(n_queries, col_blocks), dim3(256), 0, S_(stream), log_n, n_cols,
+                     reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_idx), reinterpret_cast<uint64_t*>(d_rows), row_stride);
   return (int)hipGetLastError();
 }
 int launch_merkle_verify(const void* d_consts, int mode, uint32_t n_cols, uint32_t path_len, uint32_t n_queries, const void* d_cap, const void* d_idx,
