@@ -897,6 +897,69 @@ int32_t tmx_trace_commit_set_streamed_device(tmx_ctx* ctx, int32_t kind, uint32_
                                              uint32_t chunk_cols, uint32_t log_blowup, uint32_t cap_height, const void* d_trace_rows,
                                              uint64_t* d_caps, void* hip_stream);
 
+/* ---- the constraint quotient of the ladder rows -------------------------------------------------------------------------------------
+ * The proofs above show that committed columns are low-degree and that their openings are right; they say nothing about the rows.  This
+ * block adds the step plonky2's `prove` takes between the commitment and the openings -- the constraint quotient -- for the ladders table
+ * (TMX_TRACE_LADDERS): a second oracle q, committed after the trace, with  sum gamma^i C_i(x) = q(x) (x^N - 1)  checked at zeta from the
+ * openings every batch proof already carries (each column at zeta AND at the next row, zeta omega_N).  Same field, extension, duplex, NTT
+ * domain convention and caveats as the FRI / DEEP / batch blocks (PARITY UNPINNED against plonky2); nothing above changes.
+ *   table      n_proofs * 65 columns over M = 2^log_n points x_i = s w^i (tmx_lde_goldilocks_device's output), N = M / 2^log_blowup rows;
+ *              the "next row" of point i is point (i + 2^log_blowup) mod M.  Column offsets inside a proof's 65: bit 0, acc 1 .. 16,
+ *              dbl 17 .. 32, add 33 .. 48, nxt 49 .. 64; each point is its x limbs, then its y limbs; words taken mod p.
+ *   constraints  the ones that are polynomial in the columns as they stand (32-bit limbs, no helper columns), 33 per proof:
+ *              C_0      = bit^2 - bit
+ *              C_(1+l)  = nxt_l - dbl_l - bit (add_l - dbl_l)                l < 16
+ *              C_(17+l) = S(x) (acc_l(omega_N x) - nxt_l(x))                 l < 16
+ *              S(x) = x^(N/256) - omega_256^-1, omega_256 = omega_N^(N/256): zero exactly on the rows r = 255 mod 256, so neither the seam
+ *              between two ladders nor the wrap-around is constrained.  Zero padding rows and the all-zero ladders of undecodable lanes
+ *              satisfy all 33, which is why the boundary acc_0 = (0, 1) is NOT in the set.
+ *   NOT PROVED by this block (the follow-ups): the curve arithmetic (dbl = 2 acc, add = dbl + P), the limb ranges, the boundary rows, the
+ *              link to the Level-1 points, and every SHA table.  A changed acc at r = 0, dbl where bit = 1 or add where bit = 0 goes
+ *              undetected (tests/test_air.py records it).
+ *   challenge  a fresh duplex (as the FRI block defines it): observe 2^33 (no other transcript starts at or above 2^32 except the batch's
+ *              2^32 + K, K <= 8), then the constraint-set id 1, log_n, log_blowup, cap_height, n_proofs, then the trace cap
+ *              (4 << min(cap_height, log_n) words); gamma = (challenge(), challenge()), drawn again while gamma.c1 == 0.
+ *   quotient   q(x_i) = (sum_p sum_(j < 33) gamma^(33 p + j) C_(p,j)(x_i)) / (x_i^N - 1) in F_p^2, written planar (all c0, then all c1),
+ *              canonical: the buffer IS a column-major 2-column oracle of log_n rows.  Pointwise: defined for any input columns, satisfying
+ *              or not (x^N - 1 has no zero on the coset).  For satisfying rows of degree < N it has degree < N (measured: N - 2).
+ *   identity   t^0, t^1 the trace openings at zeta and zeta omega_N, u_0, u_1 the quotient columns' openings at zeta:
+ *              sum gamma^(33 p + j) C_(p,j)(t^0, t^1; zeta) == (u_0 + X u_1) (zeta^N - 1),  X (a, b) = (7 b, a).
+ *   binding    gamma depends on the trace cap only; the batch transcript observes both caps before it draws zeta.  The batch proof is
+ *              used UNCHANGED: the quotient is one more oracle, directly after its table (same log_n, n_cols = 2).
+ *   tmx_air_ladder_quotient_device        gamma from d_cap, then the quotient of caller columns d_cols into d_quot (2 << log_n words), under
+ *                                         the context's CURRENT NTT domain.  TMX_ERR_BAD_ARG before anything is enqueued: FRI's rules on log_n
+ *                                         and log_blowup, log_n - log_blowup >= 8, n_proofs >= 1, 65 n_proofs <= 2^24.
+ *   tmx_air_ladder_quotient_range_device  the same over the proofs [proof_lo, proof_hi) of the table only (d_cols still the whole table's
+ *                                         column 0; gamma still over n_proofs), added to what d_quot holds if accumulate = 1: a table fed in
+ *                                         pieces gives the same words.  Also refused: an empty range, proof_hi > n_proofs, accumulate > 1.
+ *   tmx_air_last_gamma                    blocks, then gamma of the last quotient call (set-level included); TMX_ERR_BAD_ARG if none.
+ *   tmx_air_verify_device                 tmx_batch_verify_device, then the identity for oracle k_trace (the table) and k_trace + 1 (its
+ *                                         quotient): a failed identity rejects every query.  TMX_ERR_BAD_ARG unless oracle k_trace has a
+ *                                         multiple of 65 columns and oracle k_trace + 1 the same log_n and 2 columns (and the rules above).
+ *   tmx_trace_commit_set_air_device       on a commit set that holds TMX_TRACE_LADDERS: gamma from the ladders' cap, the quotient, its
+ *                                         Poseidon tree (d_cap_q receives 4 << min(cap_height, log_n) words), and the quotient registered as
+ *                                         a member right after the ladders.  tmx_trace_commit_set_shape then reports K + 1 oracles with
+ *                                         TMX_TRACE_LADDERS_QUOTIENT in section_of, and tmx_trace_commit_set_prove_device proves the enlarged
+ *                                         list as it is (the quotient has no pre-LDE columns: its openings read the strided subset of its
+ *                                         extended columns, the same words by definition).  A STREAMED ladders member is fed in chunks of
+ *                                         floor(chunk_cols / 65) whole proofs, each extended once more into the set's chunk buffer under the
+ *                                         set's domain, the kernel accumulating: TMX_ERR_BAD_ARG if chunk_cols < 65.  The equality promise
+ *                                         extends: the quotient cap and every proof word equal the resident set's.  A second call on the same
+ *                                         set, a set without the ladders or a full set (8 oracles) is refused; a set without the call behaves
+ *                                         exactly as before.
+ * Asynchronous on hip_stream, no host synchronisation and no device-to-host copy inside (gamma is drawn on the device and stays there);
+ * the scratch is the context's own (grows on first use, which waits for the device once). */
+#define TMX_TRACE_LADDERS_QUOTIENT 64u
+int32_t tmx_air_ladder_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                       const uint64_t* d_cols, const uint64_t* d_cap, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_ladder_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                             const uint64_t* d_cap, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_last_gamma(tmx_ctx* ctx, uint64_t g[2]);
+int32_t tmx_air_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                              uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_device(tmx_ctx* ctx, uint64_t* d_cap_q, void* hip_stream);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

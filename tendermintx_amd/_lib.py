@@ -16,6 +16,7 @@ KERNEL_NAMES = ("k_eddsa", "k_proof", "k_verdict", "k_serialize")
 ED_STRIDE = 448
 SEC_HINT, SEC_DERIVED, SEC_ALL = 1, 2, 3   # TMX_SEC_*
 TRACE_LADDERS, TRACE_SHA512, TRACE_SHA256, TRACE_MATCH, TRACE_TREE, TRACE_HEADER, TRACE_ALL = 1, 2, 4, 8, 16, 32, 63   # TMX_TRACE_*
+TRACE_LADDERS_QUOTIENT = 64   # TMX_TRACE_LADDERS_QUOTIENT: the constraint quotient as a member of a commit set
 
 
 class ValidatorRec(C.Structure):
@@ -304,6 +305,12 @@ def lib():
         L.tmx_trace_commit_set_bytes.restype = C.c_uint64
         L.tmx_trace_commit_set_streamed_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_ladder_quotient_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.tmx_air_ladder_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 4
+        L.tmx_air_last_gamma.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.tmx_air_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise
@@ -324,6 +331,12 @@ def lib():
     try:
         L.tmx_comm_abort.argtypes = [C.c_void_p]
         L.tmx_comm_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.tmx_air_ladder_quotient_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.tmx_air_ladder_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 4
+        L.tmx_air_last_gamma.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.tmx_air_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has both
         if not os.environ.get("TMX_LIB"):
             raise

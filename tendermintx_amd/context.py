@@ -433,6 +433,35 @@ class Context:
         """one proof over the commit set (same stream, after it); the oracle list, log_blowup and cap_height must match the set"""
         check(self._L.tmx_trace_commit_set_prove_device(self._h, C.byref(self._batch_params(params)), d_proof, self._stream(stream)), self._h)
 
+    # ---- the constraint quotient of the ladder rows (include/tmx.h "the constraint quotient of the ladder rows")
+    def air_ladder_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_cap, d_quot, stream=None, proof_range=None,
+                                   accumulate=False):
+        """gamma from the trace cap d_cap, then the constraint quotient of the n_proofs * 65 extended ladder columns at d_cols into d_quot
+        (planar, 2 << log_n words).  proof_range = (lo, hi): those proofs' terms only, added to what d_quot holds if accumulate"""
+        if proof_range is None and not accumulate:
+            check(self._L.tmx_air_ladder_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_cap, d_quot,
+                                                         self._stream(stream)), self._h)
+            return
+        lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+        check(self._L.tmx_air_ladder_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols, d_cap,
+                                                           d_quot, self._stream(stream)), self._h)
+
+    def air_last_gamma(self):
+        """(blocks) gamma of the last quotient call as (c0, c1); TmxError if there was none"""
+        g = (C.c_uint64 * 2)()
+        check(self._L.tmx_air_last_gamma(self._h, g), self._h)
+        return int(g[0]), int(g[1])
+
+    def air_verify_device(self, params, k_trace, d_caps, d_proof, d_ok, stream=None):
+        """batch_verify_device, then the constraint identity at zeta for oracle k_trace (the ladders) and k_trace + 1 (its quotient): a
+        failed identity clears every d_ok[q]"""
+        check(self._L.tmx_air_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, d_caps, d_proof, d_ok, self._stream(stream)),
+              self._h)
+
+    def trace_commit_set_air_device(self, d_cap_q, stream=None):
+        """adds the ladders' constraint quotient to the commit set as the oracle right after the ladders; d_cap_q receives its cap"""
+        check(self._L.tmx_trace_commit_set_air_device(self._h, d_cap_q, self._stream(stream)), self._h)
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "air.h"
 #include "fri.h"
 #include "ntt.h"
 #include "poseidon.h"
@@ -419,9 +420,18 @@ struct tmx_ctx {
   size_t set_bytes = 0;
   struct SetRec {
     bool valid; uint32_t n_oracles, log_blowup, cap_height; uint64_t root, shift;
-    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed; } o[8];
+    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed, ext; } o[8];
     uint32_t chunk_cols; size_t state_off, chunk_off;
   } set = {};
+  // the constraint quotient (tmx_air_*): d_air = prover transcript state 32 | challenges 72 (gamma at FRI_GAMMA_AT) | verifier state 32 |
+  // verifier challenges 72 | the tables of one quotient launch (air.h); ev_air behind the last quotient (tmx_air_last_gamma waits for it).
+  // d_set_air: the quotient member of the commit set (Oracle.ext: lde_off and lev_off are offsets into it, not into d_set; no pre-LDE columns).
+  void* d_air = nullptr;
+  size_t air_bytes = 0;
+  hipEvent_t ev_air = nullptr;
+  bool air_valid = false;
+  void* d_set_air = nullptr;
+  size_t set_air_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1409,6 +1419,9 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_fri) (void)hipFree(c->d_fri);
   if (c->d_deepv) (void)hipFree(c->d_deepv);
   if (c->d_set) (void)hipFree(c->d_set);
+  if (c->d_set_air) (void)hipFree(c->d_set_air);
+  if (c->d_air) (void)hipFree(c->d_air);
+  if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
     if (sl.d) (void)hipFree(sl.d);
@@ -3962,7 +3975,7 @@ static int32_t set_plan(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_
     uint32_t at = r.n_oracles++;
     while (at && r.o[at - 1].log_m < log_n + log_blowup) { r.o[at] = r.o[at - 1]; P.geo[at] = P.geo[at - 1]; at--; }
     // (a member that fits one chunk takes the resident path: nothing to carry between chunks)
-    r.o[at] = {bit, log_n + log_blowup, n_proofs * width, 0, 0, 0, (streamed & bit) != 0 && n_proofs * width > chunk_cols};
+    r.o[at] = {bit, log_n + log_blowup, n_proofs * width, 0, 0, 0, (streamed & bit) != 0 && n_proofs * width > chunk_cols, false};
     P.geo[at].width = width; P.geo[at].log_n = log_n;
     (void)trace_section_geom((uint32_t)kind, n_max, bit, &P.geo[at].off, &P.geo[at].rows, &width);
   }
@@ -4098,6 +4111,15 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
   bool any = false;
   for (uint32_t k = 0; k < r.n_oracles; k++) {
     if (r.o[k].streamed) { any = true; src.chunk_cols[k] = r.chunk_cols; }
+    if (r.o[k].ext) {
+      // the constraint quotient (tmx_trace_commit_set_air_device): extended columns and levels in a scratch of its own, no pre-LDE columns --
+      // its openings read the strided subset of the extended columns, as the caller-oracle path of tmx_batch_prove_device does
+      const uint8_t* ab = reinterpret_cast<const uint8_t*>(c->d_set_air);
+      src.cols[k] = reinterpret_cast<const uint64_t*>(ab + r.o[k].lde_off);
+      src.levels[k] = reinterpret_cast<const uint64_t*>(ab + r.o[k].lev_off);
+      src.deep[k] = {src.cols[k], r.o[k].log_m, r.log_blowup, r.shift % 0xffffffff00000001ull};
+      continue;
+    }
     src.cols[k] = r.o[k].streamed ? nullptr : reinterpret_cast<const uint64_t*>(base + r.o[k].lde_off);
     src.levels[k] = reinterpret_cast<const uint64_t*>(base + r.o[k].lev_off);
     // the openings read the pre-LDE columns (n_cols x N_k, on the subgroup itself), as tmx_trace_commit_deep_device does
@@ -4117,6 +4139,212 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
     if (!st) st = back;
   }
   return st;
+}
+
+}  // extern "C"
+
+// ---- the constraint quotient of the ladder rows (include/tmx.h "the constraint quotient of the ladder rows") -------------------------------
+// The domain constants of one quotient: x_i = s w^i over M = 2^log_n points, N = M >> log_blowup
+struct AirGeo { uint64_t s_n, w_n, s_n256, w_n256, om256_inv; };
+
+static int32_t air_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
+  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
+  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
+  if (log_n - log_blowup < 8) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 8: a ladder is 256 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * AIR_LADDER_WIDTH > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "65 n_proofs must be at most 2^24");
+  return TMX_OK;
+}
+
+static int32_t air_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, AirGeo& A) {
+  const uint64_t P = 0xffffffff00000001ull;
+  const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
+  A.s_n = gl_pow_host(s, n); A.w_n = gl_pow_host(w, n);
+  A.s_n256 = gl_pow_host(s, n >> 8); A.w_n256 = gl_pow_host(w, n >> 8);
+  A.om256_inv = gl_pow_host(gl_pow_host(w, 1ull << (log_n - 8)), P - 2);  // omega_256 = omega_N^(N/256) = w^(M/256)
+  uint64_t x = A.s_n;
+  for (uint32_t k = 0; k < (1u << log_blowup); k++, x = (uint64_t)(((unsigned __int128)x * A.w_n) % P))
+    if (x == 1) return fail(c, TMX_ERR_BAD_ARG, "x^N - 1 vanishes on the evaluation domain: the coset shift lies in the trace domain");
+  return TMX_OK;
+}
+
+static int32_t air_scratch(tmx_ctx* c, uint32_t log_blowup) {
+  const size_t want = (2 * (32 + AIR_CHAL_WORDS) + air_table_words(6)) * 8;
+  (void)log_blowup;
+  if (c->air_bytes < want) {
+    if (c->d_air) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air)); c->d_air = nullptr; c->air_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air, want));
+    c->air_bytes = want;
+  }
+  if (!c->ev_air) HIPCK(c, hipEventCreate(&c->ev_air));
+  return TMX_OK;
+}
+
+// gamma from the trace cap, into the prover's (verifier = false) or the verifier's challenge words of d_air
+static int32_t air_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cap, bool verifier,
+                         hipStream_t s) {
+  FriGeom G;
+  std::memset(&G, 0, sizeof G);
+  const uint32_t obs[5] = {1 /* the constraint-set id: the ladder rows */, log_n, log_blowup, cap_height, n_proofs};
+  std::memcpy(G.params, obs, sizeof obs);
+  G.cap_height = std::min(cap_height, log_n);
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
+  const int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 9, 0, d_cap, nullptr, W, W + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// one piece of the table: n proofs whose first is proof `first` of the table, their extended columns at cols
+static int32_t air_piece(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo& A, uint32_t first, uint32_t n, const uint64_t* cols,
+                         bool accumulate, uint64_t* d_quot, hipStream_t s) {
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
+  uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
+  int rc = launch_air_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, W + 32 + FRI_GAMMA_AT, tab, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_ladder_quotient(log_n, log_blowup, n, cols, tab, accumulate ? 1 : 0, d_quot, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_air_ladder_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_cap,
+                                             uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = air_check(c, log_n, log_blowup, n_proofs);
+  if (st) return st;
+  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
+  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
+  if (!d_cols || !d_cap || !d_quot) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_cap and d_quot must be set");
+  AirGeo A;
+  if ((st = air_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if ((st = air_gamma(c, log_n, log_blowup, cap_height, n_proofs, d_cap, false, s))) return st;
+  if ((st = air_piece(c, log_n, log_blowup, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_LADDER_WIDTH) << log_n),
+                      accumulate != 0, d_quot, s)))
+    return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  return TMX_OK;
+}
+
+int32_t tmx_air_ladder_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
+                                       const uint64_t* d_cap, uint64_t* d_quot, void* hip_stream) {
+  return tmx_air_ladder_quotient_range_device(c, log_n, log_blowup, cap_height, n_proofs, 0, n_proofs, 0, d_cols, d_cap, d_quot, hip_stream);
+}
+
+int32_t tmx_air_last_gamma(tmx_ctx* c, uint64_t g[2]) {
+  if (!c || !g) return TMX_ERR_BAD_ARG;
+  if (!c->air_valid) return fail(c, TMX_ERR_BAD_ARG, "no constraint quotient has completed on this context");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  HIPCK(c, hipEventSynchronize(c->ev_air));
+  HIPCK(c, hipMemcpy(g, reinterpret_cast<uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT, 16, hipMemcpyDeviceToHost));
+  return TMX_OK;
+}
+
+int32_t tmx_air_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok,
+                              void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (k_trace + 1 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, "k_trace and k_trace + 1 must both be oracles of the proof");
+  if (p->n_cols[k_trace] % AIR_LADDER_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 65 columns");
+  if (p->log_n[k_trace + 1] != p->log_n[k_trace] || p->n_cols[k_trace + 1] != 2)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_LADDER_WIDTH;
+  if ((st = air_check(c, log_n, p->log_blowup, n_proofs))) return st;
+  AirGeo A;
+  if ((st = air_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  if ((st = air_scratch(c, p->log_blowup))) return st;
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // zeta as the batch transcript draws it, gamma from the trace cap: both into the verifier's words of d_air, then the identity
+  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
+  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = air_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, d_caps + G.o_cap_at[k_trace], true, s))) return st;
+  rc = launch_air_ladder_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, d_proof + L.off_open[k_trace],
+                               d_proof + L.off_open[k_trace + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_check launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
+  if (st) return st;
+  if (!d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_q is null");
+  tmx_ctx::SetRec r = c->set;
+  uint32_t kt = r.n_oracles;
+  for (uint32_t k = 0; k < r.n_oracles; k++) {
+    if (r.o[k].section == TMX_TRACE_LADDERS_QUOTIENT) return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the ladders' constraint quotient");
+    if (r.o[k].section == TMX_TRACE_LADDERS) kt = k;
+  }
+  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold TMX_TRACE_LADDERS");
+  if (r.n_oracles >= TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for one more oracle");
+  const tmx_ctx::SetRec::Oracle lad = r.o[kt];
+  const uint32_t log_m = lad.log_m, log_sub = log_m - r.log_blowup, n_proofs = lad.n_cols / AIR_LADDER_WIDTH, h = std::min(r.cap_height, log_m);
+  if ((st = air_check(c, log_m, r.log_blowup, n_proofs))) return st;
+  if (lad.streamed && r.chunk_cols < AIR_LADDER_WIDTH)
+    return fail(c, TMX_ERR_BAD_ARG, "a streamed ladders member is fed in chunks of whole proofs: chunk_cols must be at least 65");
+  AirGeo A;
+  if ((st = air_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, r.log_blowup))) return st;
+  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
+  const size_t quot_b = ((size_t)2 << log_m) * 8, want = quot_b + (size_t)n_dig * 32;
+  if (c->set_air_bytes < want) {
+    if (c->d_set_air) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_air)); c->d_set_air = nullptr; c->set_air_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_set_air, want));
+    c->set_air_bytes = want;
+  }
+  uint8_t* base = reinterpret_cast<uint8_t*>(c->d_set);
+  uint64_t* quot = reinterpret_cast<uint64_t*>(c->d_set_air);
+  uint64_t* lev_q = quot + ((size_t)2 << log_m);
+  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + lad.lev_off);
+  if ((st = air_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, lev_t + 4 * (n_dig - n_cap), false, s))) return st;
+  if (!lad.streamed) {
+    if ((st = air_piece(c, log_m, r.log_blowup, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + lad.lde_off), false, quot, s))) return st;
+  } else {
+    // chunks of whole proofs, each extended once more into the set's chunk buffer under the set's domain (as the streamed prove does: if
+    // tmx_ntt_set_domain has changed the context's since, it is put back for this call and restored after it)
+    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+    const bool moved = root != r.root || shift != r.shift;
+    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+    const uint64_t* cols = reinterpret_cast<const uint64_t*>(base + lad.cols_off);
+    uint64_t* chunk = reinterpret_cast<uint64_t*>(base + r.chunk_off);
+    const uint32_t per = r.chunk_cols / AIR_LADDER_WIDTH;
+    for (uint32_t p0 = 0; p0 < n_proofs && !st; p0 += per) {
+      const uint32_t n = std::min(per, n_proofs - p0);
+      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * AIR_LADDER_WIDTH, cols + (((uint64_t)p0 * AIR_LADDER_WIDTH) << log_sub), chunk, hip_stream);
+      if (!st) st = air_piece(c, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
+    }
+    if (moved) {
+      const int32_t back = tmx_ntt_set_domain(c, root, shift);
+      if (!st) st = back;
+    }
+    if (st) return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  for (uint32_t k = r.n_oracles; k > kt + 1; k--) r.o[k] = r.o[k - 1];
+  r.o[kt + 1] = {TMX_TRACE_LADDERS_QUOTIENT, log_m, 2, 0, 0, quot_b, false, true};
+  r.n_oracles++;
+  c->set = r;
+  return TMX_OK;
 }
 
 }  // extern "C"

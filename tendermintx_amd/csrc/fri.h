@@ -41,6 +41,9 @@ constexpr uint32_t FRI_ZETA_AT = 2 + 2 * FRI_MAX_LAYERS + 2;
 // where the grinding prover keeps the search's two words: chal[FRI_POW_AT] = the smallest satisfying nonce so far (2^64 - 1: none),
 // chal[FRI_POW_AT + 1] = the candidates evaluated.  The search gives up after 2^(pow_bits + FRI_POW_SLACK_BITS) candidates.
 constexpr uint32_t FRI_POW_AT = FRI_ZETA_AT + 2, FRI_POW_SLACK_BITS = 6, FRI_POW_MAX_BITS = 24;
+// where a constraint-challenge transcript (phase 9; include/tmx.h "the constraint quotient of the ladder rows") leaves gamma:
+// chal[FRI_GAMMA_AT], chal[FRI_GAMMA_AT + 1] -- word 64 on: such a transcript brings challenge words of its own (air.h AIR_CHAL_WORDS)
+constexpr uint32_t FRI_GAMMA_AT = FRI_POW_AT + 2;
 
 // apow[c] = alpha^c (c < n_cols, pairs of u64), alpha at d_alpha
 int launch_fri_alpha_powers(uint32_t n_cols, const void* d_alpha, void* d_apow, void* stream);
@@ -87,6 +90,8 @@ int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_
 // at d_commit_cap) -> alpha.  The other phases serve it unchanged (G.log_n = the largest oracle's).
 // Grinding splits phase 2: phase 5 (2a): final coefficients and pow_bits observed, the duplex left in d_state, the search's words reset;
 // phase 6 (2b): the nonce the search left -> the proof, observed, r drawn, then the indices as phase 2.
+// The constraint challenge: phase 9: a fresh duplex, 2^33, G.params[0 .. 5) (set id, log_n, log_blowup, cap_height, n_proofs), the trace cap
+// at d_commit_cap (4 << G.cap_height words) -> gamma (chal[FRI_GAMMA_AT]).
 int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
                           void* d_state, void* d_chal, void* d_qidx, void* stream);
 // The search between phases 5 and 6: the smallest nonce whose challenge has pow_bits leading zero bits, from the duplex in d_state, into

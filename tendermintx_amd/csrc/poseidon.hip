@@ -463,6 +463,8 @@ __device__ __forceinline__ gl2 chal_start_batch(FriChal& c, const PosConsts& K, 
 // with its point count and the commit cap -> zeta (phase 3), the openings root at commit_cap -> alpha (phase 4).  Grinding: phase 2 in two
 // halves around k_fri_grind: the final coefficients and pow_bits observed (phase 5), the nonce observed and r drawn -> the indices (phase 6).
 // The batch proof: its start over the K caps at commit_cap -> zeta (phase 7), the K openings roots at commit_cap -> alpha (phase 8).
+// The constraint challenge (include/tmx.h "the constraint quotient of the ladder rows"): a transcript of its own over the trace cap at
+// commit_cap -> gamma (phase 9).
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
                                                        const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
@@ -482,6 +484,18 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
     const gl2 z = chal_start_batch<MODE>(c, K, G, commit_cap);
     chal[FRI_ZETA_AT] = z.c0;
     chal[FRI_ZETA_AT + 1] = z.c1;
+  } else if (phase == 9) {
+    chal_init(c);
+    chal_observe<MODE>(c, K, 1ull << 33);
+    for (int k = 0; k < 5; k++) chal_observe<MODE>(c, K, G.params[k]);
+    chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
+    gl2 g;
+    do {
+      g.c0 = chal_challenge<MODE>(c, K);
+      g.c1 = chal_challenge<MODE>(c, K);
+    } while (g.c1 == 0);
+    chal[FRI_GAMMA_AT] = g.c0;
+    chal[FRI_GAMMA_AT + 1] = g.c1;
   } else if (phase == 4 || phase == 8) {
     chal_load(c, state);
     chal_observe_span<MODE>(c, K, commit_cap, phase == 4 ? 4 : 4 * G.n_oracles);

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""The ladder rows' constraint quotient (tmx_air_*) next to what it is measured against: one JSON line per mode (MODE=kernels,set by default).
+  kernels  COLS_PROOFS proofs x 65 random columns of 2^LOG_M words resident on the device (the SHA-512-sized shape: 70 x 65 = 4550 columns of
+           2^18): the quotient call (transcript + tables + k_air_ladder_quotient) and a plain FRI prove over the SAME columns, alternating,
+           REPS calls each per round.  The prove's "combine" stage (tmx_fri_last_ms) is k_fri_combine over the same bytes.  Run the tool
+           under `rocprofv3 --kernel-trace --stats -- python tools/air_bench.py` (MODE=kernels) for the two kernels' own times in one run.
+  set      P proofs at N = n (64 x 128 by default: the ladders fit resident), all five tables: the set prove without and with the quotient
+           oracle, alternating; the set-air call on a resident and on a streamed (CHUNK columns) ladders member.  The streamed call extends
+           every chunk once more: its excess over the resident call is the re-LDE.
+  parent   the set commit + prove WITHOUT any air call, for library builds named in LIBS (comma separated), one subprocess per measurement,
+           alternating under TMX_LIB (differences between boxes exceed most changes: compare inside one call).
+Times per call from HIP events around REPS back-to-back calls after one warm call.
+   P=64 N=128 python tools/air_bench.py   (BLOWUP=3 CAP=4 ARITY=4 FINAL=5 QUERIES=28 CHUNK=512 REPS=5 ROUNDS=3 by default)"""
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+modes = os.environ.get("MODE", "kernels,set").split(",")
+P, n = int(os.environ.get("P", "64")), int(os.environ.get("N", "128"))
+log_blowup, cap_h, reps = int(os.environ.get("BLOWUP", "3")), int(os.environ.get("CAP", "4")), int(os.environ.get("REPS", "5"))
+arity, final_max, nq = int(os.environ.get("ARITY", "4")), int(os.environ.get("FINAL", "5")), int(os.environ.get("QUERIES", "28"))
+chunk, rounds = int(os.environ.get("CHUNK", "512")), int(os.environ.get("ROUNDS", "3"))
+r4 = lambda x: round(x, 4)
+
+if "parent" in modes:
+    libs = [os.path.abspath(x) for x in os.environ["LIBS"].split(",")]
+    res = {os.path.basename(os.path.dirname(l)) + "/" + os.path.basename(l): [] for l in libs}
+    for _ in range(rounds):
+        for l, key in zip(libs, res):
+            o = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, MODE="set_plain", TMX_LIB=l), capture_output=True, text=True)
+            line = [x for x in o.stdout.splitlines() if x.startswith("{")]
+            res[key].append(json.loads(line[-1]) if line else {"failed": o.stderr[-300:]})
+    print(json.dumps({"mode": "parent", "proofs": P, "n": n, "runs": res}), flush=True)
+    modes = [m for m in modes if m != "parent"]
+    if not modes:
+        sys.exit(0)
+
+import torch  # noqa: E402
+from tendermintx_amd import Context, _lib  # noqa: E402
+from tendermintx_amd.context import KIND_SKIP  # noqa: E402
+
+dev = torch.device("cuda:0")
+
+
+def timed(fn, k, before=None):
+    """ms per call; `before` runs ahead of every call, outside the timed events (a call that can only be made once per set)"""
+    (before or (lambda: None))()
+    fn()  # (warm: the scratch grows on first use)
+    torch.cuda.synchronize(dev)
+    total = 0.0
+    for _ in range(k):
+        if before:
+            before()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize(dev)
+        total += a.elapsed_time(b)
+    return total / k
+
+
+if "kernels" in modes:
+    log_m, cp = int(os.environ.get("LOG_M", "18")), int(os.environ.get("COLS_PROOFS", "70"))
+    n_cols = 65 * cp
+    ctx = Context(4, b"celestia", device=0)
+    cols = torch.randint(0, 2**62, (n_cols << log_m,), dtype=torch.int64, device=dev)
+    lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+    ctx.poseidon_merkle_device(log_m, n_cols, cols.data_ptr(), cap_h, lv.data_ptr(), 0)
+    cap = lv[-(4 << cap_h):]
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    fp = dict(log_n=log_m, n_cols=n_cols, cap_height=cap_h, log_blowup=log_blowup, arity_bits=arity, final_log_max=final_max, n_queries=nq)
+    proof = torch.empty(ctx.fri_layout(fp)["words"], dtype=torch.int64, device=dev)
+    res = {"mode": "kernels", "columns": n_cols, "log_m": log_m, "table_gib": round(n_cols * 8 * 2**log_m / 2**30, 2), "reps": reps,
+           "air_quotient_call_ms": [], "fri_prove_ms": [], "fri_combine_stage_ms": []}
+    for _ in range(rounds):
+        res["air_quotient_call_ms"].append(r4(timed(lambda: ctx.air_ladder_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), cap.data_ptr(),
+                                                                                           quot.data_ptr(), 0), reps)))
+        res["fri_prove_ms"].append(r4(timed(lambda: ctx.fri_prove_device(fp, cols.data_ptr(), lv.data_ptr(), proof.data_ptr(), 0), reps)))
+        res["fri_combine_stage_ms"].append(r4(ctx.fri_last_ms()["combine"]))
+    best = min(res["air_quotient_call_ms"])
+    res["air_gb_per_s"] = round(n_cols * 8 * 2**log_m / best / 1e6, 1)
+    res["ratio_air_over_combine"] = round(best / min(res["fri_combine_stage_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols, lv, quot, proof
+    torch.cuda.empty_cache()
+
+if "set" in modes or "set_plain" in modes:
+    from tendermintx_amd.synth import bench_workload
+    plain = "set_plain" in modes
+    w = bench_workload("survey8d", n, P, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=P)
+    out = torch.empty(P * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(P * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(P * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, P, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, P, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    ALL, LADDERS = 1 | 2 | 4 | 16 | 32, 1
+    caps = torch.zeros(5 * (4 << cap_h), dtype=torch.int64, device=dev)
+    cap_q = torch.zeros(4 << cap_h, dtype=torch.int64, device=dev)
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+
+    def commit(streamed):
+        if streamed:
+            ctx.trace_commit_set_streamed_device(KIND_SKIP, P, ALL, LADDERS, chunk, log_blowup, cap_h, tr.data_ptr(), caps.data_ptr(), 0)
+        else:
+            ctx.trace_commit_set_device(KIND_SKIP, P, ALL, log_blowup, cap_h, tr.data_ptr(), caps.data_ptr(), 0)
+
+    def params():
+        shape, order = ctx.trace_commit_set_shape()
+        return dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0), order
+
+    def prove_ms():
+        bp, _ = params()
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        return r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)), bp, proof
+
+    res = {"mode": "set_plain" if plain else "set", "proofs": P, "n": n, "chunk_cols": chunk, "reps": reps}
+    if plain:
+        res["commit_ms"] = r4(timed(lambda: commit(False), 2))
+        res["prove_ms"] = [prove_ms()[0] for _ in range(rounds)]
+    else:
+        res.update(prove_without_ms=[], prove_with_ms=[], air_resident_ms=[], air_streamed_ms=[])
+        for _ in range(rounds):
+            commit(False)
+            res["prove_without_ms"].append(prove_ms()[0])
+            res["air_resident_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_device(cap_q.data_ptr(), 0), reps, before=lambda: commit(False))))
+            ms, bp, proof = prove_ms()
+            res["prove_with_ms"].append(ms)
+            res["degree_ok"] = ctx.fri_last_degree_ok()
+            kt = params()[1].index(LADDERS)
+            cw = 4 << cap_h
+            all_caps = torch.cat([caps[:(kt + 1) * cw], cap_q, caps[(kt + 1) * cw:]])
+            res["verify_ms"] = r4(timed(lambda: ctx.air_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
+            res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+            keep = cap_q.clone()
+            res["air_streamed_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_device(cap_q.data_ptr(), 0), reps, before=lambda: commit(True))))
+            res["streamed_cap_equal"] = bool(torch.equal(keep, cap_q))
+            del proof
+        res.update(order=params()[1], log_n=bp["log_n"], columns=bp["n_cols"])
+        res["re_lde_share_of_streamed"] = round(1 - min(res["air_resident_ms"]) / min(res["air_streamed_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
