@@ -915,7 +915,8 @@ int32_t tmx_trace_commit_set_streamed_device(tmx_ctx* ctx, int32_t kind, uint32_
  *              satisfy all 33, which is why the boundary acc_0 = (0, 1) is NOT in the set.
  *   NOT PROVED by this block (the follow-ups): the curve arithmetic (dbl = 2 acc, add = dbl + P), the limb ranges, the boundary rows, the
  *              link to the Level-1 points, and every SHA table.  A changed acc at r = 0, dbl where bit = 1 or add where bit = 0 goes
- *              undetected (tests/test_air.py records it).
+ *              undetected (tests/test_air.py records it).  The boundary rows and the link to the Level-1 points are constraint set 2,
+ *              the next block.
  *   challenge  a fresh duplex (as the FRI block defines it): observe 2^33 (no other transcript starts at or above 2^32 except the batch's
  *              2^32 + K, K <= 8), then the constraint-set id 1, log_n, log_blowup, cap_height, n_proofs, then the trace cap
  *              (4 << min(cap_height, log_n) words); gamma = (challenge(), challenge()), drawn again while gamma.c1 == 0.
@@ -959,6 +960,70 @@ int32_t tmx_air_last_gamma(tmx_ctx* ctx, uint64_t g[2]);
 int32_t tmx_air_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
                               uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_device(tmx_ctx* ctx, uint64_t* d_cap_q, void* hip_stream);
+
+/* ---- the boundary constraints of the ladder rows (constraint set 2) ------------------------------------------------------------------
+ * Set 1 above holds for ANY chain of acc / nxt values, wherever it starts and ends, and it is blind on row 255 of a ladder (the chain is
+ * switched off there: dbl / add and nxt can change together).  Set 2 is set 1 plus 32 boundary constraints per proof that pin the first
+ * accumulator and the last nxt of every ladder to a PUBLIC TABLE the verifier holds: the Level-1 end points s*B and h*A of every lane, which
+ * the element rows already carry (D.1b, docs/witness_layout.md).  Built beside set 1: set 1's transcript, gamma, quotient words, kernels and
+ * calls are what they were; the proof format, the batch prover and the batch verifier do not change; the quotient is again one two-column
+ * oracle directly behind its table (TMX_TRACE_LADDERS_QUOTIENT).  Notation as above: N rows, M = N B points x_i = s w^i, omega = omega_N,
+ * K = N / 256 ladders (padding included), S(x) = x^K - omega_256^-1 (zero exactly on the last rows r = 255 mod 256).  2 <= K <= 2^12, i.e.
+ * 9 <= log_n - log_blowup <= 20: TMX_ERR_BAD_ARG outside.
+ *   pub        the public table, column-major, 17 n_proofs columns of K rows, canonical words.  Column 17 p + l, l < 16, row k: limb l of the
+ *              Level-1 end point of ladder k of proof p (x limbs, then y limbs); ladder 2 i is s*B of lane i, ladder 2 i + 1 is h*A.
+ *              Column 17 p + 16, row k: live = 1 if the 16 end words are not all zero, else 0.  Ladders beyond 2 n_max (padding) and lanes
+ *              whose Level-1 points are zero are all zero; (0, 0) is not on the curve, so live is well defined.
+ *   constraints  65 per proof: C_0 .. C_32 as in set 1, and with T(x) = (x^N - 1) / S(x)
+ *              C_(33+l) = T(x) (nxt_l(x) - E_l(x))                       l < 16    E_l of degree < K, E_l(omega^(256 k + 255)) = pub[17 p + l][k]
+ *              C_(49+l) = T(x) (acc_l(omega x) - [l = 8] L(x))           l < 16    L of degree < K, L(omega^(256 k + 255)) = pub[17 p + 16][(k + 1) mod K]
+ *              The second group states the first-row boundary acc_0 = (0, live) on the row BEFORE it (the wrap-around included), so that both
+ *              groups share the row set and the divisor, and it reads acc(omega x) only: acc at the lane's own row stays unread.
+ *   NOT PROVED by set 2: the curve arithmetic (dbl = 2 acc, add = dbl + P), the limb ranges, and every SHA table.  dbl where bit = 1 and
+ *              add where bit = 0 still go undetected (tests/test_air_boundary.py records it).
+ *   challenge  a transcript of its own, as set 1's with the set id 2: observe 2^33, then 2, log_n, log_blowup, cap_height, n_proofs, then the
+ *              trace cap, then the four words of the PUBLIC DIGEST: the Poseidon Merkle root (cap height 0) of pub taken as a column-major
+ *              oracle of log2 K rows and 17 n_proofs columns, exactly as tmx_poseidon_merkle_device defines it.  gamma drawn as in set 1.
+ *   quotient   weights gamma^(65 p + j).  The public side collapses to one F_p^2 polynomial:
+ *              V_k = sum_p [ sum_(l < 16) gamma^(65 p + 33 + l) pub[17 p + l][k] + gamma^(65 p + 57) pub[17 p + 16][(k + 1) mod K] ]
+ *              Pub_gamma = the interpolant of degree < K of V_k on the points y_k = omega^(256 k + 255)
+ *              q(x_i) = [sum_p sum_(j < 33) gamma^(65 p + j) C_(p,j)(x_i)] / (x_i^N - 1)
+ *                     + [sum_p sum_(l < 16) (gamma^(65 p + 33 + l) nxt_(p,l)(x_i) + gamma^(65 p + 49 + l) acc_(p,l)(omega x_i)) - Pub_gamma(x_i)] / S(x_i)
+ *              planar and canonical as in set 1; pointwise defined for any columns and any pub.  In the range form the piece with
+ *              proof_lo == 0 carries the - Pub_gamma / S term: any split into whole-proof pieces adds up to the same words.  For satisfying
+ *              rows of degree < N it has degree < N (measured: N - 2; the boundary part alone N - 1 - K).
+ *   identity   division-free, with Z = zeta^N - 1, t^0, t^1, u_0, u_1 as in set 1:
+ *              S(zeta) sum_p sum_(j < 33) gamma^(65 p + j) C_(p,j)(t^0, t^1; zeta)
+ *                + Z [sum_p sum_l (gamma^(65 p + 33 + l) t^0[nxt_(p,l)] + gamma^(65 p + 49 + l) t^1[acc_(p,l)]) - Pub_gamma(zeta)]
+ *                == (u_0 + X u_1) Z S(zeta)
+ *              Pub_gamma(zeta) = S(zeta) / (K omega_256^-1) sum_k V_k y_k / (zeta - y_k), from the verifier's own V_k.  A failed identity
+ *              clears every query's verdict.
+ *   tmx_air_ladder_public_shape           host only: log2 K and the column count 17 n_proofs of pub for (kind, n_max, n_proofs);
+ *                                         TMX_ERR_BAD_ARG if the ladders table of that shape has K outside 2 .. 2^12 or n_proofs = 0.
+ *   tmx_air_ladder_public_device          pub (17 n_proofs << log2 K words at d_pub) from the element rows as tmx_witness_batch_device leaves
+ *                                         them (u64, row stride tmx_elem_stride, section D.1b) for the context's n_max.
+ *   tmx_air_ladder_boundary_quotient_device, .._range_device   as tmx_air_ladder_quotient_device / _range_device plus d_pub: the digest and
+ *                                         gamma, then (proof_lo == 0) V, Pub_gamma on the coset, then the pass.  Set 1's rules, and
+ *                                         log_n - log_blowup in 9 .. 20.
+ *   tmx_air_boundary_verify_device        tmx_batch_verify_device, then the set-2 identity with d_pub (the verifier hashes d_pub itself).
+ *                                         tmx_air_verify_device's rules, and log_n - log_blowup in 9 .. 20, d_pub set.
+ *   tmx_trace_commit_set_air_boundary_device   tmx_trace_commit_set_air_device for set 2: resident and streamed ladders members (chunks of
+ *                                         whole proofs, re-extended under the set's domain, accumulating), the same quotient member
+ *                                         registered.  Pub_gamma is extended by kernels of its own from the set's root and shift, not through
+ *                                         the context's NTT domain.  The two set-level calls exclude each other on one set: whichever comes
+ *                                         second is refused.  The equality promise extends as for set 1.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers these calls too. */
+int32_t tmx_air_ladder_public_shape(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols);
+int32_t tmx_air_ladder_public_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub, void* hip_stream);
+int32_t tmx_air_ladder_boundary_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                const uint64_t* d_cols, const uint64_t* d_cap, const uint64_t* d_pub, uint64_t* d_quot,
+                                                void* hip_stream);
+int32_t tmx_air_ladder_boundary_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                      uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                      const uint64_t* d_cap, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_boundary_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                                       const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d_pub, uint64_t* d_cap_q, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

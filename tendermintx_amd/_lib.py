@@ -340,6 +340,17 @@ def lib():
     except AttributeError:   # only an older build named by $TMX_LIB (tools/ab_lib.py compares library builds): the in-tree library has both
         if not os.environ.get("TMX_LIB"):
             raise
+    try:   # constraint set 2 (include/tmx.h "the boundary constraints of the ladder rows")
+        L.tmx_air_ladder_public_shape.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.tmx_air_ladder_public_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_ladder_boundary_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 5
+        L.tmx_air_ladder_boundary_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 5
+        L.tmx_air_boundary_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.tmx_trace_commit_set_air_boundary_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
     L.tmx_witness_batch_sharded_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_uint32, C.c_void_p]
     L.tmx_witness_validator_sharded_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -462,6 +462,35 @@ class Context:
         """adds the ladders' constraint quotient to the commit set as the oracle right after the ladders; d_cap_q receives its cap"""
         check(self._L.tmx_trace_commit_set_air_device(self._h, d_cap_q, self._stream(stream)), self._h)
 
+    # ---- constraint set 2: the boundary constraints of the ladder rows (include/tmx.h)
+    def air_ladder_public_shape(self, kind, n_proofs):
+        """(log2 K, columns) of the public table of n_proofs proofs at this context's n_max"""
+        return air_ladder_public_shape(kind, self.n_max, n_proofs)
+
+    def air_ladder_public_device(self, kind, n_proofs, d_elems, d_pub, stream=None):
+        """the public table (column-major, 17 n_proofs columns of K words at d_pub) from the element rows witness_batch_device wrote"""
+        check(self._L.tmx_air_ladder_public_device(self._h, kind, n_proofs, d_elems, d_pub, self._stream(stream)), self._h)
+
+    def air_ladder_boundary_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_cap, d_pub, d_quot, stream=None,
+                                            proof_range=None, accumulate=False):
+        """air_ladder_quotient_device for constraint set 2: the 33 row constraints and the 32 boundary constraints against d_pub"""
+        if proof_range is None and not accumulate:
+            check(self._L.tmx_air_ladder_boundary_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_cap, d_pub, d_quot,
+                                                                  self._stream(stream)), self._h)
+            return
+        lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+        check(self._L.tmx_air_ladder_boundary_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                                    d_cap, d_pub, d_quot, self._stream(stream)), self._h)
+
+    def air_boundary_verify_device(self, params, k_trace, d_caps, d_proof, d_pub, d_ok, stream=None):
+        """batch_verify_device, then the set-2 identity at zeta against the public table d_pub: a failed identity clears every d_ok[q]"""
+        check(self._L.tmx_air_boundary_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, d_caps, d_proof, d_pub, d_ok,
+                                                     self._stream(stream)), self._h)
+
+    def trace_commit_set_air_boundary_device(self, d_pub, d_cap_q, stream=None):
+        """trace_commit_set_air_device for constraint set 2; the two exclude each other on one set"""
+        check(self._L.tmx_trace_commit_set_air_boundary_device(self._h, d_pub, d_cap_q, self._stream(stream)), self._h)
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -599,3 +628,11 @@ def trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols
     would refuse"""
     L = L or _lib.lib()
     return int(L.tmx_trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height))
+
+
+def air_ladder_public_shape(kind, n_max, n_proofs, L=None):
+    """tmx_air_ladder_public_shape (no context, no device): (log2 K, columns) of the public table of constraint set 2"""
+    L = L or _lib.lib()
+    log_k, n_cols = C.c_uint32(), C.c_uint32()
+    check(L.tmx_air_ladder_public_shape(kind, n_max, n_proofs, C.byref(log_k), C.byref(n_cols)))
+    return int(log_k.value), int(n_cols.value)

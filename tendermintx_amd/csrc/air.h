@@ -30,4 +30,37 @@ int launch_air_ladder_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_p
 int launch_air_ladder_check(uint32_t n_proofs, uint32_t log_r, uint32_t log_sub, uint64_t om256_inv, const void* d_open_t, const void* d_open_q,
                             const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
 
+// ---- constraint set 2: set 1 plus the boundary constraints against a public table (include/tmx.h "the boundary constraints of the ladder
+// rows").  65 constraints per proof; gamma comes from phase 10 of the transcript kernel (the public digest observed behind the trace cap).
+constexpr uint32_t AIR_BOUNDARY_CONSTRAINTS = 65, AIR_PUBLIC_WIDTH = 17, AIR_PUBLIC_MAX_LOG_K = 12;
+// The tables one set-2 quotient launch reads (u64 words at d_tab; a layout of its own, set 1's stays as it is):
+//   gpow  [68][2]                gamma^0 .. gamma^66, then gamma^(65 first)
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+//   sel   [256 << log_blowup]    S(x_i), by i mod (256 << log_blowup)
+//   sinv  [256 << log_blowup]    1 / S(x_i), same period (x_i^K = s^K (w^K)^i, w^K of order 256 B)
+constexpr uint32_t AIR2_TAB_GPOW = 0, AIR2_TAB_ZINV = 136, AIR2_TAB_SEL = 200, AIR2_TAB_SINV = AIR2_TAB_SEL + (256u << 6);
+constexpr uint64_t AIR2_TAB_WORDS = AIR2_TAB_SINV + (256u << 6);
+int launch_air_boundary_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n256, uint64_t w_n256,
+                               uint64_t om256_inv, const void* d_gamma, void* d_tab, void* stream);
+// pub (column-major, 17 n_proofs columns of 2^log_k words) from the element rows: row p's lane i has its D.1b words at
+// d_rows + p elem_stride + d1b_start + i lane_elems, the sixteen words of sB then hA at point_off within them
+int launch_air_public_gather(const void* d_rows, uint64_t elem_stride, uint32_t d1b_start, uint32_t lane_elems, uint32_t point_off, uint32_t n_max,
+                             uint32_t log_k, uint32_t n_proofs, void* d_pub, void* stream);
+// d_v[2 k], d_v[2 k + 1] = V_k (k < 2^log_k) from pub and gamma (2 words at d_gamma)
+int launch_air_public_combine(uint32_t log_k, uint32_t n_proofs, const void* d_pub, const void* d_gamma, void* d_v, void* stream);
+// the twiddles of the size-K transforms: d_tw[e] = om_k^e, d_tw[K/2 + e] = om_k^-e, e < K/2
+int launch_air_public_twiddles(uint32_t log_k, uint64_t om_k, void* d_tw, void* stream);
+// the coefficients of Pub_gamma (planar, 2 K words at d_coef) from V: a size-K inverse transform, then c_j = d_j om255_inv^j / K
+int launch_air_public_coefs(uint32_t log_k, uint64_t k_inv, uint64_t om255_inv, const void* d_v, const void* d_tw, void* d_coef, void* stream);
+// Pub_gamma on the M = 2^log_m points x_i = s w^i (planar, 2 M words at d_ext): workgroup a < M / K scales the coefficients by x_a^j and runs
+// a size-K transform of both planes in LDS; point a + (M / K) b receives output b
+int launch_air_public_extend(uint32_t log_m, uint32_t log_k, uint64_t s, uint64_t w, const void* d_coef, const void* d_tw, void* d_ext, void* stream);
+// The set-2 hot pass; d_pubext = null: a piece that does not carry the public term
+int launch_air_ladder_boundary_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_tab,
+                                        const void* d_pubext, int accumulate, void* d_quot, void* stream);
+// The set-2 identity at zeta (one workgroup), with Pub_gamma(zeta) barycentric over the K points y_k = om255 om_k^k from d_v
+int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t log_sub, uint64_t om256_inv, uint64_t om255, uint64_t om_k,
+                                     uint64_t bary_inv, const void* d_open_t, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                                     const void* d_v, uint32_t n_queries, void* d_ok, void* stream);
+
 }  // namespace tmx

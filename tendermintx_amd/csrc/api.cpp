@@ -432,6 +432,10 @@ struct tmx_ctx {
   bool air_valid = false;
   void* d_set_air = nullptr;
   size_t set_air_bytes = 0;
+  // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
+  // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
+  void* d_air2 = nullptr;
+  size_t air2_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1421,6 +1425,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_set) (void)hipFree(c->d_set);
   if (c->d_set_air) (void)hipFree(c->d_set_air);
   if (c->d_air) (void)hipFree(c->d_air);
+  if (c->d_air2) (void)hipFree(c->d_air2);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -4329,6 +4334,270 @@ int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip
       const uint32_t n = std::min(per, n_proofs - p0);
       st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * AIR_LADDER_WIDTH, cols + (((uint64_t)p0 * AIR_LADDER_WIDTH) << log_sub), chunk, hip_stream);
       if (!st) st = air_piece(c, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
+    }
+    if (moved) {
+      const int32_t back = tmx_ntt_set_domain(c, root, shift);
+      if (!st) st = back;
+    }
+    if (st) return st;
+  }
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  for (uint32_t k = r.n_oracles; k > kt + 1; k--) r.o[k] = r.o[k - 1];
+  r.o[kt + 1] = {TMX_TRACE_LADDERS_QUOTIENT, log_m, 2, 0, 0, quot_b, false, true};
+  r.n_oracles++;
+  c->set = r;
+  return TMX_OK;
+}
+
+}  // extern "C"
+
+// ---- constraint set 2: the boundary constraints of the ladder rows (include/tmx.h "the boundary constraints of the ladder rows") ----------
+// Beside set 1: the functions above are not touched.  K = N / 256 ladders; the public table is 17 n_proofs columns of K words.
+struct AirGeo2 { uint32_t log_k; uint64_t s, w, om_k, om255, om255_inv, k_inv, bary_inv; };
+constexpr uint64_t AIR2_K_MAX = 1ull << AIR_PUBLIC_MAX_LOG_K;
+constexpr uint64_t AIR2_OFF_TW = AIR2_TAB_WORDS, AIR2_OFF_VP = AIR2_OFF_TW + AIR2_K_MAX, AIR2_OFF_VV = AIR2_OFF_VP + 2 * AIR2_K_MAX,
+                   AIR2_OFF_COEF = AIR2_OFF_VV + 2 * AIR2_K_MAX, AIR2_OFF_LEVP = AIR2_OFF_COEF + 2 * AIR2_K_MAX,
+                   AIR2_OFF_LEVV = AIR2_OFF_LEVP + 8 * AIR2_K_MAX, AIR2_OFF_EXT = AIR2_OFF_LEVV + 8 * AIR2_K_MAX;
+
+static int32_t air2_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
+  const int32_t st = air_check(c, log_n, log_blowup, n_proofs);
+  if (st) return st;
+  if (log_n - log_blowup < 9) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 9: the boundary constraints need two ladders");
+  if (log_n - log_blowup > 8 + AIR_PUBLIC_MAX_LOG_K) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at most 20: at most 2^12 ladders");
+  return TMX_OK;
+}
+
+static void air2_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, const AirGeo& A, AirGeo2& B) {
+  const uint64_t P = 0xffffffff00000001ull;
+  B.log_k = log_n - log_blowup - 8;
+  B.s = shift % P;
+  B.w = gl_pow_host(root_2_32, 1ull << (32 - log_n));
+  B.om_k = gl_pow_host(B.w, 1ull << (8 + log_blowup));  // omega_N^256 = w^(256 B)
+  B.om255 = gl_pow_host(B.w, 255ull << log_blowup);
+  B.om255_inv = gl_pow_host(B.om255, P - 2);
+  B.k_inv = gl_pow_host(1ull << B.log_k, P - 2);
+  B.bary_inv = (uint64_t)(((unsigned __int128)B.k_inv * gl_pow_host(A.om256_inv, P - 2)) % P);  // 1 / (K omega_256^-1)
+}
+
+// the set-2 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
+static int32_t air2_scratch(tmx_ctx* c, uint32_t log_m) {
+  const size_t want = (AIR2_OFF_EXT + (log_m ? (size_t)2 << log_m : 0)) * 8;
+  if (c->air2_bytes < want) {
+    if (c->d_air2) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air2)); c->d_air2 = nullptr; c->air2_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air2, want));
+    c->air2_bytes = want;
+  }
+  return TMX_OK;
+}
+
+// gamma of set 2: the public table's digest (its Poseidon Merkle root), then phase 10 over the trace cap and the digest
+static int32_t air2_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t log_k, const uint64_t* d_cap,
+                          const uint64_t* d_pub, bool verifier, void* hip_stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air2) + (verifier ? AIR2_OFF_LEVV : AIR2_OFF_LEVP);
+  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, hip_stream);
+  if (st) return st;
+  FriGeom G;
+  std::memset(&G, 0, sizeof G);
+  const uint32_t obs[5] = {2 /* the constraint-set id: the ladder rows with their boundaries */, log_n, log_blowup, cap_height, n_proofs};
+  std::memcpy(G.params, obs, sizeof obs);
+  G.cap_height = std::min(cap_height, log_n);
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
+  const int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 10, 0, d_cap, lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32,
+                                       nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// Pub_gamma on the coset from the public table and the prover's gamma: V, the coefficients, the extension
+static int32_t air2_public(tmx_ctx* c, uint32_t log_m, const AirGeo2& B, uint32_t n_proofs, const uint64_t* d_pub, hipStream_t s) {
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  int rc = launch_air_public_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR2_OFF_VP, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR2_OFF_TW, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_coefs(B.log_k, B.k_inv, B.om255_inv, X + AIR2_OFF_VP, X + AIR2_OFF_TW, X + AIR2_OFF_COEF, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR2_OFF_COEF, X + AIR2_OFF_TW, X + AIR2_OFF_EXT, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// one piece of the table, as air_piece; the piece whose first proof is proof 0 carries - Pub_gamma / S
+static int32_t air2_piece(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo& A, uint32_t first, uint32_t n, const uint64_t* cols,
+                          bool accumulate, uint64_t* d_quot, hipStream_t s) {
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  int rc = launch_air_boundary_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, gamma, X, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_boundary_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_ladder_boundary_quotient(log_n, log_blowup, n, cols, X, first == 0 ? X + AIR2_OFF_EXT : nullptr, accumulate ? 1 : 0, d_quot, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_air_ladder_public_shape(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols) {
+  uint32_t log_rows = 0, width = 0;
+  if (n_proofs < 1 || tmx_trace_commit_shape(kind, n_max, TMX_TRACE_LADDERS, &log_rows, &width) != TMX_OK) return TMX_ERR_BAD_ARG;
+  if (log_rows < 9 || log_rows > 8 + AIR_PUBLIC_MAX_LOG_K || (uint64_t)n_proofs * AIR_LADDER_WIDTH > TMX_DEEP_MAX_COLS) return TMX_ERR_BAD_ARG;
+  if (log_k) *log_k = log_rows - 8;
+  if (n_cols) *n_cols = AIR_PUBLIC_WIDTH * n_proofs;
+  return TMX_OK;
+}
+
+int32_t tmx_air_ladder_public_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (kind != TMX_KIND_SKIP && kind != TMX_KIND_STEP) return fail(c, TMX_ERR_BAD_ARG, "kind must be TMX_KIND_SKIP or TMX_KIND_STEP");
+  uint32_t log_k = 0;
+  if (tmx_air_ladder_public_shape(kind, c->cfg.n_max, n_proofs, &log_k, nullptr))
+    return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1 (65 n_proofs at most 2^24) and the ladders table 2 .. 2^12 ladders");
+  if (!d_elems || !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_elems and d_pub must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const Program& prog = c->prog[kind];
+  // D.1b of a lane: h (8), then A.x A.y R.x R.y, then sB.x sB.y hA.x hA.y: the sixteen words of sB start at element 40
+  const int rc = launch_air_public_gather(d_elems, prog.sp.elem_stride, prog.d1b_start, D1B_LANE_ELEMS, 8 + 4 * 8, c->cfg.n_max, log_k, n_proofs, d_pub,
+                                          hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_gather launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_air_ladder_boundary_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                      uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                      const uint64_t* d_cap, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = air2_check(c, log_n, log_blowup, n_proofs);
+  if (st) return st;
+  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
+  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
+  if (!d_cols || !d_cap || !d_pub || !d_quot) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_cap, d_pub and d_quot must be set");
+  AirGeo A;
+  if ((st = air_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  AirGeo2 B;
+  air2_geo(log_n, log_blowup, c->ntt_root, c->ntt_shift, A, B);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if ((st = air2_scratch(c, log_n))) return st;
+  if ((st = air2_gamma(c, log_n, log_blowup, cap_height, n_proofs, B.log_k, d_cap, d_pub, false, hip_stream))) return st;
+  if (proof_lo == 0 && (st = air2_public(c, log_n, B, n_proofs, d_pub, s))) return st;
+  if ((st = air2_piece(c, log_n, log_blowup, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_LADDER_WIDTH) << log_n),
+                       accumulate != 0, d_quot, s)))
+    return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  return TMX_OK;
+}
+
+int32_t tmx_air_ladder_boundary_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                const uint64_t* d_cols, const uint64_t* d_cap, const uint64_t* d_pub, uint64_t* d_quot,
+                                                void* hip_stream) {
+  return tmx_air_ladder_boundary_quotient_range_device(c, log_n, log_blowup, cap_height, n_proofs, 0, n_proofs, 0, d_cols, d_cap, d_pub, d_quot,
+                                                       hip_stream);
+}
+
+int32_t tmx_air_boundary_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                                       const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (k_trace + 1 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, "k_trace and k_trace + 1 must both be oracles of the proof");
+  if (p->n_cols[k_trace] % AIR_LADDER_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 65 columns");
+  if (p->log_n[k_trace + 1] != p->log_n[k_trace] || p->n_cols[k_trace + 1] != 2)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_LADDER_WIDTH;
+  if ((st = air2_check(c, log_n, p->log_blowup, n_proofs))) return st;
+  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
+  AirGeo A;
+  if ((st = air_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  AirGeo2 B;
+  air2_geo(log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A, B);
+  if (!d_caps || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_caps, d_proof and d_ok must be set");
+  if ((st = air_scratch(c, p->log_blowup))) return st;
+  if ((st = air2_scratch(c, 0))) return st;
+  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // zeta as the batch transcript draws it, gamma from the trace cap and the verifier's own digest of d_pub, V from d_pub, then the identity
+  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
+  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = air2_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, B.log_k, d_caps + G.o_cap_at[k_trace], d_pub, true, hip_stream))) return st;
+  rc = launch_air_public_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, X + AIR2_OFF_VV, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_ladder_boundary_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, B.om255, B.om_k, B.bary_inv,
+                                        d_proof + L.off_open[k_trace], d_proof + L.off_open[k_trace + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
+                                        X + AIR2_OFF_VV, p->n_queries, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_check launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_pub, uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
+  if (st) return st;
+  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
+  if (!d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_q is null");
+  tmx_ctx::SetRec r = c->set;
+  uint32_t kt = r.n_oracles;
+  for (uint32_t k = 0; k < r.n_oracles; k++) {
+    if (r.o[k].section == TMX_TRACE_LADDERS_QUOTIENT) return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the ladders' constraint quotient");
+    if (r.o[k].section == TMX_TRACE_LADDERS) kt = k;
+  }
+  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold TMX_TRACE_LADDERS");
+  if (r.n_oracles >= TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for one more oracle");
+  const tmx_ctx::SetRec::Oracle lad = r.o[kt];
+  const uint32_t log_m = lad.log_m, log_sub = log_m - r.log_blowup, n_proofs = lad.n_cols / AIR_LADDER_WIDTH, h = std::min(r.cap_height, log_m);
+  if ((st = air2_check(c, log_m, r.log_blowup, n_proofs))) return st;
+  if (lad.streamed && r.chunk_cols < AIR_LADDER_WIDTH)
+    return fail(c, TMX_ERR_BAD_ARG, "a streamed ladders member is fed in chunks of whole proofs: chunk_cols must be at least 65");
+  AirGeo A;
+  if ((st = air_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
+  AirGeo2 B;
+  air2_geo(log_m, r.log_blowup, r.root, r.shift, A, B);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, r.log_blowup))) return st;
+  if ((st = air2_scratch(c, log_m))) return st;
+  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
+  const size_t quot_b = ((size_t)2 << log_m) * 8, want = quot_b + (size_t)n_dig * 32;
+  if (c->set_air_bytes < want) {
+    if (c->d_set_air) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_air)); c->d_set_air = nullptr; c->set_air_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_set_air, want));
+    c->set_air_bytes = want;
+  }
+  uint8_t* base = reinterpret_cast<uint8_t*>(c->d_set);
+  uint64_t* quot = reinterpret_cast<uint64_t*>(c->d_set_air);
+  uint64_t* lev_q = quot + ((size_t)2 << log_m);
+  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + lad.lev_off);
+  if ((st = air2_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, B.log_k, lev_t + 4 * (n_dig - n_cap), d_pub, false, hip_stream))) return st;
+  // Pub_gamma is extended by kernels of its own from the set's root and shift: the context's NTT domain plays no part in it
+  if ((st = air2_public(c, log_m, B, n_proofs, d_pub, s))) return st;
+  if (!lad.streamed) {
+    if ((st = air2_piece(c, log_m, r.log_blowup, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + lad.lde_off), false, quot, s))) return st;
+  } else {
+    // chunks of whole proofs, as tmx_trace_commit_set_air_device feeds them
+    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+    const bool moved = root != r.root || shift != r.shift;
+    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+    const uint64_t* cols = reinterpret_cast<const uint64_t*>(base + lad.cols_off);
+    uint64_t* chunk = reinterpret_cast<uint64_t*>(base + r.chunk_off);
+    const uint32_t per = r.chunk_cols / AIR_LADDER_WIDTH;
+    for (uint32_t p0 = 0; p0 < n_proofs && !st; p0 += per) {
+      const uint32_t n = std::min(per, n_proofs - p0);
+      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * AIR_LADDER_WIDTH, cols + (((uint64_t)p0 * AIR_LADDER_WIDTH) << log_sub), chunk, hip_stream);
+      if (!st) st = air2_piece(c, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
     }
     if (moved) {
       const int32_t back = tmx_ntt_set_domain(c, root, shift);

@@ -91,7 +91,8 @@ int launch_deep_quotient(uint32_t log_m, uint64_t s, uint64_t w, uint64_t omega_
 // Grinding splits phase 2: phase 5 (2a): final coefficients and pow_bits observed, the duplex left in d_state, the search's words reset;
 // phase 6 (2b): the nonce the search left -> the proof, observed, r drawn, then the indices as phase 2.
 // The constraint challenge: phase 9: a fresh duplex, 2^33, G.params[0 .. 5) (set id, log_n, log_blowup, cap_height, n_proofs), the trace cap
-// at d_commit_cap (4 << G.cap_height words) -> gamma (chal[FRI_GAMMA_AT]).
+// at d_commit_cap (4 << G.cap_height words) -> gamma (chal[FRI_GAMMA_AT]).  phase 10: the same, then the 4 words of the public table's
+// digest, READ at d_proof, before gamma is drawn (constraint set 2).
 int launch_fri_transcript(const void* d_consts, int mode, const FriGeom& G, int phase, uint32_t layer, const void* d_commit_cap, void* d_proof,
                           void* d_state, void* d_chal, void* d_qidx, void* stream);
 // The search between phases 5 and 6: the smallest nonce whose challenge has pow_bits leading zero bits, from the duplex in d_state, into

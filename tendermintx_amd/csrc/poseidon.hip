@@ -464,7 +464,7 @@ __device__ __forceinline__ gl2 chal_start_batch(FriChal& c, const PosConsts& K, 
 // halves around k_fri_grind: the final coefficients and pow_bits observed (phase 5), the nonce observed and r drawn -> the indices (phase 6).
 // The batch proof: its start over the K caps at commit_cap -> zeta (phase 7), the K openings roots at commit_cap -> alpha (phase 8).
 // The constraint challenge (include/tmx.h "the constraint quotient of the ladder rows"): a transcript of its own over the trace cap at
-// commit_cap -> gamma (phase 9).
+// commit_cap -> gamma (phase 9); constraint set 2: the same with the public table's digest (4 words at `proof`) behind the cap (phase 10).
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restrict__ consts, FriGeom G, int phase, uint32_t layer,
                                                        const uint64_t* __restrict__ commit_cap, uint64_t* __restrict__ proof, uint64_t* __restrict__ state,
@@ -489,6 +489,21 @@ __global__ __launch_bounds__(64) void k_fri_transcript(const uint64_t* __restric
     chal_observe<MODE>(c, K, 1ull << 33);
     for (int k = 0; k < 5; k++) chal_observe<MODE>(c, K, G.params[k]);
     chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
+    gl2 g;
+    do {
+      g.c0 = chal_challenge<MODE>(c, K);
+      g.c1 = chal_challenge<MODE>(c, K);
+    } while (g.c1 == 0);
+    chal[FRI_GAMMA_AT] = g.c0;
+    chal[FRI_GAMMA_AT + 1] = g.c1;
+  } else if (phase == 10) {
+    // constraint set 2 (include/tmx.h "the boundary constraints of the ladder rows"): as phase 9 with G.params[0] = 2, then the four words
+    // of the public table's digest, read at `proof` (nothing is written there)
+    chal_init(c);
+    chal_observe<MODE>(c, K, 1ull << 33);
+    for (int k = 0; k < 5; k++) chal_observe<MODE>(c, K, G.params[k]);
+    chal_observe_span<MODE>(c, K, commit_cap, 4ull << G.cap_height);
+    chal_observe_span<MODE>(c, K, proof, 4);
     gl2 g;
     do {
       g.c0 = chal_challenge<MODE>(c, K);

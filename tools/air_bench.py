@@ -7,6 +7,11 @@
   set      P proofs at N = n (64 x 128 by default: the ladders fit resident), all five tables: the set prove without and with the quotient
            oracle, alternating; the set-air call on a resident and on a streamed (CHUNK columns) ladders member.  The streamed call extends
            every chunk once more: its excess over the resident call is the re-LDE.
+  kernels2 the same resident columns as `kernels` with a random public table: the set-1 quotient call and the set-2 call (digest, transcript,
+           V, coefficients, extension, tables, k_air_ladder_boundary_quotient), alternating.  Under `rocprofv3 --kernel-trace --stats` (MODE=
+           kernels2,set2) both hot passes and the public-side kernels show in ONE trace.
+  set2     as `set` for constraint set 2 next to set 1: the gather, then the set-level calls of both sets on a resident and on a streamed
+           ladders member, alternating inside one process; the prove and tmx_air_boundary_verify_device over the set-2 quotient.
   parent   the set commit + prove WITHOUT any air call, for library builds named in LIBS (comma separated), one subprocess per measurement,
            alternating under TMX_LIB (differences between boxes exceed most changes: compare inside one call).
 Times per call from HIP events around REPS back-to-back calls after one warm call.
@@ -87,6 +92,84 @@ if "kernels" in modes:
     print(json.dumps(res), flush=True)
     ctx.close()
     del cols, lv, quot, proof
+    torch.cuda.empty_cache()
+
+if "kernels2" in modes:
+    log_m, cp = int(os.environ.get("LOG_M", "18")), int(os.environ.get("COLS_PROOFS", "70"))
+    n_cols, log_k = 65 * cp, log_m - log_blowup - 8
+    ctx = Context(4, b"celestia", device=0)
+    cols = torch.randint(0, 2**62, (n_cols << log_m,), dtype=torch.int64, device=dev)
+    pub = torch.randint(0, 2**62, ((17 * cp) << log_k,), dtype=torch.int64, device=dev)
+    lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+    ctx.poseidon_merkle_device(log_m, n_cols, cols.data_ptr(), cap_h, lv.data_ptr(), 0)
+    cap = lv[-(4 << cap_h):]
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    res = {"mode": "kernels2", "columns": n_cols, "log_m": log_m, "log_k": log_k, "table_gib": round(n_cols * 8 * 2**log_m / 2**30, 2), "reps": reps,
+           "set1_call_ms": [], "set2_call_ms": []}
+    for _ in range(rounds):
+        res["set1_call_ms"].append(r4(timed(lambda: ctx.air_ladder_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), cap.data_ptr(),
+                                                                                   quot.data_ptr(), 0), reps)))
+        res["set2_call_ms"].append(r4(timed(lambda: ctx.air_ladder_boundary_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), cap.data_ptr(),
+                                                                                            pub.data_ptr(), quot.data_ptr(), 0), reps)))
+    res["set2_gb_per_s"] = round(n_cols * 8 * 2**log_m / min(res["set2_call_ms"]) / 1e6, 1)
+    res["ratio_set2_over_set1_call"] = round(min(res["set2_call_ms"]) / min(res["set1_call_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols, pub, lv, quot
+    torch.cuda.empty_cache()
+
+if "set2" in modes:
+    from tendermintx_amd.synth import bench_workload
+    w = bench_workload("survey8d", n, P, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=P)
+    out = torch.empty(P * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(P * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(P * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, P, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, P, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    ALL, LADDERS = 1 | 2 | 4 | 16 | 32, 1
+    log_k, pub_cols = ctx.air_ladder_public_shape(KIND_SKIP, P)
+    pub = torch.empty(pub_cols << log_k, dtype=torch.int64, device=dev)
+    caps = torch.zeros(5 * (4 << cap_h), dtype=torch.int64, device=dev)
+    cap_q = torch.zeros(4 << cap_h, dtype=torch.int64, device=dev)
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+
+    def commit2(streamed):
+        if streamed:
+            ctx.trace_commit_set_streamed_device(KIND_SKIP, P, ALL, LADDERS, chunk, log_blowup, cap_h, tr.data_ptr(), caps.data_ptr(), 0)
+        else:
+            ctx.trace_commit_set_device(KIND_SKIP, P, ALL, log_blowup, cap_h, tr.data_ptr(), caps.data_ptr(), 0)
+
+    air1 = lambda: ctx.trace_commit_set_air_device(cap_q.data_ptr(), 0)
+    air2 = lambda: ctx.trace_commit_set_air_boundary_device(pub.data_ptr(), cap_q.data_ptr(), 0)
+    res = {"mode": "set2", "proofs": P, "n": n, "chunk_cols": chunk, "reps": reps, "log_k": log_k, "public_columns": pub_cols,
+           "gather_ms": r4(timed(lambda: ctx.air_ladder_public_device(KIND_SKIP, P, out.data_ptr(), pub.data_ptr(), 0), reps)),
+           "set1_resident_ms": [], "set2_resident_ms": [], "set1_streamed_ms": [], "set2_streamed_ms": [], "prove_with_set2_ms": []}
+    for _ in range(rounds):
+        res["set1_resident_ms"].append(r4(timed(air1, reps, before=lambda: commit2(False))))
+        res["set2_resident_ms"].append(r4(timed(air2, reps, before=lambda: commit2(False))))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_set2_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt, cw = order.index(LADDERS), 4 << cap_h
+        all_caps = torch.cat([caps[:(kt + 1) * cw], cap_q, caps[(kt + 1) * cw:]])
+        res["verify_set2_ms"] = r4(timed(lambda: ctx.air_boundary_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), pub.data_ptr(),
+                                                                                ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        keep = cap_q.clone()
+        res["set1_streamed_ms"].append(r4(timed(air1, reps, before=lambda: commit2(True))))
+        res["set2_streamed_ms"].append(r4(timed(air2, reps, before=lambda: commit2(True))))
+        res["streamed_cap_equal"] = bool(torch.equal(keep, cap_q))
+        del proof
+    res["ratio_set2_over_set1_resident"] = round(min(res["set2_resident_ms"]) / min(res["set1_resident_ms"]), 3)
+    res["ratio_set2_over_set1_streamed"] = round(min(res["set2_streamed_ms"]) / min(res["set1_streamed_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del out, tr, pub
     torch.cuda.empty_cache()
 
 if "set" in modes or "set_plain" in modes:
