@@ -346,6 +346,19 @@ int32_t tmx_sync(tmx_ctx* ctx);
  * walked a per-key table (a key resident in the key cache, or a new key with >= 8 lanes per key on average; TMX_DEDUP=0|1|2 forces
  * never / automatic / whenever a table fits).  Blocks. */
 int32_t tmx_last_dedup(tmx_ctx* ctx, uint32_t* n_unique, uint32_t* used_tables);
+/* Which launch computed the proof-level values (header and validator trees, tallies, trusted-key match) of the last batch enqueued on
+ * this context: the small path's two launches, k_proof as role workgroups, or one workgroup per proof in the instantiation for
+ * VALIDATOR_SET_SIZE_MAX <= 128 / <= 256 / <= 512.  A host-side field: no device traffic, does not block.  NONE before the first batch;
+ * calls that run no proof stage (the EdDSA-only, trace and commitment entry points) leave it as it is; TMX_ERR_BAD_ARG for a null context. */
+enum tmx_proof_path {
+  TMX_PROOF_PATH_NONE = 0,
+  TMX_PROOF_PATH_TINY = 1,
+  TMX_PROOF_PATH_ROLES = 2,
+  TMX_PROOF_PATH_R168 = 3,
+  TMX_PROOF_PATH_K256 = 4,
+  TMX_PROOF_PATH_WIDE = 5
+};
+int32_t tmx_last_proof_path(tmx_ctx* ctx);
 
 /* ---- multi-GPU: one process per GPU, the exchange step behind this ABI so that the host the reference actually has -- the
  * Rust process of bin/skip.rs, reached only through SkipOffchainInputs::hint (reference circuits/skip.rs:64-102) -- can shard without

@@ -15,6 +15,7 @@ N_KERNELS = 4
 KERNEL_NAMES = ("k_eddsa", "k_proof", "k_verdict", "k_serialize")
 ED_STRIDE = 448
 SEC_HINT, SEC_DERIVED, SEC_ALL = 1, 2, 3   # TMX_SEC_*
+PROOF_PATH_NONE, PROOF_PATH_TINY, PROOF_PATH_ROLES, PROOF_PATH_R168, PROOF_PATH_K256, PROOF_PATH_WIDE = range(6)   # TMX_PROOF_PATH_*
 TRACE_LADDERS, TRACE_SHA512, TRACE_SHA256, TRACE_MATCH, TRACE_TREE, TRACE_HEADER, TRACE_ALL = 1, 2, 4, 8, 16, 32, 63   # TMX_TRACE_*
 TRACE_LADDERS_QUOTIENT = 64   # TMX_TRACE_LADDERS_QUOTIENT: the constraint quotient as a member of a commit set
 
@@ -364,6 +365,8 @@ def lib():
     L.tmx_ctx_stream.argtypes = [C.c_void_p]
     L.tmx_sync.argtypes = [C.c_void_p]
     L.tmx_last_dedup.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.tmx_last_proof_path.restype = C.c_int32
+    L.tmx_last_proof_path.argtypes = [C.c_void_p]
     L.tmx_key_cache_stats.argtypes = [C.c_void_p, C.POINTER(KeyCacheInfo)]
     L.tmx_key_cache_flush.argtypes = [C.c_void_p]
     L.tmx_key_cache_config.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]

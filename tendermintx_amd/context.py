@@ -547,6 +547,13 @@ class Context:
         check(self._L.tmx_last_dedup(self._h, C.byref(u), C.byref(t)), self._h)
         return int(u.value), bool(t.value)
 
+    def last_proof_path(self):
+        """Which launch computed the proof-level values of the last batch (tmx_last_proof_path): one of _lib.PROOF_PATH_*.  Host-side, does not block."""
+        path = int(self._L.tmx_last_proof_path(self._h))
+        if path < 0:
+            check(path, self._h)
+        return path
+
     # ---- persistent per-key table cache (tmx_key_cache_*)
     def key_cache_stats(self):
         info = _lib.KeyCacheInfo()

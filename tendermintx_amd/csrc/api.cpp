@@ -452,6 +452,7 @@ struct tmx_ctx {
   void* d_shadow = nullptr;    // key bytes + flags of the lanes of a small launch (TINY_MAX_LANES records): what its key pipeline reads
   bool slot_tiny[EV_RING_DECL] = {};  // which event sets of the ring belong to small launches (their four events mark other points)
   uint64_t last_lanes = 0;
+  int32_t last_proof_path = TMX_PROOF_PATH_NONE;  // which launch computed the proof-level values of the last batch (tmx_last_proof_path)
   // scratch sized for cfg.max_batch proofs
   void *d_ed = nullptr, *d_tl = nullptr, *d_lr = nullptr, *d_pf = nullptr, *d_nodes_t = nullptr, *d_nodes_r = nullptr, *d_reports = nullptr;
   // staging for the host-buffer entry points
@@ -613,6 +614,8 @@ static int32_t run_batch(tmx_ctx* c, int32_t kind, uint32_t n_proofs, const void
   // vs 0.41 ms) and k_proof is hidden behind it anyway (32 / 64 proofs: +-1 %)
   const uint64_t lanes_all = (uint64_t)n_proofs * n;
   const bool roles = K.proof_roles && c->d_tiny && (lanes_all <= 2048 || (!eddsa_writes_rows && lanes_all <= 16384));
+  static_assert(PROOF_KERNEL_R168 == TMX_PROOF_PATH_R168 && PROOF_KERNEL_K256 == TMX_PROOF_PATH_K256 && PROOF_KERNEL_WIDE == TMX_PROOF_PATH_WIDE, "tmx.h");
+  c->last_proof_path = roles ? TMX_PROOF_PATH_ROLES : (int32_t)proof_kernel_of(n);   // (launch_proof picks its kernel by the same function)
   if (!roles && c->setc.table && ++c->setc_epoch == 0) c->setc_epoch = 1;  // (ages are differences mod 2^32: a wrap is harmless)
   rc = roles
            ? launch_proof_roles(proof_params(c, kind, leaves_first), n_proofs, d_proofs, d_targets, d_trusteds, tl + TL_OFF_LT, TL_STRIDE, c->d_lr, c->d_pf,
@@ -942,6 +945,7 @@ static int32_t run_tiny(tmx_ctx* c, int32_t kind, uint32_t n_proofs, const void*
   if (!x) HIPCK(c, hipEventRecord(ev[3], s));
   // (enqueued after both launches of the caller's stream: the key pipeline is nobody's critical path)
   if ((st = tiny_key_pipeline(c, n_proofs * n, ev[1]))) return st;
+  c->last_proof_path = TMX_PROOF_PATH_TINY;
   c->slot_tiny[slot] = true;
   c->last_stream = s; c->last_stream_valid = true;
   c->ev_done = ev[3];
@@ -1596,6 +1600,8 @@ int32_t tmx_last_dedup(tmx_ctx* c, uint32_t* n_unique, uint32_t* used_tables) {
   *used_tables = (c->knobs.dedup_mode != 0 && (st[KC_LAST_HIT_LANES] != 0 || (st[KC_LAST_BUILT] != 0 && st[KC_LAST_USE_NEW] != 0))) ? 1u : 0u;
   return TMX_OK;
 }
+
+int32_t tmx_last_proof_path(tmx_ctx* c) { return c ? c->last_proof_path : TMX_ERR_BAD_ARG; }
 
 int32_t tmx_key_cache_stats(tmx_ctx* c, tmx_key_cache_info* out) {
   if (!c || !out) return TMX_ERR_BAD_ARG;

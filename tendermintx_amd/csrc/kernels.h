@@ -80,6 +80,10 @@ int launch_ed_mul_tab(const EdQuad& Q, uint32_t part, uint32_t parts, void* stre
 int launch_ed_base(const EdQuad& Q, void* stream, void* done = nullptr);  // s*B alone (the hash role ran as k_ed_hash)
 // which: 0 every lane, 1 only lanes of resident keys (cache hits), 2 only the others (the split warm schedule finishes them on the side stream)
 int launch_ed_fin(const EdQuad& Q, void* stream, bool fused_direct = false, uint32_t which = 0);
+// which instantiation of proof_body<NMAX> launch_proof runs at VALIDATOR_SET_SIZE_MAX = n: k_proof_r168 (NMAX 128), k_proof (256), k_proof_wide (512);
+// the values are tmx.h's TMX_PROOF_PATH_R168 / _K256 / _WIDE (api.cpp asserts it)
+enum ProofKernel : int32_t { PROOF_KERNEL_R168 = 3, PROOF_KERNEL_K256 = 4, PROOF_KERNEL_WIDE = 5 };
+inline ProofKernel proof_kernel_of(uint32_t n) { return n <= 128 ? PROOF_KERNEL_R168 : (n > 256 ? PROOF_KERNEL_WIDE : PROOF_KERNEL_K256); }
 int launch_proof(const ProofParams& P, uint32_t n_proofs, const void* d_proofs, const void* d_target, const void* d_trusted, void* d_lt,
                  uint32_t lt_stride, void* d_lr, void* d_pf, void* d_nodes_t, void* d_nodes_r, void* d_reports, void* stream, void* started = nullptr,
                  void* done = nullptr, const SetCache& SC = SetCache{});

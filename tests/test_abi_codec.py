@@ -22,6 +22,21 @@ def test_exports_every_declared_symbol(built_lib):
         assert hasattr(built_lib, n), f"libtmx.so does not export {n}"
 
 
+def test_symbols_and_wrappers_exist_for_the_proof_path(built_lib):
+    """tmx_last_proof_path is in the built library, bound in _lib.py and wrapped in context.py; _lib's PROOF_PATH_* are the header's enum;
+    a null context is refused (the accessor reads a host-side field of the context: no GPU needed to say so)"""
+    from tendermintx_amd import _lib
+    from tendermintx_amd.context import Context
+    assert built_lib.tmx_last_proof_path.argtypes == [C.c_void_p] and built_lib.tmx_last_proof_path.restype is C.c_int32
+    assert callable(Context.last_proof_path)
+    hdr = open(os.path.join(ROOT, "include", "tmx.h")).read()
+    enum = {name: int(v) for name, v in re.findall(r"\bTMX_PROOF_PATH_([A-Z0-9]+)\s*=\s*(\d+)", hdr)}
+    assert enum == {"NONE": 0, "TINY": 1, "ROLES": 2, "R168": 3, "K256": 4, "WIDE": 5}
+    for name, v in enum.items():
+        assert getattr(_lib, "PROOF_PATH_" + name) == v
+    assert built_lib.tmx_last_proof_path(None) == -1      # TMX_ERR_BAD_ARG
+
+
 def test_no_hip_runtime_dt_needed():
     """libtmx.so must not pin a HIP runtime: the process (PyTorch or a C/Rust host) provides it -- INTEGRATION.md"""
     import subprocess

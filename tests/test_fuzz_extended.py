@@ -13,7 +13,7 @@ from test_gpu_parity import _check_vs_oracle
 pytestmark = pytest.mark.gpu
 
 SEEDS = int(os.environ.get("TMX_FUZZ_SEEDS", "64"))
-NSET = tuple(int(v) for v in os.environ.get("TMX_FUZZ_NSET", "1,2,4,7,16,31,32,33,64,100,128").split(","))   # e.g. 200,256,300,512: the wide k_proof
+NSET = tuple(int(v) for v in os.environ.get("TMX_FUZZ_NSET", "1,2,4,7,16,31,32,33,64,100,128").split(","))   # (N > 128 -- k_proof, k_proof_wide: test_large_sets.py)
 CHAIN_IDS = (b"celestia", b"mocha-4", b"a", b"thirteen-char")          # what the synthetic sign-bytes can carry
 CTX_CHAIN_IDS = CHAIN_IDS + (b"x" * 50, b"celestia-but-longer")              # what a context can be configured for
 EXTREME_BYTES = (0x00, 0x01, 0x7f, 0x80, 0xfe, 0xff)

@@ -456,6 +456,7 @@ def test_batch_equals_individual_and_is_idempotent(tmx, oracle):
 def test_device_resident_path_with_torch(tmx, oracle):
     """tmx_witness_batch_device on PyTorch-owned HBM buffers and PyTorch's current stream (one HIP runtime per process)"""
     import torch
+    from tendermintx_amd import _lib
     from tendermintx_amd.synth import Workload
     n, P = 128, 12
     wl = Workload(0, n, P, 128, chain_id=b"celestia", seed=31337, signed_permille=900)
@@ -472,6 +473,7 @@ def test_device_resident_path_with_torch(tmx, oracle):
         ms = ctx.kernel_ms_mean(1)
         # (1536 lanes = the largest small launch: k_tiny is attributed ONCE, to the EdDSA slot -- the four figures are disjoint intervals of the launch)
         assert all(v >= 0 for v in ms.values()) and ms["k_eddsa"] > 0 and ms["k_verdict"] > 0 and ms["k_proof"] == 0
+        assert ctx.last_proof_path() == _lib.PROOF_PATH_TINY
     got = out[:, :count].cpu().numpy().view(np.uint64)
     want, oreps = oracle.witness_batch(0, P, wl.proofs, wl.targets, wl.trusteds, n, b"celestia", 100800, n_threads=8)
     assert np.array_equal(got, want)
