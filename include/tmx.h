@@ -1038,6 +1038,85 @@ int32_t tmx_air_boundary_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, 
                                        const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d_pub, uint64_t* d_cap_q, void* hip_stream);
 
+/* ---- the round constraints of the SHA-256 tables (constraint set 3) ---------------------------------------------------------------------
+ * Sets 1 and 2 argue about the ladders; three of the five committed row tables are SHA-256 round tables -- T.3 the validator leaf hashes
+ * (TMX_TRACE_SHA256), T.5 the validator-tree nodes (TMX_TRACE_TREE), T.6 the header inclusion proofs (TMX_TRACE_HEADER) -- and the proofs
+ * above say nothing about their rows.  Set 3 proves the SHA-256 ROUND FUNCTION on them: a helper oracle of bits committed behind the table,
+ * 315 constraints per proof, one two-column quotient oracle behind the helper, and the identity at zeta.  Built beside sets 1 and 2: no
+ * existing kernel, transcript phase, proof word or call changes; the batch prover, its proof format and tmx_batch_verify_device are used
+ * UNCHANGED.  Notation as above: N rows, M = N B points x_i = s w^i, omega = omega_N, omega_64 = omega^(N/64) (N >= 64),
+ * S(x) = x^(N/64) - omega_64^-1 (zero exactly on the rows r = 63 mod 64), K(x) = P_K(x^(N/64)) with P_K of degree < 64 and
+ * P_K(omega_64^t) = K256[t], the SHA-256 round constants.  Same field, extension, duplex and caveats as the blocks above (PARITY UNPINNED).
+ *   table      9 n_proofs columns; inside a proof W 0, a 1, b 2, c 3, d 4, e 5, f 6, g 7, h 8; row t of a block holds W_t and the state after
+ *              round t (docs/level2_rows.md); every block sits on a 64-row boundary.
+ *   helper     300 columns per proof, the table's rows, bits LSB first.  Offsets inside a proof:
+ *                0 .. 31   A   bits of a            128 .. 159  F   bits of f             256 .. 287  V   V_i = A_i B_i
+ *               32 .. 63   B   bits of b            160 .. 191  G   bits of g             288 S0 = Sigma0(a)   289 S1 = Sigma1(e)   (words)
+ *               64 .. 95   C   bits of c            192 .. 223  U0  U0_i = A_(i+2) xor A_(i+13)   290 CH = Ch(e,f,g)   291 MAJ = Maj(a,b,c)
+ *               96 .. 127  E   bits of e            224 .. 255  U1  U1_i = E_(i+6) xor E_(i+11)   292 LIVE   293 KL   294 .. 296 CA   297 .. 299 CE
+ *              (indices of A and E mod 32).  LIVE = 1 iff row r - r mod 64 of the proof's table has a nonzero word; KL = LIVE K256[r mod 64];
+ *              CA, CE the carry bits of the a and e updates.  Defined for ANY input: the operands are the low 32 bits of each table word;
+ *              on rows r != 63 mod 64, with primed values from row r + 1,  CA = ((h + S1 + CH + KL' + W' + S0 + MAJ) >> 32) & 7  and
+ *              CE = ((d + h + S1 + CH + KL' + W') >> 32) & 7;  both are 0 on rows r = 63 mod 64.
+ *   constraints  315 per proof, at index j; a prime is the value at omega x:
+ *                0 .. 191   X^2 - X for helper columns 0 .. 191          192 .. 197  X^2 - X for helper columns 294 .. 299
+ *              198          LIVE^2 - LIVE
+ *              199 .. 204   word - sum_i 2^i bit_i for (a, A), (b, B), (c, C), (e, E), (f, F), (g, G)
+ *              205 + i      U0_i - (A_(i+2) + A_(i+13) - 2 A_(i+2) A_(i+13))
+ *              237 + i      U1_i - (E_(i+6) + E_(i+11) - 2 E_(i+6) E_(i+11))
+ *              269 + i      V_i - A_i B_i
+ *              301          S0 - sum 2^i (U0_i + A_(i+22) - 2 U0_i A_(i+22))     302   S1 - sum 2^i (U1_i + E_(i+25) - 2 U1_i E_(i+25))
+ *              303          CH - sum 2^i (G_i + E_i (F_i - G_i))                 304   MAJ - sum 2^i (V_i + C_i (A_i + B_i - 2 V_i))
+ *              305          KL - LIVE K(x)
+ *              306 .. 311   S(x) (b' - a), (c' - b), (d' - c), (f' - e), (g' - f), (h' - g)         312   S(x) (LIVE' - LIVE)
+ *              313          S(x) (a' + 2^32 (CA_0 + 2 CA_1 + 4 CA_2) - h - S1 - CH - KL' - W' - S0 - MAJ)
+ *              314          S(x) (e' + 2^32 (CE_0 + 2 CE_1 + 4 CE_2) - d - h - S1 - CH - KL' - W')
+ *              Every nonlinear constraint has degree 2 and no selector, every selected one is linear in the columns: the honest quotient has
+ *              degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks and zero padding satisfy all 315 with
+ *              LIVE = 0, which is why K enters through KL.
+ *   NOT PROVED by set 3 (the follow-ups): the message schedule (W_t for t >= 16); row 0 of a block against the IV or the chaining value; the
+ *              feed-forward between the two blocks of T.5 / T.6 hashes; LIVE against anything public; the digest's link to Level-1; SHA-512.
+ *              A block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
+ *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
+ *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
+ *   quotient   q(x_i) = sum_p sum_(j < 315) gamma^(315 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical as in set 1; pointwise: defined
+ *              for any columns.
+ *   identity   t^0, t^1, h^0, h^1 the table's and the helper's openings at zeta and zeta omega_N, u_0, u_1 the quotient's at zeta:
+ *              sum gamma^(315 p + j) C_(p,j)(t, h; zeta) == (u_0 + X u_1) (zeta^N - 1); K(zeta) by Horner on P_K's 64 coefficients at
+ *              zeta^(N/64).  A failed identity clears every query's verdict.
+ *   tmx_air_sha256_helper_device        the helper (300 n_proofs columns of 2^log_rows words at d_helper) from PRE-LDE table columns
+ *                                       (9 n_proofs columns at d_table).  TMX_ERR_BAD_ARG: log_rows outside 6 .. 27, n_proofs = 0,
+ *                                       300 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha256_quotient_device      gamma from d_cap and d_cap_helper, then the quotient of the EXTENDED columns d_cols and d_helper_cols
+ *                                       into d_quot (2 << log_n words), under the context's CURRENT NTT domain.  TMX_ERR_BAD_ARG: FRI's rules
+ *                                       on log_n and log_blowup, log_n - log_blowup < 6, n_proofs = 0, 300 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha256_verify_device        tmx_batch_verify_device, then the identity for the oracles k_trace (the table), k_trace + 1 (the
+ *                                       helper) and k_trace + 2 (the quotient).  TMX_ERR_BAD_ARG unless their column counts are 9 k, 300 k
+ *                                       and 2 and their log_n equal (and the rules above).
+ *   tmx_trace_commit_set_air_sha256_device   on a commit set that holds `section` (TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER) as a
+ *                                       RESIDENT member: the helper from the member's pre-LDE columns, extended under the set's domain and
+ *                                       committed as a normal resident member directly behind the table (d_cap_h receives its cap), gamma, the
+ *                                       quotient and its tree behind the helper (d_cap_q).  tmx_trace_commit_set_shape then reports K + 2
+ *                                       oracles with TMX_TRACE_SHA256_HELPER and TMX_TRACE_SHA256_QUOTIENT in section_of.  It may be called
+ *                                       for several sections of one set and beside the ladders' calls.  Refused: a streamed or absent
+ *                                       section, a second call on the same section, a set that would exceed 8 oracles.  The helper is 33x
+ *                                       its table and is NOT streamed: the call needs (300 n_proofs (N + M) + 2 M) 8 bytes plus two trees of
+ *                                       its own, and the LDE scratch of 300 columns (TMX_ERR_CAPACITY if the card cannot hold it).
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream, no device-to-host copy inside, the scratch is the
+ * context's own; tmx_air_last_gamma covers these calls too. */
+#define TMX_AIR_SHA256_HELPER_COLS 300
+#define TMX_AIR_SHA256_CONSTRAINTS 315
+#define TMX_TRACE_SHA256_HELPER 128u
+#define TMX_TRACE_SHA256_QUOTIENT 256u
+int32_t tmx_air_sha256_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                     void* hip_stream);
+int32_t tmx_air_sha256_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                       const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                       uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                                     uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

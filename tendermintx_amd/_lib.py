@@ -18,6 +18,8 @@ SEC_HINT, SEC_DERIVED, SEC_ALL = 1, 2, 3   # TMX_SEC_*
 PROOF_PATH_NONE, PROOF_PATH_TINY, PROOF_PATH_ROLES, PROOF_PATH_R168, PROOF_PATH_K256, PROOF_PATH_WIDE = range(6)   # TMX_PROOF_PATH_*
 TRACE_LADDERS, TRACE_SHA512, TRACE_SHA256, TRACE_MATCH, TRACE_TREE, TRACE_HEADER, TRACE_ALL = 1, 2, 4, 8, 16, 32, 63   # TMX_TRACE_*
 TRACE_LADDERS_QUOTIENT = 64   # TMX_TRACE_LADDERS_QUOTIENT: the constraint quotient as a member of a commit set
+AIR_SHA256_HELPER_COLS, AIR_SHA256_CONSTRAINTS = 300, 315   # TMX_AIR_SHA256_*: constraint set 3, the SHA-256 round constraints
+TRACE_SHA256_HELPER, TRACE_SHA256_QUOTIENT = 128, 256   # TMX_TRACE_SHA256_*: the helper and the quotient of set 3 as members of a commit set
 
 
 class ValidatorRec(C.Structure):
@@ -349,6 +351,14 @@ def lib():
         L.tmx_air_boundary_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]
         L.tmx_trace_commit_set_air_boundary_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
+    try:
+        L.tmx_air_sha256_helper_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha256_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 6
+        L.tmx_air_sha256_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha256_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -63,4 +63,33 @@ int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t
                                      uint64_t bary_inv, const void* d_open_t, const void* d_open_q, const void* d_zeta, const void* d_gamma,
                                      const void* d_v, uint32_t n_queries, void* d_ok, void* stream);
 
+// ---- constraint set 3: the round constraints of the SHA-256 tables (include/tmx.h "the round constraints of the SHA-256 tables").  A table
+// of 9 columns per proof, a helper oracle of 300 columns per proof (bits), 315 constraints per proof; gamma comes from a lone-lane transcript
+// kernel of its own (poseidon.hip k_air_sha_gamma: k_fri_transcript stays as it is).
+constexpr uint32_t AIR_SHA_WIDTH = 9, AIR_SHA_HELPER_COLS = 300, AIR_SHA_CONSTRAINTS = 315;
+// The tables one set-3 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
+//   gpow  [316][2]               gamma^0 .. gamma^315
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+//   sel   [64 << log_blowup]     S(x_i) = x_i^(N/64) - omega_64^-1, by i mod (64 << log_blowup)
+//   kx    [64 << log_blowup]     K(x_i) = P_K(x_i^(N/64)), same period
+constexpr uint32_t AIR3_TAB_GPOW = 0, AIR3_TAB_ZINV = 640, AIR3_TAB_SEL = 704, AIR3_TAB_K = AIR3_TAB_SEL + (64u << 6);
+constexpr uint64_t AIR3_TAB_WORDS = AIR3_TAB_K + (64u << 6);
+static_assert(AIR3_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6), "the set-3 tables live in the table part of set 1's scratch");
+// gamma of set 3 (one lane): 2^33, obs[0 .. 5) = {3, log_n, log_blowup, cap_height, n_proofs}, cap_words words at d_cap, cap_words words
+// at d_cap_helper; the duplex is left at d_state (32 words), gamma at d_chal[FRI_GAMMA_AT]
+int launch_air_sha_gamma(const void* d_consts, int mode, const uint32_t obs[5], uint32_t cap_words, const void* d_cap, const void* d_cap_helper,
+                         void* d_state, void* d_chal, void* stream);
+// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 300 n_proofs
+int launch_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
+// s_n = s^N, w_n = w^N, s_n64 = s^(N/64), w_n64 = w^(N/64), om64_inv = omega_64^-1; gamma at d_gamma (2 words)
+int launch_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+                          void* d_tab, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(315 p + j) C_(p,j) / (x^N - 1)
+int launch_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_tab,
+                            void* d_quot, void* stream);
+// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
+int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
+                         const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                         void* stream);
+
 }  // namespace tmx

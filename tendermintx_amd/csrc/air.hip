@@ -8,6 +8,7 @@
 
 #include "air.h"
 #include "goldilocks_ext.hpp"
+#include "sha2.hpp"
 
 namespace tmx {
 
@@ -556,6 +557,370 @@ int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t
   hipLaunchKernelGGL(k_air_ladder_boundary_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r, log_sub, om256_inv, om255, om_k,
                      bary_inv, reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_q),
                      reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<const uint64_t*>(d_v),
+                     n_queries, reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
+// ---- constraint set 3: the round constraints of the SHA-256 tables (include/tmx.h "the round constraints of the SHA-256 tables") ------------
+// Siblings again: nothing above changes.  Helper column offsets inside a proof's 300, and the constraint indices inside its 315.
+constexpr uint32_t H_A = 0, H_B = 32, H_C = 64, H_E = 96, H_F = 128, H_G = 160, H_U0 = 192, H_U1 = 224, H_V = 256, H_S0 = 288, H_S1 = 289, H_CH = 290,
+                   H_MAJ = 291, H_LIVE = 292, H_KL = 293, H_CA = 294, H_CE = 297;
+constexpr uint32_t T_W = 0, T_A = 1, T_B = 2, T_C = 3, T_D = 4, T_E = 5, T_F = 6, T_G = 7, T_H = 8;
+constexpr uint32_t J_CARRY = 192, J_LIVE = 198, J_WORD = 199, J_U0 = 205, J_U1 = 237, J_V = 269, J_S0 = 301, J_S1 = 302, J_CH = 303, J_MAJ = 304,
+                   J_KL = 305, J_SHIFT = 306, J_LIVEN = 312, J_NA = 313, J_NE = 314;
+
+// One lane per (proof, row) of the pre-LDE table: the nine words of the row, the block's first row (LIVE) and W of the next row (the
+// carries), then 300 stores, each of them consecutive words of one column across the wave.  Operands are the low 32 bits of the words.
+__global__ __launch_bounds__(256) void k_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                        uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows);
+  const uint64_t r = idx & ((1ull << log_rows) - 1), r0 = r & ~63ull;
+  const uint32_t rnd = (uint32_t)(r & 63);
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA_WIDTH) << log_rows);
+  uint32_t w[AIR_SHA_WIDTH];
+  uint64_t any = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < AIR_SHA_WIDTH; c++) {
+    w[c] = (uint32_t)t[((uint64_t)c << log_rows) + r];
+    any |= t[((uint64_t)c << log_rows) + r0];
+  }
+  const uint32_t live = any ? 1u : 0u;
+  const uint32_t a = w[T_A], b = w[T_B], c = w[T_C], e = w[T_E], f = w[T_F], g = w[T_G];
+  auto rot = [](uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); };
+  const uint32_t s0 = rot(a, 2) ^ rot(a, 13) ^ rot(a, 22), s1 = rot(e, 6) ^ rot(e, 11) ^ rot(e, 25);
+  const uint32_t chv = (e & f) ^ (~e & g), mjv = (a & b) ^ (a & c) ^ (b & c);
+  const uint32_t u0 = rot(a, 2) ^ rot(a, 13), u1 = rot(e, 6) ^ rot(e, 11), v = a & b;
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 32; i++) {
+    put(H_A + i, (a >> i) & 1);
+    put(H_B + i, (b >> i) & 1);
+    put(H_C + i, (c >> i) & 1);
+    put(H_E + i, (e >> i) & 1);
+    put(H_F + i, (f >> i) & 1);
+    put(H_G + i, (g >> i) & 1);
+    put(H_U0 + i, (u0 >> i) & 1);
+    put(H_U1 + i, (u1 >> i) & 1);
+    put(H_V + i, (v >> i) & 1);
+  }
+  put(H_S0, s0);
+  put(H_S1, s1);
+  put(H_CH, chv);
+  put(H_MAJ, mjv);
+  put(H_LIVE, live);
+  put(H_KL, live ? K_SHA256[rnd] : 0u);
+  uint32_t ca = 0, ce = 0;
+  if (rnd != 63) {
+    const uint32_t wn = (uint32_t)t[((uint64_t)T_W << log_rows) + r + 1];
+    const uint64_t t1 = (uint64_t)w[T_H] + s1 + chv + (live ? K_SHA256[rnd + 1] : 0u) + wn;
+    ca = (uint32_t)((t1 + s0 + mjv) >> 32) & 7;
+    ce = (uint32_t)((t1 + w[T_D]) >> 32) & 7;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 3; k++) {
+    put(H_CA + k, (ca >> k) & 1);
+    put(H_CE + k, (ce >> k) & 1);
+  }
+}
+
+// P_K, the polynomial of degree < 64 with P_K(omega_64^t) = K256[t], into LDS: thread j < 64 takes coefficient j, an inverse transform
+// written out (64 terms; launch-sized work).  Every thread of the workgroup calls it; 64^-1 = p - (p - 1) / 64.
+__device__ __forceinline__ void air_sha_pk(uint64_t om64_inv, uint64_t* pk) {
+  if (threadIdx.x < 64) {
+    const uint64_t step = gl_pow(om64_inv, threadIdx.x);
+    uint64_t cur = 1, acc = 0;
+    for (uint32_t t = 0; t < 64; t++, cur = gl_mul(cur, step)) acc = gl_add(acc, gl_mul(cur, K_SHA256[t]));
+    pk[threadIdx.x] = gl_mul(acc, GL_P - (GL_P - 1) / 64);
+  }
+  __syncthreads();
+}
+
+// One thread per table entry: S and K by i mod 64 B (K by Horner on P_K's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 315.
+__global__ __launch_bounds__(256) void k_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+                                                        uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  __shared__ uint64_t pk[64];
+  air_sha_pk(om64_inv, pk);
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < (64u << log_blowup)) {
+    const uint64_t y = gl_mul(s_n64, gl_pow(w_n64, k));
+    tab[AIR3_TAB_SEL + k] = gl_sub(y, om64_inv);
+    uint64_t acc = 0;
+    for (int j = 63; j >= 0; j--) acc = gl_add(gl_mul(acc, y), pk[j]);
+    tab[AIR3_TAB_K + k] = acc;
+  }
+  if (k < (1u << log_blowup)) tab[AIR3_TAB_ZINV + k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
+  if (k <= AIR_SHA_CONSTRAINTS) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
+    tab[AIR3_TAB_GPOW + 2 * k] = g.c0;
+    tab[AIR3_TAB_GPOW + 2 * k + 1] = g.c1;
+  }
+}
+
+// The set-3 hot pass, k_air_ladder_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^315), the nine table columns and the 300 helper columns read once from HBM.  On the coset a bit column is a full field element, so
+// the pass never holds the 300 words: it walks the bit index b from 31 down to 0 and per b holds the nine bit words A_b .. V_b and the six
+// rotated ones (A_(b+2), A_(b+13), A_(b+22), E_(b+6), E_(b+11), E_(b+25)), which are re-read through the cache (another b of the same lane
+// reads them as its own).  Per b: nine constraints (six X^2 - X, U0, U1, V), and one Horner step by 2 of the ten word sums (a, b, c, e,
+// f, g, Sigma0, Sigma1, Ch, Maj), so that no power of two is multiplied.  13 reduced column products and 18 gamma weights per b; behind
+// the loop 8 more column products, the word constraints and the nine selected ones, whose S(x) is factored out of their gamma sum.
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                  const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                  const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR3_TAB_GPOW;
+  const uint64_t sel = tab[AIR3_TAB_SEL + (i & ((64ull << log_blowup) - 1))];
+  const uint64_t kx = tab[AIR3_TAB_K + (i & ((64ull << log_blowup) - 1))];
+  const uint64_t zinv = tab[AIR3_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g315 = {gp[2 * AIR_SHA_CONSTRAINTS], gp[2 * AIR_SHA_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);
+    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_SHA_HELPER_COLS) << log_m);
+    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
+    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
+    auto tbl = [&](uint32_t col, uint64_t at) { return gl_canon(c[((uint64_t)col << log_m) + at]); };
+    uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;  // the plain and the selected gamma sums, lazy
+    auto plain = [&](uint32_t j, uint64_t v) {
+      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
+      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto selected = [&](uint32_t j, uint64_t v) {
+      b0 = gl_add_lazy(b0, gl_mul(gp[2 * j], v));
+      b1 = gl_add_lazy(b1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
+    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
+      const uint64_t xy = gl_mul(x, y);
+      return gl_sub(gl_add(x, y), gl_add(xy, xy));
+    };
+    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
+    uint64_t wa = 0, wb = 0, wc = 0, we = 0, wf = 0, wg = 0, ws0 = 0, ws1 = 0, wch = 0, wmj = 0;
+#pragma unroll 2
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint64_t A = again(H_A + b), B = once(H_B + b), C = once(H_C + b), E = again(H_E + b), F = once(H_F + b), G = once(H_G + b);
+      const uint64_t U0 = once(H_U0 + b), U1 = once(H_U1 + b), V = once(H_V + b);
+      const uint64_t A2 = again(H_A + ((b + 2) & 31)), A13 = again(H_A + ((b + 13) & 31)), A22 = again(H_A + ((b + 22) & 31));
+      const uint64_t E6 = again(H_E + ((b + 6) & 31)), E11 = again(H_E + ((b + 11) & 31)), E25 = again(H_E + ((b + 25) & 31));
+      plain(H_A + b, boolean(A));
+      plain(H_B + b, boolean(B));
+      plain(H_C + b, boolean(C));
+      plain(H_E + b, boolean(E));
+      plain(H_F + b, boolean(F));
+      plain(H_G + b, boolean(G));
+      plain(J_U0 + b, gl_sub(U0, exor(A2, A13)));
+      plain(J_U1 + b, gl_sub(U1, exor(E6, E11)));
+      const uint64_t AB = gl_mul(A, B);
+      plain(J_V + b, gl_sub(V, AB));
+      wa = dbl_add(wa, A);
+      wb = dbl_add(wb, B);
+      wc = dbl_add(wc, C);
+      we = dbl_add(we, E);
+      wf = dbl_add(wf, F);
+      wg = dbl_add(wg, G);
+      ws0 = dbl_add(ws0, exor(U0, A22));
+      ws1 = dbl_add(ws1, exor(U1, E25));
+      wch = dbl_add(wch, gl_add(G, gl_mul(E, gl_sub(F, G))));
+      wmj = dbl_add(wmj, gl_add(V, gl_mul(C, gl_sub(gl_add(A, B), gl_add(V, V)))));
+    }
+    const uint64_t ta = tbl(T_A, i), tb = tbl(T_B, i), tc = tbl(T_C, i), td = tbl(T_D, i), te = tbl(T_E, i), tf = tbl(T_F, i), tg = tbl(T_G, i),
+                   th = tbl(T_H, i);
+    plain(J_WORD + 0, gl_sub(ta, wa));
+    plain(J_WORD + 1, gl_sub(tb, wb));
+    plain(J_WORD + 2, gl_sub(tc, wc));
+    plain(J_WORD + 3, gl_sub(te, we));
+    plain(J_WORD + 4, gl_sub(tf, wf));
+    plain(J_WORD + 5, gl_sub(tg, wg));
+    const uint64_t S0 = once(H_S0), S1 = once(H_S1), CH = once(H_CH), MAJ = once(H_MAJ), LIVE = again(H_LIVE), KL = again(H_KL);
+    plain(J_S0, gl_sub(S0, ws0));
+    plain(J_S1, gl_sub(S1, ws1));
+    plain(J_CH, gl_sub(CH, wch));
+    plain(J_MAJ, gl_sub(MAJ, wmj));
+    plain(J_LIVE, boolean(LIVE));
+    plain(J_KL, gl_sub(KL, gl_mul(LIVE, kx)));
+    uint64_t carry[6];
+#pragma unroll
+    for (uint32_t k = 0; k < 6; k++) {
+      carry[k] = once(H_CA + k);
+      plain(J_CARRY + k, boolean(carry[k]));
+    }
+    selected(J_SHIFT + 0, gl_sub(tbl(T_B, nx), ta));
+    selected(J_SHIFT + 1, gl_sub(tbl(T_C, nx), tb));
+    selected(J_SHIFT + 2, gl_sub(tbl(T_D, nx), tc));
+    selected(J_SHIFT + 3, gl_sub(tbl(T_F, nx), te));
+    selected(J_SHIFT + 4, gl_sub(tbl(T_G, nx), tf));
+    selected(J_SHIFT + 5, gl_sub(tbl(T_H, nx), tg));
+    selected(J_LIVEN, gl_sub(gl_canon(h[((uint64_t)H_LIVE << log_m) + nx]), LIVE));
+    const uint64_t kln = gl_canon(h[((uint64_t)H_KL << log_m) + nx]);
+    const uint64_t t1 = gl_add(gl_add(gl_add(th, S1), gl_add(CH, kln)), tbl(T_W, nx));
+    auto c32 = [](uint64_t x0, uint64_t x1, uint64_t x2) { return gl_mul(gl_add(x0, gl_add(gl_add(x1, x1), gl_mul(x2, 4))), 1ull << 32); };
+    selected(J_NA, gl_sub(gl_add(tbl(T_A, nx), c32(carry[0], carry[1], carry[2])), gl_add(t1, gl_add(S0, MAJ))));
+    selected(J_NE, gl_sub(gl_add(tbl(T_E, nx), c32(carry[3], carry[4], carry[5])), gl_add(td, t1)));
+    const gl2 v = {gl_add(gl_canon(a0), gl_mul(sel, b0)), gl_add(gl_canon(a1), gl_mul(sel, b1))};
+    t = gl2_add(gl2_mul(t, g315), v);
+  }
+  const gl2 q = gl2_scale(t, zinv);
+  out[i] = q.c0;
+  out[M + i] = q.c1;
+}
+
+// The set-3 identity at zeta, one workgroup: gamma^0 .. gamma^315 and P_K go to LDS first; thread t takes the proofs t, t + 256, ... and
+// evaluates their 315 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the order of
+// the hot pass; K(zeta) by Horner on P_K at zeta^(N/64).  The sums meet in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1).
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                      uint64_t om64_inv, const uint64_t* __restrict__ open_t,
+                                                                      const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
+                                                                      const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
+                                                                      uint32_t n_queries, uint32_t* __restrict__ ok) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint64_t gpw[2 * (AIR_SHA_CONSTRAINTS + 1)];
+  __shared__ uint64_t pk[64];
+  __shared__ uint32_t holds;
+  const uint32_t t = threadIdx.x;
+  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
+  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
+  for (uint32_t k = t; k <= AIR_SHA_CONSTRAINTS; k += AIR_CHECK_THREADS) {
+    const gl2 gk = gl2_pow(g, k);
+    gpw[2 * k] = gk.c0;
+    gpw[2 * k + 1] = gk.c1;
+  }
+  air_sha_pk(om64_inv, pk);  // (ends with a barrier: gpw is complete behind it too)
+  gl2 zp = z;  // zeta^(N/64)
+  for (uint32_t k = 6; k < log_sub; k++) zp = gl2_mul(zp, zp);
+  const gl2 S = {gl_sub(zp.c0, om64_inv), zp.c1};
+  gl2 K = {0, 0};
+  for (int j = 63; j >= 0; j--) {
+    K = gl2_mul(K, zp);
+    K.c0 = gl_add(K.c0, pk[j]);
+  }
+  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
+  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
+  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
+  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
+  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
+  auto exor = [](gl2 x, gl2 y) {
+    const gl2 xy = gl2_mul(x, y);
+    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
+  };
+  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
+  gl2 sum = {0, 0};
+  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
+    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_SHA_HELPER_COLS;
+    gl2 a = {0, 0}, bsel = {0, 0};
+    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    auto selected = [&](uint32_t j, gl2 v) { bsel = gl2_add(bsel, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    gl2 wa = {0, 0}, wb = wa, wc = wa, we = wa, wf = wa, wg = wa, ws0 = wa, ws1 = wa, wch = wa, wmj = wa;
+    for (uint32_t b = 32; b-- > 0;) {
+      const gl2 A = h0(chh + H_A + b), B = h0(chh + H_B + b), C = h0(chh + H_C + b), E = h0(chh + H_E + b), F = h0(chh + H_F + b),
+                G = h0(chh + H_G + b), U0 = h0(chh + H_U0 + b), U1 = h0(chh + H_U1 + b), V = h0(chh + H_V + b);
+      const gl2 A2 = h0(chh + H_A + ((b + 2) & 31)), A13 = h0(chh + H_A + ((b + 13) & 31)), A22 = h0(chh + H_A + ((b + 22) & 31));
+      const gl2 E6 = h0(chh + H_E + ((b + 6) & 31)), E11 = h0(chh + H_E + ((b + 11) & 31)), E25 = h0(chh + H_E + ((b + 25) & 31));
+      plain(H_A + b, boolean(A));
+      plain(H_B + b, boolean(B));
+      plain(H_C + b, boolean(C));
+      plain(H_E + b, boolean(E));
+      plain(H_F + b, boolean(F));
+      plain(H_G + b, boolean(G));
+      plain(J_U0 + b, gl2_sub(U0, exor(A2, A13)));
+      plain(J_U1 + b, gl2_sub(U1, exor(E6, E11)));
+      plain(J_V + b, gl2_sub(V, gl2_mul(A, B)));
+      wa = dbl_add(wa, A);
+      wb = dbl_add(wb, B);
+      wc = dbl_add(wc, C);
+      we = dbl_add(we, E);
+      wf = dbl_add(wf, F);
+      wg = dbl_add(wg, G);
+      ws0 = dbl_add(ws0, exor(U0, A22));
+      ws1 = dbl_add(ws1, exor(U1, E25));
+      wch = dbl_add(wch, gl2_add(G, gl2_mul(E, gl2_sub(F, G))));
+      wmj = dbl_add(wmj, gl2_add(V, gl2_mul(C, gl2_sub(gl2_add(A, B), gl2_add(V, V)))));
+    }
+    const gl2 ta = t0(ct + T_A), tb = t0(ct + T_B), tc = t0(ct + T_C), td = t0(ct + T_D), te = t0(ct + T_E), tf = t0(ct + T_F), tg = t0(ct + T_G),
+              th = t0(ct + T_H);
+    plain(J_WORD + 0, gl2_sub(ta, wa));
+    plain(J_WORD + 1, gl2_sub(tb, wb));
+    plain(J_WORD + 2, gl2_sub(tc, wc));
+    plain(J_WORD + 3, gl2_sub(te, we));
+    plain(J_WORD + 4, gl2_sub(tf, wf));
+    plain(J_WORD + 5, gl2_sub(tg, wg));
+    const gl2 S0 = h0(chh + H_S0), S1 = h0(chh + H_S1), CH = h0(chh + H_CH), MAJ = h0(chh + H_MAJ), LIVE = h0(chh + H_LIVE), KL = h0(chh + H_KL);
+    plain(J_S0, gl2_sub(S0, ws0));
+    plain(J_S1, gl2_sub(S1, ws1));
+    plain(J_CH, gl2_sub(CH, wch));
+    plain(J_MAJ, gl2_sub(MAJ, wmj));
+    plain(J_LIVE, boolean(LIVE));
+    plain(J_KL, gl2_sub(KL, gl2_mul(LIVE, K)));
+    gl2 carry[6];
+    for (uint32_t k = 0; k < 6; k++) {
+      carry[k] = h0(chh + H_CA + k);
+      plain(J_CARRY + k, boolean(carry[k]));
+    }
+    selected(J_SHIFT + 0, gl2_sub(t1(ct + T_B), ta));
+    selected(J_SHIFT + 1, gl2_sub(t1(ct + T_C), tb));
+    selected(J_SHIFT + 2, gl2_sub(t1(ct + T_D), tc));
+    selected(J_SHIFT + 3, gl2_sub(t1(ct + T_F), te));
+    selected(J_SHIFT + 4, gl2_sub(t1(ct + T_G), tf));
+    selected(J_SHIFT + 5, gl2_sub(t1(ct + T_H), tg));
+    selected(J_LIVEN, gl2_sub(h1(chh + H_LIVE), LIVE));
+    const gl2 tt = gl2_add(gl2_add(gl2_add(th, S1), gl2_add(CH, h1(chh + H_KL))), t1(ct + T_W));
+    auto c32 = [](gl2 x0, gl2 x1, gl2 x2) { return gl2_scale(gl2_add(x0, gl2_add(gl2_add(x1, x1), gl2_scale(x2, 4))), 1ull << 32); };
+    selected(J_NA, gl2_sub(gl2_add(t1(ct + T_A), c32(carry[0], carry[1], carry[2])), gl2_add(tt, gl2_add(S0, MAJ))));
+    selected(J_NE, gl2_sub(gl2_add(t1(ct + T_E), c32(carry[3], carry[4], carry[5])), gl2_add(td, tt)));
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA_CONSTRAINTS * p), gl2_add(a, gl2_mul(S, bsel))));
+  }
+  red[0][t] = sum.c0;
+  red[1][t] = sum.c1;
+  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
+    __syncthreads();
+    if (t < hh) {
+      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
+      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
+    for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
+    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
+    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
+    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(q, {gl_sub(zn.c0, 1), zn.c1})) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!holds)
+    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sha_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+                          void* d_tab, void* stream) {
+  // (at least two workgroups: the 316 gamma powers)
+  const uint32_t blocks = ((64u << log_blowup) + 255) / 256;
+  hipLaunchKernelGGL(k_air_sha_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, s_n, w_n, s_n64, w_n64, om64_inv,
+                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_tab,
+                            void* d_quot, void* stream) {
+  hipLaunchKernelGGL(k_air_sha_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream), log_m,
+                     log_blowup, n_proofs, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
+                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+  return (int)hipGetLastError();
+}
+int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
+                         const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                         void* stream) {
+  hipLaunchKernelGGL(k_air_sha_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub, om64_inv,
+                     reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_h),
+                     reinterpret_cast<const uint64_t*>(d_open_q), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma),
                      n_queries, reinterpret_cast<uint32_t*>(d_ok));
   return (int)hipGetLastError();
 }

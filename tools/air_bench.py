@@ -12,6 +12,11 @@
            kernels2,set2) both hot passes and the public-side kernels show in ONE trace.
   set2     as `set` for constraint set 2 next to set 1: the gather, then the set-level calls of both sets on a resident and on a streamed
            ladders member, alternating inside one process; the prove and tmx_air_boundary_verify_device over the set-2 quotient.
+  sha      constraint set 3 (tmx_air_sha256_*): SHA_PROOFS proofs x 9 random table columns of 2^LOG_M words (64 proofs at 2^16 by default; the
+           helper is 300 columns per proof, 33x the table): the helper kernel on the pre-LDE shape, the quotient call (transcript + tables +
+           k_air_sha_quotient) beside a plain FRI prove over the SAME table, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha)
+           k_air_sha_helper, k_air_sha_quotient and k_fri_combine show in ONE trace -- and the set-level call on the HEADER member of a set of
+           SHA_SET_P proofs at N = n (skip), with the prove and tmx_air_sha256_verify_device over the enlarged set.
   parent   the set commit + prove WITHOUT any air call, for library builds named in LIBS (comma separated), one subprocess per measurement,
            alternating under TMX_LIB (differences between boxes exceed most changes: compare inside one call).
 Times per call from HIP events around REPS back-to-back calls after one warm call.
@@ -116,6 +121,78 @@ if "kernels2" in modes:
     print(json.dumps(res), flush=True)
     ctx.close()
     del cols, pub, lv, quot
+    torch.cuda.empty_cache()
+
+if "sha" in modes:
+    log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("SHA_PROOFS", "64"))
+    log_rows, n_cols, n_hcols = log_m - log_blowup, 9 * cp, 300 * cp
+    ctx = Context(4, b"celestia", device=0)
+    table = torch.randint(0, 2**62, (n_cols << log_rows,), dtype=torch.int64, device=dev)
+    pre = torch.empty(n_hcols << log_rows, dtype=torch.int64, device=dev)
+    cols = torch.randint(0, 2**62, (n_cols << log_m,), dtype=torch.int64, device=dev)
+    hcols = torch.randint(0, 2**62, (n_hcols << log_m,), dtype=torch.int64, device=dev)
+    caps = []
+    for c_, k_ in ((cols, n_cols), (hcols, n_hcols)):
+        lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+        ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+        caps.append(lv)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    fp = dict(log_n=log_m, n_cols=n_cols, cap_height=cap_h, log_blowup=log_blowup, arity_bits=arity, final_log_max=final_max, n_queries=nq)
+    proof = torch.empty(ctx.fri_layout(fp)["words"], dtype=torch.int64, device=dev)
+    words = (n_cols + n_hcols) << log_m
+    res = {"mode": "sha", "proofs": cp, "log_m": log_m, "table_columns": n_cols, "helper_columns": n_hcols, "read_gib": round(words * 8 / 2**30, 2),
+           "reps": reps, "helper_kernel_ms": [], "sha_quotient_call_ms": [], "fri_prove_table_ms": [], "fri_combine_stage_ms": []}
+    for _ in range(rounds):
+        res["helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha256_helper_device(log_rows, cp, table.data_ptr(), pre.data_ptr(), 0), reps)))
+        res["sha_quotient_call_ms"].append(r4(timed(lambda: ctx.air_sha256_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols.data_ptr(),
+                                                                                            caps[0][-(4 << cap_h):].data_ptr(),
+                                                                                            caps[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0), reps)))
+        res["fri_prove_table_ms"].append(r4(timed(lambda: ctx.fri_prove_device(fp, cols.data_ptr(), caps[0].data_ptr(), proof.data_ptr(), 0), reps)))
+        res["fri_combine_stage_ms"].append(r4(ctx.fri_last_ms()["combine"]))
+    best = min(res["sha_quotient_call_ms"])
+    res["sha_gb_per_s"] = round(words * 8 / best / 1e6, 1)
+    res["helper_store_gb_per_s"] = round((n_hcols << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e6, 1)
+    res["ns_per_point_proof"] = round(best * 1e6 / (cp << log_m), 2)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del table, pre, cols, hcols, caps, quot, proof
+    torch.cuda.empty_cache()
+    # the set-level call on HEADER
+    from tendermintx_amd.synth import bench_workload
+    sp = int(os.environ.get("SHA_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    SHA256, HEADER = 4, 32
+    cw = 4 << cap_h
+    scaps, cap_h_, cap_q = torch.zeros(2 * cw, dtype=torch.int64, device=dev), torch.zeros(cw, dtype=torch.int64, device=dev), torch.zeros(cw, dtype=torch.int64, device=dev)
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit3 = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA256 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    res = {"mode": "sha_set", "proofs": sp, "n": n, "reps": reps, "commit_ms": r4(timed(commit3, 2)), "air_sha256_header_ms": [], "prove_with_ms": []}
+    for _ in range(rounds):
+        res["air_sha256_header_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_sha256_device(HEADER, cap_h_.data_ptr(), cap_q.data_ptr(), 0), reps,
+                                                    before=commit3)))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(HEADER)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
+        res["verify_ms"] = r4(timed(lambda: ctx.air_sha256_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del tr
     torch.cuda.empty_cache()
 
 if "set2" in modes:
