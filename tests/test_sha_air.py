@@ -339,9 +339,10 @@ def test_quotient_of_random_columns_equals_the_model(ctx, oracle, log_blowup, n_
     assert np.array_equal(got, want), np.flatnonzero(got != want)[:10]
 
 
-def _chain(ctx, oracle, table, log_blowup, quot_override=None):
+def _chain(ctx, oracle, table, log_blowup, quot_override=None, n_queries=6, front=None):
     """caller-level chain: helper -> LDE -> caps -> quotient -> one batch proof over [table, helper, quotient].  Returns (params, d_caps,
-    proof words, extended table, extended helper, quotient words)"""
+    proof words, extended table, extended helper, quotient words).  front: the extended columns [n][2^(log_n + 1)] of one more oracle that
+    goes in front of the table (the table is then oracle 1)"""
     import torch
     n_proofs, log_rows = table.shape[0] // W, table.shape[1].bit_length() - 1
     log_n = log_rows + log_blowup
@@ -353,12 +354,17 @@ def _chain(ctx, oracle, table, log_blowup, quot_override=None):
     d_lv_h, d_cap_h = _tree(ctx, d_hext, log_n, n_proofs * HC)
     d_quot = _device_quotient(ctx, log_n, log_blowup, n_proofs, d_ext, d_hext, d_cap_t, d_cap_h) if quot_override is None else _up(quot_override)
     d_lv_q, d_cap_q = _tree(ctx, d_quot, log_n, 2)
-    p = bparams([log_n] * 3, [n_proofs * W, n_proofs * HC, 2], CAP_H, log_blowup, 2, 2, 6)
+    log_ns, n_cols = [log_n] * 3, [n_proofs * W, n_proofs * HC, 2]
+    d_cols, d_lvs, d_caps = [d_ext, d_hext, d_quot], [d_lv_t, d_lv_h, d_lv_q], [d_cap_t, d_cap_h, d_cap_q]
+    if front is not None:
+        d_front = _up(front)
+        d_lv_f, d_cap_f = _tree(ctx, d_front, log_n + 1, front.shape[0])
+        log_ns, n_cols = [log_n + 1] + log_ns, [front.shape[0]] + n_cols
+        d_cols, d_lvs, d_caps = [d_front] + d_cols, [d_lv_f] + d_lvs, [d_cap_f] + d_caps
+    p = bparams(log_ns, n_cols, CAP_H, log_blowup, 2, 2, n_queries)
     words = bm.layout(p)["words"]
-    proof = _guarded(words, lambda out: ctx.batch_prove_device(p, [d_ext.data_ptr(), d_hext.data_ptr(), d_quot.data_ptr()],
-                                                               [d_lv_t.data_ptr(), d_lv_h.data_ptr(), d_lv_q.data_ptr()], out, 0))
-    return (p, torch.cat([d_cap_t, d_cap_h, d_cap_q]), _down(proof), _down(d_ext).reshape(n_proofs * W, -1),
-            _down(d_hext).reshape(n_proofs * HC, -1), _down(d_quot))
+    proof = _guarded(words, lambda out: ctx.batch_prove_device(p, [d.data_ptr() for d in d_cols], [d.data_ptr() for d in d_lvs], out, 0))
+    return (p, torch.cat(d_caps), _down(proof), _down(d_ext).reshape(n_proofs * W, -1), _down(d_hext).reshape(n_proofs * HC, -1), _down(d_quot))
 
 
 def _verdicts(ctx, p, k_trace, d_caps, proof, batch_only=False):
