@@ -1074,9 +1074,10 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d
  *              Every nonlinear constraint has degree 2 and no selector, every selected one is linear in the columns: the honest quotient has
  *              degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks and zero padding satisfy all 315 with
  *              LIVE = 0, which is why K enters through KL.
- *   NOT PROVED by set 3 (the follow-ups): the message schedule (W_t for t >= 16); row 0 of a block against the IV or the chaining value; the
- *              feed-forward between the two blocks of T.5 / T.6 hashes; LIVE against anything public; the digest's link to Level-1; SHA-512.
- *              A block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
+ *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; and, still open (the follow-ups):
+ *              row 0 of a block against the IV or the chaining value; the feed-forward between the two blocks of T.5 / T.6 hashes; LIVE
+ *              against anything public; the digest's link to Level-1; SHA-512.  Under set 3 ALONE a block re-run consistently from a changed
+ *              W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
  *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
  *   quotient   q(x_i) = sum_p sum_(j < 315) gamma^(315 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical as in set 1; pointwise: defined
@@ -1116,6 +1117,81 @@ int32_t tmx_air_sha256_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t lo
 int32_t tmx_air_sha256_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
                                      uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+
+/* ---- the message schedule of the SHA-256 tables (constraint set 4) ------------------------------------------------------------------------
+ * Set 3 proves the round function row to row and leaves the W column free.  Set 4 proves the MESSAGE SCHEDULE on the same three tables:
+ * W_t = sigma1(W_(t-2)) + W_(t-7) + sigma0(W_(t-15)) + W_(t-16) mod 2^32 for t = 16 .. 63 of every block.  With set 3, every live block of
+ * T.3, T.5 and T.6 is then a real SHA-256 compression of its first sixteen W words from its row-0 state.  Built beside set 3 with the same
+ * machinery: a helper oracle of its own, 117 constraints per proof, one two-column quotient oracle, the identity at zeta; no existing kernel,
+ * transcript phase, proof word, call or refusal changes.  Notation of the block above: N rows, 9 columns per proof with W as column 0,
+ * M = N B points, omega = omega_N, y = x^(N/64), a prime is the value at omega x.  Same field, extension, duplex and caveats (PARITY UNPINNED).
+ *   helper     115 columns per proof, the table's rows, bits LSB first, rows taken CYCLICALLY inside one proof's 2^log_rows rows (row -1 is
+ *              the last row).  Offsets inside a proof:
+ *                0 .. 31   WB   bits of W (the low 32 bits of the table word, as in set 3)
+ *               32 .. 63   X0   X0_i = WB_(i+7) xor WB_(i+18)  (indices mod 32)       64 .. 95   X1   X1_i = WB_(i+17) xor WB_(i+19)
+ *               96  G0 = sigma0(W) = rotr7 ^ rotr18 ^ shr3     97  G1 = sigma1(W) = rotr17 ^ rotr19 ^ shr10   (words)
+ *               98 .. 112  Q_1 .. Q_15   the schedule sum as a pipeline: Q_1(r) = W(r-1) + G0(r),
+ *                          Q_k(r) = Q_(k-1)(r-1) + [k = 9] W(r) + [k = 14] G1(r) for k = 2 .. 15, so that
+ *                          Q_15(r) = W(r-15) + sigma0(W(r-14)) + W(r-6) + sigma1(W(r-1)), the unreduced W_t for t = r + 1, always < 2^34
+ *              113, 114   CW_0, CW_1   CW = (Q_15 >> 32) & 3 on the rows with r mod 64 in 15 .. 62, and 0 elsewhere
+ *              Defined for ANY input; the pipeline runs across block boundaries and the wrap, which is harmless: only the last constraint is
+ *              selected.
+ *   constraints  117 per proof, at index j:
+ *                0 .. 31    WB_i^2 - WB_i                          32, 33   CW_k^2 - CW_k               34   W - sum 2^i WB_i
+ *               35 + i      X0_i - xor(WB_(i+7), WB_(i+18))        67 + i   X1_i - xor(WB_(i+17), WB_(i+19)),   xor(x, y) = x + y - 2 x y
+ *               99          G0 - sum 2^i g0_i,  g0_i = xor(X0_i, WB_(i+3)) for i < 29 and X0_i for i >= 29
+ *              100          G1 - sum 2^i g1_i,  g1_i = xor(X1_i, WB_(i+10)) for i < 22 and X1_i for i >= 22
+ *              101          Q_1' - W - G0'
+ *              100 + k      Q_k' - Q_(k-1) - [k = 9] W' - [k = 14] G1'    for k = 2 .. 15
+ *              116          F(x) (W' + 2^32 (CW_0 + 2 CW_1) - Q_15)
+ *              F(x) = P_F(y), P_F of degree < 64 with P_F(omega_64^t) = 1 for 15 <= t <= 62 and 0 otherwise: the NEXT row is a schedule row.
+ *              Every nonlinear constraint has degree 2 and no selector; the one selected constraint is linear, its degree below 63 N / 64 + N:
+ *              the honest quotient has degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks, promoted slots
+ *              and zero padding satisfy all 117 without a LIVE column.
+ *   NOT PROVED by sets 3 and 4 (the follow-ups): row 0 of a block against the IV or the chaining value; the feed-forward between the two
+ *              blocks of T.5 / T.6 hashes; the first sixteen W of a block against Level-1; LIVE against anything public; SHA-512.  A block
+ *              re-run consistently (schedule and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected
+ *              (tests/test_sha_sched.py records it).
+ *   challenge  as set 3 with the set id 4: a fresh duplex observes 2^33, then 4, log_n, log_blowup, cap_height, n_proofs, then the table cap,
+ *              then THIS helper's cap; gamma drawn as in set 1.
+ *   quotient   q(x_i) = sum_p sum_(j < 117) gamma^(117 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical; pointwise: defined for any
+ *              columns.
+ *   identity   sum gamma^(117 p + j) C_(p,j)(t, h; zeta) == (u_0 + X u_1) (zeta^N - 1) from the openings at zeta and zeta omega_N; F(zeta) by
+ *              Horner on P_F's 64 coefficients at zeta^(N/64).  A failed identity clears every query's verdict.
+ *   tmx_air_sha256_sched_helper_device     the helper (115 n_proofs columns of 2^log_rows words at d_helper) from PRE-LDE table columns
+ *                                          (9 n_proofs columns at d_table).  TMX_ERR_BAD_ARG: log_rows outside 6 .. 27, n_proofs = 0,
+ *                                          115 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha256_sched_quotient_device   gamma from d_cap and d_cap_helper, then the quotient of the EXTENDED columns d_cols and
+ *                                          d_helper_cols into d_quot (2 << log_n words), under the context's CURRENT NTT domain.  Set 3's
+ *                                          rules for refusing arguments, with 115 n_proofs <= 2^24.
+ *   tmx_air_sha256_sched_verify_device     tmx_batch_verify_device, then the identity for the oracles k_trace (the table), k_helper (this
+ *                                          helper) and k_helper + 1 (this quotient): the helper's index is explicit because set 3's pair may
+ *                                          sit between the table and this one.  TMX_ERR_BAD_ARG unless the column counts are 9 k, 115 k and 2,
+ *                                          the log_n equal, k_helper > k_trace and k_helper + 1 < n_oracles.
+ *   tmx_trace_commit_set_air_sha256_sched_device   mirrors tmx_trace_commit_set_air_sha256_device: the helper from the resident member's
+ *                                          pre-LDE columns, extended one proof's 115 columns at a time under the set's domain and committed
+ *                                          (d_cap_h), gamma, the quotient and its tree (d_cap_q), in a scratch of its own per section.  The pair
+ *                                          goes behind the table, or behind set 3's helper and quotient when those already follow the table;
+ *                                          set 3's call, run afterwards, inserts directly behind the table and moves this pair back by two:
+ *                                          both orders end as table, H3, Q3, H4, Q4.  tmx_trace_commit_set_shape reports
+ *                                          TMX_TRACE_SHA256_SCHED_HELPER and TMX_TRACE_SHA256_SCHED_QUOTIENT in section_of.  Refused: a wrong,
+ *                                          absent or streamed section, a second call on the section, a set that would exceed 8 oracles.  The
+ *                                          helper is NOT streamed: the call needs (115 n_proofs (N + M) + 2 M) 8 bytes plus two trees
+ *                                          (TMX_ERR_CAPACITY if the card cannot hold it).
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream, no device-to-host copy inside;
+ * tmx_air_last_gamma covers these calls too. */
+#define TMX_AIR_SHA256_SCHED_HELPER_COLS 115
+#define TMX_AIR_SHA256_SCHED_CONSTRAINTS 117
+#define TMX_TRACE_SHA256_SCHED_HELPER 512u
+#define TMX_TRACE_SHA256_SCHED_QUOTIENT 1024u
+int32_t tmx_air_sha256_sched_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                           void* hip_stream);
+int32_t tmx_air_sha256_sched_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                             const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                           const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

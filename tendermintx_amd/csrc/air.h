@@ -92,4 +92,29 @@ int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, 
                          const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
                          void* stream);
 
+// ---- constraint set 4: the message schedule of the SHA-256 tables (include/tmx.h "the message schedule of the SHA-256 tables").  The same
+// table, a helper oracle of 115 columns per proof, 117 constraints per proof; gamma comes from set 3's lone-lane kernel with the set id 4 in
+// obs[0] (launch_air_sha_gamma: the kernel is the same code object, so neither it nor k_fri_transcript changes).
+constexpr uint32_t AIR_SCHED_HELPER_COLS = 115, AIR_SCHED_CONSTRAINTS = 117;
+// The tables one set-4 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
+//   gpow  [118][2]               gamma^0 .. gamma^117
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+//   fx    [64 << log_blowup]     F(x_i) = P_F(x_i^(N/64)), by i mod (64 << log_blowup)
+constexpr uint32_t AIR4_TAB_GPOW = 0, AIR4_TAB_ZINV = 256, AIR4_TAB_F = 320;
+constexpr uint64_t AIR4_TAB_WORDS = AIR4_TAB_F + (64u << 6);
+static_assert(2 * (AIR_SCHED_CONSTRAINTS + 1) <= AIR4_TAB_ZINV && AIR4_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-4 tables live in the table part of set 1's scratch");
+// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 115 n_proofs
+int launch_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
+// s_n = s^N, w_n = w^N, s_n64 = s^(N/64), w_n64 = w^(N/64), om64_inv = omega_64^-1; gamma at d_gamma (2 words)
+int launch_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+                            void* d_tab, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(117 p + j) C_(p,j) / (x^N - 1)
+int launch_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                              const void* d_tab, void* d_quot, void* stream);
+// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
+int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
+                           const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                           void* stream);
+
 }  // namespace tmx

@@ -925,4 +925,283 @@ int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, 
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 4: the message schedule of the SHA-256 tables (include/tmx.h "the message schedule of the SHA-256 tables") --------------
+// Siblings again: nothing above changes.  Helper column offsets inside a proof's 115 (Q_k at S_Q + k), constraint indices inside its 117
+// (Q_k's at JS_Q + k).
+constexpr uint32_t S_WB = 0, S_X0 = 32, S_X1 = 64, S_G0 = 96, S_G1 = 97, S_Q = 97, S_CW = 113;
+constexpr uint32_t JS_CW = 32, JS_WORD = 34, JS_X0 = 35, JS_X1 = 67, JS_G0 = 99, JS_G1 = 100, JS_Q = 100, JS_NEXT = 116;
+
+__device__ __forceinline__ uint32_t sched_rot(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
+__device__ __forceinline__ uint32_t sched_s0(uint32_t w) { return sched_rot(w, 7) ^ sched_rot(w, 18) ^ (w >> 3); }
+__device__ __forceinline__ uint32_t sched_s1(uint32_t w) { return sched_rot(w, 17) ^ sched_rot(w, 19) ^ (w >> 10); }
+
+// One lane per (proof, row) of the pre-LDE table, 115 stores, each of them consecutive words of one column across the wave.  The pipeline
+// unrolled: Q_k(r) = W(r-k) + sigma0(W(r-k+1)) + [k >= 9] W(r-k+9) + [k >= 14] sigma1(W(r-k+14)), rows cyclic inside the proof, so the lane
+// reads W of the sixteen rows r - 15 .. r (its neighbours' lines) and recomputes sigma0 / sigma1 instead of exchanging them; Q_15 needs
+// W at r, r - 1, r - 6, r - 14 and r - 15 only.  W is the low 32 bits of the table word.
+__global__ __launch_bounds__(256) void k_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                          uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows);
+  const uint64_t mask = (1ull << log_rows) - 1, r = idx & mask;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA_WIDTH) << log_rows);  // (W is column 0)
+  uint32_t w[16];  // w[d] = W(r - d)
+#pragma unroll
+  for (uint32_t d = 0; d < 16; d++) w[d] = (uint32_t)t[(r - d) & mask];
+  const uint32_t w0 = w[0], x0 = sched_rot(w0, 7) ^ sched_rot(w0, 18), x1 = sched_rot(w0, 17) ^ sched_rot(w0, 19);
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SCHED_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 32; i++) {
+    put(S_WB + i, (w0 >> i) & 1);
+    put(S_X0 + i, (x0 >> i) & 1);
+    put(S_X1 + i, (x1 >> i) & 1);
+  }
+  put(S_G0, sched_s0(w0));
+  put(S_G1, sched_s1(w0));
+  uint64_t q15 = 0;
+#pragma unroll
+  for (uint32_t k = 1; k <= 15; k++) {
+    uint64_t q = (uint64_t)w[k] + sched_s0(w[k - 1]);
+    if (k >= 9) q += w[k - 9];
+    if (k >= 14) q += sched_s1(w[k - 14]);
+    put(S_Q + k, q);
+    q15 = q;
+  }
+  const uint32_t rnd = (uint32_t)(r & 63);
+  const uint32_t cw = (rnd >= 15 && rnd <= 62) ? (uint32_t)(q15 >> 32) & 3 : 0;
+  put(S_CW, cw & 1);
+  put(S_CW + 1, cw >> 1);
+}
+
+// P_F, the polynomial of degree < 64 with P_F(omega_64^t) = 1 for 15 <= t <= 62 and 0 otherwise (the next row is a schedule row), into
+// LDS: thread j < 64 takes coefficient j, an inverse transform written out.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void air_sched_pf(uint64_t om64_inv, uint64_t* pf) {
+  if (threadIdx.x < 64) {
+    const uint64_t step = gl_pow(om64_inv, threadIdx.x);
+    uint64_t cur = gl_pow(step, 15), acc = 0;
+    for (uint32_t t = 15; t <= 62; t++, cur = gl_mul(cur, step)) acc = gl_add(acc, cur);
+    pf[threadIdx.x] = gl_mul(acc, GL_P - (GL_P - 1) / 64);
+  }
+  __syncthreads();
+}
+
+// One thread per table entry: F by i mod 64 B (Horner on P_F's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 117.
+__global__ __launch_bounds__(256) void k_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+                                                          uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  __shared__ uint64_t pf[64];
+  air_sched_pf(om64_inv, pf);
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < (64u << log_blowup)) {
+    const uint64_t y = gl_mul(s_n64, gl_pow(w_n64, k));
+    uint64_t acc = 0;
+    for (int j = 63; j >= 0; j--) acc = gl_add(gl_mul(acc, y), pf[j]);
+    tab[AIR4_TAB_F + k] = acc;
+  }
+  if (k < (1u << log_blowup)) tab[AIR4_TAB_ZINV + k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
+  if (k <= AIR_SCHED_CONSTRAINTS) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
+    tab[AIR4_TAB_GPOW + 2 * k] = g.c0;
+    tab[AIR4_TAB_GPOW + 2 * k + 1] = g.c1;
+  }
+}
+
+// The set-4 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^117), W and the 115 helper columns.  It walks the bit index b from 31 down to 0 and per b holds WB_b, X0_b, X1_b and the six
+// rotated or shifted bit words (WB_(b+7), WB_(b+18), WB_(b+17), WB_(b+19), and WB_(b+3) for b < 29, WB_(b+10) for b < 22), which are re-read
+// through the cache.  Per b: three constraints (X^2 - X, X0, X1) and one Horner step by 2 of the three word sums (W, sigma0, sigma1), so
+// that no power of two is multiplied: 5 reduced column products and 6 gamma weights.  Behind the loop the three word constraints, the two
+// carry bits, the fifteen pipeline constraints (linear: W', G0', G1' and Q_1' .. Q_15' at i + B) and the selected one, whose F(x) is
+// applied once to its value.  The gamma sums are lazy, as in set 3's pass.
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                    const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                    const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR4_TAB_GPOW;
+  const uint64_t fx = tab[AIR4_TAB_F + (i & ((64ull << log_blowup) - 1))];
+  const uint64_t zinv = tab[AIR4_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g117 = {gp[2 * AIR_SCHED_CONSTRAINTS], gp[2 * AIR_SCHED_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);  // (W is column 0)
+    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_SCHED_HELPER_COLS) << log_m);
+    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
+    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
+    auto next = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + nx]); };
+    uint64_t a0 = 0, a1 = 0;  // the gamma sums, lazy
+    auto plain = [&](uint32_t j, uint64_t v) {
+      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
+      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
+    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
+      const uint64_t xy = gl_mul(x, y);
+      return gl_sub(gl_add(x, y), gl_add(xy, xy));
+    };
+    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
+    uint64_t ww = 0, wg0 = 0, wg1 = 0;
+#pragma unroll 2
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint64_t WB = again(S_WB + b), X0 = once(S_X0 + b), X1 = once(S_X1 + b);
+      const uint64_t W7 = again(S_WB + ((b + 7) & 31)), W18 = again(S_WB + ((b + 18) & 31));
+      const uint64_t W17 = again(S_WB + ((b + 17) & 31)), W19 = again(S_WB + ((b + 19) & 31));
+      plain(S_WB + b, boolean(WB));
+      plain(JS_X0 + b, gl_sub(X0, exor(W7, W18)));
+      plain(JS_X1 + b, gl_sub(X1, exor(W17, W19)));
+      ww = dbl_add(ww, WB);
+      wg0 = dbl_add(wg0, b < 29 ? exor(X0, again(S_WB + ((b + 3) & 31))) : X0);   // (b is uniform: a scalar branch)
+      wg1 = dbl_add(wg1, b < 22 ? exor(X1, again(S_WB + ((b + 10) & 31))) : X1);
+    }
+    const uint64_t W = gl_canon(c[i]), Wn = gl_canon(c[nx]);
+    const uint64_t G0 = again(S_G0), G1 = again(S_G1), CW0 = once(S_CW), CW1 = once(S_CW + 1);
+    plain(JS_WORD, gl_sub(W, ww));
+    plain(JS_G0, gl_sub(G0, wg0));
+    plain(JS_G1, gl_sub(G1, wg1));
+    plain(JS_CW, boolean(CW0));
+    plain(JS_CW + 1, boolean(CW1));
+    uint64_t prev = gl_add(W, next(S_G0));  // what Q_k' must equal: W + G0' for k = 1, then Q_(k-1) (+ W' for k = 9, + G1' for k = 14)
+#pragma unroll
+    for (uint32_t k = 1; k <= 15; k++) {
+      plain(JS_Q + k, gl_sub(next(S_Q + k), prev));
+      prev = again(S_Q + k);
+      if (k + 1 == 9) prev = gl_add(prev, Wn);
+      if (k + 1 == 14) prev = gl_add(prev, next(S_G1));
+    }
+    // (prev = Q_15)  F(x) (W' + 2^32 (CW_0 + 2 CW_1) - Q_15)
+    const uint64_t carry = gl_mul(gl_add(CW0, gl_add(CW1, CW1)), 1ull << 32);
+    plain(JS_NEXT, gl_mul(fx, gl_sub(gl_add(Wn, carry), prev)));
+    t = gl2_add(gl2_mul(t, g117), {gl_canon(a0), gl_canon(a1)});
+  }
+  const gl2 q = gl2_scale(t, zinv);
+  out[i] = q.c0;
+  out[M + i] = q.c1;
+}
+
+// The set-4 identity at zeta, one workgroup: gamma^0 .. gamma^117 and P_F go to LDS first; thread t takes the proofs t, t + 256, ... and
+// evaluates their 117 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the order of
+// the hot pass; F(zeta) by Horner on P_F at zeta^(N/64).  The sums meet in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1).
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                        uint64_t om64_inv, const uint64_t* __restrict__ open_t,
+                                                                        const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
+                                                                        const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
+                                                                        uint32_t n_queries, uint32_t* __restrict__ ok) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint64_t gpw[2 * (AIR_SCHED_CONSTRAINTS + 1)];
+  __shared__ uint64_t pf[64];
+  __shared__ uint32_t holds;
+  const uint32_t t = threadIdx.x;
+  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
+  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
+  for (uint32_t k = t; k <= AIR_SCHED_CONSTRAINTS; k += AIR_CHECK_THREADS) {
+    const gl2 gk = gl2_pow(g, k);
+    gpw[2 * k] = gk.c0;
+    gpw[2 * k + 1] = gk.c1;
+  }
+  air_sched_pf(om64_inv, pf);  // (ends with a barrier: gpw is complete behind it too)
+  gl2 zp = z;  // zeta^(N/64)
+  for (uint32_t k = 6; k < log_sub; k++) zp = gl2_mul(zp, zp);
+  gl2 F = {0, 0};
+  for (int j = 63; j >= 0; j--) {
+    F = gl2_mul(F, zp);
+    F.c0 = gl_add(F.c0, pf[j]);
+  }
+  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
+  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
+  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
+  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
+  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
+  auto exor = [](gl2 x, gl2 y) {
+    const gl2 xy = gl2_mul(x, y);
+    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
+  };
+  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
+  gl2 sum = {0, 0};
+  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
+    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_SCHED_HELPER_COLS;
+    gl2 a = {0, 0};
+    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    gl2 ww = {0, 0}, wg0 = ww, wg1 = ww;
+    for (uint32_t b = 32; b-- > 0;) {
+      const gl2 WB = h0(chh + S_WB + b), X0 = h0(chh + S_X0 + b), X1 = h0(chh + S_X1 + b);
+      const gl2 W7 = h0(chh + S_WB + ((b + 7) & 31)), W18 = h0(chh + S_WB + ((b + 18) & 31));
+      const gl2 W17 = h0(chh + S_WB + ((b + 17) & 31)), W19 = h0(chh + S_WB + ((b + 19) & 31));
+      plain(S_WB + b, boolean(WB));
+      plain(JS_X0 + b, gl2_sub(X0, exor(W7, W18)));
+      plain(JS_X1 + b, gl2_sub(X1, exor(W17, W19)));
+      ww = dbl_add(ww, WB);
+      wg0 = dbl_add(wg0, b < 29 ? exor(X0, h0(chh + S_WB + ((b + 3) & 31))) : X0);
+      wg1 = dbl_add(wg1, b < 22 ? exor(X1, h0(chh + S_WB + ((b + 10) & 31))) : X1);
+    }
+    const gl2 W = t0(ct), Wn = t1(ct);
+    const gl2 G0 = h0(chh + S_G0), G1 = h0(chh + S_G1), CW0 = h0(chh + S_CW), CW1 = h0(chh + S_CW + 1);
+    plain(JS_WORD, gl2_sub(W, ww));
+    plain(JS_G0, gl2_sub(G0, wg0));
+    plain(JS_G1, gl2_sub(G1, wg1));
+    plain(JS_CW, boolean(CW0));
+    plain(JS_CW + 1, boolean(CW1));
+    gl2 prev = gl2_add(W, h1(chh + S_G0));
+    for (uint32_t k = 1; k <= 15; k++) {
+      plain(JS_Q + k, gl2_sub(h1(chh + S_Q + k), prev));
+      prev = h0(chh + S_Q + k);
+      if (k + 1 == 9) prev = gl2_add(prev, Wn);
+      if (k + 1 == 14) prev = gl2_add(prev, h1(chh + S_G1));
+    }
+    const gl2 carry = gl2_scale(gl2_add(CW0, gl2_add(CW1, CW1)), 1ull << 32);
+    plain(JS_NEXT, gl2_mul(F, gl2_sub(gl2_add(Wn, carry), prev)));
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SCHED_CONSTRAINTS * p), a));
+  }
+  red[0][t] = sum.c0;
+  red[1][t] = sum.c1;
+  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
+    __syncthreads();
+    if (t < hh) {
+      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
+      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
+    for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
+    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
+    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
+    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(q, {gl_sub(zn.c0, 1), zn.c1})) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!holds)
+    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sched_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+                            void* d_tab, void* stream) {
+  hipLaunchKernelGGL(k_air_sched_tables, dim3(((64u << log_blowup) + 255) / 256), dim3(256), 0, S_(stream), log_blowup, s_n, w_n, s_n64, w_n64,
+                     om64_inv, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                              const void* d_tab, void* d_quot, void* stream) {
+  hipLaunchKernelGGL(k_air_sched_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream),
+                     log_m, log_blowup, n_proofs, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
+                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+  return (int)hipGetLastError();
+}
+int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
+                           const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                           void* stream) {
+  hipLaunchKernelGGL(k_air_sched_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub, om64_inv,
+                     reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_h),
+                     reinterpret_cast<const uint64_t*>(d_open_q), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma),
+                     n_queries, reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx
