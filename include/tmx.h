@@ -1074,10 +1074,10 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d
  *              Every nonlinear constraint has degree 2 and no selector, every selected one is linear in the columns: the honest quotient has
  *              degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks and zero padding satisfy all 315 with
  *              LIVE = 0, which is why K enters through KL.
- *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; and, still open (the follow-ups):
- *              row 0 of a block against the IV or the chaining value; the feed-forward between the two blocks of T.5 / T.6 hashes; LIVE
- *              against anything public; the digest's link to Level-1; SHA-512.  Under set 3 ALONE a block re-run consistently from a changed
- *              W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
+ *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; row 0 of a block against the IV or
+ *              the chaining value and the feed-forward between the two blocks of T.5 / T.6 hashes, which constraint set 5 below proves;
+ *              and, still open (the follow-ups): LIVE against anything public; the digest's link to Level-1; SHA-512.  Under set 3 ALONE a
+ *              block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
  *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
  *   quotient   q(x_i) = sum_p sum_(j < 315) gamma^(315 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical as in set 1; pointwise: defined
@@ -1148,10 +1148,10 @@ int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, u
  *              Every nonlinear constraint has degree 2 and no selector; the one selected constraint is linear, its degree below 63 N / 64 + N:
  *              the honest quotient has degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks, promoted slots
  *              and zero padding satisfy all 117 without a LIVE column.
- *   NOT PROVED by sets 3 and 4 (the follow-ups): row 0 of a block against the IV or the chaining value; the feed-forward between the two
- *              blocks of T.5 / T.6 hashes; the first sixteen W of a block against Level-1; LIVE against anything public; SHA-512.  A block
- *              re-run consistently (schedule and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected
- *              (tests/test_sha_sched.py records it).
+ *   NOT PROVED by sets 3 and 4: row 0 of a block against the IV or the chaining value and the feed-forward between the two blocks of
+ *              T.5 / T.6 hashes, which constraint set 5 below proves; and, still open (the follow-ups): the first sixteen W of a block
+ *              against Level-1; LIVE against anything public; SHA-512.  Under sets 3 and 4 ALONE a block re-run consistently (schedule
+ *              and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected (tests/test_sha_sched.py records it).
  *   challenge  as set 3 with the set id 4: a fresh duplex observes 2^33, then 4, log_n, log_blowup, cap_height, n_proofs, then the table cap,
  *              then THIS helper's cap; gamma drawn as in set 1.
  *   quotient   q(x_i) = sum_p sum_(j < 117) gamma^(117 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical; pointwise: defined for any
@@ -1192,6 +1192,105 @@ int32_t tmx_air_sha256_sched_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint3
 int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
                                            const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+
+/* ---- the block starts of the SHA-256 tables (constraint set 5) --------------------------------------------------------------------------
+ * Sets 3 and 4 prove the round function and the message schedule: every live block is a real SHA-256 compression of its first sixteen W
+ * words FROM ITS ROW-0 STATE, and row 0 itself is tied to nothing.  Set 5 proves on the same three tables that every live hash starts from
+ * the SHA-256 IV, and that the second block of a two-block hash (T.5, T.6) starts from IV + (the state after round 63 of the first block).
+ * Row 0 of a block is round 0 applied to the words H_0 .. H_7 the block starts from: b = H_0, c = H_1, d = H_2, f = H_4, g = H_5, h = H_6,
+ * a = T1 + T2, e = H_3 + T1 with T1 = H_7 + Sigma1(H_4) + Ch(H_4, H_5, H_6) + K_0 + W_0 and T2 = Sigma0(H_0) + Maj(H_0, H_1, H_2).  Six
+ * of the eight words stand in row 0 itself, so set 3's bit machinery runs on the columns b, c, d, f, g, h of the same row (the register
+ * names shifted by one); H_3 and H_7 enter two sums mod 2^32 only, and the link to the row before is linear.  Built beside sets 3 and 4 with
+ * the same machinery: a helper oracle of its own, 337 constraints per proof, one two-column quotient oracle, the identity at zeta; no
+ * existing kernel, transcript phase, proof word, call or refusal changes.  Notation of the blocks above: N rows, 9 columns per proof (W 0,
+ * a 1 .. h 8; s_j is the state column 1 + j), M = N B points, omega = omega_N, a prime is the value at omega x, rows cyclic inside a proof,
+ * operands the low 32 bits of a table word; IV_0 .. IV_7 and K_0 = 0x428a2f98 the SHA-256 constants.  Same field, extension, duplex and
+ * caveats (PARITY UNPINNED).
+ *   chain      a mode in {0, 1}, a parameter of every call.  chain = 0: every block is a hash of its own (T.3).  chain = 1: hashes are pairs of
+ *              blocks on 128-row boundaries (T.5, T.6); N >= 128.  A row r = 63 (mod 64) is a BOUNDARY row; under chain = 1 a row
+ *              r = 63 (mod 128) is a CHAIN row (the next row continues a hash); every other boundary row is a START row.  The wrap from row
+ *              N - 1 to row 0 is a start boundary.
+ *   helper     315 columns per proof, the table's rows, bits LSB first, defined for ANY input.  Offsets inside a proof:
+ *                0 .. 191   B, C, D, F, G, H   bits of b, c, d, f, g, h of the row
+ *              192 .. 223   U0   U0_i = B_(i+2) xor B_(i+13)  (indices mod 32)         224 .. 255   U1   U1_i = F_(i+6) xor F_(i+11)
+ *              256 .. 287   V    V_i = B_i C_i
+ *              288 S0 = Sigma0(b)   289 S1 = Sigma1(f)   290 CH = Ch(f, g, h)   291 MAJ = Maj(b, c, d)   (words)
+ *              292  LV   1 iff row r - r mod 64 of the proof's table has a nonzero word (set 3's LIVE rule)
+ *              293 .. 300   PZ_j(r) = LV(r + 1) ((IV_j + s_j(r)) mod 2^32), on every row
+ *              301 .. 308   CZ_j(r) = (IV_j + s_j(r)) >> 32, on every row
+ *              309 .. 311   CA   on boundary rows the three bits of the a-sum >> 32, 0 elsewhere
+ *              312 .. 314   CE   on boundary rows the three bits of the e-sum >> 32, 0 elsewhere
+ *              The a-sum and the e-sum are those of constraints 327 / 328 on a start row and of 335 / 336 on a chain row: seven terms below
+ *              2^32 (carry <= 6) and six (carry <= 5).
+ *   constraints  337 per proof, at index j:
+ *                0 .. 191   X^2 - X for the helper columns 0 .. 191     192 .. 199   for CZ     200 .. 205   for CA, CE     206   LV^2 - LV
+ *              207 .. 212   word - sum 2^i bit_i   for (b, B), (c, C), (d, D), (f, F), (g, G), (h, H)
+ *              213 + i      U0_i - xor(B_(i+2), B_(i+13))     245 + i   U1_i - xor(F_(i+6), F_(i+11))     277 + i   V_i - B_i C_i
+ *              309   S0 - sum 2^i xor(U0_i, B_(i+22))         310   S1 - sum 2^i xor(U1_i, F_(i+25)),   xor(x, y) = x + y - 2 x y
+ *              311   CH - sum 2^i (H_i + F_i (G_i - H_i))     312   MAJ - sum 2^i (V_i + D_i (B_i + C_i - 2 V_i))
+ *              313 + j, j < 8   PZ_j - LV' (IV_j + s_j - 2^32 CZ_j)      degree 2, no selector: it holds on every row by construction
+ *              321 .. 326   E_s:  x' - IV_j LV'   for (x, j) = (b, 0), (c, 1), (d, 2), (f, 4), (g, 5), (h, 6)
+ *              327          E_s:  a' + 2^32 (CA_0 + 2 CA_1 + 4 CA_2) - (IV_7 + K_0) LV' - S1' - CH' - W' - S0' - MAJ'
+ *              328          E_s:  e' + 2^32 (CE_0 + 2 CE_1 + 4 CE_2) - (IV_3 + IV_7 + K_0) LV' - S1' - CH' - W'
+ *              329 .. 334   E_c:  x' - PZ_j       for the same six pairs
+ *              335          E_c:  a' + 2^32 CA - PZ_7 - K_0 LV' - S1' - CH' - W' - S0' - MAJ'
+ *              336          E_c:  e' + 2^32 CE - PZ_3 - PZ_7 - K_0 LV' - S1' - CH' - W'
+ *              Selectors, with y = x^(N/64), z = x^(N/128), rho = omega_128^-1: chain = 0: E_s = (x^N - 1) / (y - omega_64^-1), E_c = 0;
+ *              chain = 1: E_s = (x^N - 1) / (z - rho), nonzero exactly on r = 127 (mod 128), and E_c = (x^N - 1) / (z + rho), nonzero exactly
+ *              on r = 63 (mod 128) (omega_128^64 = -1).  Every nonlinear constraint has degree 2 and no selector, every selected one is
+ *              linear in the columns: the honest quotient has degree < N and one two-column quotient oracle is enough.  Zero blocks,
+ *              promoted slots, unused second blocks and zero padding satisfy all 337 with LV = 0, which is why K_0 and the IV enter
+ *              multiplied by LV' and why PZ carries LV'.
+ *   NOT PROVED by sets 3 + 4 + 5 (the follow-ups): the first sixteen W of a block against Level-1; the digest (IV or chaining value plus
+ *              the state after the last round) against Level-1; LV against anything public -- a hash whose live second block is replaced
+ *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512; the ladders' curve arithmetic
+ *              and limb ranges (tests/test_sha_init.py records the first and the third).
+ *   challenge  set 3's lone-lane kernel: a fresh duplex observes 2^33, then 5 | chain << 8, log_n, log_blowup, cap_height, n_proofs, then the
+ *              table cap, then THIS helper's cap; gamma drawn as in set 1.
+ *   quotient   with D_s and D_c the selectors' denominators (y - omega_64^-1 under chain = 0; z - rho and z + rho under chain = 1),
+ *              q(x_i) = sum_p [ sum_(j < 321) gamma^(337 p + j) C_j / (x_i^N - 1) + sum_(321 <= j < 329) gamma^(337 p + j) L_j / D_s
+ *                               + sum_(j >= 329) gamma^(337 p + j) L_j / D_c ],   L_j the linear forms behind E_s and E_c above (the last
+ *              sum is absent under chain = 0); planar and canonical; pointwise: defined for any columns.
+ *   identity   division-free, from the openings at zeta and zeta omega_N.  chain = 1, with S = D_s D_c at zeta:
+ *              S sum_unselected + (zeta^N - 1) (D_c sum_start + D_s sum_chain) == (u_0 + X u_1) (zeta^N - 1) S;   chain = 0, with S = D_s:
+ *              S sum_unselected + (zeta^N - 1) sum_start == (u_0 + X u_1) (zeta^N - 1) S.  A failed identity clears every query's verdict.
+ *   tmx_air_sha256_init_helper_device      the helper (315 n_proofs columns of 2^log_rows words at d_helper) from PRE-LDE table columns
+ *                                          (9 n_proofs columns at d_table).  TMX_ERR_BAD_ARG: log_rows outside 6 .. 27, n_proofs = 0,
+ *                                          315 n_proofs > 2^24, chain > 1, chain = 1 with log_rows < 7, a null pointer.
+ *   tmx_air_sha256_init_quotient_device    gamma from d_cap and d_cap_helper, then the quotient of the EXTENDED columns d_cols and
+ *                                          d_helper_cols into d_quot (2 << log_n words), under the context's CURRENT NTT domain.  Set 4's
+ *                                          rules for refusing arguments, with 315 n_proofs <= 2^24; chain > 1 and chain = 1 with fewer than
+ *                                          128 rows are refused.
+ *   tmx_air_sha256_init_verify_device      tmx_batch_verify_device, then the identity for the oracles k_trace (the table), k_helper (this
+ *                                          helper) and k_helper + 1 (this quotient).  TMX_ERR_BAD_ARG unless the column counts are 9 k, 315 k
+ *                                          and 2, the log_n equal, k_helper > k_trace, k_helper + 1 < n_oracles, and chain as above.
+ *   tmx_trace_commit_set_air_sha256_init_device   mirrors tmx_trace_commit_set_air_sha256_sched_device: the helper from the resident member's
+ *                                          pre-LDE columns, extended one proof's 315 columns at a time under the set's domain and committed
+ *                                          (d_cap_h), gamma, the quotient and its tree (d_cap_q), in a scratch of its own per section; chain
+ *                                          is 0 for TMX_TRACE_SHA256 and 1 for TMX_TRACE_TREE and TMX_TRACE_HEADER.  The pair goes behind the
+ *                                          last helper/quotient pair that already follows the table; set 3's and set 4's calls, unchanged,
+ *                                          insert in front of later members: every order of the three calls ends as table, H3, Q3, H4, Q4,
+ *                                          H5, Q5.  tmx_trace_commit_set_shape reports TMX_TRACE_SHA256_INIT_HELPER and
+ *                                          TMX_TRACE_SHA256_INIT_QUOTIENT in section_of.  Refused: a wrong, absent or streamed section, a
+ *                                          second call on the section, a set that would exceed 8 oracles.  The helper is NOT streamed: the
+ *                                          call needs (315 n_proofs (N + M) + 2 M) 8 bytes plus two trees (TMX_ERR_CAPACITY if the card
+ *                                          cannot hold it); at 256 proofs and blow-up 8 that is 23.8 GB for HEADER (N = 2^12), 95.1 GB for
+ *                                          T.3 (N = 2^14) and 190 GB for TREE (N = 2^15): as with set 3, only HEADER is meant to run
+ *                                          resident at full size.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream, no device-to-host copy inside;
+ * tmx_air_last_gamma covers these calls too. */
+#define TMX_AIR_SHA256_INIT_HELPER_COLS 315
+#define TMX_AIR_SHA256_INIT_CONSTRAINTS 337
+#define TMX_TRACE_SHA256_INIT_HELPER 2048u
+#define TMX_TRACE_SHA256_INIT_QUOTIENT 4096u
+int32_t tmx_air_sha256_init_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
+                                          uint64_t* d_helper, void* hip_stream);
+int32_t tmx_air_sha256_init_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_init_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
+                                          const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

@@ -22,6 +22,8 @@ AIR_SHA256_HELPER_COLS, AIR_SHA256_CONSTRAINTS = 300, 315   # TMX_AIR_SHA256_*: 
 TRACE_SHA256_HELPER, TRACE_SHA256_QUOTIENT = 128, 256   # TMX_TRACE_SHA256_*: the helper and the quotient of set 3 as members of a commit set
 AIR_SHA256_SCHED_HELPER_COLS, AIR_SHA256_SCHED_CONSTRAINTS = 115, 117   # TMX_AIR_SHA256_SCHED_*: constraint set 4, the SHA-256 message schedule
 TRACE_SHA256_SCHED_HELPER, TRACE_SHA256_SCHED_QUOTIENT = 512, 1024   # TMX_TRACE_SHA256_SCHED_*: the helper and the quotient of set 4
+AIR_SHA256_INIT_HELPER_COLS, AIR_SHA256_INIT_CONSTRAINTS = 315, 337   # TMX_AIR_SHA256_INIT_*: constraint set 5, the SHA-256 block starts
+TRACE_SHA256_INIT_HELPER, TRACE_SHA256_INIT_QUOTIENT = 2048, 4096   # TMX_TRACE_SHA256_INIT_*: the helper and the quotient of set 5
 
 
 class ValidatorRec(C.Structure):
@@ -370,6 +372,15 @@ def lib():
         L.tmx_air_sha256_sched_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p]
         L.tmx_trace_commit_set_air_sha256_sched_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
+    try:
+        L.tmx_air_sha256_init_helper_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha256_init_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] * 6
+        L.tmx_air_sha256_init_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha256_init_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -533,6 +533,29 @@ class Context:
         table or behind set 3's pair"""
         check(self._L.tmx_trace_commit_set_air_sha256_sched_device(self._h, section, d_cap_h, d_cap_q, self._stream(stream)), self._h)
 
+    # ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h)
+    def air_sha256_init_helper_device(self, log_rows, n_proofs, chain, d_table, d_helper, stream=None):
+        """the block-start helper (315 n_proofs columns of 2^log_rows words at d_helper) from the pre-LDE table columns (9 n_proofs) at
+        d_table; chain = 0: every block a hash of its own (T.3), chain = 1: pairs of blocks on 128-row boundaries (T.5, T.6)"""
+        check(self._L.tmx_air_sha256_init_helper_device(self._h, log_rows, n_proofs, chain, d_table, d_helper, self._stream(stream)), self._h)
+
+    def air_sha256_init_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot,
+                                        stream=None):
+        """gamma from the table cap and the helper cap, then the quotient of the 337 constraints per proof over the extended table and helper
+        columns into d_quot (planar, 2 << log_n words)"""
+        check(self._L.tmx_air_sha256_init_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap,
+                                                          d_cap_helper, d_quot, self._stream(stream)), self._h)
+
+    def air_sha256_init_verify_device(self, params, k_trace, k_helper, chain, d_caps, d_proof, d_ok, stream=None):
+        """batch_verify_device, then the set-5 identity at zeta for the oracles k_trace (table), k_helper (helper), k_helper + 1 (quotient)"""
+        check(self._L.tmx_air_sha256_init_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, k_helper, chain, d_caps, d_proof,
+                                                        d_ok, self._stream(stream)), self._h)
+
+    def trace_commit_set_air_sha256_init_device(self, section, d_cap_h, d_cap_q, stream=None):
+        """adds the block-start helper and quotient of the resident member `section` (SHA256, TREE or HEADER) to the commit set, behind the
+        last helper/quotient pair that already follows the table"""
+        check(self._L.tmx_trace_commit_set_air_sha256_init_device(self._h, section, d_cap_h, d_cap_q, self._stream(stream)), self._h)
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)

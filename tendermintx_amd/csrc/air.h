@@ -117,4 +117,33 @@ int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h
                            const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
                            void* stream);
 
+// ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h "the block starts of the SHA-256 tables").  The same table, a
+// helper oracle of 315 columns per proof, 337 constraints per proof, a mode chain in {0, 1}; gamma comes from set 3's lone-lane kernel with
+// 5 | chain << 8 in obs[0] (launch_air_sha_gamma: the same code object, so neither it nor k_fri_transcript changes).
+constexpr uint32_t AIR_INIT_HELPER_COLS = 315, AIR_INIT_CONSTRAINTS = 337;
+// The tables one set-5 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
+//   gpow  [338][2]               gamma^0 .. gamma^337
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+//   sel   [64 << log_blowup]     chain = 0: 1 / D_s(x_i), D_s = x^(N/64) - omega_64^-1, by i mod (64 << log_blowup)
+//         [128 << log_blowup]    chain = 1: 1 / D_s(x_i), D_s = x^(N/128) - omega_128^-1, by i mod (128 << log_blowup); 1 / D_c(x_i), D_c =
+//                                x^(N/128) + omega_128^-1, is the negated entry (64 << log_blowup) places on
+constexpr uint32_t AIR5_TAB_GPOW = 0, AIR5_TAB_ZINV = 704, AIR5_TAB_SEL = 768;
+constexpr uint64_t AIR5_TAB_WORDS = AIR5_TAB_SEL + (128u << 6);
+static_assert(2 * (AIR_INIT_CONSTRAINTS + 1) <= AIR5_TAB_ZINV && AIR5_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-5 tables live in the table part of set 1's scratch");
+// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 315 n_proofs
+int launch_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream);
+// s_n = s^N, w_n = w^N; s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0; s^(N/128), w^(N/128), omega_128^-1 under
+// chain = 1; gamma at d_gamma (2 words)
+int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
+                           const void* d_gamma, void* d_tab, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p (sum_(j < 321) gamma^(337 p + j) C_(p,j) / (x^N - 1)
+// + sum_(321 <= j < 329) gamma^(337 p + j) L_(p,j) / D_s + sum_(j >= 329) gamma^(337 p + j) L_(p,j) / D_c)
+int launch_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
+                             const void* d_tab, void* d_quot, void* stream);
+// The division-free identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
+int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho,
+                          const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                          uint32_t n_queries, void* d_ok, void* stream);
+
 }  // namespace tmx

@@ -1204,4 +1204,450 @@ int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h "the block starts of the SHA-256 tables") ----------------------
+// Siblings again: nothing above changes.  Row 0 of a block is round 0 applied to the words the block starts from, so six of those eight
+// words stand in row 0 itself (b, c, d, f, g, h) and set 3's bit machinery runs on them with the register names shifted by one.  Helper
+// column offsets inside a proof's 315, constraint indices inside its 337.
+constexpr uint32_t I_B = 0, I_C = 32, I_D = 64, I_F = 96, I_G = 128, I_H = 160, I_U0 = 192, I_U1 = 224, I_V = 256, I_S0 = 288, I_S1 = 289, I_CH = 290,
+                   I_MAJ = 291, I_LV = 292, I_PZ = 293, I_CZ = 301, I_CA = 309, I_CE = 312;
+constexpr uint32_t JI_CZ = 192, JI_CARRY = 200, JI_LV = 206, JI_WORD = 207, JI_U0 = 213, JI_U1 = 245, JI_V = 277, JI_S0 = 309, JI_S1 = 310, JI_CH = 311,
+                   JI_MAJ = 312, JI_PZ = 313, JI_START = 321, JI_CHAIN = 329;
+__device__ __constant__ const uint32_t IV_SHA256[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                                                       0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+constexpr uint64_t INIT_IV3 = 0xa54ff53aull, INIT_IV7 = 0x5be0cd19ull, INIT_K0 = 0x428a2f98ull;
+
+__device__ __forceinline__ uint32_t init_rot(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
+__device__ __forceinline__ uint32_t init_big0(uint32_t b) { return init_rot(b, 2) ^ init_rot(b, 13) ^ init_rot(b, 22); }
+__device__ __forceinline__ uint32_t init_big1(uint32_t f) { return init_rot(f, 6) ^ init_rot(f, 11) ^ init_rot(f, 25); }
+
+// One lane per (proof, row) of the pre-LDE table: the nine words of the row, the first row of its block (LV) and of the next row's block
+// (LV'; rows are cyclic inside the proof), on a boundary row also the nine words of the next row (the two round-0 sums), then 315 stores,
+// each of them consecutive words of one column across the wave.  Operands are the low 32 bits of the words.
+__global__ __launch_bounds__(256) void k_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* __restrict__ table,
+                                                         uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows);
+  const uint64_t mask = (1ull << log_rows) - 1, r = idx & mask, rn = (r + 1) & mask;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA_WIDTH) << log_rows);
+  uint32_t w[AIR_SHA_WIDTH];
+  uint64_t any = 0, any_next = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < AIR_SHA_WIDTH; c++) {
+    w[c] = (uint32_t)t[((uint64_t)c << log_rows) + r];
+    any |= t[((uint64_t)c << log_rows) + (r & ~63ull)];
+    any_next |= t[((uint64_t)c << log_rows) + (rn & ~63ull)];
+  }
+  const uint32_t live = any ? 1u : 0u, live_next = any_next ? 1u : 0u;
+  const uint32_t b = w[T_B], c = w[T_C], d = w[T_D], f = w[T_F], g = w[T_G], hh = w[T_H];
+  const uint32_t u0 = init_rot(b, 2) ^ init_rot(b, 13), u1 = init_rot(f, 6) ^ init_rot(f, 11), v = b & c;
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_INIT_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 32; i++) {
+    put(I_B + i, (b >> i) & 1);
+    put(I_C + i, (c >> i) & 1);
+    put(I_D + i, (d >> i) & 1);
+    put(I_F + i, (f >> i) & 1);
+    put(I_G + i, (g >> i) & 1);
+    put(I_H + i, (hh >> i) & 1);
+    put(I_U0 + i, (u0 >> i) & 1);
+    put(I_U1 + i, (u1 >> i) & 1);
+    put(I_V + i, (v >> i) & 1);
+  }
+  put(I_S0, init_big0(b));
+  put(I_S1, init_big1(f));
+  put(I_CH, (f & g) ^ (~f & hh));
+  put(I_MAJ, (b & c) ^ (b & d) ^ (c & d));
+  put(I_LV, live);
+  uint32_t pz[8];
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t s = (uint64_t)IV_SHA256[j] + w[1 + j];
+    pz[j] = live_next ? (uint32_t)s : 0u;
+    put(I_PZ + j, pz[j]);
+    put(I_CZ + j, s >> 32);
+  }
+  uint32_t ca = 0, ce = 0;
+  if ((r & 63) == 63) {  // a boundary row: round 0 of the next row's block, from the IV (a start row) or from PZ (a chain row)
+    uint32_t n[AIR_SHA_WIDTH];
+#pragma unroll
+    for (uint32_t k = 0; k < AIR_SHA_WIDTH; k++) n[k] = (uint32_t)t[((uint64_t)k << log_rows) + rn];
+    const bool chained = chain && (r & 127) == 63;
+    const uint64_t t1 = (uint64_t)init_big1(n[T_F]) + ((n[T_F] & n[T_G]) ^ (~n[T_F] & n[T_H])) + n[T_W] + (live_next ? INIT_K0 : 0);
+    const uint64_t t2 = (uint64_t)init_big0(n[T_B]) + ((n[T_B] & n[T_C]) ^ (n[T_B] & n[T_D]) ^ (n[T_C] & n[T_D]));
+    const uint64_t h7 = chained ? pz[7] : live_next ? INIT_IV7 : 0, h3 = chained ? pz[3] : live_next ? INIT_IV3 : 0;
+    ca = (uint32_t)((h7 + t1 + t2) >> 32) & 7;
+    ce = (uint32_t)((h3 + h7 + t1) >> 32) & 7;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 3; k++) {
+    put(I_CA + k, (ca >> k) & 1);
+    put(I_CE + k, (ce >> k) & 1);
+  }
+}
+
+// n <= 8 nonzero values inverted with one field inversion (Montgomery's trick)
+__device__ __forceinline__ void air_init_batch_inverse(uint64_t (&v)[8], uint32_t n) {
+  uint64_t pre[8], acc = 1;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++)
+    if (j < n) {
+      pre[j] = acc;
+      acc = gl_mul(acc, v[j]);
+    }
+  uint64_t inv = gl_pow(acc, GL_P - 2);
+#pragma unroll
+  for (uint32_t j = 8; j-- > 0;)
+    if (j < n) {
+      const uint64_t x = gl_mul(inv, pre[j]);
+      inv = gl_mul(inv, v[j]);
+      v[j] = x;
+    }
+}
+
+// One thread per eight table entries, inverted as a batch: 1 / D_s(x_i) by i mod 64 B (chain = 0: D_s = x^(N/64) - omega_64^-1) or by
+// i mod 128 B (chain = 1: D_s = x^(N/128) - rho, rho = omega_128^-1), from s_sel = s^(N/64) or s^(N/128) and w_sel likewise; 1 / (x^N - 1)
+// by i mod B; and one thread per power gamma^0 .. gamma^337.  Under chain = 1 the same table holds 1 / D_c: x^(N/128) changes its sign
+// 64 B points on, so D_c(x_i) = x_i^(N/128) + rho = -D_s(x_(i + 64 B)).  No entry vanishes: D_s divides x^N - 1, which the caller checked.
+__global__ __launch_bounds__(256) void k_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel,
+                                                         uint64_t w_sel, uint64_t rho, const uint64_t* __restrict__ gamma,
+                                                         uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, first = 8 * k;
+  const uint32_t n_sel = (chain ? 128u : 64u) << log_blowup, n_z = 1u << log_blowup;
+  uint64_t v[8];
+  if (first < n_sel) {  // (n_sel is a multiple of 8)
+    uint64_t x = gl_mul(s_sel, gl_pow(w_sel, first));
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++, x = gl_mul(x, w_sel)) v[j] = gl_sub(x, rho);
+    air_init_batch_inverse(v, 8);
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) tab[AIR5_TAB_SEL + first + j] = v[j];
+  }
+  if (first < n_z) {
+    const uint32_t n = n_z - first < 8 ? n_z - first : 8;
+    uint64_t x = gl_mul(s_n, gl_pow(w_n, first));
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++, x = gl_mul(x, w_n)) v[j] = gl_sub(x, 1);
+    air_init_batch_inverse(v, n);
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++)
+      if (j < n) tab[AIR5_TAB_ZINV + first + j] = v[j];
+  }
+  if (k <= AIR_INIT_CONSTRAINTS) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
+    tab[AIR5_TAB_GPOW + 2 * k] = g.c0;
+    tab[AIR5_TAB_GPOW + 2 * k + 1] = g.c1;
+  }
+}
+
+// The set-5 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^337), the nine table columns and the 315 helper columns.  It walks the bit index b from 31 down to 0 and per b holds the nine bit
+// words B_b .. V_b and the six rotated ones (B_(b+2), B_(b+13), B_(b+22), F_(b+6), F_(b+11), F_(b+25)), which are re-read through the
+// cache, so the 288 bit words are never held.  Per b: nine constraints (six X^2 - X, U0, U1, V) and one Horner step by 2 of the ten word
+// sums: 13 reduced column products and 18 gamma weights.  Behind the loop the word constraints, LV, the eight PZ constraints with their CZ
+// bits, the six carry bits, and the sixteen selected linear forms at i + B in two gamma sums of their own: 1 / D_s is applied once to the
+// start sum, 1 / D_c once to the chain sum (skipped under chain = 0: E_c = 0), 1 / (x^N - 1) once to the rest.  The gamma sums are lazy.
+__global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain,
+                                                                   const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                   const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR5_TAB_GPOW;
+  const uint64_t sel_mask = ((chain ? 128ull : 64ull) << log_blowup) - 1;
+  const uint64_t dsinv = tab[AIR5_TAB_SEL + (i & sel_mask)];
+  const uint64_t dcinv = chain ? gl_neg(tab[AIR5_TAB_SEL + ((i + (64ull << log_blowup)) & sel_mask)]) : 0;
+  const uint64_t zinv = tab[AIR5_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g337 = {gp[2 * AIR_INIT_CONSTRAINTS], gp[2 * AIR_INIT_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);
+    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_INIT_HELPER_COLS) << log_m);
+    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
+    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
+    auto next = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + nx]); };
+    auto tbl = [&](uint32_t col, uint64_t at) { return gl_canon(c[((uint64_t)col << log_m) + at]); };
+    uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0, c0 = 0, c1 = 0;  // the plain, the start and the chain gamma sums, lazy
+    auto plain = [&](uint32_t j, uint64_t v) {
+      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
+      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto started = [&](uint32_t j, uint64_t v) {
+      b0 = gl_add_lazy(b0, gl_mul(gp[2 * j], v));
+      b1 = gl_add_lazy(b1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto chained = [&](uint32_t j, uint64_t v) {
+      c0 = gl_add_lazy(c0, gl_mul(gp[2 * j], v));
+      c1 = gl_add_lazy(c1, gl_mul(gp[2 * j + 1], v));
+    };
+    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
+    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
+      const uint64_t xy = gl_mul(x, y);
+      return gl_sub(gl_add(x, y), gl_add(xy, xy));
+    };
+    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
+    uint64_t wb = 0, wc = 0, wd = 0, wf = 0, wg = 0, wh = 0, ws0 = 0, ws1 = 0, wch = 0, wmj = 0;
+#pragma unroll 2
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint64_t B = again(I_B + b), C = once(I_C + b), D = once(I_D + b), F = again(I_F + b), G = once(I_G + b), H = once(I_H + b);
+      const uint64_t U0 = once(I_U0 + b), U1 = once(I_U1 + b), V = once(I_V + b);
+      const uint64_t B2 = again(I_B + ((b + 2) & 31)), B13 = again(I_B + ((b + 13) & 31)), B22 = again(I_B + ((b + 22) & 31));
+      const uint64_t F6 = again(I_F + ((b + 6) & 31)), F11 = again(I_F + ((b + 11) & 31)), F25 = again(I_F + ((b + 25) & 31));
+      plain(I_B + b, boolean(B));
+      plain(I_C + b, boolean(C));
+      plain(I_D + b, boolean(D));
+      plain(I_F + b, boolean(F));
+      plain(I_G + b, boolean(G));
+      plain(I_H + b, boolean(H));
+      plain(JI_U0 + b, gl_sub(U0, exor(B2, B13)));
+      plain(JI_U1 + b, gl_sub(U1, exor(F6, F11)));
+      plain(JI_V + b, gl_sub(V, gl_mul(B, C)));
+      wb = dbl_add(wb, B);
+      wc = dbl_add(wc, C);
+      wd = dbl_add(wd, D);
+      wf = dbl_add(wf, F);
+      wg = dbl_add(wg, G);
+      wh = dbl_add(wh, H);
+      ws0 = dbl_add(ws0, exor(U0, B22));
+      ws1 = dbl_add(ws1, exor(U1, F25));
+      wch = dbl_add(wch, gl_add(H, gl_mul(F, gl_sub(G, H))));
+      wmj = dbl_add(wmj, gl_add(V, gl_mul(D, gl_sub(gl_add(B, C), gl_add(V, V)))));
+    }
+    plain(JI_WORD + 0, gl_sub(tbl(T_B, i), wb));
+    plain(JI_WORD + 1, gl_sub(tbl(T_C, i), wc));
+    plain(JI_WORD + 2, gl_sub(tbl(T_D, i), wd));
+    plain(JI_WORD + 3, gl_sub(tbl(T_F, i), wf));
+    plain(JI_WORD + 4, gl_sub(tbl(T_G, i), wg));
+    plain(JI_WORD + 5, gl_sub(tbl(T_H, i), wh));
+    plain(JI_S0, gl_sub(again(I_S0), ws0));
+    plain(JI_S1, gl_sub(again(I_S1), ws1));
+    plain(JI_CH, gl_sub(again(I_CH), wch));
+    plain(JI_MAJ, gl_sub(again(I_MAJ), wmj));
+    plain(JI_LV, boolean(again(I_LV)));
+    // the six carry bits, folded into the two words 2^32 CA and 2^32 CE at once
+    uint64_t ca32 = 0, ce32 = 0;
+#pragma unroll
+    for (uint32_t k = 3; k-- > 0;) {
+      const uint64_t CA = once(I_CA + k), CE = once(I_CE + k);
+      plain(JI_CARRY + k, boolean(CA));
+      plain(JI_CARRY + 3 + k, boolean(CE));
+      ca32 = dbl_add(ca32, CA);
+      ce32 = dbl_add(ce32, CE);
+    }
+    ca32 = gl_mul(ca32, 1ull << 32);
+    ce32 = gl_mul(ce32, 1ull << 32);
+    // PZ_j - LV' (IV_j + s_j - 2^32 CZ_j), and with each of the six words that stand in row 0 its two selected linear forms: the next
+    // row's word against IV_j LV' (start rows) and against PZ_j (chain rows; skipped under chain = 0, uniformly)
+    const uint64_t LVn = next(I_LV);
+    uint64_t pz3 = 0, pz7 = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 8; j++) {
+      const uint64_t CZ = once(I_CZ + j), PZ = once(I_PZ + j);
+      plain(JI_CZ + j, boolean(CZ));
+      plain(JI_PZ + j, gl_sub(PZ, gl_mul(LVn, gl_sub(gl_add(tbl(T_A + j, i), IV_SHA256[j]), gl_mul(CZ, 1ull << 32)))));
+      if (j == 3) pz3 = PZ;
+      if (j == 7) pz7 = PZ;
+      if (j != 3 && j != 7) {
+        const uint32_t k = j < 3 ? j : j - 1;
+        const uint64_t xn = tbl(T_B + j, nx);
+        started(JI_START + k, gl_sub(xn, gl_mul(LVn, IV_SHA256[j])));
+        if (chain) chained(JI_CHAIN + k, gl_sub(xn, PZ));
+      }
+    }
+    // round 0 of the next row's block: a' and e' against the two sums
+    const uint64_t t1 = gl_add(gl_add(next(I_S1), next(I_CH)), tbl(T_W, nx)), t12 = gl_add(t1, gl_add(next(I_S0), next(I_MAJ)));
+    const uint64_t an = gl_add(tbl(T_A, nx), ca32), en = gl_add(tbl(T_E, nx), ce32);
+    started(JI_START + 6, gl_sub(an, gl_add(gl_mul(LVn, INIT_IV7 + INIT_K0), t12)));
+    started(JI_START + 7, gl_sub(en, gl_add(gl_mul(LVn, INIT_IV3 + INIT_IV7 + INIT_K0), t1)));
+    uint64_t v0 = gl_add(gl_mul(gl_canon(a0), zinv), gl_mul(gl_canon(b0), dsinv));
+    uint64_t v1 = gl_add(gl_mul(gl_canon(a1), zinv), gl_mul(gl_canon(b1), dsinv));
+    if (chain) {  // (uniform)
+      const uint64_t kl = gl_mul(LVn, INIT_K0);
+      chained(JI_CHAIN + 6, gl_sub(an, gl_add(gl_add(pz7, kl), t12)));
+      chained(JI_CHAIN + 7, gl_sub(en, gl_add(gl_add(pz3, pz7), gl_add(kl, t1))));
+      v0 = gl_add(v0, gl_mul(gl_canon(c0), dcinv));
+      v1 = gl_add(v1, gl_mul(gl_canon(c1), dcinv));
+    }
+    t = gl2_add(gl2_mul(t, g337), {v0, v1});
+  }
+  out[i] = t.c0;
+  out[M + i] = t.c1;
+}
+
+// The set-5 identity at zeta, one workgroup, division-free: gamma^0 .. gamma^337 go to LDS first; thread t takes the proofs t, t + 256, ...
+// and evaluates their 337 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the
+// order of the hot pass, in three sums.  With z = zeta^(N/128), D_s = z - rho, D_c = z + rho and S = D_s D_c under chain = 1 (z =
+// zeta^(N/64), S = z - rho, D_c = 1 and no chain sum under chain = 0), a proof contributes S a + (zeta^N - 1) (D_c b + D_s c); the sums meet
+// in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1) S.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                       uint32_t chain, uint64_t rho, const uint64_t* __restrict__ open_t,
+                                                                       const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
+                                                                       const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
+                                                                       uint32_t n_queries, uint32_t* __restrict__ ok) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint64_t gpw[2 * (AIR_INIT_CONSTRAINTS + 1)];
+  __shared__ uint32_t holds;
+  const uint32_t t = threadIdx.x;
+  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
+  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
+  for (uint32_t k = t; k <= AIR_INIT_CONSTRAINTS; k += AIR_CHECK_THREADS) {
+    const gl2 gk = gl2_pow(g, k);
+    gpw[2 * k] = gk.c0;
+    gpw[2 * k + 1] = gk.c1;
+  }
+  __syncthreads();
+  const uint32_t log_sel = chain ? 7 : 6;
+  gl2 zp = z;  // zeta^(N/128) or zeta^(N/64)
+  for (uint32_t k = log_sel; k < log_sub; k++) zp = gl2_mul(zp, zp);
+  gl2 zn = zp;  // zeta^N
+  for (uint32_t k = 0; k < log_sel; k++) zn = gl2_mul(zn, zn);
+  const gl2 zn1 = {gl_sub(zn.c0, 1), zn.c1};
+  const gl2 Ds = {gl_sub(zp.c0, rho), zp.c1}, Dc = chain ? gl2{gl_add(zp.c0, rho), zp.c1} : gl2{1, 0};
+  const gl2 S = chain ? gl2_mul(Ds, Dc) : Ds;
+  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
+  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
+  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
+  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
+  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
+  auto exor = [](gl2 x, gl2 y) {
+    const gl2 xy = gl2_mul(x, y);
+    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
+  };
+  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
+  gl2 sum = {0, 0};
+  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
+    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_INIT_HELPER_COLS;
+    gl2 a = {0, 0}, bs = {0, 0}, bc = {0, 0};
+    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    auto started = [&](uint32_t j, gl2 v) { bs = gl2_add(bs, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    auto chained = [&](uint32_t j, gl2 v) { bc = gl2_add(bc, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
+    gl2 wb = {0, 0}, wc = wb, wd = wb, wf = wb, wg = wb, wh = wb, ws0 = wb, ws1 = wb, wch = wb, wmj = wb;
+    for (uint32_t b = 32; b-- > 0;) {
+      const gl2 B = h0(chh + I_B + b), C = h0(chh + I_C + b), D = h0(chh + I_D + b), F = h0(chh + I_F + b), G = h0(chh + I_G + b),
+                H = h0(chh + I_H + b), U0 = h0(chh + I_U0 + b), U1 = h0(chh + I_U1 + b), V = h0(chh + I_V + b);
+      const gl2 B2 = h0(chh + I_B + ((b + 2) & 31)), B13 = h0(chh + I_B + ((b + 13) & 31)), B22 = h0(chh + I_B + ((b + 22) & 31));
+      const gl2 F6 = h0(chh + I_F + ((b + 6) & 31)), F11 = h0(chh + I_F + ((b + 11) & 31)), F25 = h0(chh + I_F + ((b + 25) & 31));
+      plain(I_B + b, boolean(B));
+      plain(I_C + b, boolean(C));
+      plain(I_D + b, boolean(D));
+      plain(I_F + b, boolean(F));
+      plain(I_G + b, boolean(G));
+      plain(I_H + b, boolean(H));
+      plain(JI_U0 + b, gl2_sub(U0, exor(B2, B13)));
+      plain(JI_U1 + b, gl2_sub(U1, exor(F6, F11)));
+      plain(JI_V + b, gl2_sub(V, gl2_mul(B, C)));
+      wb = dbl_add(wb, B);
+      wc = dbl_add(wc, C);
+      wd = dbl_add(wd, D);
+      wf = dbl_add(wf, F);
+      wg = dbl_add(wg, G);
+      wh = dbl_add(wh, H);
+      ws0 = dbl_add(ws0, exor(U0, B22));
+      ws1 = dbl_add(ws1, exor(U1, F25));
+      wch = dbl_add(wch, gl2_add(H, gl2_mul(F, gl2_sub(G, H))));
+      wmj = dbl_add(wmj, gl2_add(V, gl2_mul(D, gl2_sub(gl2_add(B, C), gl2_add(V, V)))));
+    }
+    plain(JI_WORD + 0, gl2_sub(t0(ct + T_B), wb));
+    plain(JI_WORD + 1, gl2_sub(t0(ct + T_C), wc));
+    plain(JI_WORD + 2, gl2_sub(t0(ct + T_D), wd));
+    plain(JI_WORD + 3, gl2_sub(t0(ct + T_F), wf));
+    plain(JI_WORD + 4, gl2_sub(t0(ct + T_G), wg));
+    plain(JI_WORD + 5, gl2_sub(t0(ct + T_H), wh));
+    plain(JI_S0, gl2_sub(h0(chh + I_S0), ws0));
+    plain(JI_S1, gl2_sub(h0(chh + I_S1), ws1));
+    plain(JI_CH, gl2_sub(h0(chh + I_CH), wch));
+    plain(JI_MAJ, gl2_sub(h0(chh + I_MAJ), wmj));
+    plain(JI_LV, boolean(h0(chh + I_LV)));
+    gl2 ca32 = {0, 0}, ce32 = {0, 0};
+    for (uint32_t k = 3; k-- > 0;) {
+      const gl2 CA = h0(chh + I_CA + k), CE = h0(chh + I_CE + k);
+      plain(JI_CARRY + k, boolean(CA));
+      plain(JI_CARRY + 3 + k, boolean(CE));
+      ca32 = dbl_add(ca32, CA);
+      ce32 = dbl_add(ce32, CE);
+    }
+    ca32 = gl2_scale(ca32, 1ull << 32);
+    ce32 = gl2_scale(ce32, 1ull << 32);
+    const gl2 LVn = h1(chh + I_LV);
+    gl2 pz3 = {0, 0}, pz7 = {0, 0};
+#pragma unroll 1
+    for (uint32_t j = 0; j < 8; j++) {
+      const gl2 CZ = h0(chh + I_CZ + j), PZ = h0(chh + I_PZ + j);
+      gl2 s = t0(ct + T_A + j);
+      s.c0 = gl_add(s.c0, IV_SHA256[j]);
+      plain(JI_CZ + j, boolean(CZ));
+      plain(JI_PZ + j, gl2_sub(PZ, gl2_mul(LVn, gl2_sub(s, gl2_scale(CZ, 1ull << 32)))));
+      if (j == 3) pz3 = PZ;
+      if (j == 7) pz7 = PZ;
+      if (j != 3 && j != 7) {
+        const uint32_t k = j < 3 ? j : j - 1;
+        const gl2 xn = t1(ct + T_B + j);
+        started(JI_START + k, gl2_sub(xn, gl2_scale(LVn, IV_SHA256[j])));
+        if (chain) chained(JI_CHAIN + k, gl2_sub(xn, PZ));
+      }
+    }
+    const gl2 tt = gl2_add(gl2_add(h1(chh + I_S1), h1(chh + I_CH)), t1(ct + T_W)), tt2 = gl2_add(tt, gl2_add(h1(chh + I_S0), h1(chh + I_MAJ)));
+    const gl2 an = gl2_add(t1(ct + T_A), ca32), en = gl2_add(t1(ct + T_E), ce32);
+    started(JI_START + 6, gl2_sub(an, gl2_add(gl2_scale(LVn, INIT_IV7 + INIT_K0), tt2)));
+    started(JI_START + 7, gl2_sub(en, gl2_add(gl2_scale(LVn, INIT_IV3 + INIT_IV7 + INIT_K0), tt)));
+    if (chain) {
+      const gl2 kl = gl2_scale(LVn, INIT_K0);
+      chained(JI_CHAIN + 6, gl2_sub(an, gl2_add(gl2_add(pz7, kl), tt2)));
+      chained(JI_CHAIN + 7, gl2_sub(en, gl2_add(gl2_add(pz3, pz7), gl2_add(kl, tt))));
+    }
+    const gl2 v = gl2_add(gl2_mul(S, a), gl2_mul(zn1, gl2_add(gl2_mul(Dc, bs), gl2_mul(Ds, bc))));
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_INIT_CONSTRAINTS * p), v));
+  }
+  red[0][t] = sum.c0;
+  red[1][t] = sum.c1;
+  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
+    __syncthreads();
+    if (t < hh) {
+      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
+      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
+    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
+    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(gl2_mul(q, zn1), S)) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!holds)
+    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_init_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs, chain,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
+                           const void* d_gamma, void* d_tab, void* stream) {
+  // (at least two workgroups: the 338 gamma powers)
+  const uint32_t blocks = ((((chain ? 128u : 64u) << log_blowup) / 8) + 255) / 256;
+  hipLaunchKernelGGL(k_air_init_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, chain, s_n, w_n, s_sel, w_sel, rho,
+                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
+                             const void* d_tab, void* d_quot, void* stream) {
+  hipLaunchKernelGGL(k_air_init_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream),
+                     log_m, log_blowup, n_proofs, chain, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
+                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+  return (int)hipGetLastError();
+}
+int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho,
+                          const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                          uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_init_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub, chain, rho,
+                     reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_h),
+                     reinterpret_cast<const uint64_t*>(d_open_q), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma),
+                     n_queries, reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx

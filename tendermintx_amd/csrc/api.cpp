@@ -440,6 +440,9 @@ struct tmx_ctx {
   // constraint set 4 (tmx_trace_commit_set_air_sha256_sched_device): the same layout per section for the schedule's helper and quotient
   void* d_set_sched[3] = {};
   size_t set_sched_bytes[3] = {};
+  // constraint set 5 (tmx_trace_commit_set_air_sha256_init_device): the same layout per section for the block starts' helper and quotient
+  void* d_set_init[3] = {};
+  size_t set_init_bytes[3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
@@ -1439,6 +1442,8 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   for (void* b : c->d_set_sha)
     if (b) (void)hipFree(b);
   for (void* b : c->d_set_sched)
+    if (b) (void)hipFree(b);
+  for (void* b : c->d_set_init)
     if (b) (void)hipFree(b);
   if (c->d_air) (void)hipFree(c->d_air);
   if (c->d_air2) (void)hipFree(c->d_air2);
@@ -5016,6 +5021,218 @@ int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* c, uint32_t sectio
   for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
   r.o[at] = {TMX_TRACE_SHA256_SCHED_HELPER, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
   r.o[at + 1] = {TMX_TRACE_SHA256_SCHED_QUOTIENT, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
+  r.n_oracles += 2;
+  c->set = r;
+  return TMX_OK;
+}
+
+}  // extern "C"
+
+// ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h "the block starts of the SHA-256 tables") ---------------------
+// Built beside sets 3 and 4: their checks, kernels and calls are what they were.  The geometry (AirGeo3, plus the selector's own root and
+// shift), the gamma kernel (with the set id 5 and the mode in obs[0]) and the challenge words are set 3's; the set-5 tables of a quotient
+// launch sit in the table part of d_air (air.h AIR5_TAB_*).
+struct AirGeo5 { uint64_t s_sel, w_sel, rho; };  // chain = 0: s^(N/64), w^(N/64), omega_64^-1; chain = 1: s^(N/128), w^(N/128), omega_128^-1
+
+static int32_t air5_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain) {
+  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
+  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
+  if (log_n - log_blowup < 6) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * AIR_INIT_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "315 n_proofs must be at most 2^24");
+  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
+  if (chain && log_n - log_blowup < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
+  return TMX_OK;
+}
+
+static int32_t air5_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, AirGeo3& A, AirGeo5& I) {
+  const int32_t st = air3_geo(c, log_n, log_blowup, root_2_32, shift, A);
+  if (st) return st;
+  if (!chain) {
+    I.s_sel = A.s_n64; I.w_sel = A.w_n64; I.rho = A.om64_inv;
+    return TMX_OK;
+  }
+  const uint64_t P = 0xffffffff00000001ull;
+  const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
+  I.s_sel = gl_pow_host(s, n >> 7); I.w_sel = gl_pow_host(w, n >> 7);
+  I.rho = gl_pow_host(gl_pow_host(w, 1ull << (log_n - 7)), P - 2);  // omega_128 = omega_N^(N/128) = w^(M/128)
+  return TMX_OK;
+}
+
+static int32_t air5_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
+                          const uint64_t* d_cap, const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
+  const uint32_t obs[5] = {5u | chain << 8 /* the constraint-set id: the SHA-256 block starts, and the mode */, log_n, log_blowup, cap_height, n_proofs};
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
+  const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper, W, W + 32, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+static int32_t air5_pass(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const AirGeo3& A, const AirGeo5& I, uint32_t n_proofs,
+                         const uint64_t* cols, const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
+  uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
+  int rc = launch_air_init_tables(log_blowup, chain, A.s_n, A.w_n, I.s_sel, I.w_sel, I.rho, W + 32 + FRI_GAMMA_AT, tab, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_init_quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, d_quot, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_air_sha256_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
+                                          uint64_t* d_helper, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * AIR_INIT_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "315 n_proofs must be at most 2^24");
+  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
+  if (chain && log_rows < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
+  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const int rc = launch_air_init_helper(log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_helper launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha256_init_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = air5_check(c, log_n, log_blowup, n_proofs, chain);
+  if (st) return st;
+  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
+    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
+  AirGeo3 A;
+  AirGeo5 I;
+  if ((st = air5_geo(c, log_n, log_blowup, chain, c->ntt_root, c->ntt_shift, A, I))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if ((st = air5_gamma(c, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, false, s))) return st;
+  if ((st = air5_pass(c, log_n, log_blowup, chain, A, I, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha256_init_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
+                                          const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles)
+    return fail(c, TMX_ERR_BAD_ARG, "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof");
+  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
+  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)AIR_INIT_HELPER_COLS * n_proofs)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper must be the helper: the log_n of oracle k_trace and 315 columns per proof");
+  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
+  if ((st = air5_check(c, log_n, p->log_blowup, n_proofs, chain))) return st;
+  AirGeo3 A;
+  AirGeo5 I;
+  if ((st = air5_geo(c, log_n, p->log_blowup, chain, c->ntt_root, c->ntt_shift, A, I))) return st;
+  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  if ((st = air_scratch(c, p->log_blowup))) return st;
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
+  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
+  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = air5_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, chain, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], true, s)))
+    return st;
+  rc = launch_air_init_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, I.rho, d_proof + L.off_open[k_trace],
+                             d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
+                             p->n_queries, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_check launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
+  if (st) return st;
+  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
+  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
+  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
+  const uint32_t chain = section == TMX_TRACE_SHA256 ? 0u : 1u;  // T.3 hashes are single blocks, T.5 and T.6 hashes pairs of blocks
+  tmx_ctx::SetRec r = c->set;
+  uint32_t kt = r.n_oracles;
+  for (uint32_t k = 0; k < r.n_oracles; k++)
+    if (r.o[k].section == section) kt = k;
+  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
+  // the pair goes behind the last helper/quotient pair that already follows the table (set 3's, then set 4's)
+  uint32_t at = kt + 1;
+  while (at < r.n_oracles && (r.o[at].section == TMX_TRACE_SHA256_HELPER || r.o[at].section == TMX_TRACE_SHA256_SCHED_HELPER)) at += 2;
+  if (at < r.n_oracles && r.o[at].section == TMX_TRACE_SHA256_INIT_HELPER)
+    return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the block-start helper and quotient of that section");
+  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
+  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
+  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
+  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
+  if ((st = air5_check(c, log_m, r.log_blowup, n_proofs, chain))) return st;
+  AirGeo3 A;
+  AirGeo5 I;
+  if ((st = air5_geo(c, log_m, r.log_blowup, chain, r.root, r.shift, A, I))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, r.log_blowup))) return st;
+  // the section's scratch: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
+  const uint32_t n_hcols = n_proofs * AIR_INIT_HELPER_COLS;
+  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
+  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
+               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
+  if (c->set_init_bytes[slot] < want) {
+    if (c->d_set_init[slot]) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_init[slot])); c->d_set_init[slot] = nullptr; c->set_init_bytes[slot] = 0; }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
+      return fail(c, TMX_ERR_CAPACITY, "the block-start helper member needs " + std::to_string(want >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
+    HIPCK(c, hipMalloc(&c->d_set_init[slot], want));
+    c->set_init_bytes[slot] = want;
+  }
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
+  uint8_t* sb = reinterpret_cast<uint8_t*>(c->d_set_init[slot]);
+  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
+  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + pre_b);
+  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b);
+  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
+  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
+  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
+  int rc = launch_air_init_helper(log_sub, n_proofs, chain, base + tabm.cols_off, hpre, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_helper launch: ") + hipGetErrorString((hipError_t)rc));
+  {
+    // the helper extended under the set's domain, one proof's 315 columns at a time (the LDE's own scratch is twice what it extends at once)
+    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+    const bool moved = root != r.root || shift != r.shift;
+    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+    for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += AIR_INIT_HELPER_COLS)
+      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, AIR_INIT_HELPER_COLS, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
+    if (moved) {
+      const int32_t back = tmx_ntt_set_domain(c, root, shift);
+      if (!st) st = back;
+    }
+    if (st) return st;
+  }
+  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  if ((st = air5_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
+  if ((st = air5_pass(c, log_m, r.log_blowup, chain, A, I, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
+  r.o[at] = {TMX_TRACE_SHA256_INIT_HELPER, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
+  r.o[at + 1] = {TMX_TRACE_SHA256_INIT_QUOTIENT, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
   r.n_oracles += 2;
   c->set = r;
   return TMX_OK;

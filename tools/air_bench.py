@@ -22,8 +22,14 @@
            call and the set-3 quotient call, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sched, or MODE=sha,sched)
            k_air_sched_quotient and k_air_sha_quotient show in ONE trace -- and both set-level calls on the HEADER member of one set of
            SHA_SET_P proofs at N = n (skip), alternating, with the prove and both verifiers over the set of five oracles.
-  parent   the set commit + prove WITHOUT any air call, for library builds named in LIBS (comma separated), one subprocess per measurement,
-           alternating under TMX_LIB (differences between boxes exceed most changes: compare inside one call).
+  init     constraint set 5 (tmx_air_sha256_init_*) beside set 3 over the SAME table: SHA_PROOFS proofs x 9 random table columns of 2^LOG_M
+           words, set 5's helper (315 columns per proof, CHAIN=1 by default) and set 3's (300): k_air_init_helper on the pre-LDE shape, then
+           the set-5 quotient call and the set-3 quotient call, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha,init)
+           k_air_init_quotient and k_air_sha_quotient show in ONE trace -- and the three set-level calls on the HEADER member of one set of
+           SHA_SET_P proofs at N = n (skip), alternating, with the prove and the three verifiers over the set of seven oracles.
+  parent   the set commit + prove WITHOUT any air call, then the set-3 and set-4 set-level calls on HEADER (MODE=set_plain,sets34), for library
+           builds named in LIBS (comma separated), one subprocess per measurement, alternating under TMX_LIB (differences between boxes exceed
+           most changes: compare inside one call).
 Times per call from HIP events around REPS back-to-back calls after one warm call.
    P=64 N=128 python tools/air_bench.py   (BLOWUP=3 CAP=4 ARITY=4 FINAL=5 QUERIES=28 CHUNK=512 REPS=5 ROUNDS=3 by default)"""
 import json
@@ -45,9 +51,9 @@ if "parent" in modes:
     res = {os.path.basename(os.path.dirname(l)) + "/" + os.path.basename(l): [] for l in libs}
     for _ in range(rounds):
         for l, key in zip(libs, res):
-            o = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, MODE="set_plain", TMX_LIB=l), capture_output=True, text=True)
-            line = [x for x in o.stdout.splitlines() if x.startswith("{")]
-            res[key].append(json.loads(line[-1]) if line else {"failed": o.stderr[-300:]})
+            o = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, MODE="sets34,set_plain", TMX_LIB=l), capture_output=True, text=True)
+            line = [json.loads(x) for x in o.stdout.splitlines() if x.startswith("{")]
+            res[key].append(line if line else {"failed": o.stderr[-300:]})
     print(json.dumps({"mode": "parent", "proofs": P, "n": n, "runs": res}), flush=True)
     modes = [m for m in modes if m != "parent"]
     if not modes:
@@ -272,6 +278,97 @@ if "sched" in modes:
         res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
         del proof
     res["ratio_sched_over_sha_set_call"] = round(min(res["air_sha256_sched_header_ms"]) / min(res["air_sha256_header_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del tr
+    torch.cuda.empty_cache()
+
+if "init" in modes or "sets34" in modes:
+    from tendermintx_amd.synth import bench_workload
+    SHA256, HEADER = 4, 32
+    only34 = "init" not in modes  # (the calls an older library has too)
+    if not only34:
+        log_m, cp, chain = int(os.environ.get("LOG_M", "16")), int(os.environ.get("SHA_PROOFS", "64")), int(os.environ.get("CHAIN", "1"))
+        log_rows, n_cols, n_h3, n_h5 = log_m - log_blowup, 9 * cp, 300 * cp, 315 * cp
+        ctx = Context(4, b"celestia", device=0)
+        table = torch.randint(0, 2**62, (n_cols << log_rows,), dtype=torch.int64, device=dev)
+        pre = torch.empty(n_h5 << log_rows, dtype=torch.int64, device=dev)
+        cols = torch.randint(0, 2**62, (n_cols << log_m,), dtype=torch.int64, device=dev)
+        h3 = torch.randint(0, 2**62, (n_h3 << log_m,), dtype=torch.int64, device=dev)
+        h5 = torch.randint(0, 2**62, (n_h5 << log_m,), dtype=torch.int64, device=dev)
+        caps = []
+        for c_, k_ in ((cols, n_cols), (h3, n_h3), (h5, n_h5)):
+            lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+            ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+            caps.append(lv[-(4 << cap_h):])
+        quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+        res = {"mode": "init", "proofs": cp, "log_m": log_m, "chain": chain, "table_columns": n_cols, "init_helper_columns": n_h5,
+               "sha_helper_columns": n_h3, "reps": reps, "init_helper_kernel_ms": [], "init_quotient_call_ms": [], "sha_quotient_call_ms": []}
+        for _ in range(rounds):
+            res["init_helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha256_init_helper_device(log_rows, cp, chain, table.data_ptr(), pre.data_ptr(), 0),
+                                                         reps)))
+            res["init_quotient_call_ms"].append(r4(timed(lambda: ctx.air_sha256_init_quotient_device(
+                log_m, log_blowup, cap_h, cp, chain, cols.data_ptr(), h5.data_ptr(), caps[0].data_ptr(), caps[2].data_ptr(), quot.data_ptr(), 0), reps)))
+            res["sha_quotient_call_ms"].append(r4(timed(lambda: ctx.air_sha256_quotient_device(
+                log_m, log_blowup, cap_h, cp, cols.data_ptr(), h3.data_ptr(), caps[0].data_ptr(), caps[1].data_ptr(), quot.data_ptr(), 0), reps)))
+        best = min(res["init_quotient_call_ms"])
+        res["init_gb_per_s"] = round(((n_cols + n_h5) << log_m) * 8 / best / 1e6, 1)
+        res["helper_store_gb_per_s"] = round((n_h5 << log_rows) * 8 / min(res["init_helper_kernel_ms"]) / 1e6, 1)
+        res["ns_per_point_proof"] = round(best * 1e6 / (cp << log_m), 2)
+        res["ratio_init_over_sha_call"] = round(best / min(res["sha_quotient_call_ms"]), 3)
+        print(json.dumps(res), flush=True)
+        ctx.close()
+        del table, pre, cols, h3, h5, caps, quot
+        torch.cuda.empty_cache()
+    # the set-level calls on HEADER
+    sp = int(os.environ.get("SHA_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    cw = 4 << cap_h
+    scaps = torch.zeros(2 * cw, dtype=torch.int64, device=dev)
+    c3, c4, c5 = (torch.zeros(2 * cw, dtype=torch.int64, device=dev) for _ in range(3))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit5 = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA256 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    air3 = lambda: ctx.trace_commit_set_air_sha256_device(HEADER, c3[:cw].data_ptr(), c3[cw:].data_ptr(), 0)
+    air4 = lambda: ctx.trace_commit_set_air_sha256_sched_device(HEADER, c4[:cw].data_ptr(), c4[cw:].data_ptr(), 0)
+    res = {"mode": "sets34" if only34 else "init_set", "proofs": sp, "n": n, "reps": reps, "air_sha256_header_ms": [], "air_sha256_sched_header_ms": []}
+    if not only34:
+        air5 = lambda: ctx.trace_commit_set_air_sha256_init_device(HEADER, c5[:cw].data_ptr(), c5[cw:].data_ptr(), 0)
+        res.update(air_sha256_init_header_ms=[], prove_with_all_ms=[])
+    for _ in range(rounds):
+        res["air_sha256_header_ms"].append(r4(timed(air3, reps, before=commit5)))
+        res["air_sha256_sched_header_ms"].append(r4(timed(air4, reps, before=commit5)))
+        if only34:
+            continue
+        res["air_sha256_init_header_ms"].append(r4(timed(air5, reps, before=commit5)))
+        air3()
+        air4()  # (the set now holds table, H3, Q3, H4, Q4, H5, Q5)
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_all_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(HEADER)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], c3, c4, c5, scaps[(kt + 1) * cw:]])
+        res["verify_init_ms"] = r4(timed(lambda: ctx.air_sha256_init_verify_device(bp, kt, kt + 5, 1, all_caps.data_ptr(), proof.data_ptr(),
+                                                                                  ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        ctx.air_sha256_sched_verify_device(bp, kt, kt + 3, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+        res["all_ok_set4"] = bool((ok.cpu().numpy() == 1).all())
+        ctx.air_sha256_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+        res["all_ok_set3"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
+    if not only34:
+        res["ratio_init_over_sha_set_call"] = round(min(res["air_sha256_init_header_ms"]) / min(res["air_sha256_header_ms"]), 3)
     print(json.dumps(res), flush=True)
     ctx.close()
     del tr
