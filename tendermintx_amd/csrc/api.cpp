@@ -433,16 +433,11 @@ struct tmx_ctx {
   bool air_valid = false;
   void* d_set_air = nullptr;
   size_t set_air_bytes = 0;
-  // constraint set 3 (tmx_trace_commit_set_air_sha256_device): per section (SHA256, TREE, HEADER) one scratch that holds the helper member --
-  // pre-LDE columns | extended columns | tree levels -- and the quotient member -- extended columns | tree levels (Oracle.buf names it)
-  void* d_set_sha[3] = {};
-  size_t set_sha_bytes[3] = {};
-  // constraint set 4 (tmx_trace_commit_set_air_sha256_sched_device): the same layout per section for the schedule's helper and quotient
-  void* d_set_sched[3] = {};
-  size_t set_sched_bytes[3] = {};
-  // constraint set 5 (tmx_trace_commit_set_air_sha256_init_device): the same layout per section for the block starts' helper and quotient
-  void* d_set_init[3] = {};
-  size_t set_init_bytes[3] = {};
+  // constraint sets 3, 4 and 5 (tmx_trace_commit_set_air_sha256_device, _sched_device, _init_device), [set (ShaSet.scratch)][section (SHA256,
+  // TREE, HEADER)]: one scratch that holds the set's helper member of that section -- pre-LDE columns | extended columns | tree levels --
+  // and its quotient member -- extended columns | tree levels (Oracle.buf names it)
+  void* d_set_sha[3][3] = {};
+  size_t set_sha_bytes[3][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
@@ -1439,12 +1434,9 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_deepv) (void)hipFree(c->d_deepv);
   if (c->d_set) (void)hipFree(c->d_set);
   if (c->d_set_air) (void)hipFree(c->d_set_air);
-  for (void* b : c->d_set_sha)
-    if (b) (void)hipFree(b);
-  for (void* b : c->d_set_sched)
-    if (b) (void)hipFree(b);
-  for (void* b : c->d_set_init)
-    if (b) (void)hipFree(b);
+  for (auto& of_set : c->d_set_sha)
+    for (void* b : of_set)
+      if (b) (void)hipFree(b);
   if (c->d_air) (void)hipFree(c->d_air);
   if (c->d_air2) (void)hipFree(c->d_air2);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
@@ -4643,26 +4635,105 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 
 }  // extern "C"
 
-// ---- constraint set 3: the round constraints of the SHA-256 tables (include/tmx.h "the round constraints of the SHA-256 tables") -----------
-// Built beside sets 1 and 2: their checks, scratch layout, kernels and calls are what they were.  The set-3 tables of a quotient launch sit
-// in the table part of d_air (air.h AIR3_TAB_*), the challenge words where set 1 keeps its own.
-struct AirGeo3 { uint64_t s_n, w_n, s_n64, w_n64, om64_inv; };
+// ---- constraint sets 3, 4 and 5 on the SHA-256 tables: the round constraints, the message schedule and the block starts (include/tmx.h
+// "the round constraints of the SHA-256 tables", "the message schedule ...", "the block starts ...") ----------------------------------------
+// One host path drives all three: the same argument checks, the same geometry, the gamma kernel (the set id, and set 5's mode, in obs[0]),
+// the same tables-then-quotient pass and the same scratch layout.  The tables of a quotient launch sit in the table part of d_air (air.h
+// AIR3_TAB_*, AIR4_TAB_*, AIR5_TAB_*), the challenge words where set 1 keeps its own.  What differs between the sets is a ShaSet: the id,
+// the helper's column count, whether the set has a chain mode, the two section ids, the row of tmx_ctx::d_set_sha, the words its messages
+// differ in, and its four launches under set 5's signatures (sets 3 and 4 have no mode: their adapters drop `chain`).
+struct ShaSet {
+  uint32_t id, helper_cols;
+  bool has_chain;
+  uint32_t helper_section, quotient_section;
+  int scratch;
+  const char *stem, *word, *already;           // k_air_<stem>_*, "the <word> member", the refusal of a second set-level call
+  const char *at_helper, *at_quot, *bad_index;  // how the verifier's messages name the helper's and the quotient's oracle index
+  int (*helper)(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream);
+  int (*tables)(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho, const void* d_gamma,
+                void* d_tab, void* stream);
+  int (*quotient)(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
+                  const void* d_tab, void* d_quot, void* stream);
+  int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho, const void* d_open_t,
+               const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
+};
 
-static int32_t air3_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
+static int sha3_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
+  return launch_air_sha_helper(log_rows, n_proofs, d_table, d_helper, stream);
+}
+static int sha3_tables(uint32_t log_blowup, uint32_t, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv,
+                       const void* d_gamma, void* d_tab, void* stream) {
+  return launch_air_sha_tables(log_blowup, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
+}
+static int sha3_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t, const void* d_cols, const void* d_helper_cols,
+                         const void* d_tab, void* d_quot, void* stream) {
+  return launch_air_sha_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, d_quot, stream);
+}
+static int sha3_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t, uint64_t om64_inv, const void* d_open_t,
+                      const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                      void* stream) {
+  return launch_air_sha_check(n_proofs, log_r_t, log_r_h, log_sub, om64_inv, d_open_t, d_open_h, d_open_q, d_zeta, d_gamma, n_queries, d_ok, stream);
+}
+static int sha4_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
+  return launch_air_sched_helper(log_rows, n_proofs, d_table, d_helper, stream);
+}
+static int sha4_tables(uint32_t log_blowup, uint32_t, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv,
+                       const void* d_gamma, void* d_tab, void* stream) {
+  return launch_air_sched_tables(log_blowup, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
+}
+static int sha4_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t, const void* d_cols, const void* d_helper_cols,
+                         const void* d_tab, void* d_quot, void* stream) {
+  return launch_air_sched_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, d_quot, stream);
+}
+static int sha4_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t, uint64_t om64_inv, const void* d_open_t,
+                      const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
+                      void* stream) {
+  return launch_air_sched_check(n_proofs, log_r_t, log_r_h, log_sub, om64_inv, d_open_t, d_open_h, d_open_q, d_zeta, d_gamma, n_queries, d_ok, stream);
+}
+
+// by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
+static const ShaSet SHA_SETS[3] = {
+    {3, AIR_SHA_HELPER_COLS, false, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, "sha", "helper",
+     "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
+     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check},
+    {4, AIR_SCHED_HELPER_COLS, false, TMX_TRACE_SHA256_SCHED_HELPER, TMX_TRACE_SHA256_SCHED_QUOTIENT, 1, "sched", "schedule helper",
+     "the commit set already holds the schedule helper and quotient of that section", "k_helper", "k_helper + 1",
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check},
+    {5, AIR_INIT_HELPER_COLS, true, TMX_TRACE_SHA256_INIT_HELPER, TMX_TRACE_SHA256_INIT_QUOTIENT, 2, "init", "block-start helper",
+     "the commit set already holds the block-start helper and quotient of that section", "k_helper", "k_helper + 1",
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", launch_air_init_helper, launch_air_init_tables,
+     launch_air_init_quotient, launch_air_init_check},
+};
+
+static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
+  return fail(c, TMX_ERR_HIP, std::string("k_air_") + d.stem + "_" + kernel + " launch: " + hipGetErrorString((hipError_t)rc));
+}
+
+static std::string sha_too_many_cols(const ShaSet& d) { return std::to_string(d.helper_cols) + " n_proofs must be at most 2^24"; }
+
+// chain is 0 for a set without a mode
+static int32_t sha_check(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain) {
   if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
   if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
   if (log_n - log_blowup < 6) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows");
   if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_SHA_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "300 n_proofs must be at most 2^24");
+  if ((uint64_t)n_proofs * d.helper_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, sha_too_many_cols(d));
+  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
+  if (chain && log_n - log_blowup < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
   return TMX_OK;
 }
 
-static int32_t air3_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, AirGeo3& A) {
+// s_n = s^N, w_n = w^N; the selector's period is 64 << chain rows: s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0,
+// s^(N/128), w^(N/128), omega_128^-1 under chain = 1
+struct ShaGeo { uint64_t s_n, w_n, s_sel, w_sel, rho; };
+
+static int32_t sha_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, ShaGeo& A) {
   const uint64_t P = 0xffffffff00000001ull;
   const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
+  const uint32_t log_per = 6 + chain;
   A.s_n = gl_pow_host(s, n); A.w_n = gl_pow_host(w, n);
-  A.s_n64 = gl_pow_host(s, n >> 6); A.w_n64 = gl_pow_host(w, n >> 6);
-  A.om64_inv = gl_pow_host(gl_pow_host(w, 1ull << (log_n - 6)), P - 2);  // omega_64 = omega_N^(N/64) = w^(M/64)
+  A.s_sel = gl_pow_host(s, n >> log_per); A.w_sel = gl_pow_host(w, n >> log_per);
+  A.rho = gl_pow_host(gl_pow_host(w, 1ull << (log_n - log_per)), P - 2);  // omega_64 = omega_N^(N/64) = w^(M/64), omega_128 = w^(M/128)
   uint64_t x = A.s_n;
   for (uint32_t k = 0; k < (1u << log_blowup); k++, x = (uint64_t)(((unsigned __int128)x * A.w_n) % P))
     if (x == 1) return fail(c, TMX_ERR_BAD_ARG, "x^N - 1 vanishes on the evaluation domain: the coset shift lies in the trace domain");
@@ -4670,9 +4741,9 @@ static int32_t air3_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint64_
 }
 
 // gamma from the table cap and the helper cap, into the prover's (verifier = false) or the verifier's challenge words of d_air
-static int32_t air3_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cap,
-                          const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
-  const uint32_t obs[5] = {3 /* the constraint-set id: the SHA-256 round constraints */, log_n, log_blowup, cap_height, n_proofs};
+static int32_t sha_gamma(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
+                         const uint64_t* d_cap, const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
+  const uint32_t obs[5] = {d.id | chain << 8 /* the constraint-set id, and set 5's mode */, log_n, log_blowup, cap_height, n_proofs};
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
   const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper, W, W + 32, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
@@ -4680,562 +4751,233 @@ static int32_t air3_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint3
 }
 
 // the tables from the prover's gamma, then the pass
-static int32_t air3_pass(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo3& A, uint32_t n_proofs, const uint64_t* cols,
-                         const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
+static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const ShaGeo& A, uint32_t n_proofs,
+                        const uint64_t* cols, const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
   uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = launch_air_sha_tables(log_blowup, A.s_n, A.w_n, A.s_n64, A.w_n64, A.om64_inv, W + 32 + FRI_GAMMA_AT, tab, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_sha_quotient(log_n, log_blowup, n_proofs, cols, hcols, tab, d_quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  int rc = d.tables(log_blowup, chain, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s);
+  if (rc) return sha_launch_failed(c, d, "tables", rc);
+  rc = d.quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, d_quot, s);
+  if (rc) return sha_launch_failed(c, d, "quotient", rc);
+  return TMX_OK;
+}
+
+static int32_t sha_helper_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
+                               uint64_t* d_helper, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * d.helper_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, sha_too_many_cols(d));
+  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
+  if (chain && log_rows < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
+  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const int rc = d.helper(log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "helper", rc);
+  return TMX_OK;
+}
+
+static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                 uint32_t chain, const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                 const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = sha_check(c, d, log_n, log_blowup, n_proofs, chain);
+  if (st) return st;
+  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
+    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
+  ShaGeo A;
+  if ((st = sha_geo(c, log_n, log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, false, s))) return st;
+  if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  return TMX_OK;
+}
+
+static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
+                               const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, d.bad_index);
+  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
+  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)d.helper_cols * n_proofs)
+    return fail(c, TMX_ERR_BAD_ARG, std::string("oracle ") + d.at_helper + " must be the helper: the log_n of oracle k_trace and " +
+                                        std::to_string(d.helper_cols) + " columns per proof");
+  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
+    return fail(c, TMX_ERR_BAD_ARG, std::string("oracle ") + d.at_quot + " must be the quotient: the log_n of oracle k_trace and 2 columns");
+  if ((st = sha_check(c, d, log_n, p->log_blowup, n_proofs, chain))) return st;
+  ShaGeo A;
+  if ((st = sha_geo(c, log_n, p->log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
+  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  if ((st = air_scratch(c, p->log_blowup))) return st;
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
+  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
+  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = sha_gamma(c, d, log_n, p->log_blowup, p->cap_height, n_proofs, chain, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], true, s)))
+    return st;
+  rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, d_proof + L.off_open[k_trace],
+               d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+  if (rc) return sha_launch_failed(c, d, "check", rc);
+  return TMX_OK;
+}
+
+static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
+  if (st) return st;
+  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
+  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
+  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
+  const uint32_t chain = d.has_chain && section != TMX_TRACE_SHA256;  // T.3 hashes are single blocks, T.5 and T.6 hashes pairs of blocks
+  tmx_ctx::SetRec r = c->set;
+  uint32_t kt = r.n_oracles;
+  for (uint32_t k = 0; k < r.n_oracles; k++)
+    if (r.o[k].section == section) kt = k;
+  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
+  // the pair goes behind the pairs of every lower-numbered set that follow the table
+  uint32_t at = kt + 1;
+  for (const ShaSet* lower = SHA_SETS; lower != &d; lower++)
+    if (at < r.n_oracles && r.o[at].section == lower->helper_section) at += 2;
+  if (at < r.n_oracles && r.o[at].section == d.helper_section) return fail(c, TMX_ERR_BAD_ARG, d.already);
+  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
+  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
+  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
+  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
+  if ((st = sha_check(c, d, log_m, r.log_blowup, n_proofs, chain))) return st;
+  ShaGeo A;
+  if ((st = sha_geo(c, log_m, r.log_blowup, chain, r.root, r.shift, A))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, r.log_blowup))) return st;
+  // the scratch of this set and section: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
+  const uint32_t n_hcols = n_proofs * d.helper_cols;
+  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
+  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
+               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
+  void*& d_scratch = c->d_set_sha[d.scratch][slot];
+  size_t& scratch_bytes = c->set_sha_bytes[d.scratch][slot];
+  if (scratch_bytes < want) {
+    if (d_scratch) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(d_scratch)); d_scratch = nullptr; scratch_bytes = 0; }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
+      return fail(c, TMX_ERR_CAPACITY, "the " + std::string(d.word) + " member needs " + std::to_string(want >> 20) + " MiB of scratch, " +
+                                           std::to_string(free_b >> 20) + " MiB free");
+    HIPCK(c, hipMalloc(&d_scratch, want));
+    scratch_bytes = want;
+  }
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
+  uint8_t* sb = reinterpret_cast<uint8_t*>(d_scratch);
+  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
+  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + pre_b);
+  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b);
+  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
+  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
+  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
+  const int rc = d.helper(log_sub, n_proofs, chain, base + tabm.cols_off, hpre, s);
+  if (rc) return sha_launch_failed(c, d, "helper", rc);
+  {
+    // the helper extended under the set's domain, one proof's columns at a time (the LDE's own scratch is twice what it extends at once)
+    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+    const bool moved = root != r.root || shift != r.shift;
+    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+    for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += d.helper_cols)
+      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, d.helper_cols, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
+    if (moved) {
+      const int32_t back = tmx_ntt_set_domain(c, root, shift);
+      if (!st) st = back;
+    }
+    if (st) return st;
+  }
+  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  if ((st = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
+  if ((st = sha_pass(c, d, log_m, r.log_blowup, chain, A, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
+  r.o[at] = {d.helper_section, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
+  r.o[at + 1] = {d.quotient_section, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
+  r.n_oracles += 2;
+  c->set = r;
   return TMX_OK;
 }
 
 extern "C" {
 
 int32_t tmx_air_sha256_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_SHA_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "300 n_proofs must be at most 2^24");
-  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = launch_air_sha_helper(log_rows, n_proofs, d_table, d_helper, hip_stream);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_helper_call(c, SHA_SETS[0], log_rows, n_proofs, 0, d_table, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
                                        const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
                                        void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = air3_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
-    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = air3_gamma(c, log_n, log_blowup, cap_height, n_proofs, d_cap, d_cap_helper, false, s))) return st;
-  if ((st = air3_pass(c, log_n, log_blowup, A, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
+  return sha_quotient_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
 }
 
+// (the helper sits directly behind the table; a k_trace + 1 that wraps to 0 fails the index rule as it should)
 int32_t tmx_air_sha256_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
                                      uint32_t* d_ok, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = batch_check(c, p);
-  if (st) return st;
-  if ((uint64_t)k_trace + 2 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof");
-  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
-  if (p->log_n[k_trace + 1] != log_n || (uint64_t)p->n_cols[k_trace + 1] != (uint64_t)AIR_SHA_HELPER_COLS * n_proofs)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 1 must be the helper: the log_n of oracle k_trace and 300 columns per proof");
-  if (p->log_n[k_trace + 2] != log_n || p->n_cols[k_trace + 2] != 2)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 2 must be the quotient: the log_n of oracle k_trace and 2 columns");
-  if ((st = air3_check(c, log_n, p->log_blowup, n_proofs))) return st;
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  if ((st = air_scratch(c, p->log_blowup))) return st;
-  tmx_batch_layout L;
-  batch_layout(*p, L);
-  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
-  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
-  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = air3_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_trace + 1], true, s)))
-    return st;
-  rc = launch_air_sha_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_trace + 1], log_n - p->log_blowup, A.om64_inv, d_proof + L.off_open[k_trace],
-                            d_proof + L.off_open[k_trace + 1], d_proof + L.off_open[k_trace + 2], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
-                            p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_check launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_verify_call(c, SHA_SETS[0], p, k_trace, k_trace + 1, 0, d_caps, d_proof, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
-  if (st) return st;
-  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
-  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
-  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
-  tmx_ctx::SetRec r = c->set;
-  uint32_t kt = r.n_oracles;
-  for (uint32_t k = 0; k < r.n_oracles; k++)
-    if (r.o[k].section == section) kt = k;
-  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
-  if (kt + 1 < r.n_oracles && r.o[kt + 1].section == TMX_TRACE_SHA256_HELPER)
-    return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the helper and the quotient of that section");
-  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
-  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
-  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
-  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = air3_check(c, log_m, r.log_blowup, n_proofs))) return st;
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, r.log_blowup))) return st;
-  // the section's scratch: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
-  const uint32_t n_hcols = n_proofs * AIR_SHA_HELPER_COLS;
-  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
-               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
-  if (c->set_sha_bytes[slot] < want) {
-    if (c->d_set_sha[slot]) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_sha[slot])); c->d_set_sha[slot] = nullptr; c->set_sha_bytes[slot] = 0; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
-      return fail(c, TMX_ERR_CAPACITY, "the helper member needs " + std::to_string(want >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
-    HIPCK(c, hipMalloc(&c->d_set_sha[slot], want));
-    c->set_sha_bytes[slot] = want;
-  }
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
-  uint8_t* sb = reinterpret_cast<uint8_t*>(c->d_set_sha[slot]);
-  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
-  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + pre_b);
-  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b);
-  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
-  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
-  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
-  int rc = launch_air_sha_helper(log_sub, n_proofs, base + tabm.cols_off, hpre, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  {
-    // the helper extended under the set's domain, one proof's 300 columns at a time (the LDE's own scratch is twice what it extends at once)
-    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
-    const bool moved = root != r.root || shift != r.shift;
-    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
-    for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += AIR_SHA_HELPER_COLS)
-      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, AIR_SHA_HELPER_COLS, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
-    if (moved) {
-      const int32_t back = tmx_ntt_set_domain(c, root, shift);
-      if (!st) st = back;
-    }
-    if (st) return st;
-  }
-  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  if ((st = air3_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
-  if ((st = air3_pass(c, log_m, r.log_blowup, A, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  for (uint32_t k = r.n_oracles + 1; k > kt + 2; k--) r.o[k] = r.o[k - 2];
-  r.o[kt + 1] = {TMX_TRACE_SHA256_HELPER, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
-  r.o[kt + 2] = {TMX_TRACE_SHA256_QUOTIENT, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
-  r.n_oracles += 2;
-  c->set = r;
-  return TMX_OK;
+  return sha_set_call(c, SHA_SETS[0], section, d_cap_h, d_cap_q, hip_stream);
 }
-
-}  // extern "C"
-
-// ---- constraint set 4: the message schedule of the SHA-256 tables (include/tmx.h "the message schedule of the SHA-256 tables") -------------
-// Built beside set 3: its checks, kernels and calls are what they were.  The geometry (AirGeo3), the gamma kernel (with the set id 4) and
-// the challenge words are set 3's; the set-4 tables of a quotient launch sit in the table part of d_air (air.h AIR4_TAB_*).
-static int32_t air4_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
-  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
-  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
-  if (log_n - log_blowup < 6) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_SCHED_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "115 n_proofs must be at most 2^24");
-  return TMX_OK;
-}
-
-static int32_t air4_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cap,
-                          const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
-  const uint32_t obs[5] = {4 /* the constraint-set id: the SHA-256 message schedule */, log_n, log_blowup, cap_height, n_proofs};
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper, W, W + 32, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-static int32_t air4_pass(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo3& A, uint32_t n_proofs, const uint64_t* cols,
-                         const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
-  uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = launch_air_sched_tables(log_blowup, A.s_n, A.w_n, A.s_n64, A.w_n64, A.om64_inv, W + 32 + FRI_GAMMA_AT, tab, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sched_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_sched_quotient(log_n, log_blowup, n_proofs, cols, hcols, tab, d_quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sched_quotient launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-extern "C" {
 
 int32_t tmx_air_sha256_sched_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
                                            void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_SCHED_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "115 n_proofs must be at most 2^24");
-  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = launch_air_sched_helper(log_rows, n_proofs, d_table, d_helper, hip_stream);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sched_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_helper_call(c, SHA_SETS[1], log_rows, n_proofs, 0, d_table, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                              const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                              const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = air4_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
-    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = air4_gamma(c, log_n, log_blowup, cap_height, n_proofs, d_cap, d_cap_helper, false, s))) return st;
-  if ((st = air4_pass(c, log_n, log_blowup, A, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
+  return sha_quotient_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
                                            const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = batch_check(c, p);
-  if (st) return st;
-  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles)
-    return fail(c, TMX_ERR_BAD_ARG, "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof");
-  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
-  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)AIR_SCHED_HELPER_COLS * n_proofs)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper must be the helper: the log_n of oracle k_trace and 115 columns per proof");
-  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
-  if ((st = air4_check(c, log_n, p->log_blowup, n_proofs))) return st;
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  if ((st = air_scratch(c, p->log_blowup))) return st;
-  tmx_batch_layout L;
-  batch_layout(*p, L);
-  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
-  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
-  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = air4_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], true, s)))
-    return st;
-  rc = launch_air_sched_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, A.om64_inv, d_proof + L.off_open[k_trace],
-                              d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
-                              p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sched_check launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_verify_call(c, SHA_SETS[1], p, k_trace, k_helper, 0, d_caps, d_proof, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
-  if (st) return st;
-  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
-  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
-  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
-  tmx_ctx::SetRec r = c->set;
-  uint32_t kt = r.n_oracles;
-  for (uint32_t k = 0; k < r.n_oracles; k++)
-    if (r.o[k].section == section) kt = k;
-  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
-  // the pair goes behind the table, or behind set 3's helper and quotient when those follow the table
-  uint32_t at = kt + 1;
-  if (at < r.n_oracles && r.o[at].section == TMX_TRACE_SHA256_HELPER) at += 2;
-  if (at < r.n_oracles && r.o[at].section == TMX_TRACE_SHA256_SCHED_HELPER)
-    return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the schedule helper and quotient of that section");
-  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
-  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
-  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
-  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = air4_check(c, log_m, r.log_blowup, n_proofs))) return st;
-  AirGeo3 A;
-  if ((st = air3_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, r.log_blowup))) return st;
-  // the section's scratch: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
-  const uint32_t n_hcols = n_proofs * AIR_SCHED_HELPER_COLS;
-  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
-               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
-  if (c->set_sched_bytes[slot] < want) {
-    if (c->d_set_sched[slot]) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_sched[slot])); c->d_set_sched[slot] = nullptr; c->set_sched_bytes[slot] = 0; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
-      return fail(c, TMX_ERR_CAPACITY, "the schedule helper member needs " + std::to_string(want >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
-    HIPCK(c, hipMalloc(&c->d_set_sched[slot], want));
-    c->set_sched_bytes[slot] = want;
-  }
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
-  uint8_t* sb = reinterpret_cast<uint8_t*>(c->d_set_sched[slot]);
-  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
-  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + pre_b);
-  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b);
-  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
-  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
-  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
-  int rc = launch_air_sched_helper(log_sub, n_proofs, base + tabm.cols_off, hpre, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sched_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  {
-    // the helper extended under the set's domain, one proof's 115 columns at a time (the LDE's own scratch is twice what it extends at once)
-    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
-    const bool moved = root != r.root || shift != r.shift;
-    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
-    for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += AIR_SCHED_HELPER_COLS)
-      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, AIR_SCHED_HELPER_COLS, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
-    if (moved) {
-      const int32_t back = tmx_ntt_set_domain(c, root, shift);
-      if (!st) st = back;
-    }
-    if (st) return st;
-  }
-  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  if ((st = air4_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
-  if ((st = air4_pass(c, log_m, r.log_blowup, A, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
-  r.o[at] = {TMX_TRACE_SHA256_SCHED_HELPER, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
-  r.o[at + 1] = {TMX_TRACE_SHA256_SCHED_QUOTIENT, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
-  r.n_oracles += 2;
-  c->set = r;
-  return TMX_OK;
+  return sha_set_call(c, SHA_SETS[1], section, d_cap_h, d_cap_q, hip_stream);
 }
-
-}  // extern "C"
-
-// ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h "the block starts of the SHA-256 tables") ---------------------
-// Built beside sets 3 and 4: their checks, kernels and calls are what they were.  The geometry (AirGeo3, plus the selector's own root and
-// shift), the gamma kernel (with the set id 5 and the mode in obs[0]) and the challenge words are set 3's; the set-5 tables of a quotient
-// launch sit in the table part of d_air (air.h AIR5_TAB_*).
-struct AirGeo5 { uint64_t s_sel, w_sel, rho; };  // chain = 0: s^(N/64), w^(N/64), omega_64^-1; chain = 1: s^(N/128), w^(N/128), omega_128^-1
-
-static int32_t air5_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain) {
-  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
-  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
-  if (log_n - log_blowup < 6) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_INIT_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "315 n_proofs must be at most 2^24");
-  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
-  if (chain && log_n - log_blowup < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
-  return TMX_OK;
-}
-
-static int32_t air5_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, AirGeo3& A, AirGeo5& I) {
-  const int32_t st = air3_geo(c, log_n, log_blowup, root_2_32, shift, A);
-  if (st) return st;
-  if (!chain) {
-    I.s_sel = A.s_n64; I.w_sel = A.w_n64; I.rho = A.om64_inv;
-    return TMX_OK;
-  }
-  const uint64_t P = 0xffffffff00000001ull;
-  const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
-  I.s_sel = gl_pow_host(s, n >> 7); I.w_sel = gl_pow_host(w, n >> 7);
-  I.rho = gl_pow_host(gl_pow_host(w, 1ull << (log_n - 7)), P - 2);  // omega_128 = omega_N^(N/128) = w^(M/128)
-  return TMX_OK;
-}
-
-static int32_t air5_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
-                          const uint64_t* d_cap, const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
-  const uint32_t obs[5] = {5u | chain << 8 /* the constraint-set id: the SHA-256 block starts, and the mode */, log_n, log_blowup, cap_height, n_proofs};
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper, W, W + 32, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-static int32_t air5_pass(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const AirGeo3& A, const AirGeo5& I, uint32_t n_proofs,
-                         const uint64_t* cols, const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
-  uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = launch_air_init_tables(log_blowup, chain, A.s_n, A.w_n, I.s_sel, I.w_sel, I.rho, W + 32 + FRI_GAMMA_AT, tab, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_init_quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, d_quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_quotient launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-extern "C" {
 
 int32_t tmx_air_sha256_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
                                           uint64_t* d_helper, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_INIT_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "315 n_proofs must be at most 2^24");
-  if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
-  if (chain && log_rows < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
-  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = launch_air_init_helper(log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_helper_call(c, SHA_SETS[2], log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                             const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = air5_check(c, log_n, log_blowup, n_proofs, chain);
-  if (st) return st;
-  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
-    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
-  AirGeo3 A;
-  AirGeo5 I;
-  if ((st = air5_geo(c, log_n, log_blowup, chain, c->ntt_root, c->ntt_shift, A, I))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = air5_gamma(c, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, false, s))) return st;
-  if ((st = air5_pass(c, log_n, log_blowup, chain, A, I, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
+  return sha_quotient_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
                                           const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = batch_check(c, p);
-  if (st) return st;
-  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles)
-    return fail(c, TMX_ERR_BAD_ARG, "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof");
-  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
-  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)AIR_INIT_HELPER_COLS * n_proofs)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper must be the helper: the log_n of oracle k_trace and 315 columns per proof");
-  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
-  if ((st = air5_check(c, log_n, p->log_blowup, n_proofs, chain))) return st;
-  AirGeo3 A;
-  AirGeo5 I;
-  if ((st = air5_geo(c, log_n, p->log_blowup, chain, c->ntt_root, c->ntt_shift, A, I))) return st;
-  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  if ((st = air_scratch(c, p->log_blowup))) return st;
-  tmx_batch_layout L;
-  batch_layout(*p, L);
-  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
-  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
-  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = air5_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, chain, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], true, s)))
-    return st;
-  rc = launch_air_init_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, I.rho, d_proof + L.off_open[k_trace],
-                             d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
-                             p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_check launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_verify_call(c, SHA_SETS[2], p, k_trace, k_helper, chain, d_caps, d_proof, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
-  if (st) return st;
-  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
-  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
-  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
-  const uint32_t chain = section == TMX_TRACE_SHA256 ? 0u : 1u;  // T.3 hashes are single blocks, T.5 and T.6 hashes pairs of blocks
-  tmx_ctx::SetRec r = c->set;
-  uint32_t kt = r.n_oracles;
-  for (uint32_t k = 0; k < r.n_oracles; k++)
-    if (r.o[k].section == section) kt = k;
-  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
-  // the pair goes behind the last helper/quotient pair that already follows the table (set 3's, then set 4's)
-  uint32_t at = kt + 1;
-  while (at < r.n_oracles && (r.o[at].section == TMX_TRACE_SHA256_HELPER || r.o[at].section == TMX_TRACE_SHA256_SCHED_HELPER)) at += 2;
-  if (at < r.n_oracles && r.o[at].section == TMX_TRACE_SHA256_INIT_HELPER)
-    return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the block-start helper and quotient of that section");
-  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
-  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
-  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
-  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = air5_check(c, log_m, r.log_blowup, n_proofs, chain))) return st;
-  AirGeo3 A;
-  AirGeo5 I;
-  if ((st = air5_geo(c, log_m, r.log_blowup, chain, r.root, r.shift, A, I))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, r.log_blowup))) return st;
-  // the section's scratch: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
-  const uint32_t n_hcols = n_proofs * AIR_INIT_HELPER_COLS;
-  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
-               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
-  if (c->set_init_bytes[slot] < want) {
-    if (c->d_set_init[slot]) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_init[slot])); c->d_set_init[slot] = nullptr; c->set_init_bytes[slot] = 0; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
-      return fail(c, TMX_ERR_CAPACITY, "the block-start helper member needs " + std::to_string(want >> 20) + " MiB of scratch, " + std::to_string(free_b >> 20) + " MiB free");
-    HIPCK(c, hipMalloc(&c->d_set_init[slot], want));
-    c->set_init_bytes[slot] = want;
-  }
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
-  uint8_t* sb = reinterpret_cast<uint8_t*>(c->d_set_init[slot]);
-  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
-  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + pre_b);
-  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b);
-  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
-  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
-  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
-  int rc = launch_air_init_helper(log_sub, n_proofs, chain, base + tabm.cols_off, hpre, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_init_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  {
-    // the helper extended under the set's domain, one proof's 315 columns at a time (the LDE's own scratch is twice what it extends at once)
-    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
-    const bool moved = root != r.root || shift != r.shift;
-    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
-    for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += AIR_INIT_HELPER_COLS)
-      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, AIR_INIT_HELPER_COLS, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
-    if (moved) {
-      const int32_t back = tmx_ntt_set_domain(c, root, shift);
-      if (!st) st = back;
-    }
-    if (st) return st;
-  }
-  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  if ((st = air5_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
-  if ((st = air5_pass(c, log_m, r.log_blowup, chain, A, I, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
-  r.o[at] = {TMX_TRACE_SHA256_INIT_HELPER, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
-  r.o[at + 1] = {TMX_TRACE_SHA256_INIT_QUOTIENT, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
-  r.n_oracles += 2;
-  c->set = r;
-  return TMX_OK;
+  return sha_set_call(c, SHA_SETS[2], section, d_cap_h, d_cap_q, hip_stream);
 }
 
 }  // extern "C"
