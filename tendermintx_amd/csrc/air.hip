@@ -88,16 +88,41 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_ladder_quotient(uint32_t lo
   out[M + i] = q.c1;
 }
 
-// The identity at zeta, one workgroup: thread t takes the proofs t, t + 256, ...; per proof the 33 constraints over F_p^2 from the trace's
-// openings at zeta (y0) and zeta omega_N (y1: acc only), weighted with gamma^(33 p + j); the sums meet in LDS.  Thread 0 compares with
-// (u_0 + X u_1) (zeta^N - 1), X (a, b) = (7 b, a); on a mismatch every query's verdict is cleared.  Opening words are taken mod p.
+// The end of every identity check, called by all the threads of the one workgroup: their sums meet in LDS, and thread 0 compares the
+// total with (u_0 + X u_1) rhs, X (a, b) = (7 b, a), u the quotient's openings taken mod p; on a mismatch every query's verdict is cleared.
 constexpr int AIR_CHECK_THREADS = 256;
+__device__ __forceinline__ void air_check_verdict(gl2 sum, const uint64_t* __restrict__ open_q, gl2 rhs, uint32_t n_queries,
+                                                  uint32_t* __restrict__ ok) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint32_t holds;
+  const uint32_t t = threadIdx.x;
+  red[0][t] = sum.c0;
+  red[1][t] = sum.c1;
+  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h) {
+      red[0][t] = gl_add(red[0][t], red[0][t + h]);
+      red[1][t] = gl_add(red[1][t], red[1][t + h]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
+    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
+    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(q, rhs)) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!holds)
+    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+// The identity at zeta, one workgroup: thread t takes the proofs t, t + 256, ...; per proof the 33 constraints over F_p^2 from the trace's
+// openings at zeta (y0) and zeta omega_N (y1: acc only), weighted with gamma^(33 p + j); the sum is compared with (u_0 + X u_1)
+// (zeta^N - 1).  Opening words are taken mod p.
 __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_ladder_check(uint32_t n_proofs, uint32_t log_r, uint32_t log_sub, uint64_t om256_inv,
                                                                         const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_q,
                                                                         const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
                                                                         uint32_t n_queries, uint32_t* __restrict__ ok) {
-  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
-  __shared__ uint32_t holds;
   const uint32_t t = threadIdx.x;
   const uint64_t R = 1ull << log_r;
   const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
@@ -122,27 +147,9 @@ __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_ladder_check(uint32_t
       sum = gl2_add(sum, gl2_mul(gw, gl2_mul(S, gl2_sub(y1(c + L_ACC + l), y0(c + L_NXT + l)))));
     }
   }
-  red[0][t] = sum.c0;
-  red[1][t] = sum.c1;
-  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
-    __syncthreads();
-    if (t < h) {
-      red[0][t] = gl_add(red[0][t], red[0][t + h]);
-      red[1][t] = gl_add(red[1][t], red[1][t + h]);
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    gl2 zn = zp;  // zeta^N = (zeta^(N/256))^256
-    for (uint32_t k = 0; k < 8; k++) zn = gl2_mul(zn, zn);
-    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
-    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
-    const gl2 rhs = gl2_mul(q, {gl_sub(zn.c0, 1), zn.c1});
-    holds = gl2_eq({red[0][0], red[1][0]}, rhs) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!holds)
-    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+  gl2 zn = zp;  // zeta^N = (zeta^(N/256))^256
+  for (uint32_t k = 0; k < 8; k++) zn = gl2_mul(zn, zn);
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
 }
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -415,8 +422,6 @@ __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_ladder_boundary_check
                                                                                  const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
                                                                                  const uint64_t* __restrict__ vk, uint32_t n_queries,
                                                                                  uint32_t* __restrict__ ok) {
-  __shared__ uint64_t red[6][AIR_CHECK_THREADS];
-  __shared__ uint32_t holds;
   const uint32_t t = threadIdx.x, K = 1u << (log_sub - 8);
   const uint64_t R = 1ull << log_r;
   const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
@@ -475,31 +480,12 @@ __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_ladder_boundary_check
       }
     }
   }
-  red[0][t] = sum.c0;
-  red[1][t] = sum.c1;
-  red[2][t] = bsum.c0;
-  red[3][t] = bsum.c1;
-  red[4][t] = psum.c0;
-  red[5][t] = psum.c1;
-  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
-    __syncthreads();
-    if (t < h)
-      for (uint32_t r = 0; r < 6; r++) red[r][t] = gl_add(red[r][t], red[r][t + h]);
-  }
-  __syncthreads();
-  if (t == 0) {
-    gl2 zn = zp;  // zeta^N = (zeta^(N/256))^256
-    for (uint32_t k = 0; k < 8; k++) zn = gl2_mul(zn, zn);
-    const gl2 Z = {gl_sub(zn.c0, 1), zn.c1};
-    const gl2 pub = gl2_mul(gl2_scale(S, bary_inv), {red[4][0], red[5][0]});
-    const gl2 lhs = gl2_add(gl2_mul(S, {red[0][0], red[1][0]}), gl2_mul(Z, gl2_sub({red[2][0], red[3][0]}, pub)));
-    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
-    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
-    holds = gl2_eq(lhs, gl2_mul(q, gl2_mul(Z, S))) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!holds)
-    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+  gl2 zn = zp;  // zeta^N = (zeta^(N/256))^256
+  for (uint32_t k = 0; k < 8; k++) zn = gl2_mul(zn, zn);
+  const gl2 Z = {gl_sub(zn.c0, 1), zn.c1};
+  // (the left side is linear in the three sums and S, Z are uniform: every thread folds its own share, and one sum meets in LDS)
+  const gl2 pub = gl2_mul(gl2_scale(S, bary_inv), psum);
+  air_check_verdict(gl2_add(gl2_mul(S, sum), gl2_mul(Z, gl2_sub(bsum, pub))), open_q, gl2_mul(Z, S), n_queries, ok);
 }
 
 int launch_air_boundary_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n256, uint64_t w_n256,
@@ -561,8 +547,202 @@ int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t
   return (int)hipGetLastError();
 }
 
+// ---- constraint sets 3, 4 and 5: the SHA-256 tables ------------------------------------------------------------------------------------------
+// Siblings of the ladder sets: nothing above changes.  Every constraint of these sets is written once, in an evaluator templated on a field
+// policy and on a view of "one proof at one point".  The hot pass instantiates it over F_p at a coset point (CosetView), the identity check
+// over F_p^2 at zeta (ZetaView): prover and verifier agree term for term and index for index because they are the same source.  How a
+// kernel combines a proof's gamma sums stays in the kernel: there the hot passes and the checks differ on purpose.
+
+// The two field policies: F_p on canonical words, and F_p^2.  scale and add_const take a base-field constant.
+struct FieldP {
+  using T = uint64_t;
+  static __device__ __forceinline__ T zero() { return 0; }
+  static __device__ __forceinline__ T add(T a, T b) { return gl_add(a, b); }
+  static __device__ __forceinline__ T sub(T a, T b) { return gl_sub(a, b); }
+  static __device__ __forceinline__ T mul(T a, T b) { return gl_mul(a, b); }
+  static __device__ __forceinline__ T scale(T a, uint64_t s) { return gl_mul(a, s); }
+  static __device__ __forceinline__ T add_const(T a, uint64_t k) { return gl_add(a, k); }
+};
+struct FieldP2 {
+  using T = gl2;
+  static __device__ __forceinline__ T zero() { return {0, 0}; }
+  static __device__ __forceinline__ T add(T a, T b) { return gl2_add(a, b); }
+  static __device__ __forceinline__ T sub(T a, T b) { return gl2_sub(a, b); }
+  static __device__ __forceinline__ T mul(T a, T b) { return gl2_mul(a, b); }
+  static __device__ __forceinline__ T scale(T a, uint64_t s) { return gl2_scale(a, s); }
+  static __device__ __forceinline__ T add_const(T a, uint64_t k) { return {gl_add(a.c0, k), a.c1}; }
+};
+// A policy with the small forms the three sets share
+template <class F>
+struct Forms : F {
+  using T = typename F::T;
+  static __device__ __forceinline__ T boolean(T x) { return F::sub(F::mul(x, x), x); }
+  static __device__ __forceinline__ T exor(T x, T y) {  // x + y - 2 x y
+    const T xy = F::mul(x, y);
+    return F::sub(F::add(x, y), F::add(xy, xy));
+  }
+  static __device__ __forceinline__ T dbl_add(T s, T x) { return F::add(F::add(s, s), x); }
+  static __device__ __forceinline__ T c32(T x0, T x1, T x2) {  // the carry word 2^32 (x0 + 2 x1 + 4 x2)
+    return F::scale(F::add(x0, F::add(F::add(x1, x1), F::scale(x2, 4))), 1ull << 32);
+  }
+};
+
+// One proof at one point of the coset, for a hot pass: c and h are the proof's table and helper columns, i the lane's point and nx the
+// point of the next row, 2^log_blowup words further along every column.  Every word is read from HBM once (`once`, non-temporal); `again`
+// is for the columns the evaluator reads more than once per lane, through the cache, `next` for the words at nx.  Words are taken mod p.
+// The gamma sums are lazy pairs against the gamma table gp (wave-uniform entries: scalar loads): a the plain sum; b the selected sum of
+// set 3, or the start sum of set 5; c the chain sum of set 5.  The evaluator's loops are unrolled as the hot passes want them.
+struct CosetView {
+  static constexpr uint32_t BITS = 2, SHORT = 16;  // (16: every short loop in full)
+  const uint64_t* __restrict__ c;
+  const uint64_t* __restrict__ h;
+  const uint64_t* __restrict__ gp;
+  uint32_t log_m;
+  uint64_t i, nx;
+  uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0, c0 = 0, c1 = 0;
+  __device__ __forceinline__ uint64_t once(uint32_t col) const { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); }
+  __device__ __forceinline__ uint64_t again(uint32_t col) const { return gl_canon(h[((uint64_t)col << log_m) + i]); }
+  __device__ __forceinline__ uint64_t next(uint32_t col) const { return gl_canon(h[((uint64_t)col << log_m) + nx]); }
+  __device__ __forceinline__ uint64_t tbl(uint32_t col) const { return gl_canon(c[((uint64_t)col << log_m) + i]); }
+  __device__ __forceinline__ uint64_t tbl_next(uint32_t col) const { return gl_canon(c[((uint64_t)col << log_m) + nx]); }
+  __device__ __forceinline__ void weigh(uint64_t& s0, uint64_t& s1, uint32_t j, uint64_t v) const {
+    s0 = gl_add_lazy(s0, gl_mul(gp[2 * j], v));
+    s1 = gl_add_lazy(s1, gl_mul(gp[2 * j + 1], v));
+  }
+  __device__ __forceinline__ void plain(uint32_t j, uint64_t v) { weigh(a0, a1, j, v); }
+  __device__ __forceinline__ void selected(uint32_t j, uint64_t v) { weigh(b0, b1, j, v); }
+  __device__ __forceinline__ void started(uint32_t j, uint64_t v) { weigh(b0, b1, j, v); }
+  __device__ __forceinline__ void chained(uint32_t j, uint64_t v) { weigh(c0, c1, j, v); }
+};
+
+// One proof at zeta, for an identity check: t and h are the proof's columns inside the table's and the helper's openings blocks, whose
+// planes lie R words apart: the value at zeta in planes 0 and 1, at zeta omega_N (`next`) in planes 2 and 3.  The gamma powers are in
+// LDS; the sums a, b, c are CosetView's, over F_p^2.  No unrolling: a check kernel is one workgroup and must not grow.
+struct ZetaView {
+  static constexpr uint32_t BITS = 1, SHORT = 1;
+  const uint64_t* __restrict__ t;
+  const uint64_t* __restrict__ h;
+  uint64_t RT, RH;
+  const uint64_t* gpw;
+  gl2 a = {0, 0}, b = {0, 0}, c = {0, 0};
+  __device__ __forceinline__ gl2 once(uint32_t col) const { return {gl_canon(h[col]), gl_canon(h[RH + col])}; }
+  __device__ __forceinline__ gl2 again(uint32_t col) const { return once(col); }
+  __device__ __forceinline__ gl2 next(uint32_t col) const { return {gl_canon(h[2 * RH + col]), gl_canon(h[3 * RH + col])}; }
+  __device__ __forceinline__ gl2 tbl(uint32_t col) const { return {gl_canon(t[col]), gl_canon(t[RT + col])}; }
+  __device__ __forceinline__ gl2 tbl_next(uint32_t col) const { return {gl_canon(t[2 * RT + col]), gl_canon(t[3 * RT + col])}; }
+  __device__ __forceinline__ gl2 weight(uint32_t j) const { return {gpw[2 * j], gpw[2 * j + 1]}; }
+  __device__ __forceinline__ void plain(uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul(weight(j), v)); }
+  __device__ __forceinline__ void selected(uint32_t j, gl2 v) { b = gl2_add(b, gl2_mul(weight(j), v)); }
+  __device__ __forceinline__ void started(uint32_t j, gl2 v) { b = gl2_add(b, gl2_mul(weight(j), v)); }
+  __device__ __forceinline__ void chained(uint32_t j, gl2 v) { c = gl2_add(c, gl2_mul(weight(j), v)); }
+};
+
+// gamma^0 .. gamma^n into LDS, the workgroup's threads striding over the powers; the caller's next barrier completes it
+__device__ __forceinline__ void air_gamma_powers(gl2 g, uint32_t n, uint64_t* gpw) {
+  for (uint32_t k = threadIdx.x; k <= n; k += AIR_CHECK_THREADS) {
+    const gl2 gk = gl2_pow(g, k);
+    gpw[2 * k] = gk.c0;
+    gpw[2 * k + 1] = gk.c1;
+  }
+}
+
+// The polynomial of degree < 64 with P(omega_64^t) = val(t), into LDS: thread j < 64 takes coefficient j, an inverse transform written out
+// (64 terms; launch-sized work).  Every thread of the workgroup calls it, and it ends with a barrier; 64^-1 = p - (p - 1) / 64.
+template <class Val>
+__device__ __forceinline__ void air_interpolate64(uint64_t om64_inv, uint64_t* coef, Val val) {
+  if (threadIdx.x < 64) {
+    const uint64_t step = gl_pow(om64_inv, threadIdx.x);
+    uint64_t cur = 1, acc = 0;
+    for (uint32_t t = 0; t < 64; t++, cur = gl_mul(cur, step)) acc = gl_add(acc, gl_mul(cur, val(t)));
+    coef[threadIdx.x] = gl_mul(acc, GL_P - (GL_P - 1) / 64);
+  }
+  __syncthreads();
+}
+// P_K(omega_64^t) = K256[t]; P_F(omega_64^t) = 1 for 15 <= t <= 62 and 0 otherwise (the next row is a schedule row)
+struct RoundConstant {
+  __device__ __forceinline__ uint64_t operator()(uint32_t t) const { return K_SHA256[t]; }
+};
+struct ScheduleRow {
+  __device__ __forceinline__ uint64_t operator()(uint32_t t) const { return t >= 15 && t <= 62 ? 1 : 0; }
+};
+// Such a polynomial at a point of F_p and of F_p^2
+__device__ __forceinline__ uint64_t air_horner64(const uint64_t* coef, uint64_t y) {
+  uint64_t acc = 0;
+  for (int j = 63; j >= 0; j--) acc = gl_add(gl_mul(acc, y), coef[j]);
+  return acc;
+}
+__device__ __forceinline__ gl2 air_horner64(const uint64_t* coef, gl2 y) {
+  gl2 acc = {0, 0};
+  for (int j = 63; j >= 0; j--) {
+    acc = gl2_mul(acc, y);
+    acc.c0 = gl_add(acc.c0, coef[j]);
+  }
+  return acc;
+}
+
+// Thread k's share of the two tables every one of these sets has: 1 / (x^N - 1) by i mod B (one Fermat chain), gamma^0 .. gamma^n
+__device__ __forceinline__ void air_zinv_gpow(uint32_t k, uint32_t log_blowup, uint64_t s_n, uint64_t w_n, const uint64_t* __restrict__ gamma,
+                                              uint32_t n, uint64_t* __restrict__ zinv, uint64_t* __restrict__ gpow) {
+  if (k < (1u << log_blowup)) zinv[k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
+  if (k <= n) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
+    gpow[2 * k] = g.c0;
+    gpow[2 * k + 1] = g.c1;
+  }
+}
+
+// The round-bit machinery of sets 3 and 5.  It runs on six registers of a row in the roles a, b, c, e, f, g of the round function: set 3
+// fills them with a, b, c, e, f, g themselves, set 5 with b, c, d, f, g, h (row 0 of a block is round 0 applied to the words the block
+// starts from).  RoundBits holds the helper offsets of the six registers' bit columns, whose X^2 - X constraints have the same indices,
+// and the helper offsets and constraint indices of U0, U1 and V.
+struct RoundBits {
+  uint32_t a, b, c, e, f, g, u0, u1, v, j_u0, j_u1, j_v;
+};
+template <class F>
+struct RoundWords {
+  typename F::T a, b, c, e, f, g, s0, s1, ch, maj;
+};
+// On the coset a bit column is a full field element, so a pass never holds the 288 bit words: it walks the bit index b from 31 down to 0
+// and per b holds the nine bit words A_b .. V_b and the six rotated ones (A_(b+2), A_(b+13), A_(b+22), E_(b+6), E_(b+11), E_(b+25)), which
+// are re-read through the cache (another b of the same lane reads them as its own).  Per b: nine constraints (six X^2 - X, U0, U1, V), and
+// one Horner step by 2 of the ten word sums (the six registers, Sigma0, Sigma1, Ch, Maj), so that no power of two is multiplied: 13
+// reduced column products and 18 gamma weights per b.  The word sums go back to the set's evaluator.
+template <class F, class View>
+__device__ __forceinline__ RoundWords<F> air_round_bits(View& at, const RoundBits r) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  RoundWords<F> w = {F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero()};
+#pragma unroll View::BITS
+  for (uint32_t b = 32; b-- > 0;) {
+    const T A_ = at.again(r.a + b), B = at.once(r.b + b), C = at.once(r.c + b), E = at.again(r.e + b), F_ = at.once(r.f + b), G = at.once(r.g + b);
+    const T U0 = at.once(r.u0 + b), U1 = at.once(r.u1 + b), V = at.once(r.v + b);
+    const T A2 = at.again(r.a + ((b + 2) & 31)), A13 = at.again(r.a + ((b + 13) & 31)), A22 = at.again(r.a + ((b + 22) & 31));
+    const T E6 = at.again(r.e + ((b + 6) & 31)), E11 = at.again(r.e + ((b + 11) & 31)), E25 = at.again(r.e + ((b + 25) & 31));
+    at.plain(r.a + b, A::boolean(A_));
+    at.plain(r.b + b, A::boolean(B));
+    at.plain(r.c + b, A::boolean(C));
+    at.plain(r.e + b, A::boolean(E));
+    at.plain(r.f + b, A::boolean(F_));
+    at.plain(r.g + b, A::boolean(G));
+    at.plain(r.j_u0 + b, A::sub(U0, A::exor(A2, A13)));
+    at.plain(r.j_u1 + b, A::sub(U1, A::exor(E6, E11)));
+    at.plain(r.j_v + b, A::sub(V, A::mul(A_, B)));
+    w.a = A::dbl_add(w.a, A_);
+    w.b = A::dbl_add(w.b, B);
+    w.c = A::dbl_add(w.c, C);
+    w.e = A::dbl_add(w.e, E);
+    w.f = A::dbl_add(w.f, F_);
+    w.g = A::dbl_add(w.g, G);
+    w.s0 = A::dbl_add(w.s0, A::exor(U0, A22));
+    w.s1 = A::dbl_add(w.s1, A::exor(U1, E25));
+    w.ch = A::dbl_add(w.ch, A::add(G, A::mul(E, A::sub(F_, G))));
+    w.maj = A::dbl_add(w.maj, A::add(V, A::mul(C, A::sub(A::add(A_, B), A::add(V, V)))));
+  }
+  return w;
+}
+
 // ---- constraint set 3: the round constraints of the SHA-256 tables (include/tmx.h "the round constraints of the SHA-256 tables") ------------
-// Siblings again: nothing above changes.  Helper column offsets inside a proof's 300, and the constraint indices inside its 315.
+// Helper column offsets inside a proof's 300, and the constraint indices inside its 315.
 constexpr uint32_t H_A = 0, H_B = 32, H_C = 64, H_E = 96, H_F = 128, H_G = 160, H_U0 = 192, H_U1 = 224, H_V = 256, H_S0 = 288, H_S1 = 289, H_CH = 290,
                    H_MAJ = 291, H_LIVE = 292, H_KL = 293, H_CA = 294, H_CE = 297;
 constexpr uint32_t T_W = 0, T_A = 1, T_B = 2, T_C = 3, T_D = 4, T_E = 5, T_F = 6, T_G = 7, T_H = 8;
@@ -588,10 +768,9 @@ __global__ __launch_bounds__(256) void k_air_sha_helper(uint32_t log_rows, uint3
   }
   const uint32_t live = any ? 1u : 0u;
   const uint32_t a = w[T_A], b = w[T_B], c = w[T_C], e = w[T_E], f = w[T_F], g = w[T_G];
-  auto rot = [](uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); };
-  const uint32_t s0 = rot(a, 2) ^ rot(a, 13) ^ rot(a, 22), s1 = rot(e, 6) ^ rot(e, 11) ^ rot(e, 25);
+  const uint32_t s0 = rotr32(a, 2) ^ rotr32(a, 13) ^ rotr32(a, 22), s1 = rotr32(e, 6) ^ rotr32(e, 11) ^ rotr32(e, 25);
   const uint32_t chv = (e & f) ^ (~e & g), mjv = (a & b) ^ (a & c) ^ (b & c);
-  const uint32_t u0 = rot(a, 2) ^ rot(a, 13), u1 = rot(e, 6) ^ rot(e, 11), v = a & b;
+  const uint32_t u0 = rotr32(a, 2) ^ rotr32(a, 13), u1 = rotr32(e, 6) ^ rotr32(e, 11), v = a & b;
   uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA_HELPER_COLS) << log_rows) + r;
   auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
 #pragma unroll 4
@@ -626,46 +805,63 @@ __global__ __launch_bounds__(256) void k_air_sha_helper(uint32_t log_rows, uint3
   }
 }
 
-// P_K, the polynomial of degree < 64 with P_K(omega_64^t) = K256[t], into LDS: thread j < 64 takes coefficient j, an inverse transform
-// written out (64 terms; launch-sized work).  Every thread of the workgroup calls it; 64^-1 = p - (p - 1) / 64.
-__device__ __forceinline__ void air_sha_pk(uint64_t om64_inv, uint64_t* pk) {
-  if (threadIdx.x < 64) {
-    const uint64_t step = gl_pow(om64_inv, threadIdx.x);
-    uint64_t cur = 1, acc = 0;
-    for (uint32_t t = 0; t < 64; t++, cur = gl_mul(cur, step)) acc = gl_add(acc, gl_mul(cur, K_SHA256[t]));
-    pk[threadIdx.x] = gl_mul(acc, GL_P - (GL_P - 1) / 64);
-  }
-  __syncthreads();
-}
-
 // One thread per table entry: S and K by i mod 64 B (K by Horner on P_K's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 315.
 __global__ __launch_bounds__(256) void k_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
                                                         uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
   __shared__ uint64_t pk[64];
-  air_sha_pk(om64_inv, pk);
+  air_interpolate64(om64_inv, pk, RoundConstant{});
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < (64u << log_blowup)) {
     const uint64_t y = gl_mul(s_n64, gl_pow(w_n64, k));
     tab[AIR3_TAB_SEL + k] = gl_sub(y, om64_inv);
-    uint64_t acc = 0;
-    for (int j = 63; j >= 0; j--) acc = gl_add(gl_mul(acc, y), pk[j]);
-    tab[AIR3_TAB_K + k] = acc;
+    tab[AIR3_TAB_K + k] = air_horner64(pk, y);
   }
-  if (k < (1u << log_blowup)) tab[AIR3_TAB_ZINV + k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
-  if (k <= AIR_SHA_CONSTRAINTS) {
-    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
-    tab[AIR3_TAB_GPOW + 2 * k] = g.c0;
-    tab[AIR3_TAB_GPOW + 2 * k + 1] = g.c1;
+  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_SHA_CONSTRAINTS, tab + AIR3_TAB_ZINV, tab + AIR3_TAB_GPOW);
+}
+
+// The 315 constraints of one proof at one point; kx is K at the point.  Behind the bit loop 8 more column products, the word constraints
+// and the nine selected ones, which go to a gamma sum of their own: S(x) is factored out of it, the kernel applies it once.
+template <class F, class View>
+__device__ __forceinline__ void air_sha_constraints(View& at, typename F::T kx) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  const RoundWords<F> w = air_round_bits<F>(at, {H_A, H_B, H_C, H_E, H_F, H_G, H_U0, H_U1, H_V, J_U0, J_U1, J_V});
+  const T ta = at.tbl(T_A), tb = at.tbl(T_B), tc = at.tbl(T_C), td = at.tbl(T_D), te = at.tbl(T_E), tf = at.tbl(T_F), tg = at.tbl(T_G),
+          th = at.tbl(T_H);
+  at.plain(J_WORD + 0, A::sub(ta, w.a));
+  at.plain(J_WORD + 1, A::sub(tb, w.b));
+  at.plain(J_WORD + 2, A::sub(tc, w.c));
+  at.plain(J_WORD + 3, A::sub(te, w.e));
+  at.plain(J_WORD + 4, A::sub(tf, w.f));
+  at.plain(J_WORD + 5, A::sub(tg, w.g));
+  const T S0 = at.once(H_S0), S1 = at.once(H_S1), CH = at.once(H_CH), MAJ = at.once(H_MAJ), LIVE = at.again(H_LIVE), KL = at.again(H_KL);
+  at.plain(J_S0, A::sub(S0, w.s0));
+  at.plain(J_S1, A::sub(S1, w.s1));
+  at.plain(J_CH, A::sub(CH, w.ch));
+  at.plain(J_MAJ, A::sub(MAJ, w.maj));
+  at.plain(J_LIVE, A::boolean(LIVE));
+  at.plain(J_KL, A::sub(KL, A::mul(LIVE, kx)));
+  T carry[6];
+#pragma unroll View::SHORT
+  for (uint32_t k = 0; k < 6; k++) {
+    carry[k] = at.once(H_CA + k);
+    at.plain(J_CARRY + k, A::boolean(carry[k]));
   }
+  at.selected(J_SHIFT + 0, A::sub(at.tbl_next(T_B), ta));
+  at.selected(J_SHIFT + 1, A::sub(at.tbl_next(T_C), tb));
+  at.selected(J_SHIFT + 2, A::sub(at.tbl_next(T_D), tc));
+  at.selected(J_SHIFT + 3, A::sub(at.tbl_next(T_F), te));
+  at.selected(J_SHIFT + 4, A::sub(at.tbl_next(T_G), tf));
+  at.selected(J_SHIFT + 5, A::sub(at.tbl_next(T_H), tg));
+  at.selected(J_LIVEN, A::sub(at.next(H_LIVE), LIVE));
+  const T kln = at.next(H_KL);
+  const T t1 = A::add(A::add(A::add(th, S1), A::add(CH, kln)), at.tbl_next(T_W));
+  at.selected(J_NA, A::sub(A::add(at.tbl_next(T_A), A::c32(carry[0], carry[1], carry[2])), A::add(t1, A::add(S0, MAJ))));
+  at.selected(J_NE, A::sub(A::add(at.tbl_next(T_E), A::c32(carry[3], carry[4], carry[5])), A::add(td, t1)));
 }
 
 // The set-3 hot pass, k_air_ladder_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^315), the nine table columns and the 300 helper columns read once from HBM.  On the coset a bit column is a full field element, so
-// the pass never holds the 300 words: it walks the bit index b from 31 down to 0 and per b holds the nine bit words A_b .. V_b and the six
-// rotated ones (A_(b+2), A_(b+13), A_(b+22), E_(b+6), E_(b+11), E_(b+25)), which are re-read through the cache (another b of the same lane
-// reads them as its own).  Per b: nine constraints (six X^2 - X, U0, U1, V), and one Horner step by 2 of the ten word sums (a, b, c, e,
-// f, g, Sigma0, Sigma1, Ch, Maj), so that no power of two is multiplied.  13 reduced column products and 18 gamma weights per b; behind
-// the loop 8 more column products, the word constraints and the nine selected ones, whose S(x) is factored out of their gamma sum.
+// gamma^315), the nine table columns and the 300 helper columns read once from HBM.  Per proof  v = a + S(x) b; at the end 1 / (x^N - 1).
 __global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
                                                                   const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                   const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -679,88 +875,9 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m
   const gl2 g315 = {gp[2 * AIR_SHA_CONSTRAINTS], gp[2 * AIR_SHA_CONSTRAINTS + 1]};
   gl2 t = {0, 0};
   for (uint32_t p = n_proofs; p-- > 0;) {
-    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);
-    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_SHA_HELPER_COLS) << log_m);
-    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
-    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
-    auto tbl = [&](uint32_t col, uint64_t at) { return gl_canon(c[((uint64_t)col << log_m) + at]); };
-    uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;  // the plain and the selected gamma sums, lazy
-    auto plain = [&](uint32_t j, uint64_t v) {
-      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
-      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto selected = [&](uint32_t j, uint64_t v) {
-      b0 = gl_add_lazy(b0, gl_mul(gp[2 * j], v));
-      b1 = gl_add_lazy(b1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
-    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
-      const uint64_t xy = gl_mul(x, y);
-      return gl_sub(gl_add(x, y), gl_add(xy, xy));
-    };
-    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
-    uint64_t wa = 0, wb = 0, wc = 0, we = 0, wf = 0, wg = 0, ws0 = 0, ws1 = 0, wch = 0, wmj = 0;
-#pragma unroll 2
-    for (uint32_t b = 32; b-- > 0;) {
-      const uint64_t A = again(H_A + b), B = once(H_B + b), C = once(H_C + b), E = again(H_E + b), F = once(H_F + b), G = once(H_G + b);
-      const uint64_t U0 = once(H_U0 + b), U1 = once(H_U1 + b), V = once(H_V + b);
-      const uint64_t A2 = again(H_A + ((b + 2) & 31)), A13 = again(H_A + ((b + 13) & 31)), A22 = again(H_A + ((b + 22) & 31));
-      const uint64_t E6 = again(H_E + ((b + 6) & 31)), E11 = again(H_E + ((b + 11) & 31)), E25 = again(H_E + ((b + 25) & 31));
-      plain(H_A + b, boolean(A));
-      plain(H_B + b, boolean(B));
-      plain(H_C + b, boolean(C));
-      plain(H_E + b, boolean(E));
-      plain(H_F + b, boolean(F));
-      plain(H_G + b, boolean(G));
-      plain(J_U0 + b, gl_sub(U0, exor(A2, A13)));
-      plain(J_U1 + b, gl_sub(U1, exor(E6, E11)));
-      const uint64_t AB = gl_mul(A, B);
-      plain(J_V + b, gl_sub(V, AB));
-      wa = dbl_add(wa, A);
-      wb = dbl_add(wb, B);
-      wc = dbl_add(wc, C);
-      we = dbl_add(we, E);
-      wf = dbl_add(wf, F);
-      wg = dbl_add(wg, G);
-      ws0 = dbl_add(ws0, exor(U0, A22));
-      ws1 = dbl_add(ws1, exor(U1, E25));
-      wch = dbl_add(wch, gl_add(G, gl_mul(E, gl_sub(F, G))));
-      wmj = dbl_add(wmj, gl_add(V, gl_mul(C, gl_sub(gl_add(A, B), gl_add(V, V)))));
-    }
-    const uint64_t ta = tbl(T_A, i), tb = tbl(T_B, i), tc = tbl(T_C, i), td = tbl(T_D, i), te = tbl(T_E, i), tf = tbl(T_F, i), tg = tbl(T_G, i),
-                   th = tbl(T_H, i);
-    plain(J_WORD + 0, gl_sub(ta, wa));
-    plain(J_WORD + 1, gl_sub(tb, wb));
-    plain(J_WORD + 2, gl_sub(tc, wc));
-    plain(J_WORD + 3, gl_sub(te, we));
-    plain(J_WORD + 4, gl_sub(tf, wf));
-    plain(J_WORD + 5, gl_sub(tg, wg));
-    const uint64_t S0 = once(H_S0), S1 = once(H_S1), CH = once(H_CH), MAJ = once(H_MAJ), LIVE = again(H_LIVE), KL = again(H_KL);
-    plain(J_S0, gl_sub(S0, ws0));
-    plain(J_S1, gl_sub(S1, ws1));
-    plain(J_CH, gl_sub(CH, wch));
-    plain(J_MAJ, gl_sub(MAJ, wmj));
-    plain(J_LIVE, boolean(LIVE));
-    plain(J_KL, gl_sub(KL, gl_mul(LIVE, kx)));
-    uint64_t carry[6];
-#pragma unroll
-    for (uint32_t k = 0; k < 6; k++) {
-      carry[k] = once(H_CA + k);
-      plain(J_CARRY + k, boolean(carry[k]));
-    }
-    selected(J_SHIFT + 0, gl_sub(tbl(T_B, nx), ta));
-    selected(J_SHIFT + 1, gl_sub(tbl(T_C, nx), tb));
-    selected(J_SHIFT + 2, gl_sub(tbl(T_D, nx), tc));
-    selected(J_SHIFT + 3, gl_sub(tbl(T_F, nx), te));
-    selected(J_SHIFT + 4, gl_sub(tbl(T_G, nx), tf));
-    selected(J_SHIFT + 5, gl_sub(tbl(T_H, nx), tg));
-    selected(J_LIVEN, gl_sub(gl_canon(h[((uint64_t)H_LIVE << log_m) + nx]), LIVE));
-    const uint64_t kln = gl_canon(h[((uint64_t)H_KL << log_m) + nx]);
-    const uint64_t t1 = gl_add(gl_add(gl_add(th, S1), gl_add(CH, kln)), tbl(T_W, nx));
-    auto c32 = [](uint64_t x0, uint64_t x1, uint64_t x2) { return gl_mul(gl_add(x0, gl_add(gl_add(x1, x1), gl_mul(x2, 4))), 1ull << 32); };
-    selected(J_NA, gl_sub(gl_add(tbl(T_A, nx), c32(carry[0], carry[1], carry[2])), gl_add(t1, gl_add(S0, MAJ))));
-    selected(J_NE, gl_sub(gl_add(tbl(T_E, nx), c32(carry[3], carry[4], carry[5])), gl_add(td, t1)));
-    const gl2 v = {gl_add(gl_canon(a0), gl_mul(sel, b0)), gl_add(gl_canon(a1), gl_mul(sel, b1))};
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_sha_constraints<FieldP>(at, kx);
+    const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sel, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sel, at.b1))};
     t = gl2_add(gl2_mul(t, g315), v);
   }
   const gl2 q = gl2_scale(t, zinv);
@@ -769,129 +886,30 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m
 }
 
 // The set-3 identity at zeta, one workgroup: gamma^0 .. gamma^315 and P_K go to LDS first; thread t takes the proofs t, t + 256, ... and
-// evaluates their 315 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the order of
-// the hot pass; K(zeta) by Horner on P_K at zeta^(N/64).  The sums meet in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1).
+// evaluates their 315 constraints over F_p^2 from the table's and the helper's openings; K(zeta) by Horner on P_K at zeta^(N/64).  A proof
+// contributes gamma^(315 p) (a + S(zeta) b); the sum is compared with (u_0 + X u_1) (zeta^N - 1).
 __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
                                                                       uint64_t om64_inv, const uint64_t* __restrict__ open_t,
                                                                       const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
                                                                       const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
                                                                       uint32_t n_queries, uint32_t* __restrict__ ok) {
-  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
   __shared__ uint64_t gpw[2 * (AIR_SHA_CONSTRAINTS + 1)];
   __shared__ uint64_t pk[64];
-  __shared__ uint32_t holds;
-  const uint32_t t = threadIdx.x;
-  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
-  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
-  for (uint32_t k = t; k <= AIR_SHA_CONSTRAINTS; k += AIR_CHECK_THREADS) {
-    const gl2 gk = gl2_pow(g, k);
-    gpw[2 * k] = gk.c0;
-    gpw[2 * k + 1] = gk.c1;
-  }
-  air_sha_pk(om64_inv, pk);  // (ends with a barrier: gpw is complete behind it too)
-  gl2 zp = z;  // zeta^(N/64)
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_SHA_CONSTRAINTS, gpw);
+  air_interpolate64(om64_inv, pk, RoundConstant{});  // (ends with a barrier: gpw is complete behind it too)
+  gl2 zp = {zeta[0], zeta[1]};  // zeta^(N/64)
   for (uint32_t k = 6; k < log_sub; k++) zp = gl2_mul(zp, zp);
-  const gl2 S = {gl_sub(zp.c0, om64_inv), zp.c1};
-  gl2 K = {0, 0};
-  for (int j = 63; j >= 0; j--) {
-    K = gl2_mul(K, zp);
-    K.c0 = gl_add(K.c0, pk[j]);
-  }
-  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
-  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
-  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
-  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
-  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
-  auto exor = [](gl2 x, gl2 y) {
-    const gl2 xy = gl2_mul(x, y);
-    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
-  };
-  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
+  const gl2 S = {gl_sub(zp.c0, om64_inv), zp.c1}, K = air_horner64(pk, zp);
   gl2 sum = {0, 0};
-  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
-    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_SHA_HELPER_COLS;
-    gl2 a = {0, 0}, bsel = {0, 0};
-    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    auto selected = [&](uint32_t j, gl2 v) { bsel = gl2_add(bsel, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    gl2 wa = {0, 0}, wb = wa, wc = wa, we = wa, wf = wa, wg = wa, ws0 = wa, ws1 = wa, wch = wa, wmj = wa;
-    for (uint32_t b = 32; b-- > 0;) {
-      const gl2 A = h0(chh + H_A + b), B = h0(chh + H_B + b), C = h0(chh + H_C + b), E = h0(chh + H_E + b), F = h0(chh + H_F + b),
-                G = h0(chh + H_G + b), U0 = h0(chh + H_U0 + b), U1 = h0(chh + H_U1 + b), V = h0(chh + H_V + b);
-      const gl2 A2 = h0(chh + H_A + ((b + 2) & 31)), A13 = h0(chh + H_A + ((b + 13) & 31)), A22 = h0(chh + H_A + ((b + 22) & 31));
-      const gl2 E6 = h0(chh + H_E + ((b + 6) & 31)), E11 = h0(chh + H_E + ((b + 11) & 31)), E25 = h0(chh + H_E + ((b + 25) & 31));
-      plain(H_A + b, boolean(A));
-      plain(H_B + b, boolean(B));
-      plain(H_C + b, boolean(C));
-      plain(H_E + b, boolean(E));
-      plain(H_F + b, boolean(F));
-      plain(H_G + b, boolean(G));
-      plain(J_U0 + b, gl2_sub(U0, exor(A2, A13)));
-      plain(J_U1 + b, gl2_sub(U1, exor(E6, E11)));
-      plain(J_V + b, gl2_sub(V, gl2_mul(A, B)));
-      wa = dbl_add(wa, A);
-      wb = dbl_add(wb, B);
-      wc = dbl_add(wc, C);
-      we = dbl_add(we, E);
-      wf = dbl_add(wf, F);
-      wg = dbl_add(wg, G);
-      ws0 = dbl_add(ws0, exor(U0, A22));
-      ws1 = dbl_add(ws1, exor(U1, E25));
-      wch = dbl_add(wch, gl2_add(G, gl2_mul(E, gl2_sub(F, G))));
-      wmj = dbl_add(wmj, gl2_add(V, gl2_mul(C, gl2_sub(gl2_add(A, B), gl2_add(V, V)))));
-    }
-    const gl2 ta = t0(ct + T_A), tb = t0(ct + T_B), tc = t0(ct + T_C), td = t0(ct + T_D), te = t0(ct + T_E), tf = t0(ct + T_F), tg = t0(ct + T_G),
-              th = t0(ct + T_H);
-    plain(J_WORD + 0, gl2_sub(ta, wa));
-    plain(J_WORD + 1, gl2_sub(tb, wb));
-    plain(J_WORD + 2, gl2_sub(tc, wc));
-    plain(J_WORD + 3, gl2_sub(te, we));
-    plain(J_WORD + 4, gl2_sub(tf, wf));
-    plain(J_WORD + 5, gl2_sub(tg, wg));
-    const gl2 S0 = h0(chh + H_S0), S1 = h0(chh + H_S1), CH = h0(chh + H_CH), MAJ = h0(chh + H_MAJ), LIVE = h0(chh + H_LIVE), KL = h0(chh + H_KL);
-    plain(J_S0, gl2_sub(S0, ws0));
-    plain(J_S1, gl2_sub(S1, ws1));
-    plain(J_CH, gl2_sub(CH, wch));
-    plain(J_MAJ, gl2_sub(MAJ, wmj));
-    plain(J_LIVE, boolean(LIVE));
-    plain(J_KL, gl2_sub(KL, gl2_mul(LIVE, K)));
-    gl2 carry[6];
-    for (uint32_t k = 0; k < 6; k++) {
-      carry[k] = h0(chh + H_CA + k);
-      plain(J_CARRY + k, boolean(carry[k]));
-    }
-    selected(J_SHIFT + 0, gl2_sub(t1(ct + T_B), ta));
-    selected(J_SHIFT + 1, gl2_sub(t1(ct + T_C), tb));
-    selected(J_SHIFT + 2, gl2_sub(t1(ct + T_D), tc));
-    selected(J_SHIFT + 3, gl2_sub(t1(ct + T_F), te));
-    selected(J_SHIFT + 4, gl2_sub(t1(ct + T_G), tf));
-    selected(J_SHIFT + 5, gl2_sub(t1(ct + T_H), tg));
-    selected(J_LIVEN, gl2_sub(h1(chh + H_LIVE), LIVE));
-    const gl2 tt = gl2_add(gl2_add(gl2_add(th, S1), gl2_add(CH, h1(chh + H_KL))), t1(ct + T_W));
-    auto c32 = [](gl2 x0, gl2 x1, gl2 x2) { return gl2_scale(gl2_add(x0, gl2_add(gl2_add(x1, x1), gl2_scale(x2, 4))), 1ull << 32); };
-    selected(J_NA, gl2_sub(gl2_add(t1(ct + T_A), c32(carry[0], carry[1], carry[2])), gl2_add(tt, gl2_add(S0, MAJ))));
-    selected(J_NE, gl2_sub(gl2_add(t1(ct + T_E), c32(carry[3], carry[4], carry[5])), gl2_add(td, tt)));
-    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA_CONSTRAINTS * p), gl2_add(a, gl2_mul(S, bsel))));
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA_WIDTH, open_h + (uint64_t)p * AIR_SHA_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_sha_constraints<FieldP2>(at, K);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA_CONSTRAINTS * p), gl2_add(at.a, gl2_mul(S, at.b))));
   }
-  red[0][t] = sum.c0;
-  red[1][t] = sum.c1;
-  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
-    __syncthreads();
-    if (t < hh) {
-      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
-      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
-    for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
-    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
-    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
-    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(q, {gl_sub(zn.c0, 1), zn.c1})) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!holds)
-    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+  gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
+  for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
 }
 
 int launch_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
@@ -926,14 +944,12 @@ int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, 
 }
 
 // ---- constraint set 4: the message schedule of the SHA-256 tables (include/tmx.h "the message schedule of the SHA-256 tables") --------------
-// Siblings again: nothing above changes.  Helper column offsets inside a proof's 115 (Q_k at S_Q + k), constraint indices inside its 117
-// (Q_k's at JS_Q + k).
+// Helper column offsets inside a proof's 115 (Q_k at S_Q + k), constraint indices inside its 117 (Q_k's at JS_Q + k).
 constexpr uint32_t S_WB = 0, S_X0 = 32, S_X1 = 64, S_G0 = 96, S_G1 = 97, S_Q = 97, S_CW = 113;
 constexpr uint32_t JS_CW = 32, JS_WORD = 34, JS_X0 = 35, JS_X1 = 67, JS_G0 = 99, JS_G1 = 100, JS_Q = 100, JS_NEXT = 116;
 
-__device__ __forceinline__ uint32_t sched_rot(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
-__device__ __forceinline__ uint32_t sched_s0(uint32_t w) { return sched_rot(w, 7) ^ sched_rot(w, 18) ^ (w >> 3); }
-__device__ __forceinline__ uint32_t sched_s1(uint32_t w) { return sched_rot(w, 17) ^ sched_rot(w, 19) ^ (w >> 10); }
+__device__ __forceinline__ uint32_t sched_s0(uint32_t w) { return rotr32(w, 7) ^ rotr32(w, 18) ^ (w >> 3); }
+__device__ __forceinline__ uint32_t sched_s1(uint32_t w) { return rotr32(w, 17) ^ rotr32(w, 19) ^ (w >> 10); }
 
 // One lane per (proof, row) of the pre-LDE table, 115 stores, each of them consecutive words of one column across the wave.  The pipeline
 // unrolled: Q_k(r) = W(r-k) + sigma0(W(r-k+1)) + [k >= 9] W(r-k+9) + [k >= 14] sigma1(W(r-k+14)), rows cyclic inside the proof, so the lane
@@ -949,7 +965,7 @@ __global__ __launch_bounds__(256) void k_air_sched_helper(uint32_t log_rows, uin
   uint32_t w[16];  // w[d] = W(r - d)
 #pragma unroll
   for (uint32_t d = 0; d < 16; d++) w[d] = (uint32_t)t[(r - d) & mask];
-  const uint32_t w0 = w[0], x0 = sched_rot(w0, 7) ^ sched_rot(w0, 18), x1 = sched_rot(w0, 17) ^ sched_rot(w0, 19);
+  const uint32_t w0 = w[0], x0 = rotr32(w0, 7) ^ rotr32(w0, 18), x1 = rotr32(w0, 17) ^ rotr32(w0, 19);
   uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SCHED_HELPER_COLS) << log_rows) + r;
   auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
 #pragma unroll 4
@@ -975,45 +991,61 @@ __global__ __launch_bounds__(256) void k_air_sched_helper(uint32_t log_rows, uin
   put(S_CW + 1, cw >> 1);
 }
 
-// P_F, the polynomial of degree < 64 with P_F(omega_64^t) = 1 for 15 <= t <= 62 and 0 otherwise (the next row is a schedule row), into
-// LDS: thread j < 64 takes coefficient j, an inverse transform written out.  Every thread of the workgroup calls it.
-__device__ __forceinline__ void air_sched_pf(uint64_t om64_inv, uint64_t* pf) {
-  if (threadIdx.x < 64) {
-    const uint64_t step = gl_pow(om64_inv, threadIdx.x);
-    uint64_t cur = gl_pow(step, 15), acc = 0;
-    for (uint32_t t = 15; t <= 62; t++, cur = gl_mul(cur, step)) acc = gl_add(acc, cur);
-    pf[threadIdx.x] = gl_mul(acc, GL_P - (GL_P - 1) / 64);
-  }
-  __syncthreads();
-}
-
 // One thread per table entry: F by i mod 64 B (Horner on P_F's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 117.
 __global__ __launch_bounds__(256) void k_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
                                                           uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
   __shared__ uint64_t pf[64];
-  air_sched_pf(om64_inv, pf);
+  air_interpolate64(om64_inv, pf, ScheduleRow{});
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < (64u << log_blowup)) {
-    const uint64_t y = gl_mul(s_n64, gl_pow(w_n64, k));
-    uint64_t acc = 0;
-    for (int j = 63; j >= 0; j--) acc = gl_add(gl_mul(acc, y), pf[j]);
-    tab[AIR4_TAB_F + k] = acc;
+  if (k < (64u << log_blowup)) tab[AIR4_TAB_F + k] = air_horner64(pf, gl_mul(s_n64, gl_pow(w_n64, k)));
+  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_SCHED_CONSTRAINTS, tab + AIR4_TAB_ZINV, tab + AIR4_TAB_GPOW);
+}
+
+// The 117 constraints of one proof at one point; fx is F at the point.  The bit index b walks from 31 down to 0 and per b the pass holds
+// WB_b, X0_b, X1_b and the six rotated or shifted bit words (WB_(b+7), WB_(b+18), WB_(b+17), WB_(b+19), and WB_(b+3) for b < 29, WB_(b+10)
+// for b < 22), which are re-read through the cache.  Per b: three constraints (X^2 - X, X0, X1) and one Horner step by 2 of the three word
+// sums (W, sigma0, sigma1), so that no power of two is multiplied: 5 reduced column products and 6 gamma weights.  Behind the loop the
+// three word constraints, the two carry bits, the fifteen pipeline constraints (linear: W', G0', G1' and Q_1' .. Q_15' at the next row) and
+// the selected one, whose F(x) is applied once to its value.
+template <class F, class View>
+__device__ __forceinline__ void air_sched_constraints(View& at, typename F::T fx) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  T ww = F::zero(), wg0 = F::zero(), wg1 = F::zero();
+#pragma unroll View::BITS
+  for (uint32_t b = 32; b-- > 0;) {
+    const T WB = at.again(S_WB + b), X0 = at.once(S_X0 + b), X1 = at.once(S_X1 + b);
+    const T W7 = at.again(S_WB + ((b + 7) & 31)), W18 = at.again(S_WB + ((b + 18) & 31));
+    const T W17 = at.again(S_WB + ((b + 17) & 31)), W19 = at.again(S_WB + ((b + 19) & 31));
+    at.plain(S_WB + b, A::boolean(WB));
+    at.plain(JS_X0 + b, A::sub(X0, A::exor(W7, W18)));
+    at.plain(JS_X1 + b, A::sub(X1, A::exor(W17, W19)));
+    ww = A::dbl_add(ww, WB);
+    wg0 = A::dbl_add(wg0, b < 29 ? A::exor(X0, at.again(S_WB + ((b + 3) & 31))) : X0);  // (b is uniform: a scalar branch)
+    wg1 = A::dbl_add(wg1, b < 22 ? A::exor(X1, at.again(S_WB + ((b + 10) & 31))) : X1);
   }
-  if (k < (1u << log_blowup)) tab[AIR4_TAB_ZINV + k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
-  if (k <= AIR_SCHED_CONSTRAINTS) {
-    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
-    tab[AIR4_TAB_GPOW + 2 * k] = g.c0;
-    tab[AIR4_TAB_GPOW + 2 * k + 1] = g.c1;
+  const T W = at.tbl(T_W), Wn = at.tbl_next(T_W);
+  const T G0 = at.again(S_G0), G1 = at.again(S_G1), CW0 = at.once(S_CW), CW1 = at.once(S_CW + 1);
+  at.plain(JS_WORD, A::sub(W, ww));
+  at.plain(JS_G0, A::sub(G0, wg0));
+  at.plain(JS_G1, A::sub(G1, wg1));
+  at.plain(JS_CW, A::boolean(CW0));
+  at.plain(JS_CW + 1, A::boolean(CW1));
+  T prev = A::add(W, at.next(S_G0));  // what Q_k' must equal: W + G0' for k = 1, then Q_(k-1) (+ W' for k = 9, + G1' for k = 14)
+#pragma unroll View::SHORT
+  for (uint32_t k = 1; k <= 15; k++) {
+    at.plain(JS_Q + k, A::sub(at.next(S_Q + k), prev));
+    prev = at.again(S_Q + k);
+    if (k + 1 == 9) prev = A::add(prev, Wn);
+    if (k + 1 == 14) prev = A::add(prev, at.next(S_G1));
   }
+  // (prev = Q_15)  F(x) (W' + 2^32 (CW_0 + 2 CW_1) - Q_15)
+  const T carry = A::scale(A::add(CW0, A::add(CW1, CW1)), 1ull << 32);
+  at.plain(JS_NEXT, A::mul(fx, A::sub(A::add(Wn, carry), prev)));
 }
 
 // The set-4 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^117), W and the 115 helper columns.  It walks the bit index b from 31 down to 0 and per b holds WB_b, X0_b, X1_b and the six
-// rotated or shifted bit words (WB_(b+7), WB_(b+18), WB_(b+17), WB_(b+19), and WB_(b+3) for b < 29, WB_(b+10) for b < 22), which are re-read
-// through the cache.  Per b: three constraints (X^2 - X, X0, X1) and one Horner step by 2 of the three word sums (W, sigma0, sigma1), so
-// that no power of two is multiplied: 5 reduced column products and 6 gamma weights.  Behind the loop the three word constraints, the two
-// carry bits, the fifteen pipeline constraints (linear: W', G0', G1' and Q_1' .. Q_15' at i + B) and the selected one, whose F(x) is
-// applied once to its value.  The gamma sums are lazy, as in set 3's pass.
+// gamma^117), W and the 115 helper columns.  One gamma sum per proof, lazy as in set 3's pass; at the end 1 / (x^N - 1).
 __global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
                                                                     const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                     const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -1026,54 +1058,9 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log
   const gl2 g117 = {gp[2 * AIR_SCHED_CONSTRAINTS], gp[2 * AIR_SCHED_CONSTRAINTS + 1]};
   gl2 t = {0, 0};
   for (uint32_t p = n_proofs; p-- > 0;) {
-    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);  // (W is column 0)
-    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_SCHED_HELPER_COLS) << log_m);
-    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
-    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
-    auto next = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + nx]); };
-    uint64_t a0 = 0, a1 = 0;  // the gamma sums, lazy
-    auto plain = [&](uint32_t j, uint64_t v) {
-      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
-      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
-    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
-      const uint64_t xy = gl_mul(x, y);
-      return gl_sub(gl_add(x, y), gl_add(xy, xy));
-    };
-    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
-    uint64_t ww = 0, wg0 = 0, wg1 = 0;
-#pragma unroll 2
-    for (uint32_t b = 32; b-- > 0;) {
-      const uint64_t WB = again(S_WB + b), X0 = once(S_X0 + b), X1 = once(S_X1 + b);
-      const uint64_t W7 = again(S_WB + ((b + 7) & 31)), W18 = again(S_WB + ((b + 18) & 31));
-      const uint64_t W17 = again(S_WB + ((b + 17) & 31)), W19 = again(S_WB + ((b + 19) & 31));
-      plain(S_WB + b, boolean(WB));
-      plain(JS_X0 + b, gl_sub(X0, exor(W7, W18)));
-      plain(JS_X1 + b, gl_sub(X1, exor(W17, W19)));
-      ww = dbl_add(ww, WB);
-      wg0 = dbl_add(wg0, b < 29 ? exor(X0, again(S_WB + ((b + 3) & 31))) : X0);   // (b is uniform: a scalar branch)
-      wg1 = dbl_add(wg1, b < 22 ? exor(X1, again(S_WB + ((b + 10) & 31))) : X1);
-    }
-    const uint64_t W = gl_canon(c[i]), Wn = gl_canon(c[nx]);
-    const uint64_t G0 = again(S_G0), G1 = again(S_G1), CW0 = once(S_CW), CW1 = once(S_CW + 1);
-    plain(JS_WORD, gl_sub(W, ww));
-    plain(JS_G0, gl_sub(G0, wg0));
-    plain(JS_G1, gl_sub(G1, wg1));
-    plain(JS_CW, boolean(CW0));
-    plain(JS_CW + 1, boolean(CW1));
-    uint64_t prev = gl_add(W, next(S_G0));  // what Q_k' must equal: W + G0' for k = 1, then Q_(k-1) (+ W' for k = 9, + G1' for k = 14)
-#pragma unroll
-    for (uint32_t k = 1; k <= 15; k++) {
-      plain(JS_Q + k, gl_sub(next(S_Q + k), prev));
-      prev = again(S_Q + k);
-      if (k + 1 == 9) prev = gl_add(prev, Wn);
-      if (k + 1 == 14) prev = gl_add(prev, next(S_G1));
-    }
-    // (prev = Q_15)  F(x) (W' + 2^32 (CW_0 + 2 CW_1) - Q_15)
-    const uint64_t carry = gl_mul(gl_add(CW0, gl_add(CW1, CW1)), 1ull << 32);
-    plain(JS_NEXT, gl_mul(fx, gl_sub(gl_add(Wn, carry), prev)));
-    t = gl2_add(gl2_mul(t, g117), {gl_canon(a0), gl_canon(a1)});
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SCHED_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_sched_constraints<FieldP>(at, fx);
+    t = gl2_add(gl2_mul(t, g117), {gl_canon(at.a0), gl_canon(at.a1)});
   }
   const gl2 q = gl2_scale(t, zinv);
   out[i] = q.c0;
@@ -1081,98 +1068,30 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log
 }
 
 // The set-4 identity at zeta, one workgroup: gamma^0 .. gamma^117 and P_F go to LDS first; thread t takes the proofs t, t + 256, ... and
-// evaluates their 117 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the order of
-// the hot pass; F(zeta) by Horner on P_F at zeta^(N/64).  The sums meet in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1).
+// evaluates their 117 constraints over F_p^2 from the table's and the helper's openings; F(zeta) by Horner on P_F at zeta^(N/64).  A proof
+// contributes gamma^(117 p) a; the sum is compared with (u_0 + X u_1) (zeta^N - 1).
 __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
                                                                         uint64_t om64_inv, const uint64_t* __restrict__ open_t,
                                                                         const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
                                                                         const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
                                                                         uint32_t n_queries, uint32_t* __restrict__ ok) {
-  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
   __shared__ uint64_t gpw[2 * (AIR_SCHED_CONSTRAINTS + 1)];
   __shared__ uint64_t pf[64];
-  __shared__ uint32_t holds;
-  const uint32_t t = threadIdx.x;
-  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
-  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
-  for (uint32_t k = t; k <= AIR_SCHED_CONSTRAINTS; k += AIR_CHECK_THREADS) {
-    const gl2 gk = gl2_pow(g, k);
-    gpw[2 * k] = gk.c0;
-    gpw[2 * k + 1] = gk.c1;
-  }
-  air_sched_pf(om64_inv, pf);  // (ends with a barrier: gpw is complete behind it too)
-  gl2 zp = z;  // zeta^(N/64)
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_SCHED_CONSTRAINTS, gpw);
+  air_interpolate64(om64_inv, pf, ScheduleRow{});  // (ends with a barrier: gpw is complete behind it too)
+  gl2 zp = {zeta[0], zeta[1]};  // zeta^(N/64)
   for (uint32_t k = 6; k < log_sub; k++) zp = gl2_mul(zp, zp);
-  gl2 F = {0, 0};
-  for (int j = 63; j >= 0; j--) {
-    F = gl2_mul(F, zp);
-    F.c0 = gl_add(F.c0, pf[j]);
-  }
-  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
-  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
-  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
-  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
-  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
-  auto exor = [](gl2 x, gl2 y) {
-    const gl2 xy = gl2_mul(x, y);
-    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
-  };
-  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
+  const gl2 F = air_horner64(pf, zp);
   gl2 sum = {0, 0};
-  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
-    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_SCHED_HELPER_COLS;
-    gl2 a = {0, 0};
-    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    gl2 ww = {0, 0}, wg0 = ww, wg1 = ww;
-    for (uint32_t b = 32; b-- > 0;) {
-      const gl2 WB = h0(chh + S_WB + b), X0 = h0(chh + S_X0 + b), X1 = h0(chh + S_X1 + b);
-      const gl2 W7 = h0(chh + S_WB + ((b + 7) & 31)), W18 = h0(chh + S_WB + ((b + 18) & 31));
-      const gl2 W17 = h0(chh + S_WB + ((b + 17) & 31)), W19 = h0(chh + S_WB + ((b + 19) & 31));
-      plain(S_WB + b, boolean(WB));
-      plain(JS_X0 + b, gl2_sub(X0, exor(W7, W18)));
-      plain(JS_X1 + b, gl2_sub(X1, exor(W17, W19)));
-      ww = dbl_add(ww, WB);
-      wg0 = dbl_add(wg0, b < 29 ? exor(X0, h0(chh + S_WB + ((b + 3) & 31))) : X0);
-      wg1 = dbl_add(wg1, b < 22 ? exor(X1, h0(chh + S_WB + ((b + 10) & 31))) : X1);
-    }
-    const gl2 W = t0(ct), Wn = t1(ct);
-    const gl2 G0 = h0(chh + S_G0), G1 = h0(chh + S_G1), CW0 = h0(chh + S_CW), CW1 = h0(chh + S_CW + 1);
-    plain(JS_WORD, gl2_sub(W, ww));
-    plain(JS_G0, gl2_sub(G0, wg0));
-    plain(JS_G1, gl2_sub(G1, wg1));
-    plain(JS_CW, boolean(CW0));
-    plain(JS_CW + 1, boolean(CW1));
-    gl2 prev = gl2_add(W, h1(chh + S_G0));
-    for (uint32_t k = 1; k <= 15; k++) {
-      plain(JS_Q + k, gl2_sub(h1(chh + S_Q + k), prev));
-      prev = h0(chh + S_Q + k);
-      if (k + 1 == 9) prev = gl2_add(prev, Wn);
-      if (k + 1 == 14) prev = gl2_add(prev, h1(chh + S_G1));
-    }
-    const gl2 carry = gl2_scale(gl2_add(CW0, gl2_add(CW1, CW1)), 1ull << 32);
-    plain(JS_NEXT, gl2_mul(F, gl2_sub(gl2_add(Wn, carry), prev)));
-    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SCHED_CONSTRAINTS * p), a));
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA_WIDTH, open_h + (uint64_t)p * AIR_SCHED_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_sched_constraints<FieldP2>(at, F);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SCHED_CONSTRAINTS * p), at.a));
   }
-  red[0][t] = sum.c0;
-  red[1][t] = sum.c1;
-  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
-    __syncthreads();
-    if (t < hh) {
-      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
-      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
-    for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
-    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
-    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
-    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(q, {gl_sub(zn.c0, 1), zn.c1})) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!holds)
-    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+  gl2 zn = zp;  // zeta^N = (zeta^(N/64))^64
+  for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
 }
 
 int launch_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
@@ -1205,9 +1124,9 @@ int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h
 }
 
 // ---- constraint set 5: the block starts of the SHA-256 tables (include/tmx.h "the block starts of the SHA-256 tables") ----------------------
-// Siblings again: nothing above changes.  Row 0 of a block is round 0 applied to the words the block starts from, so six of those eight
-// words stand in row 0 itself (b, c, d, f, g, h) and set 3's bit machinery runs on them with the register names shifted by one.  Helper
-// column offsets inside a proof's 315, constraint indices inside its 337.
+// Row 0 of a block is round 0 applied to the words the block starts from, so six of those eight words stand in row 0 itself (b, c, d, f,
+// g, h) and the round-bit machinery runs on them with the register names shifted by one.  Helper column offsets inside a proof's 315,
+// constraint indices inside its 337.
 constexpr uint32_t I_B = 0, I_C = 32, I_D = 64, I_F = 96, I_G = 128, I_H = 160, I_U0 = 192, I_U1 = 224, I_V = 256, I_S0 = 288, I_S1 = 289, I_CH = 290,
                    I_MAJ = 291, I_LV = 292, I_PZ = 293, I_CZ = 301, I_CA = 309, I_CE = 312;
 constexpr uint32_t JI_CZ = 192, JI_CARRY = 200, JI_LV = 206, JI_WORD = 207, JI_U0 = 213, JI_U1 = 245, JI_V = 277, JI_S0 = 309, JI_S1 = 310, JI_CH = 311,
@@ -1216,9 +1135,8 @@ __device__ __constant__ const uint32_t IV_SHA256[8] = {0x6a09e667u, 0xbb67ae85u,
                                                        0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
 constexpr uint64_t INIT_IV3 = 0xa54ff53aull, INIT_IV7 = 0x5be0cd19ull, INIT_K0 = 0x428a2f98ull;
 
-__device__ __forceinline__ uint32_t init_rot(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
-__device__ __forceinline__ uint32_t init_big0(uint32_t b) { return init_rot(b, 2) ^ init_rot(b, 13) ^ init_rot(b, 22); }
-__device__ __forceinline__ uint32_t init_big1(uint32_t f) { return init_rot(f, 6) ^ init_rot(f, 11) ^ init_rot(f, 25); }
+__device__ __forceinline__ uint32_t init_big0(uint32_t b) { return rotr32(b, 2) ^ rotr32(b, 13) ^ rotr32(b, 22); }
+__device__ __forceinline__ uint32_t init_big1(uint32_t f) { return rotr32(f, 6) ^ rotr32(f, 11) ^ rotr32(f, 25); }
 
 // One lane per (proof, row) of the pre-LDE table: the nine words of the row, the first row of its block (LV) and of the next row's block
 // (LV'; rows are cyclic inside the proof), on a boundary row also the nine words of the next row (the two round-0 sums), then 315 stores,
@@ -1240,7 +1158,7 @@ __global__ __launch_bounds__(256) void k_air_init_helper(uint32_t log_rows, uint
   }
   const uint32_t live = any ? 1u : 0u, live_next = any_next ? 1u : 0u;
   const uint32_t b = w[T_B], c = w[T_C], d = w[T_D], f = w[T_F], g = w[T_G], hh = w[T_H];
-  const uint32_t u0 = init_rot(b, 2) ^ init_rot(b, 13), u1 = init_rot(f, 6) ^ init_rot(f, 11), v = b & c;
+  const uint32_t u0 = rotr32(b, 2) ^ rotr32(b, 13), u1 = rotr32(f, 6) ^ rotr32(f, 11), v = b & c;
   uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_INIT_HELPER_COLS) << log_rows) + r;
   auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
 #pragma unroll 4
@@ -1287,67 +1205,107 @@ __global__ __launch_bounds__(256) void k_air_init_helper(uint32_t log_rows, uint
   }
 }
 
-// n <= 8 nonzero values inverted with one field inversion (Montgomery's trick)
-__device__ __forceinline__ void air_init_batch_inverse(uint64_t (&v)[8], uint32_t n) {
+// Eight nonzero values inverted with one field inversion (Montgomery's trick)
+__device__ __forceinline__ void air_init_batch_inverse(uint64_t (&v)[8]) {
   uint64_t pre[8], acc = 1;
 #pragma unroll
-  for (uint32_t j = 0; j < 8; j++)
-    if (j < n) {
-      pre[j] = acc;
-      acc = gl_mul(acc, v[j]);
-    }
+  for (uint32_t j = 0; j < 8; j++) {
+    pre[j] = acc;
+    acc = gl_mul(acc, v[j]);
+  }
   uint64_t inv = gl_pow(acc, GL_P - 2);
 #pragma unroll
-  for (uint32_t j = 8; j-- > 0;)
-    if (j < n) {
-      const uint64_t x = gl_mul(inv, pre[j]);
-      inv = gl_mul(inv, v[j]);
-      v[j] = x;
-    }
+  for (uint32_t j = 8; j-- > 0;) {
+    const uint64_t x = gl_mul(inv, pre[j]);
+    inv = gl_mul(inv, v[j]);
+    v[j] = x;
+  }
 }
 
-// One thread per eight table entries, inverted as a batch: 1 / D_s(x_i) by i mod 64 B (chain = 0: D_s = x^(N/64) - omega_64^-1) or by
-// i mod 128 B (chain = 1: D_s = x^(N/128) - rho, rho = omega_128^-1), from s_sel = s^(N/64) or s^(N/128) and w_sel likewise; 1 / (x^N - 1)
-// by i mod B; and one thread per power gamma^0 .. gamma^337.  Under chain = 1 the same table holds 1 / D_c: x^(N/128) changes its sign
-// 64 B points on, so D_c(x_i) = x_i^(N/128) + rho = -D_s(x_(i + 64 B)).  No entry vanishes: D_s divides x^N - 1, which the caller checked.
+// One thread per eight selector entries, inverted as a batch: 1 / D_s(x_i) by i mod 64 B (chain = 0: D_s = x^(N/64) - omega_64^-1) or by
+// i mod 128 B (chain = 1: D_s = x^(N/128) - rho, rho = omega_128^-1), from s_sel = s^(N/64) or s^(N/128) and w_sel likewise; and one thread
+// per entry of 1 / (x^N - 1) by i mod B and per power gamma^0 .. gamma^337.  Under chain = 1 the same table holds 1 / D_c: x^(N/128)
+// changes its sign 64 B points on, so D_c(x_i) = x_i^(N/128) + rho = -D_s(x_(i + 64 B)).  No entry vanishes: D_s divides x^N - 1, which
+// the caller checked.
 __global__ __launch_bounds__(256) void k_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel,
                                                          uint64_t w_sel, uint64_t rho, const uint64_t* __restrict__ gamma,
                                                          uint64_t* __restrict__ tab) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, first = 8 * k;
-  const uint32_t n_sel = (chain ? 128u : 64u) << log_blowup, n_z = 1u << log_blowup;
-  uint64_t v[8];
-  if (first < n_sel) {  // (n_sel is a multiple of 8)
-    uint64_t x = gl_mul(s_sel, gl_pow(w_sel, first));
+  if (first < ((chain ? 128u : 64u) << log_blowup)) {  // (a multiple of 8)
+    uint64_t v[8], x = gl_mul(s_sel, gl_pow(w_sel, first));
 #pragma unroll
     for (uint32_t j = 0; j < 8; j++, x = gl_mul(x, w_sel)) v[j] = gl_sub(x, rho);
-    air_init_batch_inverse(v, 8);
+    air_init_batch_inverse(v);
 #pragma unroll
     for (uint32_t j = 0; j < 8; j++) tab[AIR5_TAB_SEL + first + j] = v[j];
   }
-  if (first < n_z) {
-    const uint32_t n = n_z - first < 8 ? n_z - first : 8;
-    uint64_t x = gl_mul(s_n, gl_pow(w_n, first));
-#pragma unroll
-    for (uint32_t j = 0; j < 8; j++, x = gl_mul(x, w_n)) v[j] = gl_sub(x, 1);
-    air_init_batch_inverse(v, n);
-#pragma unroll
-    for (uint32_t j = 0; j < 8; j++)
-      if (j < n) tab[AIR5_TAB_ZINV + first + j] = v[j];
+  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_INIT_CONSTRAINTS, tab + AIR5_TAB_ZINV, tab + AIR5_TAB_GPOW);
+}
+
+// The 337 constraints of one proof at one point; chain is uniform.  Behind the bit loop the word constraints, LV, the eight PZ constraints
+// with their CZ bits, the six carry bits, and the sixteen selected linear forms at the next row in two gamma sums of their own, so that
+// the kernel applies D_s once to the start sum and D_c once to the chain sum (empty under chain = 0: E_c = 0).
+template <class F, class View>
+__device__ __forceinline__ void air_init_constraints(View& at, uint32_t chain) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  const RoundWords<F> w = air_round_bits<F>(at, {I_B, I_C, I_D, I_F, I_G, I_H, I_U0, I_U1, I_V, JI_U0, JI_U1, JI_V});
+  at.plain(JI_WORD + 0, A::sub(at.tbl(T_B), w.a));
+  at.plain(JI_WORD + 1, A::sub(at.tbl(T_C), w.b));
+  at.plain(JI_WORD + 2, A::sub(at.tbl(T_D), w.c));
+  at.plain(JI_WORD + 3, A::sub(at.tbl(T_F), w.e));
+  at.plain(JI_WORD + 4, A::sub(at.tbl(T_G), w.f));
+  at.plain(JI_WORD + 5, A::sub(at.tbl(T_H), w.g));
+  at.plain(JI_S0, A::sub(at.again(I_S0), w.s0));
+  at.plain(JI_S1, A::sub(at.again(I_S1), w.s1));
+  at.plain(JI_CH, A::sub(at.again(I_CH), w.ch));
+  at.plain(JI_MAJ, A::sub(at.again(I_MAJ), w.maj));
+  at.plain(JI_LV, A::boolean(at.again(I_LV)));
+  // the six carry bits, folded into the two words 2^32 CA and 2^32 CE at once
+  T ca32 = F::zero(), ce32 = F::zero();
+#pragma unroll View::SHORT
+  for (uint32_t k = 3; k-- > 0;) {
+    const T CA = at.once(I_CA + k), CE = at.once(I_CE + k);
+    at.plain(JI_CARRY + k, A::boolean(CA));
+    at.plain(JI_CARRY + 3 + k, A::boolean(CE));
+    ca32 = A::dbl_add(ca32, CA);
+    ce32 = A::dbl_add(ce32, CE);
   }
-  if (k <= AIR_INIT_CONSTRAINTS) {
-    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
-    tab[AIR5_TAB_GPOW + 2 * k] = g.c0;
-    tab[AIR5_TAB_GPOW + 2 * k + 1] = g.c1;
+  ca32 = A::scale(ca32, 1ull << 32);
+  ce32 = A::scale(ce32, 1ull << 32);
+  // PZ_j - LV' (IV_j + s_j - 2^32 CZ_j), and with each of the six words that stand in row 0 its two selected linear forms: the next
+  // row's word against IV_j LV' (start rows) and against PZ_j (chain rows; skipped under chain = 0, uniformly)
+  const T LVn = at.next(I_LV);
+  T pz3 = F::zero(), pz7 = F::zero();
+#pragma unroll 1
+  for (uint32_t j = 0; j < 8; j++) {
+    const T CZ = at.once(I_CZ + j), PZ = at.once(I_PZ + j);
+    at.plain(JI_CZ + j, A::boolean(CZ));
+    at.plain(JI_PZ + j, A::sub(PZ, A::mul(LVn, A::sub(A::add_const(at.tbl(T_A + j), IV_SHA256[j]), A::scale(CZ, 1ull << 32)))));
+    if (j == 3) pz3 = PZ;
+    if (j == 7) pz7 = PZ;
+    if (j != 3 && j != 7) {
+      const uint32_t k = j < 3 ? j : j - 1;
+      const T xn = at.tbl_next(T_B + j);
+      at.started(JI_START + k, A::sub(xn, A::scale(LVn, IV_SHA256[j])));
+      if (chain) at.chained(JI_CHAIN + k, A::sub(xn, PZ));
+    }
+  }
+  // round 0 of the next row's block: a' and e' against the two sums
+  const T t1 = A::add(A::add(at.next(I_S1), at.next(I_CH)), at.tbl_next(T_W)), t12 = A::add(t1, A::add(at.next(I_S0), at.next(I_MAJ)));
+  const T an = A::add(at.tbl_next(T_A), ca32), en = A::add(at.tbl_next(T_E), ce32);
+  at.started(JI_START + 6, A::sub(an, A::add(A::scale(LVn, INIT_IV7 + INIT_K0), t12)));
+  at.started(JI_START + 7, A::sub(en, A::add(A::scale(LVn, INIT_IV3 + INIT_IV7 + INIT_K0), t1)));
+  if (chain) {  // (uniform)
+    const T kl = A::scale(LVn, INIT_K0);
+    at.chained(JI_CHAIN + 6, A::sub(an, A::add(A::add(pz7, kl), t12)));
+    at.chained(JI_CHAIN + 7, A::sub(en, A::add(A::add(pz3, pz7), A::add(kl, t1))));
   }
 }
 
 // The set-5 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^337), the nine table columns and the 315 helper columns.  It walks the bit index b from 31 down to 0 and per b holds the nine bit
-// words B_b .. V_b and the six rotated ones (B_(b+2), B_(b+13), B_(b+22), F_(b+6), F_(b+11), F_(b+25)), which are re-read through the
-// cache, so the 288 bit words are never held.  Per b: nine constraints (six X^2 - X, U0, U1, V) and one Horner step by 2 of the ten word
-// sums: 13 reduced column products and 18 gamma weights.  Behind the loop the word constraints, LV, the eight PZ constraints with their CZ
-// bits, the six carry bits, and the sixteen selected linear forms at i + B in two gamma sums of their own: 1 / D_s is applied once to the
-// start sum, 1 / D_c once to the chain sum (skipped under chain = 0: E_c = 0), 1 / (x^N - 1) once to the rest.  The gamma sums are lazy.
+// gamma^337), the nine table columns and the 315 helper columns.  Per proof 1 / D_s is applied once to the start sum, 1 / D_c once to the
+// chain sum (skipped under chain = 0), 1 / (x^N - 1) once to the rest.
 __global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain,
                                                                    const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                    const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -1362,112 +1320,13 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_
   const gl2 g337 = {gp[2 * AIR_INIT_CONSTRAINTS], gp[2 * AIR_INIT_CONSTRAINTS + 1]};
   gl2 t = {0, 0};
   for (uint32_t p = n_proofs; p-- > 0;) {
-    const uint64_t* __restrict__ c = cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m);
-    const uint64_t* __restrict__ h = hcols + (((uint64_t)p * AIR_INIT_HELPER_COLS) << log_m);
-    auto once = [&](uint32_t col) { return gl_canon(__builtin_nontemporal_load(h + ((uint64_t)col << log_m) + i)); };
-    auto again = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + i]); };
-    auto next = [&](uint32_t col) { return gl_canon(h[((uint64_t)col << log_m) + nx]); };
-    auto tbl = [&](uint32_t col, uint64_t at) { return gl_canon(c[((uint64_t)col << log_m) + at]); };
-    uint64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0, c0 = 0, c1 = 0;  // the plain, the start and the chain gamma sums, lazy
-    auto plain = [&](uint32_t j, uint64_t v) {
-      a0 = gl_add_lazy(a0, gl_mul(gp[2 * j], v));
-      a1 = gl_add_lazy(a1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto started = [&](uint32_t j, uint64_t v) {
-      b0 = gl_add_lazy(b0, gl_mul(gp[2 * j], v));
-      b1 = gl_add_lazy(b1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto chained = [&](uint32_t j, uint64_t v) {
-      c0 = gl_add_lazy(c0, gl_mul(gp[2 * j], v));
-      c1 = gl_add_lazy(c1, gl_mul(gp[2 * j + 1], v));
-    };
-    auto boolean = [](uint64_t x) { return gl_sub(gl_mul(x, x), x); };
-    auto exor = [](uint64_t x, uint64_t y) {  // x + y - 2 x y
-      const uint64_t xy = gl_mul(x, y);
-      return gl_sub(gl_add(x, y), gl_add(xy, xy));
-    };
-    auto dbl_add = [](uint64_t s, uint64_t x) { return gl_add(gl_add(s, s), x); };
-    uint64_t wb = 0, wc = 0, wd = 0, wf = 0, wg = 0, wh = 0, ws0 = 0, ws1 = 0, wch = 0, wmj = 0;
-#pragma unroll 2
-    for (uint32_t b = 32; b-- > 0;) {
-      const uint64_t B = again(I_B + b), C = once(I_C + b), D = once(I_D + b), F = again(I_F + b), G = once(I_G + b), H = once(I_H + b);
-      const uint64_t U0 = once(I_U0 + b), U1 = once(I_U1 + b), V = once(I_V + b);
-      const uint64_t B2 = again(I_B + ((b + 2) & 31)), B13 = again(I_B + ((b + 13) & 31)), B22 = again(I_B + ((b + 22) & 31));
-      const uint64_t F6 = again(I_F + ((b + 6) & 31)), F11 = again(I_F + ((b + 11) & 31)), F25 = again(I_F + ((b + 25) & 31));
-      plain(I_B + b, boolean(B));
-      plain(I_C + b, boolean(C));
-      plain(I_D + b, boolean(D));
-      plain(I_F + b, boolean(F));
-      plain(I_G + b, boolean(G));
-      plain(I_H + b, boolean(H));
-      plain(JI_U0 + b, gl_sub(U0, exor(B2, B13)));
-      plain(JI_U1 + b, gl_sub(U1, exor(F6, F11)));
-      plain(JI_V + b, gl_sub(V, gl_mul(B, C)));
-      wb = dbl_add(wb, B);
-      wc = dbl_add(wc, C);
-      wd = dbl_add(wd, D);
-      wf = dbl_add(wf, F);
-      wg = dbl_add(wg, G);
-      wh = dbl_add(wh, H);
-      ws0 = dbl_add(ws0, exor(U0, B22));
-      ws1 = dbl_add(ws1, exor(U1, F25));
-      wch = dbl_add(wch, gl_add(H, gl_mul(F, gl_sub(G, H))));
-      wmj = dbl_add(wmj, gl_add(V, gl_mul(D, gl_sub(gl_add(B, C), gl_add(V, V)))));
-    }
-    plain(JI_WORD + 0, gl_sub(tbl(T_B, i), wb));
-    plain(JI_WORD + 1, gl_sub(tbl(T_C, i), wc));
-    plain(JI_WORD + 2, gl_sub(tbl(T_D, i), wd));
-    plain(JI_WORD + 3, gl_sub(tbl(T_F, i), wf));
-    plain(JI_WORD + 4, gl_sub(tbl(T_G, i), wg));
-    plain(JI_WORD + 5, gl_sub(tbl(T_H, i), wh));
-    plain(JI_S0, gl_sub(again(I_S0), ws0));
-    plain(JI_S1, gl_sub(again(I_S1), ws1));
-    plain(JI_CH, gl_sub(again(I_CH), wch));
-    plain(JI_MAJ, gl_sub(again(I_MAJ), wmj));
-    plain(JI_LV, boolean(again(I_LV)));
-    // the six carry bits, folded into the two words 2^32 CA and 2^32 CE at once
-    uint64_t ca32 = 0, ce32 = 0;
-#pragma unroll
-    for (uint32_t k = 3; k-- > 0;) {
-      const uint64_t CA = once(I_CA + k), CE = once(I_CE + k);
-      plain(JI_CARRY + k, boolean(CA));
-      plain(JI_CARRY + 3 + k, boolean(CE));
-      ca32 = dbl_add(ca32, CA);
-      ce32 = dbl_add(ce32, CE);
-    }
-    ca32 = gl_mul(ca32, 1ull << 32);
-    ce32 = gl_mul(ce32, 1ull << 32);
-    // PZ_j - LV' (IV_j + s_j - 2^32 CZ_j), and with each of the six words that stand in row 0 its two selected linear forms: the next
-    // row's word against IV_j LV' (start rows) and against PZ_j (chain rows; skipped under chain = 0, uniformly)
-    const uint64_t LVn = next(I_LV);
-    uint64_t pz3 = 0, pz7 = 0;
-#pragma unroll 1
-    for (uint32_t j = 0; j < 8; j++) {
-      const uint64_t CZ = once(I_CZ + j), PZ = once(I_PZ + j);
-      plain(JI_CZ + j, boolean(CZ));
-      plain(JI_PZ + j, gl_sub(PZ, gl_mul(LVn, gl_sub(gl_add(tbl(T_A + j, i), IV_SHA256[j]), gl_mul(CZ, 1ull << 32)))));
-      if (j == 3) pz3 = PZ;
-      if (j == 7) pz7 = PZ;
-      if (j != 3 && j != 7) {
-        const uint32_t k = j < 3 ? j : j - 1;
-        const uint64_t xn = tbl(T_B + j, nx);
-        started(JI_START + k, gl_sub(xn, gl_mul(LVn, IV_SHA256[j])));
-        if (chain) chained(JI_CHAIN + k, gl_sub(xn, PZ));
-      }
-    }
-    // round 0 of the next row's block: a' and e' against the two sums
-    const uint64_t t1 = gl_add(gl_add(next(I_S1), next(I_CH)), tbl(T_W, nx)), t12 = gl_add(t1, gl_add(next(I_S0), next(I_MAJ)));
-    const uint64_t an = gl_add(tbl(T_A, nx), ca32), en = gl_add(tbl(T_E, nx), ce32);
-    started(JI_START + 6, gl_sub(an, gl_add(gl_mul(LVn, INIT_IV7 + INIT_K0), t12)));
-    started(JI_START + 7, gl_sub(en, gl_add(gl_mul(LVn, INIT_IV3 + INIT_IV7 + INIT_K0), t1)));
-    uint64_t v0 = gl_add(gl_mul(gl_canon(a0), zinv), gl_mul(gl_canon(b0), dsinv));
-    uint64_t v1 = gl_add(gl_mul(gl_canon(a1), zinv), gl_mul(gl_canon(b1), dsinv));
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_INIT_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_init_constraints<FieldP>(at, chain);
+    uint64_t v0 = gl_add(gl_mul(gl_canon(at.a0), zinv), gl_mul(gl_canon(at.b0), dsinv));
+    uint64_t v1 = gl_add(gl_mul(gl_canon(at.a1), zinv), gl_mul(gl_canon(at.b1), dsinv));
     if (chain) {  // (uniform)
-      const uint64_t kl = gl_mul(LVn, INIT_K0);
-      chained(JI_CHAIN + 6, gl_sub(an, gl_add(gl_add(pz7, kl), t12)));
-      chained(JI_CHAIN + 7, gl_sub(en, gl_add(gl_add(pz3, pz7), gl_add(kl, t1))));
-      v0 = gl_add(v0, gl_mul(gl_canon(c0), dcinv));
-      v1 = gl_add(v1, gl_mul(gl_canon(c1), dcinv));
+      v0 = gl_add(v0, gl_mul(gl_canon(at.c0), dcinv));
+      v1 = gl_add(v1, gl_mul(gl_canon(at.c1), dcinv));
     }
     t = gl2_add(gl2_mul(t, g337), {v0, v1});
   }
@@ -1476,147 +1335,34 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_
 }
 
 // The set-5 identity at zeta, one workgroup, division-free: gamma^0 .. gamma^337 go to LDS first; thread t takes the proofs t, t + 256, ...
-// and evaluates their 337 constraints over F_p^2 from the table's and the helper's openings at zeta (y0) and zeta omega_N (y1) in the
-// order of the hot pass, in three sums.  With z = zeta^(N/128), D_s = z - rho, D_c = z + rho and S = D_s D_c under chain = 1 (z =
-// zeta^(N/64), S = z - rho, D_c = 1 and no chain sum under chain = 0), a proof contributes S a + (zeta^N - 1) (D_c b + D_s c); the sums meet
-// in LDS; thread 0 compares with (u_0 + X u_1) (zeta^N - 1) S.
+// and evaluates their 337 constraints over F_p^2 from the table's and the helper's openings, in three sums.  With z = zeta^(N/128),
+// D_s = z - rho, D_c = z + rho and S = D_s D_c under chain = 1 (z = zeta^(N/64), S = z - rho, D_c = 1 and no chain sum under chain = 0), a
+// proof contributes gamma^(337 p) (S a + (zeta^N - 1) (D_c b + D_s c)); the sum is compared with (u_0 + X u_1) (zeta^N - 1) S.
 __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
                                                                        uint32_t chain, uint64_t rho, const uint64_t* __restrict__ open_t,
                                                                        const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
                                                                        const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
                                                                        uint32_t n_queries, uint32_t* __restrict__ ok) {
-  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
   __shared__ uint64_t gpw[2 * (AIR_INIT_CONSTRAINTS + 1)];
-  __shared__ uint32_t holds;
-  const uint32_t t = threadIdx.x;
-  const uint64_t RT = 1ull << log_r_t, RH = 1ull << log_r_h;
-  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
-  for (uint32_t k = t; k <= AIR_INIT_CONSTRAINTS; k += AIR_CHECK_THREADS) {
-    const gl2 gk = gl2_pow(g, k);
-    gpw[2 * k] = gk.c0;
-    gpw[2 * k + 1] = gk.c1;
-  }
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_INIT_CONSTRAINTS, gpw);
   __syncthreads();
   const uint32_t log_sel = chain ? 7 : 6;
-  gl2 zp = z;  // zeta^(N/128) or zeta^(N/64)
+  gl2 zp = {zeta[0], zeta[1]};  // zeta^(N/128) or zeta^(N/64)
   for (uint32_t k = log_sel; k < log_sub; k++) zp = gl2_mul(zp, zp);
   gl2 zn = zp;  // zeta^N
   for (uint32_t k = 0; k < log_sel; k++) zn = gl2_mul(zn, zn);
   const gl2 zn1 = {gl_sub(zn.c0, 1), zn.c1};
   const gl2 Ds = {gl_sub(zp.c0, rho), zp.c1}, Dc = chain ? gl2{gl_add(zp.c0, rho), zp.c1} : gl2{1, 0};
   const gl2 S = chain ? gl2_mul(Ds, Dc) : Ds;
-  auto t0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[c]), gl_canon(open_t[RT + c])}; };
-  auto t1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_t[2 * RT + c]), gl_canon(open_t[3 * RT + c])}; };
-  auto h0 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[c]), gl_canon(open_h[RH + c])}; };
-  auto h1 = [&](uint64_t c) -> gl2 { return {gl_canon(open_h[2 * RH + c]), gl_canon(open_h[3 * RH + c])}; };
-  auto boolean = [](gl2 x) { return gl2_sub(gl2_mul(x, x), x); };
-  auto exor = [](gl2 x, gl2 y) {
-    const gl2 xy = gl2_mul(x, y);
-    return gl2_sub(gl2_add(x, y), gl2_add(xy, xy));
-  };
-  auto dbl_add = [](gl2 s, gl2 x) { return gl2_add(gl2_add(s, s), x); };
   gl2 sum = {0, 0};
-  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
-    const uint64_t ct = (uint64_t)p * AIR_SHA_WIDTH, chh = (uint64_t)p * AIR_INIT_HELPER_COLS;
-    gl2 a = {0, 0}, bs = {0, 0}, bc = {0, 0};
-    auto plain = [&](uint32_t j, gl2 v) { a = gl2_add(a, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    auto started = [&](uint32_t j, gl2 v) { bs = gl2_add(bs, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    auto chained = [&](uint32_t j, gl2 v) { bc = gl2_add(bc, gl2_mul({gpw[2 * j], gpw[2 * j + 1]}, v)); };
-    gl2 wb = {0, 0}, wc = wb, wd = wb, wf = wb, wg = wb, wh = wb, ws0 = wb, ws1 = wb, wch = wb, wmj = wb;
-    for (uint32_t b = 32; b-- > 0;) {
-      const gl2 B = h0(chh + I_B + b), C = h0(chh + I_C + b), D = h0(chh + I_D + b), F = h0(chh + I_F + b), G = h0(chh + I_G + b),
-                H = h0(chh + I_H + b), U0 = h0(chh + I_U0 + b), U1 = h0(chh + I_U1 + b), V = h0(chh + I_V + b);
-      const gl2 B2 = h0(chh + I_B + ((b + 2) & 31)), B13 = h0(chh + I_B + ((b + 13) & 31)), B22 = h0(chh + I_B + ((b + 22) & 31));
-      const gl2 F6 = h0(chh + I_F + ((b + 6) & 31)), F11 = h0(chh + I_F + ((b + 11) & 31)), F25 = h0(chh + I_F + ((b + 25) & 31));
-      plain(I_B + b, boolean(B));
-      plain(I_C + b, boolean(C));
-      plain(I_D + b, boolean(D));
-      plain(I_F + b, boolean(F));
-      plain(I_G + b, boolean(G));
-      plain(I_H + b, boolean(H));
-      plain(JI_U0 + b, gl2_sub(U0, exor(B2, B13)));
-      plain(JI_U1 + b, gl2_sub(U1, exor(F6, F11)));
-      plain(JI_V + b, gl2_sub(V, gl2_mul(B, C)));
-      wb = dbl_add(wb, B);
-      wc = dbl_add(wc, C);
-      wd = dbl_add(wd, D);
-      wf = dbl_add(wf, F);
-      wg = dbl_add(wg, G);
-      wh = dbl_add(wh, H);
-      ws0 = dbl_add(ws0, exor(U0, B22));
-      ws1 = dbl_add(ws1, exor(U1, F25));
-      wch = dbl_add(wch, gl2_add(H, gl2_mul(F, gl2_sub(G, H))));
-      wmj = dbl_add(wmj, gl2_add(V, gl2_mul(D, gl2_sub(gl2_add(B, C), gl2_add(V, V)))));
-    }
-    plain(JI_WORD + 0, gl2_sub(t0(ct + T_B), wb));
-    plain(JI_WORD + 1, gl2_sub(t0(ct + T_C), wc));
-    plain(JI_WORD + 2, gl2_sub(t0(ct + T_D), wd));
-    plain(JI_WORD + 3, gl2_sub(t0(ct + T_F), wf));
-    plain(JI_WORD + 4, gl2_sub(t0(ct + T_G), wg));
-    plain(JI_WORD + 5, gl2_sub(t0(ct + T_H), wh));
-    plain(JI_S0, gl2_sub(h0(chh + I_S0), ws0));
-    plain(JI_S1, gl2_sub(h0(chh + I_S1), ws1));
-    plain(JI_CH, gl2_sub(h0(chh + I_CH), wch));
-    plain(JI_MAJ, gl2_sub(h0(chh + I_MAJ), wmj));
-    plain(JI_LV, boolean(h0(chh + I_LV)));
-    gl2 ca32 = {0, 0}, ce32 = {0, 0};
-    for (uint32_t k = 3; k-- > 0;) {
-      const gl2 CA = h0(chh + I_CA + k), CE = h0(chh + I_CE + k);
-      plain(JI_CARRY + k, boolean(CA));
-      plain(JI_CARRY + 3 + k, boolean(CE));
-      ca32 = dbl_add(ca32, CA);
-      ce32 = dbl_add(ce32, CE);
-    }
-    ca32 = gl2_scale(ca32, 1ull << 32);
-    ce32 = gl2_scale(ce32, 1ull << 32);
-    const gl2 LVn = h1(chh + I_LV);
-    gl2 pz3 = {0, 0}, pz7 = {0, 0};
-#pragma unroll 1
-    for (uint32_t j = 0; j < 8; j++) {
-      const gl2 CZ = h0(chh + I_CZ + j), PZ = h0(chh + I_PZ + j);
-      gl2 s = t0(ct + T_A + j);
-      s.c0 = gl_add(s.c0, IV_SHA256[j]);
-      plain(JI_CZ + j, boolean(CZ));
-      plain(JI_PZ + j, gl2_sub(PZ, gl2_mul(LVn, gl2_sub(s, gl2_scale(CZ, 1ull << 32)))));
-      if (j == 3) pz3 = PZ;
-      if (j == 7) pz7 = PZ;
-      if (j != 3 && j != 7) {
-        const uint32_t k = j < 3 ? j : j - 1;
-        const gl2 xn = t1(ct + T_B + j);
-        started(JI_START + k, gl2_sub(xn, gl2_scale(LVn, IV_SHA256[j])));
-        if (chain) chained(JI_CHAIN + k, gl2_sub(xn, PZ));
-      }
-    }
-    const gl2 tt = gl2_add(gl2_add(h1(chh + I_S1), h1(chh + I_CH)), t1(ct + T_W)), tt2 = gl2_add(tt, gl2_add(h1(chh + I_S0), h1(chh + I_MAJ)));
-    const gl2 an = gl2_add(t1(ct + T_A), ca32), en = gl2_add(t1(ct + T_E), ce32);
-    started(JI_START + 6, gl2_sub(an, gl2_add(gl2_scale(LVn, INIT_IV7 + INIT_K0), tt2)));
-    started(JI_START + 7, gl2_sub(en, gl2_add(gl2_scale(LVn, INIT_IV3 + INIT_IV7 + INIT_K0), tt)));
-    if (chain) {
-      const gl2 kl = gl2_scale(LVn, INIT_K0);
-      chained(JI_CHAIN + 6, gl2_sub(an, gl2_add(gl2_add(pz7, kl), tt2)));
-      chained(JI_CHAIN + 7, gl2_sub(en, gl2_add(gl2_add(pz3, pz7), gl2_add(kl, tt))));
-    }
-    const gl2 v = gl2_add(gl2_mul(S, a), gl2_mul(zn1, gl2_add(gl2_mul(Dc, bs), gl2_mul(Ds, bc))));
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA_WIDTH, open_h + (uint64_t)p * AIR_INIT_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_init_constraints<FieldP2>(at, chain);
+    const gl2 v = gl2_add(gl2_mul(S, at.a), gl2_mul(zn1, gl2_add(gl2_mul(Dc, at.b), gl2_mul(Ds, at.c))));
     sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_INIT_CONSTRAINTS * p), v));
   }
-  red[0][t] = sum.c0;
-  red[1][t] = sum.c1;
-  for (uint32_t hh = AIR_CHECK_THREADS / 2; hh; hh >>= 1) {
-    __syncthreads();
-    if (t < hh) {
-      red[0][t] = gl_add(red[0][t], red[0][t + hh]);
-      red[1][t] = gl_add(red[1][t], red[1][t + hh]);
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    const gl2 u0 = {gl_canon(open_q[0]), gl_canon(open_q[2])}, u1 = {gl_canon(open_q[1]), gl_canon(open_q[3])};
-    const gl2 q = {gl_add(u0.c0, gl_mul(u1.c1, 7)), gl_add(u0.c1, u1.c0)};
-    holds = gl2_eq({red[0][0], red[1][0]}, gl2_mul(gl2_mul(q, zn1), S)) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!holds)
-    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+  air_check_verdict(sum, open_q, gl2_mul(zn1, S), n_queries, ok);
 }
 
 int launch_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream) {

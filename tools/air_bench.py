@@ -30,8 +30,11 @@
   parent   the set commit + prove WITHOUT any air call, then the set-3 and set-4 set-level calls on HEADER (MODE=set_plain,sets34), for library
            builds named in LIBS (comma separated), one subprocess per measurement, alternating under TMX_LIB (differences between boxes exceed
            most changes: compare inside one call).
-Times per call from HIP events around REPS back-to-back calls after one warm call.
+Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
+SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
+(one of them named by TMX_LIB) say that both write the same words at the timed size.
    P=64 N=128 python tools/air_bench.py   (BLOWUP=3 CAP=4 ARITY=4 FINAL=5 QUERIES=28 CHUNK=512 REPS=5 ROUNDS=3 by default)"""
+import hashlib
 import json
 import os
 import subprocess
@@ -44,6 +47,7 @@ P, n = int(os.environ.get("P", "64")), int(os.environ.get("N", "128"))
 log_blowup, cap_h, reps = int(os.environ.get("BLOWUP", "3")), int(os.environ.get("CAP", "4")), int(os.environ.get("REPS", "5"))
 arity, final_max, nq = int(os.environ.get("ARITY", "4")), int(os.environ.get("FINAL", "5")), int(os.environ.get("QUERIES", "28"))
 chunk, rounds = int(os.environ.get("CHUNK", "512")), int(os.environ.get("ROUNDS", "3"))
+seed = int(os.environ.get("SEED", "1"))
 r4 = lambda x: round(x, 4)
 
 if "parent" in modes:
@@ -64,6 +68,13 @@ from tendermintx_amd import Context, _lib  # noqa: E402
 from tendermintx_amd.context import KIND_SKIP  # noqa: E402
 
 dev = torch.device("cuda:0")
+
+
+def words_digest(call, buf):
+    """SHA-256 of the words `call` leaves in the device buffer `buf`"""
+    call()
+    torch.cuda.synchronize(dev)
+    return hashlib.sha256(buf.cpu().numpy().tobytes()).hexdigest()
 
 
 def timed(fn, k, before=None):
@@ -137,6 +148,7 @@ if "kernels2" in modes:
 if "sha" in modes:
     log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("SHA_PROOFS", "64"))
     log_rows, n_cols, n_hcols = log_m - log_blowup, 9 * cp, 300 * cp
+    torch.manual_seed(seed)
     ctx = Context(4, b"celestia", device=0)
     table = torch.randint(0, 2**62, (n_cols << log_rows,), dtype=torch.int64, device=dev)
     pre = torch.empty(n_hcols << log_rows, dtype=torch.int64, device=dev)
@@ -160,6 +172,9 @@ if "sha" in modes:
                                                                                             caps[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0), reps)))
         res["fri_prove_table_ms"].append(r4(timed(lambda: ctx.fri_prove_device(fp, cols.data_ptr(), caps[0].data_ptr(), proof.data_ptr(), 0), reps)))
         res["fri_combine_stage_ms"].append(r4(ctx.fri_last_ms()["combine"]))
+    res["quotient_sha256"] = words_digest(lambda: ctx.air_sha256_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols.data_ptr(),
+                                                                                 caps[0][-(4 << cap_h):].data_ptr(),
+                                                                                 caps[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0), quot)
     best = min(res["sha_quotient_call_ms"])
     res["sha_gb_per_s"] = round(words * 8 / best / 1e6, 1)
     res["helper_store_gb_per_s"] = round((n_hcols << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e6, 1)
@@ -209,6 +224,7 @@ if "sha" in modes:
 if "sched" in modes:
     log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("SHA_PROOFS", "64"))
     log_rows, n_cols, n_h3, n_h4 = log_m - log_blowup, 9 * cp, 300 * cp, 115 * cp
+    torch.manual_seed(seed)
     ctx = Context(4, b"celestia", device=0)
     table = torch.randint(0, 2**62, (n_cols << log_rows,), dtype=torch.int64, device=dev)
     pre = torch.empty(n_h4 << log_rows, dtype=torch.int64, device=dev)
@@ -229,6 +245,8 @@ if "sched" in modes:
             log_m, log_blowup, cap_h, cp, cols.data_ptr(), h4.data_ptr(), caps[0].data_ptr(), caps[2].data_ptr(), quot.data_ptr(), 0), reps)))
         res["sha_quotient_call_ms"].append(r4(timed(lambda: ctx.air_sha256_quotient_device(
             log_m, log_blowup, cap_h, cp, cols.data_ptr(), h3.data_ptr(), caps[0].data_ptr(), caps[1].data_ptr(), quot.data_ptr(), 0), reps)))
+    res["quotient_sha256"] = words_digest(lambda: ctx.air_sha256_sched_quotient_device(
+        log_m, log_blowup, cap_h, cp, cols.data_ptr(), h4.data_ptr(), caps[0].data_ptr(), caps[2].data_ptr(), quot.data_ptr(), 0), quot)
     best = min(res["sched_quotient_call_ms"])
     res["sched_gb_per_s"] = round(((n_cols + n_h4) << log_m) * 8 / best / 1e6, 1)
     res["helper_store_gb_per_s"] = round((n_h4 << log_rows) * 8 / min(res["sched_helper_kernel_ms"]) / 1e6, 1)
@@ -290,6 +308,7 @@ if "init" in modes or "sets34" in modes:
     if not only34:
         log_m, cp, chain = int(os.environ.get("LOG_M", "16")), int(os.environ.get("SHA_PROOFS", "64")), int(os.environ.get("CHAIN", "1"))
         log_rows, n_cols, n_h3, n_h5 = log_m - log_blowup, 9 * cp, 300 * cp, 315 * cp
+        torch.manual_seed(seed)
         ctx = Context(4, b"celestia", device=0)
         table = torch.randint(0, 2**62, (n_cols << log_rows,), dtype=torch.int64, device=dev)
         pre = torch.empty(n_h5 << log_rows, dtype=torch.int64, device=dev)
@@ -311,6 +330,8 @@ if "init" in modes or "sets34" in modes:
                 log_m, log_blowup, cap_h, cp, chain, cols.data_ptr(), h5.data_ptr(), caps[0].data_ptr(), caps[2].data_ptr(), quot.data_ptr(), 0), reps)))
             res["sha_quotient_call_ms"].append(r4(timed(lambda: ctx.air_sha256_quotient_device(
                 log_m, log_blowup, cap_h, cp, cols.data_ptr(), h3.data_ptr(), caps[0].data_ptr(), caps[1].data_ptr(), quot.data_ptr(), 0), reps)))
+        res["quotient_sha256"] = words_digest(lambda: ctx.air_sha256_init_quotient_device(
+            log_m, log_blowup, cap_h, cp, chain, cols.data_ptr(), h5.data_ptr(), caps[0].data_ptr(), caps[2].data_ptr(), quot.data_ptr(), 0), quot)
         best = min(res["init_quotient_call_ms"])
         res["init_gb_per_s"] = round(((n_cols + n_h5) << log_m) * 8 / best / 1e6, 1)
         res["helper_store_gb_per_s"] = round((n_h5 << log_rows) * 8 / min(res["init_helper_kernel_ms"]) / 1e6, 1)
