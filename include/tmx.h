@@ -1292,6 +1292,65 @@ int32_t tmx_air_sha256_init_verify_device(tmx_ctx* ctx, const tmx_batch_params* 
                                           const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 
+/* ---- streamed helpers of the SHA-256 sets: constraint sets 3, 4 and 5 on full-size tables ----
+ * The helper oracle of a set is 300, 115 or 315 columns per proof, 13 to 35 times its table; kept extended it is what bounds the size the
+ * set-level calls above can run at.  Here the helper is fed in chunks of whole proofs and never exists extended; the table member stays
+ * resident, and so do the helper's PRE-LDE columns (the prove's openings at zeta read them).  Field arithmetic is exact, so the pieces in
+ * any order give the resident call's words: for every valid chunk size d_cap_h, d_cap_q, tmx_air_last_gamma,
+ * tmx_trace_commit_set_shape and every word of tmx_trace_commit_set_prove_device's proof equal the resident call's.  Resident and
+ * streamed pairs may be mixed within a set and within a section; the verifiers need nothing.
+ *   tmx_air_sha256_quotient_range_device, _sched_quotient_range_device, _init_quotient_range_device
+ *                                          the quotient calls over the proofs [proof_lo, proof_hi) of the table only, as
+ *                                          tmx_air_ladder_quotient_range_device: d_cols is still the whole table's column 0, but
+ *                                          d_helper_cols is the FIRST HELPER COLUMN OF PROOF proof_lo -- a buffer that holds the piece's
+ *                                          columns alone will do.  gamma is drawn over n_proofs; the piece's sum is weighted with
+ *                                          gamma^(C proof_lo), C = 315, 117 or 337, divided as the whole call divides, and written
+ *                                          (accumulate = 0) or added to what d_quot holds and written canonical (accumulate = 1).  Pieces
+ *                                          that cover [0, n_proofs) once, in any order, the first with accumulate = 0, leave the whole
+ *                                          call's words.  TMX_ERR_BAD_ARG: an empty range, proof_hi > n_proofs, accumulate > 1, and the
+ *                                          whole call's rules.
+ *   tmx_trace_commit_set_air_sha256_streamed_bytes   host only: the bytes the call below allocates for its [set][section] scratch -- pre-LDE
+ *                                          helper | helper levels | quotient | quotient levels | sponge states [12][M] | chunk
+ *                                          [chunk_proofs helper_cols][M] -- and, in *lde_scratch_bytes (may be null), the LDE's own scratch:
+ *                                          twice what is extended at once, which is one chunk (ONE transform call per chunk, as the prove's
+ *                                          gather extends a streamed member; per-proof calls would need 1 / chunk_proofs of it but the
+ *                                          prove grows it to the chunk regardless).  With chunk_proofs >= n_proofs: the resident call's
+ *                                          (helper_cols n_proofs (N + M) + 2 M) 8 bytes plus two trees, and twice one proof's helper columns.
+ *                                          0 on a refused shape: constraint_set outside 3 .. 5, chunk_proofs = 0, chunk_proofs helper_cols
+ *                                          no multiple of 8 (the sponge absorbs eight columns at a time: chunk_proofs even for set 3, a
+ *                                          multiple of 8 for sets 4 and 5), log_blowup outside 1 .. 6, fewer than 64 rows, n_proofs = 0,
+ *                                          helper_cols n_proofs > 2^24.
+ *   tmx_trace_commit_set_air_sha256_streamed_device   the set-level call of constraint_set 3, 4 or 5 on `section`.  chunk_proofs >=
+ *                                          n_proofs takes the resident path exactly.  Else: the helper kernel into the pre-LDE columns;
+ *                                          sweep 1, per chunk the LDE into the chunk buffer and k_poseidon_leaves_chunk, then the levels and
+ *                                          d_cap_h; gamma; sweep 2, per chunk the LDE again and the accumulating piece of the quotient; the
+ *                                          quotient's tree and d_cap_q.  Both sweeps run under the set's NTT domain: if
+ *                                          tmx_ntt_set_domain moved the context's it is put back for the call and restored after.  The pair
+ *                                          is registered by the resident calls' rules (same place by set id, same refusals); a streamed
+ *                                          scratch is sized exactly (a larger one left by a resident call on that set and section is
+ *                                          released).  TMX_ERR_BAD_ARG: no set, constraint_set outside 3 .. 5, a wrong, absent or streamed
+ *                                          section (the TABLE member must be resident), null caps, a chunk_proofs _bytes refuses, a second
+ *                                          call on the section in either form, a full set.  TMX_ERR_CAPACITY against free memory, the
+ *                                          LDE's scratch included.  At 256 proofs, blow-up 8 and chunk_proofs = 8 the three pairs of TREE
+ *                                          (N = 2^15) need about 49 GB of helper columns where the resident calls need about 441 GB.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream apart from a domain change. */
+int32_t tmx_air_sha256_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                             const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                             void* hip_stream);
+int32_t tmx_air_sha256_sched_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                   uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                   uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_init_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t chain, uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  uint64_t* d_quot, void* hip_stream);
+uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
+                                                        uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes);
+int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* ctx, uint32_t constraint_set, uint32_t section, uint32_t chunk_proofs,
+                                                        uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:
  * out_words[16 i .. 16 i + 7] = Fermat, out_words[16 i + 8 .. 16 i + 15] = division steps.  Host buffers, blocking. */

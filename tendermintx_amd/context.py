@@ -496,9 +496,17 @@ class Context:
         """the helper oracle (300 n_proofs columns of 2^log_rows words at d_helper) from the pre-LDE table columns (9 n_proofs) at d_table"""
         check(self._L.tmx_air_sha256_helper_device(self._h, log_rows, n_proofs, d_table, d_helper, self._stream(stream)), self._h)
 
-    def air_sha256_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, stream=None):
+    def air_sha256_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, stream=None,
+                                   proof_range=None, accumulate=0):
         """gamma from the table cap and the helper cap, then the quotient of the 315 constraints per proof over the extended table and helper
-        columns into d_quot (planar, 2 << log_n words)"""
+        columns into d_quot (planar, 2 << log_n words).  proof_range = (lo, hi): those proofs' terms only, d_cols still the whole table's
+        column 0 but d_helper_cols the first helper column of proof lo (a buffer that holds the piece alone will do); added to what d_quot
+        holds if accumulate"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha256_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                               d_helper_cols, d_cap, d_cap_helper, d_quot, self._stream(stream)), self._h)
+            return
         check(self._L.tmx_air_sha256_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper,
                                                      d_quot, self._stream(stream)), self._h)
 
@@ -517,9 +525,14 @@ class Context:
         check(self._L.tmx_air_sha256_sched_helper_device(self._h, log_rows, n_proofs, d_table, d_helper, self._stream(stream)), self._h)
 
     def air_sha256_sched_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot,
-                                         stream=None):
+                                         stream=None, proof_range=None, accumulate=0):
         """gamma from the table cap and the helper cap, then the quotient of the 117 constraints per proof over the extended table and helper
-        columns into d_quot (planar, 2 << log_n words)"""
+        columns into d_quot (planar, 2 << log_n words); proof_range and accumulate as in air_sha256_quotient_device"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha256_sched_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                                     d_helper_cols, d_cap, d_cap_helper, d_quot, self._stream(stream)), self._h)
+            return
         check(self._L.tmx_air_sha256_sched_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap,
                                                            d_cap_helper, d_quot, self._stream(stream)), self._h)
 
@@ -540,9 +553,15 @@ class Context:
         check(self._L.tmx_air_sha256_init_helper_device(self._h, log_rows, n_proofs, chain, d_table, d_helper, self._stream(stream)), self._h)
 
     def air_sha256_init_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot,
-                                        stream=None):
+                                        stream=None, proof_range=None, accumulate=0):
         """gamma from the table cap and the helper cap, then the quotient of the 337 constraints per proof over the extended table and helper
-        columns into d_quot (planar, 2 << log_n words)"""
+        columns into d_quot (planar, 2 << log_n words); proof_range and accumulate as in air_sha256_quotient_device"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha256_init_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, chain, lo, hi, int(accumulate),
+                                                                    d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, self._stream(stream)),
+                  self._h)
+            return
         check(self._L.tmx_air_sha256_init_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap,
                                                           d_cap_helper, d_quot, self._stream(stream)), self._h)
 
@@ -555,6 +574,13 @@ class Context:
         """adds the block-start helper and quotient of the resident member `section` (SHA256, TREE or HEADER) to the commit set, behind the
         last helper/quotient pair that already follows the table"""
         check(self._L.tmx_trace_commit_set_air_sha256_init_device(self._h, section, d_cap_h, d_cap_q, self._stream(stream)), self._h)
+
+    # ---- streamed helpers of constraint sets 3 - 5 (include/tmx.h "streamed helpers of the SHA-256 sets")
+    def trace_commit_set_air_sha256_streamed_device(self, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q, stream=None):
+        """the set-level call of constraint set 3, 4 or 5 with the helper fed in chunks of chunk_proofs whole proofs and never resident
+        extended: the same caps, gamma, shape and proof words as the resident call"""
+        check(self._L.tmx_trace_commit_set_air_sha256_streamed_device(self._h, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q,
+                                                                      self._stream(stream)), self._h)
 
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
@@ -700,6 +726,15 @@ def trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols
     would refuse"""
     L = L or _lib.lib()
     return int(L.tmx_trace_commit_set_bytes(kind, n_max, n_proofs, sections, streamed, chunk_cols, log_blowup, cap_height))
+
+
+def trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs, L=None):
+    """tmx_trace_commit_set_air_sha256_streamed_bytes (no context, no device): (scratch bytes of the streamed set-level call, the LDE's own
+    scratch in bytes); (0, 0) for a refused shape"""
+    L = L or _lib.lib()
+    lde = C.c_uint64(0)
+    return int(L.tmx_trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs,
+                                                                 C.byref(lde))), int(lde.value)
 
 
 def air_ladder_public_shape(kind, n_max, n_proofs, L=None):

@@ -68,25 +68,29 @@ int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t
 // kernel of its own (poseidon.hip k_air_sha_gamma: k_fri_transcript stays as it is).
 constexpr uint32_t AIR_SHA_WIDTH = 9, AIR_SHA_HELPER_COLS = 300, AIR_SHA_CONSTRAINTS = 315;
 // The tables one set-3 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [316][2]               gamma^0 .. gamma^315
+//   gpow  [317][2]               gamma^0 .. gamma^315, then gamma^(315 first): the exponent offset of a piece's first proof
 //   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
 //   sel   [64 << log_blowup]     S(x_i) = x_i^(N/64) - omega_64^-1, by i mod (64 << log_blowup)
 //   kx    [64 << log_blowup]     K(x_i) = P_K(x_i^(N/64)), same period
 constexpr uint32_t AIR3_TAB_GPOW = 0, AIR3_TAB_ZINV = 640, AIR3_TAB_SEL = 704, AIR3_TAB_K = AIR3_TAB_SEL + (64u << 6);
 constexpr uint64_t AIR3_TAB_WORDS = AIR3_TAB_K + (64u << 6);
-static_assert(AIR3_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6), "the set-3 tables live in the table part of set 1's scratch");
+static_assert(2 * (AIR_SHA_CONSTRAINTS + 2) <= AIR3_TAB_ZINV && AIR3_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6), "the set-3 tables live in the table part of set 1's scratch");
 // gamma of set 3 (one lane): 2^33, obs[0 .. 5) = {3, log_n, log_blowup, cap_height, n_proofs}, cap_words words at d_cap, cap_words words
 // at d_cap_helper; the duplex is left at d_state (32 words), gamma at d_chal[FRI_GAMMA_AT]
 int launch_air_sha_gamma(const void* d_consts, int mode, const uint32_t obs[5], uint32_t cap_words, const void* d_cap, const void* d_cap_helper,
                          void* d_state, void* d_chal, void* stream);
 // The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 300 n_proofs
 int launch_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
-// s_n = s^N, w_n = w^N, s_n64 = s^(N/64), w_n64 = w^(N/64), om64_inv = omega_64^-1; gamma at d_gamma (2 words)
-int launch_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+// s_n = s^N, w_n = w^N, s_n64 = s^(N/64), w_n64 = w^(N/64), om64_inv = omega_64^-1; gamma at d_gamma (2 words); first_proof = 0 for a whole table
+int launch_air_sha_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
                           void* d_tab, void* stream);
 // The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(315 p + j) C_(p,j) / (x^N - 1)
+// form, for this pass and its siblings of sets 4 and 5: AIR_FORM_WHOLE is the whole table.  A piece is n_proofs whole proofs whose first is
+// proof `first` of the table (the tables' first_proof): d_cols is that proof's table column 0, d_helper_cols the piece's own helper buffer
+// (its first column at offset 0), and d_quot = (AIR_FORM_PIECE) or += (AIR_FORM_PIECE_ACC) gamma^(C first) times the sum over the piece.
+constexpr int AIR_FORM_WHOLE = 0, AIR_FORM_PIECE = 1, AIR_FORM_PIECE_ACC = 2;
 int launch_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_tab,
-                            void* d_quot, void* stream);
+                            int form, void* d_quot, void* stream);
 // The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
 int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
                          const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
@@ -97,21 +101,21 @@ int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, 
 // obs[0] (launch_air_sha_gamma: the kernel is the same code object, so neither it nor k_fri_transcript changes).
 constexpr uint32_t AIR_SCHED_HELPER_COLS = 115, AIR_SCHED_CONSTRAINTS = 117;
 // The tables one set-4 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [118][2]               gamma^0 .. gamma^117
+//   gpow  [119][2]               gamma^0 .. gamma^117, then gamma^(117 first)
 //   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
 //   fx    [64 << log_blowup]     F(x_i) = P_F(x_i^(N/64)), by i mod (64 << log_blowup)
 constexpr uint32_t AIR4_TAB_GPOW = 0, AIR4_TAB_ZINV = 256, AIR4_TAB_F = 320;
 constexpr uint64_t AIR4_TAB_WORDS = AIR4_TAB_F + (64u << 6);
-static_assert(2 * (AIR_SCHED_CONSTRAINTS + 1) <= AIR4_TAB_ZINV && AIR4_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+static_assert(2 * (AIR_SCHED_CONSTRAINTS + 2) <= AIR4_TAB_ZINV && AIR4_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
               "the set-4 tables live in the table part of set 1's scratch");
 // The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 115 n_proofs
 int launch_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
 // s_n = s^N, w_n = w^N, s_n64 = s^(N/64), w_n64 = w^(N/64), om64_inv = omega_64^-1; gamma at d_gamma (2 words)
-int launch_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+int launch_air_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
                             void* d_tab, void* stream);
 // The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(117 p + j) C_(p,j) / (x^N - 1)
 int launch_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                              const void* d_tab, void* d_quot, void* stream);
+                              const void* d_tab, int form, void* d_quot, void* stream);
 // The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
 int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
                            const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
@@ -122,25 +126,25 @@ int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h
 // 5 | chain << 8 in obs[0] (launch_air_sha_gamma: the same code object, so neither it nor k_fri_transcript changes).
 constexpr uint32_t AIR_INIT_HELPER_COLS = 315, AIR_INIT_CONSTRAINTS = 337;
 // The tables one set-5 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [338][2]               gamma^0 .. gamma^337
+//   gpow  [339][2]               gamma^0 .. gamma^337, then gamma^(337 first)
 //   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
 //   sel   [64 << log_blowup]     chain = 0: 1 / D_s(x_i), D_s = x^(N/64) - omega_64^-1, by i mod (64 << log_blowup)
 //         [128 << log_blowup]    chain = 1: 1 / D_s(x_i), D_s = x^(N/128) - omega_128^-1, by i mod (128 << log_blowup); 1 / D_c(x_i), D_c =
 //                                x^(N/128) + omega_128^-1, is the negated entry (64 << log_blowup) places on
 constexpr uint32_t AIR5_TAB_GPOW = 0, AIR5_TAB_ZINV = 704, AIR5_TAB_SEL = 768;
 constexpr uint64_t AIR5_TAB_WORDS = AIR5_TAB_SEL + (128u << 6);
-static_assert(2 * (AIR_INIT_CONSTRAINTS + 1) <= AIR5_TAB_ZINV && AIR5_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+static_assert(2 * (AIR_INIT_CONSTRAINTS + 2) <= AIR5_TAB_ZINV && AIR5_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
               "the set-5 tables live in the table part of set 1's scratch");
 // The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words, d_helper 315 n_proofs
 int launch_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream);
 // s_n = s^N, w_n = w^N; s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0; s^(N/128), w^(N/128), omega_128^-1 under
 // chain = 1; gamma at d_gamma (2 words)
-int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
+int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
                            const void* d_gamma, void* d_tab, void* stream);
 // The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p (sum_(j < 321) gamma^(337 p + j) C_(p,j) / (x^N - 1)
 // + sum_(321 <= j < 329) gamma^(337 p + j) L_(p,j) / D_s + sum_(j >= 329) gamma^(337 p + j) L_(p,j) / D_c)
 int launch_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
-                             const void* d_tab, void* d_quot, void* stream);
+                             const void* d_tab, int form, void* d_quot, void* stream);
 // The division-free identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient
 int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho,
                           const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,

@@ -680,12 +680,14 @@ __device__ __forceinline__ gl2 air_horner64(const uint64_t* coef, gl2 y) {
   return acc;
 }
 
-// Thread k's share of the two tables every one of these sets has: 1 / (x^N - 1) by i mod B (one Fermat chain), gamma^0 .. gamma^n
-__device__ __forceinline__ void air_zinv_gpow(uint32_t k, uint32_t log_blowup, uint64_t s_n, uint64_t w_n, const uint64_t* __restrict__ gamma,
-                                              uint32_t n, uint64_t* __restrict__ zinv, uint64_t* __restrict__ gpow) {
+// Thread k's share of the two tables every one of these sets has: 1 / (x^N - 1) by i mod B (one Fermat chain), gamma^0 .. gamma^n and
+// behind them gamma^(n first_proof), the weight of a piece whose first proof is proof first_proof of the table (k_air_tables' last entry)
+__device__ __forceinline__ void air_zinv_gpow(uint32_t k, uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
+                                              const uint64_t* __restrict__ gamma, uint32_t n, uint64_t* __restrict__ zinv,
+                                              uint64_t* __restrict__ gpow) {
   if (k < (1u << log_blowup)) zinv[k] = gl_pow(gl_sub(gl_mul(s_n, gl_pow(w_n, k)), 1), GL_P - 2);
-  if (k <= n) {
-    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k);
+  if (k <= n + 1) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, k <= n ? (uint64_t)k : n * first_proof);
     gpow[2 * k] = g.c0;
     gpow[2 * k + 1] = g.c1;
   }
@@ -806,7 +808,7 @@ __global__ __launch_bounds__(256) void k_air_sha_helper(uint32_t log_rows, uint3
 }
 
 // One thread per table entry: S and K by i mod 64 B (K by Horner on P_K's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 315.
-__global__ __launch_bounds__(256) void k_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+__global__ __launch_bounds__(256) void k_air_sha_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
                                                         uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
   __shared__ uint64_t pk[64];
   air_interpolate64(om64_inv, pk, RoundConstant{});
@@ -816,7 +818,7 @@ __global__ __launch_bounds__(256) void k_air_sha_tables(uint32_t log_blowup, uin
     tab[AIR3_TAB_SEL + k] = gl_sub(y, om64_inv);
     tab[AIR3_TAB_K + k] = air_horner64(pk, y);
   }
-  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_SHA_CONSTRAINTS, tab + AIR3_TAB_ZINV, tab + AIR3_TAB_GPOW);
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA_CONSTRAINTS, tab + AIR3_TAB_ZINV, tab + AIR3_TAB_GPOW);
 }
 
 // The 315 constraints of one proof at one point; kx is K at the point.  Behind the bit loop 8 more column products, the word constraints
@@ -862,6 +864,11 @@ __device__ __forceinline__ void air_sha_constraints(View& at, typename F::T kx) 
 
 // The set-3 hot pass, k_air_ladder_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
 // gamma^315), the nine table columns and the 300 helper columns read once from HBM.  Per proof  v = a + S(x) b; at the end 1 / (x^N - 1).
+// FORM: AIR_FORM_WHOLE is the whole table.  A piece (AIR_FORM_PIECE, AIR_FORM_PIECE_ACC) is n_proofs whole proofs whose first is proof
+// `first` of the table: cols is that proof's table column 0, hcols the piece's own helper buffer, and the sum takes the weight
+// gamma^(315 first), the table entry behind the powers.  _ACC adds what `out` holds, loaded behind the proof loop (sets 3 and 5 sit 31
+// VGPRs under the two-wave limit: two more live words across the loop are not worth risking a wave), and writes the sum canonical.
+template <int FORM>
 __global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
                                                                   const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                   const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -880,7 +887,9 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sha_quotient(uint32_t log_m
     const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sel, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sel, at.b1))};
     t = gl2_add(gl2_mul(t, g315), v);
   }
-  const gl2 q = gl2_scale(t, zinv);
+  gl2 q = gl2_scale(t, zinv);
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA_CONSTRAINTS + 1)], gp[2 * (AIR_SHA_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
   out[i] = q.c0;
   out[M + i] = q.c1;
 }
@@ -918,19 +927,27 @@ int launch_air_sha_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_ta
                      reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
   return (int)hipGetLastError();
 }
-int launch_air_sha_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+int launch_air_sha_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
                           void* d_tab, void* stream) {
-  // (at least two workgroups: the 316 gamma powers)
+  // (at least two workgroups: the 317 gamma powers)
   const uint32_t blocks = ((64u << log_blowup) + 255) / 256;
-  hipLaunchKernelGGL(k_air_sha_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, s_n, w_n, s_n64, w_n64, om64_inv,
+  hipLaunchKernelGGL(k_air_sha_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n, s_n64, w_n64, om64_inv,
                      reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
   return (int)hipGetLastError();
 }
 int launch_air_sha_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_tab,
-                            void* d_quot, void* stream) {
-  hipLaunchKernelGGL(k_air_sha_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream), log_m,
-                     log_blowup, n_proofs, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
-                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+                            int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_sha_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_sha_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_sha_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
   return (int)hipGetLastError();
 }
 int launch_air_sha_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
@@ -992,13 +1009,13 @@ __global__ __launch_bounds__(256) void k_air_sched_helper(uint32_t log_rows, uin
 }
 
 // One thread per table entry: F by i mod 64 B (Horner on P_F's coefficients in LDS), 1 / (x^N - 1) by i mod B, gamma^0 .. 117.
-__global__ __launch_bounds__(256) void k_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+__global__ __launch_bounds__(256) void k_air_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
                                                           uint64_t om64_inv, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
   __shared__ uint64_t pf[64];
   air_interpolate64(om64_inv, pf, ScheduleRow{});
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < (64u << log_blowup)) tab[AIR4_TAB_F + k] = air_horner64(pf, gl_mul(s_n64, gl_pow(w_n64, k)));
-  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_SCHED_CONSTRAINTS, tab + AIR4_TAB_ZINV, tab + AIR4_TAB_GPOW);
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SCHED_CONSTRAINTS, tab + AIR4_TAB_ZINV, tab + AIR4_TAB_GPOW);
 }
 
 // The 117 constraints of one proof at one point; fx is F at the point.  The bit index b walks from 31 down to 0 and per b the pass holds
@@ -1045,7 +1062,8 @@ __device__ __forceinline__ void air_sched_constraints(View& at, typename F::T fx
 }
 
 // The set-4 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^117), W and the 115 helper columns.  One gamma sum per proof, lazy as in set 3's pass; at the end 1 / (x^N - 1).
+// gamma^117), W and the 115 helper columns.  One gamma sum per proof, lazy as in set 3's pass; at the end 1 / (x^N - 1).  FORM as there.
+template <int FORM>
 __global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
                                                                     const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                     const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -1062,7 +1080,9 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_sched_quotient(uint32_t log
     air_sched_constraints<FieldP>(at, fx);
     t = gl2_add(gl2_mul(t, g117), {gl_canon(at.a0), gl_canon(at.a1)});
   }
-  const gl2 q = gl2_scale(t, zinv);
+  gl2 q = gl2_scale(t, zinv);
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SCHED_CONSTRAINTS + 1)], gp[2 * (AIR_SCHED_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
   out[i] = q.c0;
   out[M + i] = q.c1;
 }
@@ -1100,17 +1120,25 @@ int launch_air_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_
                      reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
   return (int)hipGetLastError();
 }
-int launch_air_sched_tables(uint32_t log_blowup, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
+int launch_air_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv, const void* d_gamma,
                             void* d_tab, void* stream) {
-  hipLaunchKernelGGL(k_air_sched_tables, dim3(((64u << log_blowup) + 255) / 256), dim3(256), 0, S_(stream), log_blowup, s_n, w_n, s_n64, w_n64,
-                     om64_inv, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  hipLaunchKernelGGL(k_air_sched_tables, dim3(((64u << log_blowup) + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n, s_n64,
+                     w_n64, om64_inv, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
   return (int)hipGetLastError();
 }
 int launch_air_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                              const void* d_tab, void* d_quot, void* stream) {
-  hipLaunchKernelGGL(k_air_sched_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream),
-                     log_m, log_blowup, n_proofs, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
-                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+                              const void* d_tab, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_sched_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_sched_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_sched_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, out);
   return (int)hipGetLastError();
 }
 int launch_air_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64_inv, const void* d_open_t,
@@ -1227,7 +1255,7 @@ __device__ __forceinline__ void air_init_batch_inverse(uint64_t (&v)[8]) {
 // per entry of 1 / (x^N - 1) by i mod B and per power gamma^0 .. gamma^337.  Under chain = 1 the same table holds 1 / D_c: x^(N/128)
 // changes its sign 64 B points on, so D_c(x_i) = x_i^(N/128) + rho = -D_s(x_(i + 64 B)).  No entry vanishes: D_s divides x^N - 1, which
 // the caller checked.
-__global__ __launch_bounds__(256) void k_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel,
+__global__ __launch_bounds__(256) void k_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_sel,
                                                          uint64_t w_sel, uint64_t rho, const uint64_t* __restrict__ gamma,
                                                          uint64_t* __restrict__ tab) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, first = 8 * k;
@@ -1239,7 +1267,7 @@ __global__ __launch_bounds__(256) void k_air_init_tables(uint32_t log_blowup, ui
 #pragma unroll
     for (uint32_t j = 0; j < 8; j++) tab[AIR5_TAB_SEL + first + j] = v[j];
   }
-  air_zinv_gpow(k, log_blowup, s_n, w_n, gamma, AIR_INIT_CONSTRAINTS, tab + AIR5_TAB_ZINV, tab + AIR5_TAB_GPOW);
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_INIT_CONSTRAINTS, tab + AIR5_TAB_ZINV, tab + AIR5_TAB_GPOW);
 }
 
 // The 337 constraints of one proof at one point; chain is uniform.  Behind the bit loop the word constraints, LV, the eight PZ constraints
@@ -1305,7 +1333,8 @@ __device__ __forceinline__ void air_init_constraints(View& at, uint32_t chain) {
 
 // The set-5 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
 // gamma^337), the nine table columns and the 315 helper columns.  Per proof 1 / D_s is applied once to the start sum, 1 / D_c once to the
-// chain sum (skipped under chain = 0), 1 / (x^N - 1) once to the rest.
+// chain sum (skipped under chain = 0), 1 / (x^N - 1) once to the rest.  FORM as in k_air_sha_quotient.
+template <int FORM>
 __global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain,
                                                                    const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
                                                                    const uint64_t* __restrict__ tab, uint64_t* __restrict__ out) {
@@ -1330,6 +1359,8 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_init_quotient(uint32_t log_
     }
     t = gl2_add(gl2_mul(t, g337), {v0, v1});
   }
+  if (FORM != AIR_FORM_WHOLE) t = gl2_mul(t, {gp[2 * (AIR_INIT_CONSTRAINTS + 1)], gp[2 * (AIR_INIT_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) t = gl2_add(t, {gl_canon(out[i]), gl_canon(out[M + i])});
   out[i] = t.c0;
   out[M + i] = t.c1;
 }
@@ -1371,19 +1402,28 @@ int launch_air_init_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t chain,
                      reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
   return (int)hipGetLastError();
 }
-int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
+int launch_air_init_tables(uint32_t log_blowup, uint32_t chain, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
                            const void* d_gamma, void* d_tab, void* stream) {
-  // (at least two workgroups: the 338 gamma powers)
+  // (at least two workgroups: the 339 gamma powers)
   const uint32_t blocks = ((((chain ? 128u : 64u) << log_blowup) / 8) + 255) / 256;
-  hipLaunchKernelGGL(k_air_init_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, chain, s_n, w_n, s_sel, w_sel, rho,
+  hipLaunchKernelGGL(k_air_init_tables, dim3(blocks < 2 ? 2 : blocks), dim3(256), 0, S_(stream), log_blowup, chain, first_proof, s_n, w_n, s_sel, w_sel,
+                     rho,
                      reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
   return (int)hipGetLastError();
 }
 int launch_air_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
-                             const void* d_tab, void* d_quot, void* stream) {
-  hipLaunchKernelGGL(k_air_init_quotient, dim3((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), dim3(AIR_THREADS), 0, S_(stream),
-                     log_m, log_blowup, n_proofs, chain, reinterpret_cast<const uint64_t*>(d_cols), reinterpret_cast<const uint64_t*>(d_helper_cols),
-                     reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_quot));
+                             const void* d_tab, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_init_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, chain, cols, hcols, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_init_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, chain, cols, hcols, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_init_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, chain, cols, hcols, tab, out);
   return (int)hipGetLastError();
 }
 int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho,

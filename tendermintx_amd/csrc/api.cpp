@@ -421,7 +421,11 @@ struct tmx_ctx {
   struct SetRec {
     bool valid; uint32_t n_oracles, log_blowup, cap_height; uint64_t root, shift;
     // buf: the scratch the offsets refer to if it is not d_set (ext: d_set_air): a member added by tmx_trace_commit_set_air_sha256_device
-    struct Oracle { uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed, ext; const void* buf = nullptr; } o[8];
+    // chunk_cols != 0: a streamed member with a chunk buffer of its own at chunk_off of buf (a streamed helper of constraint sets 3 - 5)
+    struct Oracle {
+      uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed, ext; const void* buf = nullptr;
+      uint32_t chunk_cols = 0; size_t chunk_off = 0;
+    } o[8];
     uint32_t chunk_cols; size_t state_off, chunk_off;
   } set = {};
   // the constraint quotient (tmx_air_*): d_air = prover transcript state 32 | challenges 72 (gamma at FRI_GAMMA_AT) | verifier state 32 |
@@ -435,7 +439,9 @@ struct tmx_ctx {
   size_t set_air_bytes = 0;
   // constraint sets 3, 4 and 5 (tmx_trace_commit_set_air_sha256_device, _sched_device, _init_device), [set (ShaSet.scratch)][section (SHA256,
   // TREE, HEADER)]: one scratch that holds the set's helper member of that section -- pre-LDE columns | extended columns | tree levels --
-  // and its quotient member -- extended columns | tree levels (Oracle.buf names it)
+  // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
+  // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
+  // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
   void* d_set_sha[3][3] = {};
   size_t set_sha_bytes[3][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
@@ -3721,11 +3727,11 @@ static FriGeom batch_geom(const tmx_batch_params& p, const tmx_batch_layout& L, 
 
 // What a batch prove reads: per oracle its extended columns, its tree, and the columns its openings are evaluated from (DeepSrc)
 // A streamed oracle (chunk_cols[k] != 0, a member of a commit set) has no extended columns (cols[k] == nullptr): its deep[k] columns are the
-// set's pre-LDE columns, extended chunk_cols[k] at a time into chunk_buf (chunk_cols << log_n words for the tallest of them) when the
-// queried rows are gathered.
+// set's pre-LDE columns, extended chunk_cols[k] at a time into chunk_buf[k] (chunk_cols[k] << log_n words: the set's shared buffer, or the
+// oracle's own for a streamed helper of constraint sets 3 - 5) when the queried rows are gathered.
 struct BatchSrc {
   const uint64_t* cols[TMX_BATCH_MAX_ORACLES]; const uint64_t* levels[TMX_BATCH_MAX_ORACLES]; DeepSrc deep[TMX_BATCH_MAX_ORACLES];
-  uint32_t chunk_cols[TMX_BATCH_MAX_ORACLES]; uint64_t* chunk_buf;
+  uint32_t chunk_cols[TMX_BATCH_MAX_ORACLES]; uint64_t* chunk_buf[TMX_BATCH_MAX_ORACLES];
 };
 
 // Validated by the caller.  The stages are DEEP's, run per oracle (evaluation, openings block and its tree) and per group (combine of every
@@ -3887,8 +3893,8 @@ static int32_t batch_prove(tmx_ctx* c, const tmx_batch_params& p, const BatchSrc
       const uint32_t log_sub = p.log_n[k] - p.log_blowup;
       for (uint32_t c0 = 0; c0 < p.n_cols[k]; c0 += src.chunk_cols[k]) {
         const uint32_t n = std::min(src.chunk_cols[k], p.n_cols[k] - c0);
-        if ((st = tmx_lde_goldilocks_device(c, log_sub, p.log_blowup, n, src.deep[k].cols + ((uint64_t)c0 << log_sub), src.chunk_buf, hip_stream))) return st;
-        if ((st = launched(launch_merkle_open_chunk(p.log_n[k], n, src.chunk_buf, p.n_queries, idx, proof + L.off_init_rows[k] + c0, p.n_cols[k], s),
+        if ((st = tmx_lde_goldilocks_device(c, log_sub, p.log_blowup, n, src.deep[k].cols + ((uint64_t)c0 << log_sub), src.chunk_buf[k], hip_stream))) return st;
+        if ((st = launched(launch_merkle_open_chunk(p.log_n[k], n, src.chunk_buf[k], p.n_queries, idx, proof + L.off_init_rows[k] + c0, p.n_cols[k], s),
                            "k_merkle_open_chunk")))
           return st;
       }
@@ -4130,7 +4136,13 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
   BatchSrc src = {};
   bool any = false;
   for (uint32_t k = 0; k < r.n_oracles; k++) {
-    if (r.o[k].streamed) { any = true; src.chunk_cols[k] = r.chunk_cols; }
+    if (r.o[k].streamed) {  // (the set's chunk size and buffer, or the member's own)
+      any = true;
+      const bool own = r.o[k].chunk_cols != 0;
+      src.chunk_cols[k] = own ? r.o[k].chunk_cols : r.chunk_cols;
+      src.chunk_buf[k] = own ? reinterpret_cast<uint64_t*>(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(r.o[k].buf) + r.o[k].chunk_off))
+                             : reinterpret_cast<uint64_t*>(c->d_set) + r.chunk_off / 8;
+    }
     if (r.o[k].ext) {
       // the constraint quotient (tmx_trace_commit_set_air_device): extended columns and levels in a scratch of its own, no pre-LDE columns --
       // its openings read the strided subset of the extended columns, as the caller-oracle path of tmx_batch_prove_device does
@@ -4140,7 +4152,7 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
       src.deep[k] = {src.cols[k], r.o[k].log_m, r.log_blowup, r.shift % 0xffffffff00000001ull};
       continue;
     }
-    // (a helper member of constraint set 3 is a resident member in a scratch of its own)
+    // (a helper member of constraint sets 3 - 5 is a resident or a streamed member in a scratch of its own)
     const uint8_t* mb = r.o[k].buf ? reinterpret_cast<const uint8_t*>(r.o[k].buf) : base;
     src.cols[k] = r.o[k].streamed ? nullptr : reinterpret_cast<const uint64_t*>(mb + r.o[k].lde_off);
     src.levels[k] = reinterpret_cast<const uint64_t*>(mb + r.o[k].lev_off);
@@ -4148,7 +4160,6 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
     src.deep[k] = {reinterpret_cast<const uint64_t*>(mb + r.o[k].cols_off), r.o[k].log_m - r.log_blowup, 0, 1};
   }
   if (!any) return batch_prove(c, *p, src, r.root, r.shift, d_proof, hip_stream);
-  src.chunk_buf = reinterpret_cast<uint64_t*>(c->d_set) + r.chunk_off / 8;
   // the streamed members are extended again inside the prove, under the domain the set was committed with.  If tmx_ntt_set_domain has
   // changed the context's since, it is put back for the prove and restored after it (each change waits for the device: the tables of the
   // other domain are dropped)
@@ -4650,10 +4661,10 @@ struct ShaSet {
   const char *stem, *word, *already;           // k_air_<stem>_*, "the <word> member", the refusal of a second set-level call
   const char *at_helper, *at_quot, *bad_index;  // how the verifier's messages name the helper's and the quotient's oracle index
   int (*helper)(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream);
-  int (*tables)(uint32_t log_blowup, uint32_t chain, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho, const void* d_gamma,
-                void* d_tab, void* stream);
+  int (*tables)(uint32_t log_blowup, uint32_t chain, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
+                const void* d_gamma, void* d_tab, void* stream);
   int (*quotient)(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain, const void* d_cols, const void* d_helper_cols,
-                  const void* d_tab, void* d_quot, void* stream);
+                  const void* d_tab, int form, void* d_quot, void* stream);
   int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho, const void* d_open_t,
                const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
 };
@@ -4661,13 +4672,13 @@ struct ShaSet {
 static int sha3_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
   return launch_air_sha_helper(log_rows, n_proofs, d_table, d_helper, stream);
 }
-static int sha3_tables(uint32_t log_blowup, uint32_t, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv,
-                       const void* d_gamma, void* d_tab, void* stream) {
-  return launch_air_sha_tables(log_blowup, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
+static int sha3_tables(uint32_t log_blowup, uint32_t, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+                       uint64_t om64_inv, const void* d_gamma, void* d_tab, void* stream) {
+  return launch_air_sha_tables(log_blowup, first_proof, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
 }
 static int sha3_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t, const void* d_cols, const void* d_helper_cols,
-                         const void* d_tab, void* d_quot, void* stream) {
-  return launch_air_sha_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, d_quot, stream);
+                         const void* d_tab, int form, void* d_quot, void* stream) {
+  return launch_air_sha_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, form, d_quot, stream);
 }
 static int sha3_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t, uint64_t om64_inv, const void* d_open_t,
                       const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
@@ -4677,13 +4688,13 @@ static int sha3_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uin
 static int sha4_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
   return launch_air_sched_helper(log_rows, n_proofs, d_table, d_helper, stream);
 }
-static int sha4_tables(uint32_t log_blowup, uint32_t, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64, uint64_t om64_inv,
-                       const void* d_gamma, void* d_tab, void* stream) {
-  return launch_air_sched_tables(log_blowup, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
+static int sha4_tables(uint32_t log_blowup, uint32_t, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_n64, uint64_t w_n64,
+                       uint64_t om64_inv, const void* d_gamma, void* d_tab, void* stream) {
+  return launch_air_sched_tables(log_blowup, first_proof, s_n, w_n, s_n64, w_n64, om64_inv, d_gamma, d_tab, stream);
 }
 static int sha4_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, uint32_t, const void* d_cols, const void* d_helper_cols,
-                         const void* d_tab, void* d_quot, void* stream) {
-  return launch_air_sched_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, d_quot, stream);
+                         const void* d_tab, int form, void* d_quot, void* stream) {
+  return launch_air_sched_quotient(log_m, log_blowup, n_proofs, d_cols, d_helper_cols, d_tab, form, d_quot, stream);
 }
 static int sha4_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t, uint64_t om64_inv, const void* d_open_t,
                       const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok,
@@ -4750,14 +4761,15 @@ static int32_t sha_gamma(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t l
   return TMX_OK;
 }
 
-// the tables from the prover's gamma, then the pass
-static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const ShaGeo& A, uint32_t n_proofs,
-                        const uint64_t* cols, const uint64_t* hcols, uint64_t* d_quot, hipStream_t s) {
+// the tables from the prover's gamma, then the pass.  form = AIR_FORM_WHOLE: the whole table (first = 0).  A piece: n_proofs proofs whose
+// first is proof `first` of the table, cols that proof's table column 0 and hcols the piece's own helper columns
+static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const ShaGeo& A, uint32_t first,
+                        uint32_t n_proofs, const uint64_t* cols, const uint64_t* hcols, int form, uint64_t* d_quot, hipStream_t s) {
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
   uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = d.tables(log_blowup, chain, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s);
+  int rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s);
   if (rc) return sha_launch_failed(c, d, "tables", rc);
-  rc = d.quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, d_quot, s);
+  rc = d.quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, form, d_quot, s);
   if (rc) return sha_launch_failed(c, d, "quotient", rc);
   return TMX_OK;
 }
@@ -4777,12 +4789,16 @@ static int32_t sha_helper_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, u
   return TMX_OK;
 }
 
+// form = AIR_FORM_WHOLE: the quotient of the whole table (proof_lo = 0, proof_hi = n_proofs).  Else the piece [proof_lo, proof_hi), whose
+// helper columns alone are at d_helper_cols; gamma is drawn over n_proofs either way
 static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
-                                 uint32_t chain, const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
-                                 const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
+                                 uint32_t chain, uint32_t proof_lo, uint32_t proof_hi, int form, const uint64_t* d_cols,
+                                 const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                 void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = sha_check(c, d, log_n, log_blowup, n_proofs, chain);
   if (st) return st;
+  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
   if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
     return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
   ShaGeo A;
@@ -4793,10 +4809,22 @@ static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, ui
   c->air_valid = false;
   if ((st = air_scratch(c, log_blowup))) return st;
   if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, false, s))) return st;
-  if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, n_proofs, d_cols, d_helper_cols, d_quot, s))) return st;
+  if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_SHA_WIDTH) << log_n),
+                     d_helper_cols, form, d_quot, s)))
+    return st;
   HIPCK(c, hipEventRecord(c->ev_air, s));
   c->air_valid = true;
   return TMX_OK;
+}
+
+static int32_t sha_quotient_range_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                       uint32_t chain, uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                       const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                       void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
+  return sha_quotient_call(c, d, log_n, log_blowup, cap_height, n_proofs, chain, proof_lo, proof_hi, accumulate ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE,
+                           d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
 }
 
 static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
@@ -4833,10 +4861,44 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   return TMX_OK;
 }
 
-static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+// The scratch of one set and section.  Resident: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient
+// levels.  Streamed (chunk_proofs < n_proofs): the extended columns are absent, and behind the quotient's levels sit the sponge states
+// [12][M] and one chunk of extended helper columns [chunk_proofs helper_cols][M].  lde: the LDE's own scratch, twice what is extended at
+// once: one proof's helper columns (resident), one chunk (streamed: ONE LDE call per chunk, as the prove's gather of a streamed member
+// extends it, so the call grows the LDE's scratch to what the prove needs anyway and launches 1 / chunk_proofs as many transforms).
+struct ShaScratch { size_t pre_b, ext_b, lev_b, quot_b, state_b, chunk_b, want, lde; };
+static ShaScratch sha_scratch_plan(const ShaSet& d, uint32_t log_m, uint32_t log_blowup, uint32_t h, uint32_t n_proofs, uint32_t chunk_proofs) {
+  const bool streamed = chunk_proofs < n_proofs;
+  const size_t n_hcols = (size_t)n_proofs * d.helper_cols, chunk_cols = (size_t)chunk_proofs * d.helper_cols;
+  ShaScratch P;
+  P.pre_b = (n_hcols << (log_m - log_blowup)) * 8;
+  P.ext_b = streamed ? 0 : (n_hcols << log_m) * 8;
+  P.lev_b = (size_t)tmx_poseidon_merkle_digests(log_m, h) * 32;
+  P.quot_b = ((size_t)2 << log_m) * 8;
+  P.state_b = streamed ? ((size_t)12 << log_m) * 8 : 0;
+  P.chunk_b = streamed ? (chunk_cols << log_m) * 8 : 0;
+  P.want = P.pre_b + P.ext_b + 2 * P.lev_b + P.quot_b + P.state_b + P.chunk_b;
+  P.lde = 2 * (streamed ? P.chunk_b : ((size_t)d.helper_cols << log_m) * 8);
+  return P;
+}
+
+// what a chunk size must satisfy whatever the set holds; null: it does
+static const char* sha_chunk_refusal(const ShaSet& d, uint32_t chunk_proofs) {
+  if (chunk_proofs < 1) return "chunk_proofs must be at least 1";
+  if (((uint64_t)chunk_proofs * d.helper_cols) % 8)
+    return "chunk_proofs times the helper's columns per proof must be a multiple of 8 (the sponge absorbs eight columns at a time)";
+  return nullptr;
+}
+
+// chunk_proofs = 0: the resident calls.  Else tmx_trace_commit_set_air_sha256_streamed_device: the helper streamed in chunks of chunk_proofs
+// whole proofs, or resident exactly as from the resident calls if one chunk holds it all.
+static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint32_t chunk_proofs, bool by_chunks, uint64_t* d_cap_h, uint64_t* d_cap_q,
+                            void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
   if (st) return st;
+  if (by_chunks)
+    if (const char* why = sha_chunk_refusal(d, chunk_proofs)) return fail(c, TMX_ERR_BAD_ARG, why);
   const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
   if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
   if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
@@ -4863,17 +4925,22 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint6
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
-  // the scratch of this set and section: helper pre-LDE columns | helper extended columns | helper levels | quotient | quotient levels
+  // the scratch of this set and section (ShaScratch)
+  const bool streamed = by_chunks && chunk_proofs < n_proofs;
   const uint32_t n_hcols = n_proofs * d.helper_cols;
   const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const size_t pre_b = ((size_t)n_hcols << log_sub) * 8, ext_b = ((size_t)n_hcols << log_m) * 8, lev_b = (size_t)n_dig * 32,
-               quot_b = ((size_t)2 << log_m) * 8, want = pre_b + ext_b + 2 * lev_b + quot_b;
+  const ShaScratch SP = sha_scratch_plan(d, log_m, r.log_blowup, h, n_proofs, streamed ? chunk_proofs : n_proofs);
+  const size_t pre_b = SP.pre_b, ext_b = SP.ext_b, lev_b = SP.lev_b, quot_b = SP.quot_b, want = SP.want;
   void*& d_scratch = c->d_set_sha[d.scratch][slot];
   size_t& scratch_bytes = c->set_sha_bytes[d.scratch][slot];
-  if (scratch_bytes < want) {
+  // (a streamed call keeps exactly what it needs: a larger scratch left by a resident call is given back, which is what streaming is for)
+  if (streamed ? scratch_bytes != want : scratch_bytes < want) {
     if (d_scratch) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(d_scratch)); d_scratch = nullptr; scratch_bytes = 0; }
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
+    if (streamed && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want + SP.lde > free_b + c->ntt_tmp_bytes)
+      return fail(c, TMX_ERR_CAPACITY, "the streamed " + std::string(d.word) + " member needs " + std::to_string((want + SP.lde) >> 20) +
+                                           " MiB of scratch, the LDE's own included, " + std::to_string(free_b >> 20) + " MiB free");
+    if (!streamed && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b)
       return fail(c, TMX_ERR_CAPACITY, "the " + std::string(d.word) + " member needs " + std::to_string(want >> 20) + " MiB of scratch, " +
                                            std::to_string(free_b >> 20) + " MiB free");
     HIPCK(c, hipMalloc(&d_scratch, want));
@@ -4889,7 +4956,55 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint6
   const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
   const int rc = d.helper(log_sub, n_proofs, chain, base + tabm.cols_off, hpre, s);
   if (rc) return sha_launch_failed(c, d, "helper", rc);
-  {
+  if (streamed) {
+    // The helper never exists extended.  Sweep 1: chunk by chunk, extended into the chunk buffer and absorbed into the rows' sponge states;
+    // the last chunk leaves the leaf digests where k_poseidon_leaves would, the levels above them are the resident path's.  Then gamma
+    // and, sweep 2, every chunk extended again and its piece of the quotient added to quot (the first piece writes).  Both sweeps run
+    // under the set's domain: put back for the call if tmx_ntt_set_domain moved the context's, restored after.
+    uint64_t* state = reinterpret_cast<uint64_t*>(sb + pre_b + 2 * lev_b + quot_b);
+    uint64_t* chunk = reinterpret_cast<uint64_t*>(sb + pre_b + 2 * lev_b + quot_b + SP.state_b);
+    const uint64_t* tcols = reinterpret_cast<const uint64_t*>(base + tabm.lde_off);
+    auto extend = [&](uint32_t p0, uint32_t n) {
+      return tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * d.helper_cols, hpre + (((uint64_t)p0 * d.helper_cols) << log_sub), chunk, hip_stream);
+    };
+    auto sweeps = [&]() -> int32_t {
+      int32_t e;
+      for (uint32_t p0 = 0; p0 < n_proofs; p0 += chunk_proofs) {
+        const uint32_t n = std::min(chunk_proofs, n_proofs - p0);
+        if ((e = extend(p0, n))) return e;
+        const int lrc = launch_poseidon_leaves_chunk(c->d_pos_consts, c->pos_mode, log_m, n * d.helper_cols, chunk, p0 == 0, p0 + n == n_proofs, state,
+                                                     lev_h, s);
+        if (lrc) return fail(c, TMX_ERR_HIP, std::string("k_poseidon_leaves_chunk launch: ") + hipGetErrorString((hipError_t)lrc));
+      }
+      uint64_t* cur = lev_h;
+      for (uint32_t l = 0; l + h < log_m; l++) {
+        const uint64_t cnt = 1ull << (log_m - l);
+        const int lrc = launch_poseidon_level(c->d_pos_consts, c->pos_mode, cnt / 2, cur, cur + 4 * cnt, s);
+        if (lrc) return fail(c, TMX_ERR_HIP, std::string("k_poseidon_level launch: ") + hipGetErrorString((hipError_t)lrc));
+        cur += 4 * cnt;
+      }
+      HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+      if ((e = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s)))
+        return e;
+      for (uint32_t p0 = 0; p0 < n_proofs; p0 += chunk_proofs) {
+        const uint32_t n = std::min(chunk_proofs, n_proofs - p0);
+        if ((e = extend(p0, n))) return e;
+        if ((e = sha_pass(c, d, log_m, r.log_blowup, chain, A, p0, n, tcols + (((uint64_t)p0 * AIR_SHA_WIDTH) << log_m), chunk,
+                          p0 ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE, quot, s)))
+          return e;
+      }
+      return TMX_OK;
+    };
+    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+    const bool moved = root != r.root || shift != r.shift;
+    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+    st = sweeps();
+    if (moved) {
+      const int32_t back = tmx_ntt_set_domain(c, root, shift);
+      if (!st) st = back;
+    }
+    if (st) return st;
+  } else {
     // the helper extended under the set's domain, one proof's columns at a time (the LDE's own scratch is twice what it extends at once)
     const uint64_t root = c->ntt_root, shift = c->ntt_shift;
     const bool moved = root != r.root || shift != r.shift;
@@ -4901,17 +5016,21 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint6
       if (!st) st = back;
     }
     if (st) return st;
+    if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
+    HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+    if ((st = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s)))
+      return st;
+    if ((st = sha_pass(c, d, log_m, r.log_blowup, chain, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, AIR_FORM_WHOLE,
+                       quot, s)))
+      return st;
   }
-  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  if ((st = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s))) return st;
-  if ((st = sha_pass(c, d, log_m, r.log_blowup, chain, A, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, quot, s))) return st;
   HIPCK(c, hipEventRecord(c->ev_air, s));
   c->air_valid = true;
   if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
   HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
   for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
-  r.o[at] = {d.helper_section, log_m, n_hcols, 0, pre_b, pre_b + ext_b, false, false, sb};
+  r.o[at] = {d.helper_section, log_m, n_hcols, 0, pre_b, pre_b + ext_b, streamed, false, sb};
+  if (streamed) { r.o[at].chunk_cols = chunk_proofs * d.helper_cols; r.o[at].chunk_off = pre_b + 2 * lev_b + quot_b + SP.state_b; }
   r.o[at + 1] = {d.quotient_section, log_m, 2, 0, pre_b + ext_b + lev_b, pre_b + ext_b + lev_b + quot_b, false, true, sb};
   r.n_oracles += 2;
   c->set = r;
@@ -4927,7 +5046,8 @@ int32_t tmx_air_sha256_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_p
 int32_t tmx_air_sha256_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
                                        const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
                                        void* hip_stream) {
-  return sha_quotient_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
+  return sha_quotient_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, d_quot, hip_stream);
 }
 
 // (the helper sits directly behind the table; a k_trace + 1 that wraps to 0 fails the index rule as it should)
@@ -4937,7 +5057,7 @@ int32_t tmx_air_sha256_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint
 }
 
 int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[0], section, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[0], section, 0, false, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
@@ -4948,7 +5068,8 @@ int32_t tmx_air_sha256_sched_helper_device(tmx_ctx* c, uint32_t log_rows, uint32
 int32_t tmx_air_sha256_sched_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                              const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                              const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
-  return sha_quotient_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
+  return sha_quotient_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
@@ -4957,7 +5078,7 @@ int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* c, const tmx_batch_params* p
 }
 
 int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[1], section, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[1], section, 0, false, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
@@ -4968,7 +5089,8 @@ int32_t tmx_air_sha256_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_
 int32_t tmx_air_sha256_init_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                             const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
-  return sha_quotient_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
+  return sha_quotient_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
@@ -4977,7 +5099,48 @@ int32_t tmx_air_sha256_init_verify_device(tmx_ctx* c, const tmx_batch_params* p,
 }
 
 int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[2], section, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[2], section, 0, false, d_cap_h, d_cap_q, hip_stream);
+}
+
+int32_t tmx_air_sha256_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t proof_lo,
+                                             uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_helper_cols,
+                                             const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha256_sched_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                   uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                   uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha256_init_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols,
+                                 d_cap, d_cap_helper, d_quot, hip_stream);
+}
+
+uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
+                                                        uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes) {
+  if (lde_scratch_bytes) *lde_scratch_bytes = 0;
+  if (constraint_set < 3 || constraint_set > 5) return 0;
+  const ShaSet& d = SHA_SETS[constraint_set - 3];
+  if (sha_chunk_refusal(d, chunk_proofs) || sha_check(nullptr, d, log_m, log_blowup, n_proofs, 0)) return 0;
+  const ShaScratch SP = sha_scratch_plan(d, log_m, log_blowup, std::min(cap_height, log_m), n_proofs, std::min(chunk_proofs, n_proofs));
+  if (lde_scratch_bytes) *lde_scratch_bytes = SP.lde;
+  return SP.want;
+}
+
+int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* c, uint32_t constraint_set, uint32_t section, uint32_t chunk_proofs, uint64_t* d_cap_h,
+                                                        uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (constraint_set < 3 || constraint_set > 5) return fail(c, TMX_ERR_BAD_ARG, "constraint_set must be 3, 4 or 5");
+  return sha_set_call(c, SHA_SETS[constraint_set - 3], section, chunk_proofs, true, d_cap_h, d_cap_q, hip_stream);
 }
 
 }  // extern "C"

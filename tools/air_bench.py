@@ -30,6 +30,13 @@
   parent   the set commit + prove WITHOUT any air call, then the set-3 and set-4 set-level calls on HEADER (MODE=set_plain,sets34), for library
            builds named in LIBS (comma separated), one subprocess per measurement, alternating under TMX_LIB (differences between boxes exceed
            most changes: compare inside one call).
+  sha_streamed  the streamed helpers of constraint sets 3 - 5 (tmx_trace_commit_set_air_sha256_streamed_device) on a set SHA256 | SECTION
+           of SHA_SET_P proofs at N = n (skip), the sets named in SETS (3 by default; 3,4,5), CHUNK_PROOFS proofs per chunk (8).  SECTION=
+           HEADER (default): the resident and the streamed set-level calls, alternating in one process after a warm call, with the prove
+           after each; cap digests of both forms; and the chunk LDE alone (the two sweeps' transforms over buffers of the same sizes): the
+           helper-LDE share of the streamed call.  SECTION=TREE or SHA256: the streamed calls only, once (the resident helper does not
+           fit at full size): the bytes from tmx_trace_commit_set_air_sha256_streamed_bytes, free memory before and after, digests of
+           both caps per set, the times, and the verdicts of the three verifiers on one proof over the set.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -390,6 +397,123 @@ if "init" in modes or "sets34" in modes:
         del proof
     if not only34:
         res["ratio_init_over_sha_set_call"] = round(min(res["air_sha256_init_header_ms"]) / min(res["air_sha256_header_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del tr
+    torch.cuda.empty_cache()
+
+if "sha_streamed" in modes:
+    from tendermintx_amd.synth import bench_workload
+    from tendermintx_amd.context import trace_commit_set_air_sha256_streamed_bytes
+    SHA256 = 4
+    sec_name = os.environ.get("SECTION", "HEADER")
+    section = {"SHA256": 4, "TREE": 16, "HEADER": 32}[sec_name]
+    sets, cpf = [int(x) for x in os.environ.get("SETS", "3").split(",")], int(os.environ.get("CHUNK_PROOFS", "8"))
+    hcols = {3: 300, 4: 115, 5: 315}
+    sp = int(os.environ.get("SHA_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    cw = 4 << cap_h
+    mask = SHA256 | section
+    scaps = torch.zeros((2 if mask != SHA256 else 1) * cw, dtype=torch.int64, device=dev)
+    pair = {s_: torch.zeros(2 * cw, dtype=torch.int64, device=dev) for s_ in sets}
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, mask, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    resident = {3: ctx.trace_commit_set_air_sha256_device, 4: ctx.trace_commit_set_air_sha256_sched_device,
+                5: ctx.trace_commit_set_air_sha256_init_device}
+
+    def calls(streamed):
+        for s_ in sets:
+            if streamed:
+                ctx.trace_commit_set_air_sha256_streamed_device(s_, section, cpf, pair[s_][:cw].data_ptr(), pair[s_][cw:].data_ptr(), 0)
+            else:
+                resident[s_](section, pair[s_][:cw].data_ptr(), pair[s_][cw:].data_ptr(), 0)
+
+    digests = lambda: {str(s_): [hashlib.sha256(pair[s_][k * cw:(k + 1) * cw].cpu().numpy().tobytes()).hexdigest()[:16] for k in (0, 1)] for s_ in sets}
+    commit()
+    shape0, order0 = ctx.trace_commit_set_shape()
+    log_m = shape0["log_n"][order0.index(section)]
+    res = {"mode": "sha_streamed", "section": sec_name, "sets": sets, "proofs": sp, "n": n, "log_m": log_m, "chunk_proofs": cpf, "reps": reps,
+           "bytes": {str(s_): list(trace_commit_set_air_sha256_streamed_bytes(s_, log_m, log_blowup, cap_h, sp, cpf)) for s_ in sets},
+           "bytes_resident": {str(s_): list(trace_commit_set_air_sha256_streamed_bytes(s_, log_m, log_blowup, cap_h, sp, sp)) for s_ in sets}}
+
+    def prove_and_verify():
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        ms = r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps))
+        kt = order.index(section)
+        caps, at = [scaps[:(kt + 1) * cw]], kt + 1
+        where = {}
+        for s_ in sorted(sets):
+            caps.append(pair[s_])
+            where[s_] = at
+            at += 2
+        all_caps = torch.cat(caps + [scaps[(kt + 1) * cw:]])
+        verdicts = {}
+        for s_, kh in where.items():
+            if s_ == 3:
+                ctx.air_sha256_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            elif s_ == 4:
+                ctx.air_sha256_sched_verify_device(bp, kt, kh, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            else:
+                ctx.air_sha256_init_verify_device(bp, kt, kh, int(section != SHA256), all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            verdicts[str(s_)] = bool((ok.cpu().numpy() == 1).all())
+        return ms, verdicts, ctx.fri_last_degree_ok(), order
+
+    def all_calls_ms(streamed, k):
+        return r4(timed(lambda: calls(streamed), k, before=commit))
+
+    if sec_name == "HEADER":
+        res.update(resident_call_ms=[], streamed_call_ms=[], prove_resident_ms=[], prove_streamed_ms=[])
+        for _ in range(rounds):
+            res["resident_call_ms"].append(all_calls_ms(False, reps))
+            ms, res["verdicts_resident"], _, _ = prove_and_verify()
+            res["prove_resident_ms"].append(ms)
+            res["caps_resident"] = digests()
+            res["streamed_call_ms"].append(all_calls_ms(True, reps))
+            ms, res["verdicts_streamed"], res["degree_ok"], res["order"] = prove_and_verify()
+            res["prove_streamed_ms"].append(ms)
+            res["caps_streamed"] = digests()
+        res["caps_equal"] = res["caps_resident"] == res["caps_streamed"]
+        # the chunk LDE alone: both sweeps' transforms of every set over buffers of the sizes the call uses
+        log_sub = log_m - log_blowup
+        big = max(hcols[s_] for s_ in sets)
+        pre = torch.randint(0, 2**62, ((big * sp) << log_sub,), dtype=torch.int64, device=dev)
+        chunk_buf = torch.empty((big * cpf) << log_m, dtype=torch.int64, device=dev)
+
+        def lde_alone():
+            for s_ in sets:
+                for _sweep in (0, 1):
+                    for p0 in range(0, sp, cpf):
+                        k_ = min(cpf, sp - p0) * hcols[s_]
+                        ctx.lde_device(log_sub, log_blowup, k_, pre[(p0 * hcols[s_]) << log_sub:].data_ptr(), chunk_buf.data_ptr(), 0)
+
+        res["chunk_lde_two_sweeps_ms"] = [r4(timed(lde_alone, reps)) for _ in range(rounds)]
+        best_s, best_r = min(res["streamed_call_ms"]), min(res["resident_call_ms"])
+        res["ratio_streamed_over_resident_call"] = round(best_s / best_r, 3)
+        res["ratio_streamed_over_resident_prove"] = round(min(res["prove_streamed_ms"]) / min(res["prove_resident_ms"]), 3)
+        res["helper_lde_share_of_streamed"] = round(min(res["chunk_lde_two_sweeps_ms"]) / best_s, 3)
+        del pre, chunk_buf
+    else:
+        res["free_before_mib"] = torch.cuda.mem_get_info(dev)[0] >> 20
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        calls(True)
+        b.record()
+        torch.cuda.synchronize(dev)
+        res["streamed_call_ms"] = r4(a.elapsed_time(b))
+        res["free_after_mib"] = torch.cuda.mem_get_info(dev)[0] >> 20
+        res["caps_streamed"] = digests()
+        res["prove_streamed_ms"], res["verdicts_streamed"], res["degree_ok"], res["order"] = prove_and_verify()
     print(json.dumps(res), flush=True)
     ctx.close()
     del tr
