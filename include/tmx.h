@@ -1350,6 +1350,10 @@ uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set,
                                                         uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes);
 int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* ctx, uint32_t constraint_set, uint32_t section, uint32_t chunk_proofs,
                                                         uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+/* Host only, for tests and memory accounting: the bytes of the [set][section] scratch the context holds right now, as the last resident or
+ * streamed set-level call of constraint_set on `section` left it (a streamed call leaves exactly what _streamed_bytes returns); 0 if there
+ * is none, for a constraint_set outside 3 .. 5 and for a section that is no SHA-256 table. */
+uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* ctx, uint32_t constraint_set, uint32_t section);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

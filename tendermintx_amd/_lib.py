@@ -391,6 +391,8 @@ def lib():
         L.tmx_trace_commit_set_air_sha256_streamed_bytes.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint64)]
         L.tmx_trace_commit_set_air_sha256_streamed_bytes.restype = C.c_uint64
         L.tmx_trace_commit_set_air_sha256_streamed_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha256_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.tmx_trace_commit_set_air_sha256_scratch_bytes.restype = C.c_uint64
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

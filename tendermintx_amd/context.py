@@ -582,6 +582,10 @@ class Context:
         check(self._L.tmx_trace_commit_set_air_sha256_streamed_device(self._h, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q,
                                                                       self._stream(stream)), self._h)
 
+    def trace_commit_set_air_sha256_scratch_bytes(self, constraint_set, section):
+        """(host only) the bytes of the scratch the context holds for that set and section right now; 0 if none"""
+        return int(self._L.tmx_trace_commit_set_air_sha256_scratch_bytes(self._h, constraint_set, section))
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)

@@ -5143,4 +5143,11 @@ int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* c, uint32_t con
   return sha_set_call(c, SHA_SETS[constraint_set - 3], section, chunk_proofs, true, d_cap_h, d_cap_q, hip_stream);
 }
 
+uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* c, uint32_t constraint_set, uint32_t section) {
+  if (!c || constraint_set < 3 || constraint_set > 5) return 0;
+  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
+  if (slot < 0) return 0;
+  return c->set_sha_bytes[SHA_SETS[constraint_set - 3].scratch][slot];
+}
+
 }  // extern "C"
