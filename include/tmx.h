@@ -1076,7 +1076,8 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d
  *              LIVE = 0, which is why K enters through KL.
  *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; row 0 of a block against the IV or
  *              the chaining value and the feed-forward between the two blocks of T.5 / T.6 hashes, which constraint set 5 below proves;
- *              and, still open (the follow-ups): LIVE against anything public; the digest's link to Level-1; SHA-512.  Under set 3 ALONE a
+ *              the digest's link to Level-1, which constraint set 6 below proves; and, still open (the follow-ups): LIVE against anything
+ *              public (set 6's flags); SHA-512.  Under set 3 ALONE a
  *              block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
  *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
@@ -1149,8 +1150,9 @@ int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, u
  *              the honest quotient has degree < N (measured: N - 2) and one two-column quotient oracle is enough.  Zero blocks, promoted slots
  *              and zero padding satisfy all 117 without a LIVE column.
  *   NOT PROVED by sets 3 and 4: row 0 of a block against the IV or the chaining value and the feed-forward between the two blocks of
- *              T.5 / T.6 hashes, which constraint set 5 below proves; and, still open (the follow-ups): the first sixteen W of a block
- *              against Level-1; LIVE against anything public; SHA-512.  Under sets 3 and 4 ALONE a block re-run consistently (schedule
+ *              T.5 / T.6 hashes, which constraint set 5 below proves; the first sixteen W of a block against Level-1, which constraint
+ *              set 6 below proves; and, still open (the follow-ups): LIVE against anything public (set 6's flags); SHA-512.  Under sets
+ *              3 and 4 ALONE a block re-run consistently (schedule
  *              and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected (tests/test_sha_sched.py records it).
  *   challenge  as set 3 with the set id 4: a fresh duplex observes 2^33, then 4, log_n, log_blowup, cap_height, n_proofs, then the table cap,
  *              then THIS helper's cap; gamma drawn as in set 1.
@@ -1244,7 +1246,8 @@ int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* ctx, uint32_t sect
  *   NOT PROVED by sets 3 + 4 + 5 (the follow-ups): the first sixteen W of a block against Level-1; the digest (IV or chaining value plus
  *              the state after the last round) against Level-1; LV against anything public -- a hash whose live second block is replaced
  *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512; the ladders' curve arithmetic
- *              and limb ranges (tests/test_sha_init.py records the first and the third).
+ *              and limb ranges (tests/test_sha_init.py records the first and the third).  Constraint set 6 below ("the SHA-256 tables'
+ *              link to Level-1") closes the first three: it pins the first sixteen W, the digest and the block structure to Level-1.
  *   challenge  set 3's lone-lane kernel: a fresh duplex observes 2^33, then 5 | chain << 8, log_n, log_blowup, cap_height, n_proofs, then the
  *              table cap, then THIS helper's cap; gamma drawn as in set 1.
  *   quotient   with D_s and D_c the selectors' denominators (y - omega_64^-1 under chain = 0; z - rho and z + rho under chain = 1),
@@ -1354,6 +1357,144 @@ int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* ctx, uint32_t c
  * streamed set-level call of constraint_set on `section` left it (a streamed call leaves exactly what _streamed_bytes returns); 0 if there
  * is none, for a constraint_set outside 3 .. 5 and for a section that is no SHA-256 table. */
 uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* ctx, uint32_t constraint_set, uint32_t section);
+
+/* ---- the SHA-256 tables' link to Level-1 (constraint set 6) -------------------------------------------------------------------------------
+ * Sets 3 + 4 + 5 prove that every live block of T.3, T.5 and T.6 is a real SHA-256 compression of its first sixteen W words and that every
+ * hash starts from the IV and chains correctly.  Nothing there says WHICH message was hashed or that the result is the digest the product
+ * returns.  Set 6 is set 2's sibling for the three SHA-256 tables: a public table gathered from the Level-1 ELEMENT rows, to which the
+ * first sixteen W of every block, the digest of every hash and the block structure are pinned.  Built beside what exists: no existing
+ * kernel, transcript, proof word, call or refusal changes.  Notation of the blocks above: N rows, K = N / 64 blocks per proof (padding
+ * included), 2 <= K <= 2^12; columns W 0, a 1 .. h 8, s_j the state column 1 + j; rows and blocks cyclic inside a proof; operands the low
+ * 32 bits of a table word; IV_0 .. IV_7 the SHA-256 constants.  There is NO chain parameter: the public flags carry the block structure.
+ *   pub        the public table: 26 columns per proof, K rows (one per block of the table, in the table's order), column-major, canonical
+ *              words below 2^32.  Inside a proof's 26:
+ *                 0 .. 15   w[k][t]     the sixteen message words of block k, SHA padding included; zero for a dead block
+ *                16 .. 23   dig[k][j]   word j of the digest, big-endian words as SHA-256 emits them, set only where block k is the LAST
+ *                                       LIVE block of its hash, else zero
+ *                24         new[k]      1 iff block k is live and starts a hash
+ *                25         chn[k]      1 iff block k is live and continues the hash of block k - 1
+ *              What the gather reads per section (docs/witness_layout.md; bytes are eight big-endian bit elements, packed by the kernel):
+ *                T.3   message 00 | marshalled[0 .. validator_byte_length) of the lane (D.1a / D.2a; the length from H, clamped to 46 as
+ *                      the product clamps it); digest: the lane's leaf hash (D.1a / D.2a).  One block per hash.
+ *                T.5   message 01 | L | R over the slot's two children as Level-1 holds them (the leaf hashes below the first level,
+ *                      D.3 / D.4 above); a promoted slot is all zero with its flags clear; digest: the slot's node (D.3 / D.4).  Two blocks.
+ *                      Level-1 holds `both children enabled ? hash : L` in a node, and the rows hash every pair: on a slot whose right
+ *                      child is NOT enabled the node is L, not the hash of the rows, and the link does not hold there -- the set is
+ *                      for batches whose trees are full (nb >= N), as every committed workload is.
+ *                T.6   the leaf block 00 | leaf as the proof struct in H carries it (the chain id's 52 bytes under its encoded length, the
+ *                      height's leaf 00 08 varint9 from D.5 under its encoded length, the 34- or 72-byte leaves; lengths clamped to 79), then
+ *                      the four path nodes 01 | left | right from the aunts in H and the previous node in D.5, path bits LSB-first;
+ *                      digests: D.5.  Two blocks per hash, the second unused (zero, flags clear) but for the 72-byte leaf and the path nodes.
+ *              The block order, the liveness rules and the one-block / two-block shapes are those of docs/level2_rows.md.
+ *   helper     33 columns per proof on the table's rows, defined for ANY input; a flag of pub is SET when its low 32 bits are not zero, new
+ *              before chn.  For a row r in block k, offsets inside a proof:
+ *                 0 ..  7   CV_j    IV_j if new[k]; (IV_j + s_j(row 63 of block k - 1)) mod 2^32 if chn[k]; else 0.  Constant in a block.
+ *                 8 .. 15   DG_j    (CV_j + s_j(r)) mod 2^32, on every row          16 .. 23   CD_j   that sum's carry bit
+ *                24 .. 31   CH_j    CHN DG_j                                       32         CHN    1 iff chn[(k + 1) mod K] is set
+ *   constraints  50 per proof, weights gamma^(50 p + j), with S = x^K - omega_64^-1, zero exactly on rows r = 63 (mod 64), T = (x^N - 1) / S,
+ *              D_t = x^K - omega_64^t, zero exactly on rows r = t (mod 64), T_t = (x^N - 1) / D_t; a prime is the value at omega x:
+ *                 0 ..  7   CD_j^2 - CD_j                    8 .. 15   DG_j + 2^32 CD_j - CV_j - s_j        16 .. 23   CH_j - CHN DG_j
+ *                24 .. 31   S (CV_j' - CV_j)                32 .. 39   T (CV_j' - CH_j - IV_j NEW)          40 .. 47   T (DG_j - CH_j - DIG_j)
+ *                48         T (CHN - CHNP)                  49         sum_(t < 16) T_t (W - E_t)
+ *              NEW, DIG_j, CHNP and E_t the public polynomials of degree < K with NEW(omega^(64 k + 63)) = new[(k + 1) mod K],
+ *              CHNP(omega^(64 k + 63)) = chn[(k + 1) mod K], DIG_j(omega^(64 k + 63)) = dig[k][j], E_t(omega^(64 k + t)) = w[k][t].
+ *              Constraint 49 has ONE weight for its sixteen parts: the T_t vanish on disjoint classes of rows, so the sum is zero on the
+ *              domain exactly when each part is.  Every nonlinear constraint has degree 2 and no selector, every selected one is linear
+ *              in the columns: the honest quotient has degree < N and one two-column quotient oracle is enough.  Dead blocks, promoted
+ *              slots, unused second blocks and zero padding satisfy all 50 with their flags clear.
+ *   public side  collapses under gamma as in set 2, to seventeen F_p^2 polynomials of degree < K: P63 through
+ *              V63_k = sum_p [sum_j gamma^(50 p + 32 + j) IV_j new_p[(k + 1) % K] + sum_j gamma^(50 p + 40 + j) dig_p[k][j]
+ *                             + gamma^(50 p + 48) chn_p[(k + 1) % K]]   on the coset omega^(64 k + 63),
+ *              and P_t, t < 16, through V^t_k = sum_p gamma^(50 p + 49) w_p[k][t] on the coset omega^(64 k + t).  The prover extends each
+ *              (set 2's coefficient and extension kernels with the coset's offset) and folds them into one plane
+ *              PQ(x_i) = P63(x_i) / S(x_i) + sum_t P_t(x_i) / D_t(x_i); the 1 / S and 1 / D_t tables have period 64 B.
+ *   challenge  a lone-lane kernel with its own duplex, set 3's form with the set id 6: it observes 2^33, then 6, log_n, log_blowup,
+ *              cap_height, n_proofs, then the table cap, then THIS helper's cap, then the four words of the PUBLIC DIGEST -- the Poseidon
+ *              Merkle root, cap height 0, of pub taken as a column-major oracle of log2 K rows and 26 n_proofs columns (set 2's rule);
+ *              gamma drawn as in set 1.
+ *   quotient   q(x_i) = [sum_p sum_(j < 32) gamma^(50 p + j) C_(p,j)] / (x_i^N - 1)
+ *                     + [sum_p sum_(j = 32 .. 48) gamma^(50 p + j) (the constraint's column part: CV_j' - CH_j, DG_j - CH_j, CHN)] / S(x_i)
+ *                     + [sum_p gamma^(50 p + 49) W_p] sum_t 1 / D_t(x_i)  -  PQ(x_i);
+ *              constraints 24 .. 31 carry the factor S(x_i); planar and canonical; pointwise: defined for any columns and any pub.
+ *   identity   from the openings at zeta and zeta omega_N, with Z = zeta^N - 1 and the three gamma sums a (j < 32), b (32 .. 48), c (49):
+ *              a + Z (b / S(zeta) + c sum_t 1 / D_t(zeta) - PQ(zeta)) == (u_0 + X u_1) Z.  The verifier hashes d_pub itself, forms its
+ *              own V63 and V^t, and evaluates the seventeen polynomials barycentrically, set 2's form with K <= 2^12 per coset:
+ *              P_c(zeta) / D_c(zeta) = 1 / (K y_0^K) sum_k V_k y_k / (zeta - y_k).  A failed identity, or a zero denominator, clears
+ *              every query's verdict.
+ *   NOT PROVED by sets 3 + 4 + 5 + 6: LIVE / LV of sets 3 and 5 against set 6's public flags; SHA-512; the ladders' curve arithmetic and
+ *              limb ranges; a T.5 slot whose right child is not enabled (above); and there is no range argument for DG on chain rows --
+ *              the identities are integer identities far below p and the digest is pinned to a public word below 2^32, so the digest is
+ *              right mod 2^32 provided set 3 range-checks s_j.  TMX_BATCH_MAX_ORACLES stays 8: a section that already carries sets 3 + 4 + 5 has seven oracles
+ *              and refuses set 6's pair by the existing rule (no room for two more oracles); widening the cap changes an ABI struct
+ *              and is the next follow-up, as is a streamed form of this helper.
+ *   tmx_air_sha256_public_shape          host only: log2 K and the column count 26 n_proofs of pub for (kind, section, n_max, n_proofs);
+ *                                        either pointer may be null.  TMX_ERR_BAD_ARG: a section other than TMX_TRACE_SHA256, _TREE,
+ *                                        _HEADER, a table the kind and n_max do not have, K outside 2 .. 2^12, n_proofs = 0,
+ *                                        33 n_proofs > 2^24.
+ *   tmx_air_sha256_public_device         gathers pub (26 n_proofs columns of K words at d_pub) from the element rows at d_elems as
+ *                                        tmx_witness_batch_device leaves them (rows tmx_elem_stride apart, the context's n_max).  One lane
+ *                                        per (proof, block).  It reads neither the trace rows nor the context's Level-1 scratch.  The
+ *                                        shape call's refusals, a bad kind, a null pointer.
+ *   tmx_air_sha256_link_helper_device    the helper (33 n_proofs columns of 2^log_rows words at d_helper) from PRE-LDE table columns
+ *                                        (9 n_proofs columns at d_table) and pub's flags (26 n_proofs columns of 2^(log_rows - 6) words at
+ *                                        d_pub).  TMX_ERR_BAD_ARG: log_rows outside 7 .. 18, n_proofs = 0, 33 n_proofs > 2^24, a null
+ *                                        pointer.
+ *   tmx_air_sha256_link_quotient_device  the public digest and gamma from d_cap, d_cap_helper and d_pub, the public side, then the
+ *                                        quotient of the EXTENDED columns d_cols (9 n_proofs) and d_helper_cols (33 n_proofs) into d_quot
+ *                                        (2 << log_n words), under the context's CURRENT NTT domain (root and shift: its own twiddle
+ *                                        kernels, not the NTT's tables).  TMX_ERR_BAD_ARG: log_blowup outside 1 .. 6, log_n > 28,
+ *                                        log_n - log_blowup outside 7 .. 18 (2 <= K <= 2^12: set 2's rule), n_proofs = 0,
+ *                                        33 n_proofs > 2^24, a coset on which x^N - 1 vanishes, a null pointer.
+ *   tmx_air_sha256_link_quotient_range_device   the same over the proofs [proof_lo, proof_hi) only, as the range calls of sets 3 - 5:
+ *                                        d_cols the whole table's column 0, d_helper_cols the FIRST HELPER COLUMN OF PROOF proof_lo, gamma
+ *                                        over n_proofs, the piece weighted with gamma^(50 proof_lo), written (accumulate = 0) or added
+ *                                        (accumulate = 1).  The piece with proof_lo = 0 carries - PQ.  Pieces that cover [0, n_proofs)
+ *                                        once, in any order, the first with accumulate = 0, leave the whole call's words.  An empty
+ *                                        range, proof_hi > n_proofs and accumulate > 1 are refused.
+ *   tmx_air_sha256_link_verify_device    tmx_batch_verify_device, then the identity for the oracles k_trace (the table), k_helper (this
+ *                                        helper) and k_helper + 1 (this quotient) against d_pub.  TMX_ERR_BAD_ARG unless the column
+ *                                        counts are 9 k, 33 k and 2, the log_n equal, k_helper > k_trace, k_helper + 1 < n_oracles, the
+ *                                        quotient call's rules hold and d_pub is set.
+ *   tmx_trace_commit_set_air_sha256_link_device   mirrors tmx_trace_commit_set_air_sha256_init_device on a RESIDENT member `section`: the
+ *                                        helper from the member's pre-LDE columns and d_pub (26 n_proofs columns of K words, as the gather
+ *                                        leaves it), extended one proof's 33 columns at a time under the set's domain and committed
+ *                                        (d_cap_h); gamma over the table cap, that cap and d_pub's digest; the public side from the SET's
+ *                                        root and shift; the quotient and its tree (d_cap_q).  The pair goes behind the last
+ *                                        helper/quotient pair that already follows the table; the calls of sets 3 - 5, unchanged, insert in
+ *                                        front of it: every order ends as table, H3, Q3, H4, Q4, H5, Q5, H6, Q6 with the same caps and the
+ *                                        same proof.  tmx_trace_commit_set_shape reports TMX_TRACE_SHA256_LINK_HELPER and
+ *                                        TMX_TRACE_SHA256_LINK_QUOTIENT in section_of.  A scratch of its own per section,
+ *                                        (33 n_proofs (N + M) + 2 M) 8 bytes plus two trees, and 4 M words (one extended public
+ *                                        polynomial and PQ) in the context's set-6 scratch: 19.9 GB for TREE at 256 proofs and blow-up 8
+ *                                        (TMX_ERR_CAPACITY if the card cannot hold it).  TMX_ERR_BAD_ARG: no set, a section that is no
+ *                                        SHA-256 table, an absent or streamed section, a second call on the section, a set with no room for
+ *                                        two more oracles, K outside 2 .. 2^12, a null pointer.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream, no device-to-host copy inside -- but a scratch
+ * that has to grow is released and allocated anew, which waits for the device (hipDeviceSynchronize for the context's set-6 scratch,
+ * as the other sets' scratches do): a caller that must not stall makes one warm call at its largest shape.  Every range piece hashes
+ * d_pub and draws gamma again (only the piece with proof_lo = 0 builds the public side): repeated launch-sized work that a streamed
+ * form of the helper would hoist.  tmx_air_last_gamma covers the quotient calls and the set-level call too. */
+#define TMX_TRACE_SHA256_LINK_HELPER 8192u
+#define TMX_TRACE_SHA256_LINK_QUOTIENT 16384u
+#define TMX_AIR_SHA256_PUBLIC_WIDTH 26
+#define TMX_AIR_SHA256_LINK_HELPER_COLS 33
+#define TMX_AIR_SHA256_LINK_CONSTRAINTS 50
+int32_t tmx_air_sha256_public_shape(int32_t kind, uint32_t section, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols);
+int32_t tmx_air_sha256_public_device(tmx_ctx* ctx, int32_t kind, uint32_t section, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub,
+                                     void* hip_stream);
+int32_t tmx_air_sha256_link_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, const uint64_t* d_pub,
+                                          uint64_t* d_helper, void* hip_stream);
+int32_t tmx_air_sha256_link_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_link_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha256_link_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
+                                                    void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

@@ -24,6 +24,8 @@ AIR_SHA256_SCHED_HELPER_COLS, AIR_SHA256_SCHED_CONSTRAINTS = 115, 117   # TMX_AI
 TRACE_SHA256_SCHED_HELPER, TRACE_SHA256_SCHED_QUOTIENT = 512, 1024   # TMX_TRACE_SHA256_SCHED_*: the helper and the quotient of set 4
 AIR_SHA256_INIT_HELPER_COLS, AIR_SHA256_INIT_CONSTRAINTS = 315, 337   # TMX_AIR_SHA256_INIT_*: constraint set 5, the SHA-256 block starts
 TRACE_SHA256_INIT_HELPER, TRACE_SHA256_INIT_QUOTIENT = 2048, 4096   # TMX_TRACE_SHA256_INIT_*: the helper and the quotient of set 5
+TRACE_SHA256_LINK_HELPER, TRACE_SHA256_LINK_QUOTIENT = 8192, 16384   # TMX_TRACE_SHA256_LINK_*: the helper and the quotient of set 6
+AIR_SHA256_PUBLIC_WIDTH, AIR_SHA256_LINK_HELPER_COLS, AIR_SHA256_LINK_CONSTRAINTS = 26, 33, 50   # constraint set 6, the link to Level-1
 
 
 class ValidatorRec(C.Structure):
@@ -393,6 +395,18 @@ def lib():
         L.tmx_trace_commit_set_air_sha256_streamed_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_trace_commit_set_air_sha256_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.tmx_trace_commit_set_air_sha256_scratch_bytes.restype = C.c_uint64
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
+    try:   # constraint set 6: the public table and the helper of the SHA-256 tables' link to Level-1
+        L.tmx_air_sha256_public_shape.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.tmx_air_sha256_public_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha256_link_helper_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha256_link_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 7
+        L.tmx_air_sha256_link_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 7
+        L.tmx_trace_commit_set_air_sha256_link_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha256_link_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -575,6 +575,45 @@ class Context:
         last helper/quotient pair that already follows the table"""
         check(self._L.tmx_trace_commit_set_air_sha256_init_device(self._h, section, d_cap_h, d_cap_q, self._stream(stream)), self._h)
 
+    # ---- constraint set 6: the SHA-256 tables' link to Level-1 (include/tmx.h): the public table and the helper
+    def air_sha256_public_shape(self, kind, section, n_proofs):
+        """(log2 K, columns) of the public table of `section` (SHA256, TREE or HEADER) of n_proofs proofs at this context's n_max"""
+        return air_sha256_public_shape(kind, section, self.n_max, n_proofs)
+
+    def air_sha256_public_device(self, kind, section, n_proofs, d_elems, d_pub, stream=None):
+        """the public table of `section` (column-major, 26 n_proofs columns of K words at d_pub: per block the sixteen message words, the
+        digest, new, chn) from the element rows witness_batch_device wrote"""
+        check(self._L.tmx_air_sha256_public_device(self._h, kind, section, n_proofs, d_elems, d_pub, self._stream(stream)), self._h)
+
+    def air_sha256_link_helper_device(self, log_rows, n_proofs, d_table, d_pub, d_helper, stream=None):
+        """the link helper (33 n_proofs columns of 2^log_rows words at d_helper) from the pre-LDE table columns (9 n_proofs) at d_table and
+        the flags of the public table (26 n_proofs columns of 2^(log_rows - 6) words) at d_pub"""
+        check(self._L.tmx_air_sha256_link_helper_device(self._h, log_rows, n_proofs, d_table, d_pub, d_helper, self._stream(stream)), self._h)
+
+    def air_sha256_link_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot,
+                                        stream=None, proof_range=None, accumulate=0):
+        """gamma from the table cap, the helper cap and the digest of d_pub, the seventeen public polynomials, then the quotient of the 50
+        constraints per proof over the extended table and helper columns into d_quot (planar, 2 << log_n words); proof_range and accumulate
+        as in air_sha256_quotient_device: the piece that starts at proof 0 carries the public side"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha256_link_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                                    d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot, self._stream(stream)), self._h)
+            return
+        check(self._L.tmx_air_sha256_link_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper,
+                                                          d_pub, d_quot, self._stream(stream)), self._h)
+
+    def air_sha256_link_verify_device(self, params, k_trace, k_helper, d_caps, d_proof, d_pub, d_ok, stream=None):
+        """batch_verify_device, then the set-6 identity at zeta for the oracles k_trace (table), k_helper (helper), k_helper + 1 (quotient)
+        against the public table at d_pub, which the verifier hashes and combines itself"""
+        check(self._L.tmx_air_sha256_link_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, k_helper, d_caps, d_proof, d_pub,
+                                                        d_ok, self._stream(stream)), self._h)
+
+    def trace_commit_set_air_sha256_link_device(self, section, d_pub, d_cap_h, d_cap_q, stream=None):
+        """adds the link helper and quotient of the resident member `section` (SHA256, TREE or HEADER) against the public table at d_pub to
+        the commit set, behind the last helper/quotient pair that already follows the table"""
+        check(self._L.tmx_trace_commit_set_air_sha256_link_device(self._h, section, d_pub, d_cap_h, d_cap_q, self._stream(stream)), self._h)
+
     # ---- streamed helpers of constraint sets 3 - 5 (include/tmx.h "streamed helpers of the SHA-256 sets")
     def trace_commit_set_air_sha256_streamed_device(self, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q, stream=None):
         """the set-level call of constraint set 3, 4 or 5 with the helper fed in chunks of chunk_proofs whole proofs and never resident
@@ -739,6 +778,14 @@ def trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup
     lde = C.c_uint64(0)
     return int(L.tmx_trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs,
                                                                  C.byref(lde))), int(lde.value)
+
+
+def air_sha256_public_shape(kind, section, n_max, n_proofs, L=None):
+    """tmx_air_sha256_public_shape (no context, no device): (log2 K, columns) of the public table of constraint set 6"""
+    L = L or _lib.lib()
+    log_k, n_cols = C.c_uint32(), C.c_uint32()
+    check(L.tmx_air_sha256_public_shape(kind, section, n_max, n_proofs, C.byref(log_k), C.byref(n_cols)))
+    return int(log_k.value), int(n_cols.value)
 
 
 def air_ladder_public_shape(kind, n_max, n_proofs, L=None):

@@ -150,4 +150,60 @@ int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h,
                           const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
                           uint32_t n_queries, void* d_ok, void* stream);
 
+// ---- constraint set 6: the SHA-256 tables' link to Level-1 (include/tmx.h "the SHA-256 tables' link to Level-1").  The same table, a public
+// table of 26 columns per proof on the table's blocks, a helper oracle of 33 columns per proof, 50 constraints per proof.
+constexpr uint32_t AIR_SHA_PUBLIC_WIDTH = 26, AIR_LINK_HELPER_COLS = 33, AIR_LINK_CONSTRAINTS = 50;
+constexpr uint32_t AIR_SHA_PUBLIC_MIN_LOG_K = 1, AIR_SHA_PUBLIC_MAX_LOG_K = 12;
+// Where the gather reads in an element row (docs/witness_layout.md): the first elements of H.2 (ValidatorVariable[N]), H.3 (nb, round, the
+// proof structs), H.4 (skip: ValidatorHashFieldVariable[N]), D.1a, D.2a (skip), D.3, D.4 (skip) and D.5; section = TMX_TRACE_SHA256, _TREE
+// or _HEADER; n = the context's n_max, tn = the slots of its fixed-shape tree
+// Every offset below is recorded by build_program (api.cpp) while it emits the serializer's table, so a layout change is made there alone:
+//   h2_lane, h2_vlen   a ValidatorVariable's elements and where its validator_byte_length stands; h4_lane, h4_vlen likewise for H.4
+//   cid_len, cid, h_len   inside H.3: the encoded chain-id length, the 52 chain-id bytes, the encoded height length
+//   aunts[q], leaf[q]  inside H.3: the four aunts of header proof q and its leaf bytes (q >= 2; leaf_bytes[q] of them)
+//   d1a_lane, d2a_lane, lane_leaf   a lane's elements in D.1a / D.2a (the marshalled validator first) and where its leaf hash stands
+//   d5_proof[q], d5_hleaf   inside D.5: leaf hash and four path nodes of proof q, and the height leaf 00 08 varint9
+struct AirShaPublicGeom {
+  uint64_t elem_stride;
+  uint32_t kind, section, n, tn;
+  uint32_t h2, h3, h4, d1a, d2a, d3, d4, d5;
+  uint32_t h2_lane, h2_vlen, h4_lane, h4_vlen, cid_len, cid, h_len, aunts[5], leaf[5], leaf_bytes[5];
+  uint32_t d1a_lane, d2a_lane, lane_leaf, d5_proof[5], d5_hleaf;
+};
+// The public table from element rows: one lane per (proof, block); d_pub 26 n_proofs columns of 2^log_k words
+int launch_air_sha_public_gather(const void* d_rows, const AirShaPublicGeom& G, uint32_t log_k, uint32_t n_proofs, void* d_pub, void* stream);
+// The helper oracle from pre-LDE columns and the public flags: one lane per (proof, row); d_table 9 n_proofs columns of 2^log_rows words,
+// d_pub 26 n_proofs columns of 2^(log_rows - 6), d_helper 33 n_proofs columns of 2^log_rows
+int launch_air_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, const void* d_pub, void* d_helper, void* stream);
+// gamma of set 6: set 3's lone-lane form as a kernel of its own (poseidon.hip k_air_link_gamma; k_air_sha_gamma and k_fri_transcript stay
+// as they are): a fresh duplex over 2^33, obs (6, log_n, log_blowup, cap_height, n_proofs), the table cap, the helper cap (cap_words each),
+// the four words of the public digest
+int launch_air_link_gamma(const void* d_consts, int mode, const uint32_t obs[5], uint32_t cap_words, const void* d_cap, const void* d_cap_helper,
+                          const void* d_digest, void* d_state, void* d_chal, void* stream);
+// The tables one set-6 quotient launch reads (u64 words at d_tab, in the set's own scratch); per = i mod (64 << log_blowup):
+//   gpow  [52][2]   gamma^0 .. gamma^50, then gamma^(50 first)          zinv  [2^log_blowup]   1 / (x_i^N - 1), by i mod 2^log_blowup
+//   s, sinv [per]   S(x_i) = x_i^K - omega_64^-1 and its inverse         dsum  [per]            sum_(t < 16) 1 / D_t(x_i)
+//   dinv  [16][AIR6_PER_MAX]   1 / D_t(x_i), D_t = x^K - omega_64^t (the fold of the public side reads them; the pass reads dsum)
+constexpr uint32_t AIR6_PER_MAX = 64u << 6;
+constexpr uint32_t AIR6_TAB_GPOW = 0, AIR6_TAB_ZINV = 128, AIR6_TAB_S = 192, AIR6_TAB_SINV = AIR6_TAB_S + AIR6_PER_MAX,
+                   AIR6_TAB_DSUM = AIR6_TAB_SINV + AIR6_PER_MAX, AIR6_TAB_DINV = AIR6_TAB_DSUM + AIR6_PER_MAX;
+constexpr uint64_t AIR6_TAB_WORDS = AIR6_TAB_DINV + 16ull * AIR6_PER_MAX;
+static_assert(2 * (AIR_LINK_CONSTRAINTS + 2) <= AIR6_TAB_ZINV, "gamma^0 .. gamma^51 in front of zinv");
+// s_n = s^N, w_n = w^N, s_k = s^K, w_k = w^K (K = N / 64), om64 = omega_64; gamma at d_gamma (2 words)
+int launch_air_link_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_k, uint64_t w_k, uint64_t om64,
+                           const void* d_gamma, void* d_tab, void* stream);
+// The seventeen value vectors under gamma, one lane per (vector, block k): d_v [17][K][2] words, V63 first, then V^0 .. V^15
+int launch_air_link_combine(uint32_t log_k, uint32_t n_proofs, const void* d_pub, const void* d_gamma, void* d_v, void* stream);
+// d_pq (planar, 2 << log_m) = (first ? 0 : d_pq) + d_ext / divisor: which = 0 divides by S, 1 + t by D_t (tables at d_tab)
+int launch_air_link_fold(uint32_t log_m, uint32_t log_blowup, uint32_t which, int first, const void* d_ext, const void* d_tab, void* d_pq, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p [sum_(j < 32) gamma^(50 p + j) C_(p,j) / (x^N - 1) + sum_(32 <= j < 49)
+// gamma^(50 p + j) L_(p,j) / S + gamma^(50 p + 49) W_p sum_t 1 / D_t] - PQ; d_pq null: a piece that does not start at proof 0
+int launch_air_link_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                             const void* d_tab, const void* d_pq, int form, void* d_quot, void* stream);
+// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with the
+// seventeen public polynomials barycentric from the verifier's own d_v; om = omega_N, om_k = omega_N^64, k_inv = 1 / K
+int launch_air_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64, uint64_t om, uint64_t om_k,
+                          uint64_t k_inv, const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta,
+                          const void* d_gamma, const void* d_v, uint32_t n_queries, void* d_ok, void* stream);
+
 }  // namespace tmx

@@ -1436,4 +1436,459 @@ int launch_air_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h,
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 6: the SHA-256 tables' link to Level-1 (include/tmx.h "the SHA-256 tables' link to Level-1") -----------------------------
+// The public table and the helper oracle; sets 3 - 5 above stay as they are.
+
+// One byte of an element row: eight big-endian bit elements
+__device__ __forceinline__ uint32_t link_byte(const uint64_t* __restrict__ at) {
+  uint32_t v = 0;
+#pragma unroll
+  for (uint32_t b = 0; b < 8; b++) v = (v << 1) | ((uint32_t)at[b] & 1u);
+  return v;
+}
+
+// One hash of a table as the element row holds it: a message of `len` bytes (0: a zero hash, no block is live) -- the byte `prefix` at
+// position 0 where a_lo = 1, then the bytes at element a_at on positions [a_lo, a_hi) and those at b_at on [b_lo, b_hi), zero elsewhere --
+// and the 32 digest bytes at element dig_at.
+struct LinkHash {
+  uint32_t len, prefix, a_at, a_lo, a_hi, b_at, b_lo, b_hi, dig_at;
+};
+
+// Which hash stands at item `it` of the section's table, in the order k_trace_sha256 / k_trace_sha256x2 (trace.hip) write them.
+__device__ __forceinline__ LinkHash link_hash(const AirShaPublicGeom& G, const uint64_t* __restrict__ row, uint32_t it) {
+  LinkHash H = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const uint32_t n = G.n, sets = G.kind == 0 ? 2u : 1u;
+  if (G.section == 4u) {  // T.3: 00 | marshalled[0 .. validator_byte_length), item (set, lane)
+    if (it >= sets * n) return H;
+    const uint32_t set = it >= n ? 1u : 0u, i = it - set * n;
+    const uint32_t lane = set ? G.d2a + G.d2a_lane * i : G.d1a + G.d1a_lane * i;
+    const uint32_t vlen = (uint32_t)row[set ? G.h4 + G.h4_lane * i + G.h4_vlen : G.h2 + G.h2_lane * i + G.h2_vlen];
+    H.len = 1u + (vlen > 46u ? 46u : vlen);
+    H.a_at = lane; H.a_lo = 1; H.a_hi = 47;
+    H.dig_at = lane + G.lane_leaf;
+    return H;
+  }
+  if (G.section == 16u) {  // T.5: 01 | L | R over the slot's two children, item (set, slot); a promoted slot is a zero hash
+    if (it >= sets * G.tn) return H;
+    const uint32_t set = it >= G.tn ? 1u : 0u, nodes = set ? G.d4 : G.d3;
+    uint32_t rem = it - set * G.tn, sz = n, level = 0, first = 0, prev_first = 0;
+    for (;;) {
+      const uint32_t nx = (sz + 1u) / 2u;
+      if (rem < nx) break;
+      rem -= nx; prev_first = first; first += nx; sz = nx; level++;
+    }
+    if (2u * rem + 1u >= sz) return H;
+    const uint32_t step = level ? 256u : (set ? G.d2a_lane : G.d1a_lane);
+    const uint32_t l = level ? nodes + 256u * (prev_first + 2u * rem) : (set ? G.d2a : G.d1a) + step * 2u * rem + G.lane_leaf;
+    H.len = 65; H.prefix = 1;
+    H.a_at = l; H.a_lo = 1; H.a_hi = 33;
+    H.b_at = l + step; H.b_lo = 33; H.b_hi = 65;
+    H.dig_at = nodes + 256u * (first + rem);
+    return H;
+  }
+  // T.6: item (proof q, hash h): h = 0 the leaf 00 | leaf as the proof struct carries it, h = 1 .. 4 the path nodes 01 | left | right
+  const uint32_t nq = G.kind == 0 ? 4u : 5u, q = it / 5u, h = it - 5u * q;
+  if (q >= nq) return H;
+  const uint32_t step_kind = G.kind == 0 ? 0u : 1u;
+  const uint32_t d5q = G.d5 + G.d5_proof[q], aunts = G.h3 + G.aunts[q];
+  H.dig_at = d5q + 256u * h;
+  if (h == 0) {
+    if (q == 0) {  // the chain id: 52 bytes carried, the encoded length decides
+      const uint32_t cl = (uint32_t)row[G.h3 + G.cid_len];
+      H.len = (cl > 79u ? 79u : cl) + 1u;
+      H.a_at = G.h3 + G.cid; H.a_lo = 1; H.a_hi = 53;
+    } else if (q == 1) {  // the height leaf 00 08 varint9 of D.5
+      const uint32_t hl = (uint32_t)row[G.h3 + G.h_len];
+      H.len = (hl > 79u ? 79u : hl) + 1u;
+      H.a_at = G.d5 + G.d5_hleaf; H.a_lo = 0; H.a_hi = 11;
+    } else {
+      const uint32_t w = G.leaf_bytes[q];
+      H.len = w + 1u;
+      H.a_at = G.h3 + G.leaf[q]; H.a_lo = 1; H.a_hi = 1u + w;
+    }
+    return H;
+  }
+  const uint32_t k = h - 1u, index = q == 0 ? 1u : (q == 1 ? 2u : (q == 2 ? 7u : (q == 3 ? (step_kind ? 4u : 7u) : 8u)));
+  const uint32_t cur = d5q + 256u * k, aunt = aunts + 256u * k;
+  const bool right = (index >> k) & 1u;  // the running hash is the right child
+  H.len = 65; H.prefix = 1;
+  H.a_at = right ? aunt : cur; H.a_lo = 1; H.a_hi = 33;
+  H.b_at = right ? cur : aunt; H.b_lo = 33; H.b_hi = 65;
+  return H;
+}
+
+// Byte `pos` of the padded message: the message, 80, zeros, the bit length in the last four bytes of the last block
+__device__ __forceinline__ uint32_t link_padded_byte(const LinkHash& H, const uint64_t* __restrict__ row, uint32_t n_blocks, uint32_t pos) {
+  if (pos >= H.len) {
+    if (pos == H.len) return 0x80u;
+    const uint32_t tail = 64u * n_blocks - 1u - pos;
+    return tail < 4u ? ((8u * H.len) >> (8u * tail)) & 0xffu : 0u;
+  }
+  if (pos < H.a_lo) return H.prefix;
+  if (pos < H.a_hi) return link_byte(row + H.a_at + 8u * (pos - H.a_lo));
+  if (pos >= H.b_lo && pos < H.b_hi) return link_byte(row + H.b_at + 8u * (pos - H.b_lo));
+  return 0u;
+}
+
+// One lane per (proof, block): the sixteen message words of the block, the digest where the block is the last live one of its hash, new
+// and chn, from the element row of the proof alone.  Blocks of a zero hash, unused second blocks and the padding behind the section's own
+// blocks are all zero.  Lanes run over the blocks, so each of the 26 stores of a wave covers consecutive words of one column.
+__global__ __launch_bounds__(256) void k_air_sha_public_gather(const uint64_t* __restrict__ rows, AirShaPublicGeom G, uint32_t log_k, uint32_t n_proofs,
+                                                               uint64_t* __restrict__ pub) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_k)) return;
+  const uint32_t p = (uint32_t)(idx >> log_k), k = (uint32_t)(idx & ((1u << log_k) - 1));
+  const uint64_t* __restrict__ row = rows + (uint64_t)p * G.elem_stride;
+  const uint32_t log_per = G.section == 4u ? 0u : 1u, b = k & ((1u << log_per) - 1u);
+  const LinkHash H = link_hash(G, row, k >> log_per);
+  const uint32_t n_blocks = H.len == 0 ? 0u : (H.len + 9u > 64u ? 2u : 1u);
+  const bool live = b < n_blocks, last = live && b + 1u == n_blocks;
+  uint64_t* __restrict__ dst = pub + (((uint64_t)p * AIR_SHA_PUBLIC_WIDTH) << log_k) + k;
+#pragma unroll 1
+  for (uint32_t t = 0; t < 16; t++) {
+    uint32_t word = 0;
+    if (live) {
+#pragma unroll 1
+      for (uint32_t c = 0; c < 4; c++) word = (word << 8) | link_padded_byte(H, row, n_blocks, 64u * b + 4u * t + c);
+    }
+    dst[(uint64_t)t << log_k] = word;
+  }
+#pragma unroll 1
+  for (uint32_t j = 0; j < 8; j++) {
+    uint32_t word = 0;
+    if (last) {
+#pragma unroll
+      for (uint32_t c = 0; c < 4; c++) word = (word << 8) | link_byte(row + H.dig_at + 8u * (4u * j + c));
+    }
+    dst[(uint64_t)(16 + j) << log_k] = word;
+  }
+  dst[(uint64_t)24 << log_k] = live && b == 0 ? 1 : 0;
+  dst[(uint64_t)25 << log_k] = live && b != 0 ? 1 : 0;
+}
+
+// One lane per (proof, row) of the pre-LDE table: the row's eight state words, the flags of its block and chn of the next block (blocks
+// cyclic inside the proof), under chn the eight state words of the row in front of the block; then 33 stores, each of them consecutive
+// words of one column across the wave.  Operands are the low 32 bits of the words; a flag is set when its low 32 bits are not zero.
+__global__ __launch_bounds__(256) void k_air_link_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                         const uint64_t* __restrict__ pub, uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows), log_k = log_rows - 6;
+  const uint64_t mask = (1ull << log_rows) - 1, r = idx & mask, prev = ((r & ~63ull) - 1) & mask;
+  const uint32_t k = (uint32_t)(r >> 6), kn = (k + 1u) & ((1u << log_k) - 1u);
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA_WIDTH) << log_rows);
+  const uint64_t* __restrict__ u = pub + (((uint64_t)p * AIR_SHA_PUBLIC_WIDTH) << log_k);
+  const bool is_new = (uint32_t)u[((uint64_t)24 << log_k) + k] != 0, is_chn = !is_new && (uint32_t)u[((uint64_t)25 << log_k) + k] != 0;
+  const uint64_t chn_next = (uint32_t)u[((uint64_t)25 << log_k) + kn] != 0 ? 1 : 0;
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_LINK_HELPER_COLS) << log_rows) + r;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t* __restrict__ col = t + ((uint64_t)(1 + j) << log_rows);
+    const uint32_t cv = is_new ? IV_SHA256[j] : is_chn ? IV_SHA256[j] + (uint32_t)col[prev] : 0u;
+    const uint64_t s = (uint64_t)cv + (uint32_t)col[r];
+    o[(uint64_t)j << log_rows] = cv;
+    o[(uint64_t)(8 + j) << log_rows] = (uint32_t)s;
+    o[(uint64_t)(16 + j) << log_rows] = s >> 32;
+    o[(uint64_t)(24 + j) << log_rows] = chn_next ? (uint32_t)s : 0u;
+  }
+  o[(uint64_t)32 << log_rows] = chn_next;
+}
+
+// Helper column offsets inside a proof's 33; the constraint indices inside its 50 are written where they are used.
+constexpr uint32_t K_CV = 0, K_DG = 8, K_CD = 16, K_CH = 24, K_CHN = 32;
+
+// The 50 constraints of one proof at one point, once for prover and verifier: 0 .. 31 into the plain sum (24 .. 31 carry the factor S),
+// the column parts of 32 .. 48 into the selected sum (what T = (x^N - 1) / S multiplies, less the public polynomials), W into the third
+// sum (what sum_t T_t multiplies, less E_t).  Constraint 49 has one weight for its sixteen parts: the T_t vanish on disjoint classes of
+// rows, so the sum is zero on the domain exactly when each part is.
+template <class F, class View>
+__device__ __forceinline__ void air_link_constraints(View& at, typename F::T S) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  const T CHN = at.again(K_CHN);
+#pragma unroll View::BITS
+  for (uint32_t j = 0; j < 8; j++) {
+    const T CV = at.once(K_CV + j), DG = at.once(K_DG + j), CD = at.once(K_CD + j), CH = at.once(K_CH + j), CVn = at.next(K_CV + j);
+    at.plain(j, A::boolean(CD));
+    at.plain(8 + j, A::sub(A::add(DG, A::scale(CD, 1ull << 32)), A::add(CV, at.tbl(T_A + j))));
+    at.plain(16 + j, A::sub(CH, A::mul(CHN, DG)));
+    at.plain(24 + j, A::mul(S, A::sub(CVn, CV)));
+    at.selected(32 + j, A::sub(CVn, CH));
+    at.selected(40 + j, A::sub(DG, CH));
+  }
+  at.selected(48, CHN);
+  at.chained(49, at.tbl(T_W));
+}
+
+// One thread per entry i < 64 B of the selector tables: z = x_i^K, the seventeen denominators z - omega_64^-1 and z - omega_64^t inverted
+// with one Fermat chain (Montgomery's trick), and their sum over t; and air_zinv_gpow's share.  No entry vanishes: S and every D_t
+// divide x^N - 1, which the caller checked.
+__global__ __launch_bounds__(256) void k_air_link_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_k, uint64_t w_k,
+                                                         uint64_t om64, const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < (64u << log_blowup)) {
+    const uint64_t z = gl_mul(s_k, gl_pow(w_k, k));
+    uint64_t d[17], pre[17], acc = 1, o = 1;
+#pragma unroll
+    for (uint32_t t = 0; t < 16; t++, o = gl_mul(o, om64)) d[1 + t] = gl_sub(z, o);
+    d[0] = gl_sub(z, gl_pow(om64, 63));
+#pragma unroll
+    for (uint32_t t = 0; t < 17; t++) {
+      pre[t] = acc;
+      acc = gl_mul(acc, d[t]);
+    }
+    uint64_t inv = gl_pow(acc, GL_P - 2), dsum = 0;
+#pragma unroll
+    for (uint32_t t = 17; t-- > 0;) {
+      const uint64_t x = gl_mul(inv, pre[t]);
+      inv = gl_mul(inv, d[t]);
+      if (t) {
+        tab[AIR6_TAB_DINV + (t - 1) * AIR6_PER_MAX + k] = x;
+        dsum = gl_add(dsum, x);
+      } else {
+        tab[AIR6_TAB_SINV + k] = x;
+      }
+    }
+    tab[AIR6_TAB_S + k] = d[0];
+    tab[AIR6_TAB_DSUM + k] = dsum;
+  }
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_LINK_CONSTRAINTS, tab + AIR6_TAB_ZINV, tab + AIR6_TAB_GPOW);
+}
+
+// The seventeen value vectors, one lane per (vector, block k) -- blockIdx.y is the vector: 0 for V63, 1 + t for V^t --, Horner over the
+// proofs by gamma^50:
+//   V63_k = sum_p gamma^(50 p) [G_new new_p[k + 1] + sum_j gamma^(40 + j) dig_p[k][j] + gamma^48 chn_p[k + 1]],  G_new = sum_j gamma^(32 + j) IV_j
+//   V^t_k = gamma^49 sum_p gamma^(50 p) w_p[k][t]
+// (k + 1 mod K).  pub is column-major: a wave reads 64 consecutive words per column; the gamma powers sit in LDS, wave-uniform.
+__global__ __launch_bounds__(256) void k_air_link_combine(uint32_t log_k, uint32_t n_proofs, const uint64_t* __restrict__ pub,
+                                                          const uint64_t* __restrict__ gamma, uint64_t* __restrict__ v) {
+  __shared__ uint64_t gw[2 * 12];  // gamma^40 .. gamma^50, then G_new
+  if (threadIdx.x < 11) {
+    const gl2 g = gl2_pow({gamma[0], gamma[1]}, 40 + threadIdx.x);
+    gw[2 * threadIdx.x] = g.c0;
+    gw[2 * threadIdx.x + 1] = g.c1;
+  } else if (threadIdx.x == 11) {
+    gl2 g = gl2_pow({gamma[0], gamma[1]}, 32), s = {0, 0};
+    for (uint32_t j = 0; j < 8; j++, g = gl2_mul(g, {gamma[0], gamma[1]})) s = gl2_add(s, gl2_scale(g, IV_SHA256[j]));
+    gw[22] = s.c0;
+    gw[23] = s.c1;
+  }
+  __syncthreads();
+  const uint32_t K = 1u << log_k, k = blockIdx.x * 256 + threadIdx.x, which = blockIdx.y;
+  if (k >= K) return;
+  const uint32_t kn = (k + 1) & (K - 1);
+  const gl2 g50 = {gw[20], gw[21]};
+  gl2 t = {0, 0};
+  if (which == 0) {
+    const gl2 g48 = {gw[16], gw[17]}, g_new = {gw[22], gw[23]};
+    for (uint32_t p = n_proofs; p-- > 0;) {
+      const uint64_t* __restrict__ c = pub + (((uint64_t)p * AIR_SHA_PUBLIC_WIDTH) << log_k);
+      gl2 w = gl2_add(gl2_scale(g_new, gl_canon(c[((uint64_t)24 << log_k) + kn])), gl2_scale(g48, gl_canon(c[((uint64_t)25 << log_k) + kn])));
+#pragma unroll
+      for (uint32_t j = 0; j < 8; j++) w = gl2_add(w, gl2_scale({gw[2 * j], gw[2 * j + 1]}, gl_canon(c[((uint64_t)(16 + j) << log_k) + k])));
+      t = gl2_add(gl2_mul(t, g50), w);
+    }
+  } else {
+    for (uint32_t p = n_proofs; p-- > 0;) {
+      const uint64_t x = gl_canon(pub[(((uint64_t)p * AIR_SHA_PUBLIC_WIDTH + (which - 1)) << log_k) + k]);
+      t = gl2_mul(t, g50);
+      t.c0 = gl_add(t.c0, x);
+    }
+    t = gl2_mul(t, {gw[18], gw[19]});
+  }
+  v[((uint64_t)which << (log_k + 1)) + 2 * k] = t.c0;
+  v[((uint64_t)which << (log_k + 1)) + 2 * k + 1] = t.c1;
+}
+
+// The fold of one extended public polynomial into PQ, one lane per point: pq = (first ? 0 : pq) + ext / divisor, both planes
+__global__ __launch_bounds__(256) void k_air_link_fold(uint32_t log_m, uint32_t log_blowup, uint32_t which, uint32_t first, const uint64_t* __restrict__ ext,
+                                                       const uint64_t* __restrict__ tab, uint64_t* __restrict__ pq) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t per = i & ((64ull << log_blowup) - 1);
+  const uint64_t inv = which ? tab[AIR6_TAB_DINV + (uint64_t)(which - 1) * AIR6_PER_MAX + per] : tab[AIR6_TAB_SINV + per];
+  uint64_t q0 = gl_mul(gl_canon(ext[i]), inv), q1 = gl_mul(gl_canon(ext[M + i]), inv);
+  if (!first) {
+    q0 = gl_add(q0, pq[i]);
+    q1 = gl_add(q1, pq[M + i]);
+  }
+  pq[i] = q0;
+  pq[M + i] = q1;
+}
+
+// The set-6 hot pass, k_air_ladder_boundary_quotient's shape: one lane per point, a loop over the proofs from the last to the first
+// (Horner by gamma^50), the nine table columns and the 33 helper columns at i and the eight CV at i + B.  Per proof 1 / (x^N - 1) is applied
+// once to the plain sum, 1 / S once to the selected sum and sum_t 1 / D_t once to gamma^49 W.  pq: the folded public side, subtracted by
+// the piece that starts at proof 0 (null elsewhere).  FORM as in k_air_sha_quotient.
+template <int FORM>
+__global__ __launch_bounds__(AIR_THREADS) void k_air_link_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                   const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                   const uint64_t* __restrict__ tab, const uint64_t* __restrict__ pq,
+                                                                   uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1), per = i & ((64ull << log_blowup) - 1);
+  const uint64_t* __restrict__ gp = tab + AIR6_TAB_GPOW;
+  const uint64_t S = tab[AIR6_TAB_S + per], sinv = tab[AIR6_TAB_SINV + per], dsum = tab[AIR6_TAB_DSUM + per];
+  const uint64_t zinv = tab[AIR6_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g50 = {gp[2 * AIR_LINK_CONSTRAINTS], gp[2 * AIR_LINK_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_LINK_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_link_constraints<FieldP>(at, S);
+    const uint64_t v0 = gl_add(gl_add(gl_mul(gl_canon(at.a0), zinv), gl_mul(gl_canon(at.b0), sinv)), gl_mul(gl_canon(at.c0), dsum));
+    const uint64_t v1 = gl_add(gl_add(gl_mul(gl_canon(at.a1), zinv), gl_mul(gl_canon(at.b1), sinv)), gl_mul(gl_canon(at.c1), dsum));
+    t = gl2_add(gl2_mul(t, g50), {v0, v1});
+  }
+  if (FORM != AIR_FORM_WHOLE) t = gl2_mul(t, {gp[2 * (AIR_LINK_CONSTRAINTS + 1)], gp[2 * (AIR_LINK_CONSTRAINTS + 1) + 1]});
+  if (pq) t = gl2_sub(t, {gl_canon(pq[i]), gl_canon(pq[M + i])});
+  if (FORM == AIR_FORM_PIECE_ACC) t = gl2_add(t, {gl_canon(out[i]), gl_canon(out[M + i])});
+  out[i] = t.c0;
+  out[M + i] = t.c1;
+}
+
+// The set-6 identity at zeta, one workgroup:
+//   sum_p gamma^(50 p) (a + Z (b / S + c sum_t 1 / D_t)) - Z PQ(zeta) == (u_0 + X u_1) Z,   Z = zeta^N - 1
+// a, b, c the three sums of air_link_constraints over F_p^2 from the openings; thread t takes the proofs t, t + 256, ...  PQ(zeta) is the sum
+// over the seventeen cosets y_k = omega^off omega_K^k (off = 63, then 0 .. 15) of 1 / (K y_0^K) sum_k V_k y_k / (zeta - y_k), barycentric from
+// the verifier's own V as in k_air_ladder_boundary_check: thread t takes k = t, t + 256, ... (at most 16) of every coset and inverts its
+// zeta - y_k with one F_p^2 inversion per coset.  Every term is linear in the sums, so each thread folds its own share and one sum meets in
+// LDS.  A zero denominator (S, a D_t or a zeta - y_k: zeta lies outside F_p, so only a zeta^K inside it can do that) clears every verdict.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64,
+                                                                       uint64_t om, uint64_t om_k, uint64_t k_inv,
+                                                                       const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
+                                                                       const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
+                                                                       const uint64_t* __restrict__ gamma, const uint64_t* __restrict__ vk,
+                                                                       uint32_t n_queries, uint32_t* __restrict__ ok) {
+  __shared__ uint64_t gpw[2 * (AIR_LINK_CONSTRAINTS + 1)];
+  const uint32_t t = threadIdx.x, log_k = log_sub - 6, K = 1u << log_k;
+  const gl2 g = {gamma[0], gamma[1]}, z = {zeta[0], zeta[1]};
+  air_gamma_powers(g, AIR_LINK_CONSTRAINTS, gpw);
+  __syncthreads();
+  gl2 zk = z;  // zeta^K
+  for (uint32_t k = 0; k < log_k; k++) zk = gl2_mul(zk, zk);
+  gl2 zn = zk;  // zeta^N
+  for (uint32_t k = 0; k < 6; k++) zn = gl2_mul(zn, zn);
+  const gl2 Z = {gl_sub(zn.c0, 1), zn.c1};
+  const gl2 S = {gl_sub(zk.c0, gl_pow(om64, 63)), zk.c1};
+  bool bad = gl2_eq(S, {0, 0});
+  gl2 dsum = {0, 0};
+  {
+    uint64_t o = 1;
+    for (uint32_t k = 0; k < 16; k++, o = gl_mul(o, om64)) {
+      const gl2 d = {gl_sub(zk.c0, o), zk.c1};
+      bad = bad || gl2_eq(d, {0, 0});
+      dsum = gl2_add(dsum, gl2_inv(d));
+    }
+  }
+  const gl2 sinv = gl2_inv(S);
+  gl2 sum = {0, 0};
+  for (uint32_t p = t; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA_WIDTH, open_h + (uint64_t)p * AIR_LINK_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_link_constraints<FieldP2>(at, S);
+    const gl2 v = gl2_add(at.a, gl2_mul(Z, gl2_add(gl2_mul(at.b, sinv), gl2_mul(at.c, dsum))));
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_LINK_CONSTRAINTS * p), v));
+  }
+  gl2 pqz = {0, 0};
+  const uint64_t stride = gl_pow(om_k, AIR_CHECK_THREADS);
+#pragma unroll 1
+  for (uint32_t c = 0; c < 17; c++) {
+    const uint32_t off = c ? c - 1 : 63;
+    const uint64_t* __restrict__ v = vk + ((uint64_t)c << (log_k + 1));
+    gl2 pre[AIR_BARY_PER];
+    uint64_t yk[AIR_BARY_PER];
+    gl2 run = {1, 0}, psum = {0, 0};
+    uint64_t y = gl_mul(gl_pow(om, off), gl_pow(om_k, t));
+#pragma unroll
+    for (int m = 0; m < AIR_BARY_PER; m++) {
+      const bool in = t + m * AIR_CHECK_THREADS < K;
+      yk[m] = y;
+      pre[m] = run;
+      if (in) {
+        const gl2 d = {gl_sub(z.c0, y), z.c1};
+        bad = bad || gl2_eq(d, {0, 0});
+        run = gl2_mul(run, d);
+      }
+      y = gl_mul(y, stride);
+    }
+    gl2 inv = gl2_inv(run);
+#pragma unroll
+    for (int m = AIR_BARY_PER - 1; m >= 0; m--) {
+      const uint32_t k = t + m * AIR_CHECK_THREADS;
+      if (k < K) {
+        const gl2 di = gl2_mul(inv, pre[m]);  // 1 / (zeta - y_k)
+        inv = gl2_mul(inv, {gl_sub(z.c0, yk[m]), z.c1});
+        const gl2 V = {gl_canon(v[2 * k]), gl_canon(v[2 * k + 1])};
+        psum = gl2_add(psum, gl2_mul(gl2_scale(V, yk[m]), di));
+      }
+    }
+    // 1 / (K y_0^K), y_0^K = omega_64^off
+    pqz = gl2_add(pqz, gl2_scale(psum, gl_mul(k_inv, gl_pow(om64, 64 - off))));
+  }
+  sum = gl2_sub(sum, gl2_mul(Z, pqz));
+  __shared__ uint32_t any_bad;
+  if (t == 0) any_bad = 0;
+  __syncthreads();
+  if (bad) any_bad = 1;  // (a thread's own zeta - y_k: not uniform)
+  air_check_verdict(sum, open_q, Z, n_queries, ok);
+  if (any_bad)
+    for (uint32_t q = t; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_link_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_k, uint64_t w_k, uint64_t om64,
+                           const void* d_gamma, void* d_tab, void* stream) {
+  const uint32_t blocks = ((64u << log_blowup) + 255) / 256;
+  hipLaunchKernelGGL(k_air_link_tables, dim3(blocks), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n, s_k, w_k, om64,
+                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_link_combine(uint32_t log_k, uint32_t n_proofs, const void* d_pub, const void* d_gamma, void* d_v, void* stream) {
+  hipLaunchKernelGGL(k_air_link_combine, dim3(((1u << log_k) + 255) / 256, 17), dim3(256), 0, S_(stream), log_k, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_pub), reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_v));
+  return (int)hipGetLastError();
+}
+int launch_air_link_fold(uint32_t log_m, uint32_t log_blowup, uint32_t which, int first, const void* d_ext, const void* d_tab, void* d_pq, void* stream) {
+  hipLaunchKernelGGL(k_air_link_fold, dim3((uint32_t)(((1ull << log_m) + 255) / 256)), dim3(256), 0, S_(stream), log_m, log_blowup, which,
+                     first ? 1u : 0u, reinterpret_cast<const uint64_t*>(d_ext), reinterpret_cast<const uint64_t*>(d_tab), reinterpret_cast<uint64_t*>(d_pq));
+  return (int)hipGetLastError();
+}
+int launch_air_link_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                             const void* d_tab, const void* d_pq, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  const uint64_t* pq = reinterpret_cast<const uint64_t*>(d_pq);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_link_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, pq, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_link_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, pq, out);
+  else
+    hipLaunchKernelGGL(k_air_link_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, tab, pq, out);
+  return (int)hipGetLastError();
+}
+int launch_air_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t om64, uint64_t om, uint64_t om_k,
+                          uint64_t k_inv, const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta,
+                          const void* d_gamma, const void* d_v, uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_link_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub, om64, om, om_k, k_inv,
+                     reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_h),
+                     reinterpret_cast<const uint64_t*>(d_open_q), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma),
+                     reinterpret_cast<const uint64_t*>(d_v), n_queries, reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
+int launch_air_sha_public_gather(const void* d_rows, const AirShaPublicGeom& G, uint32_t log_k, uint32_t n_proofs, void* d_pub, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_k;
+  hipLaunchKernelGGL(k_air_sha_public_gather, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), reinterpret_cast<const uint64_t*>(d_rows), G,
+                     log_k, n_proofs, reinterpret_cast<uint64_t*>(d_pub));
+  return (int)hipGetLastError();
+}
+int launch_air_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, const void* d_pub, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_link_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<const uint64_t*>(d_pub), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx

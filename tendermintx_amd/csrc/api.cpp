@@ -86,8 +86,11 @@ uint32_t tree_nodes(uint32_t n) {
 }
 
 // MerkleInclusionProofVariable<4, LEAF>: proof[4] (Bytes32 each) then leaf bytes  (variables.rs:58-62)
-void emit_inclusion_proof(LutBuilder& L, int q, uint32_t leaf_src_off, uint32_t leaf_size) {
+// (*aunts_at, *leaf_at: where the two fields start in the table, for the readers of the row that need them)
+void emit_inclusion_proof(LutBuilder& L, int q, uint32_t leaf_src_off, uint32_t leaf_size, uint32_t* aunts_at, uint32_t* leaf_at) {
+  *aunts_at = (uint32_t)L.v.size();
   L.bytes(PF_OFF_AUNTS + 128 * q, 128);
+  *leaf_at = (uint32_t)L.v.size();
   L.bytes(leaf_src_off, leaf_size);
 }
 // derived: leaf hash + the four path nodes of proof q
@@ -102,6 +105,7 @@ struct Program {
   uint32_t hint_elems;
   uint32_t d1b_start = 0;  // first element of D.1b in a row (the EdDSA finish writes that section directly: RowOut)
   uint32_t mask_hint = 0, mask_derived = 0;  // sections of H / of D (tmx_witness_batch_opts: a caller may ask for one of them only)
+  AirShaPublicGeom pub = {};  // where tmx_air_sha256_public_device reads in a row: recorded while the table is emitted (air.h)
   uint32_t tail_dep_elem = 0;  // first element of a row whose value is written by the final checks (verdicts, check words, all_ok): the small-launch tail
 };
 
@@ -139,29 +143,43 @@ Program build_program(int kind, uint32_t n) {
   L.bytes(VR_OFF_MSG, 124);
   L.u16(VR_OFF_MLEN);
   L.u64(VR_OFF_POWER);
+  P.pub.h2_vlen = (uint32_t)L.v.size() - mark;
   L.u8(VR_OFF_VLEN);
   L.flag0(VR_OFF_FLAGS);
+  P.pub.h2 = elem; P.pub.h2_lane = (uint32_t)L.v.size() - mark;
   add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_TARGET, 0);
 
   // H.3 nb_validators, round, ChainIdProofVariable, HeightProofVariable, validators-hash proof, then
   //     skip: trusted nb + trusted validators-hash proof ; step: last_block_id proof + prev next_validators_hash proof
   mark = (uint32_t)L.v.size();
+  auto here = [&]() { return (uint32_t)L.v.size(); };
+  AirShaPublicGeom& U = P.pub;
   L.u32(PF_OFF_NB_A);
   L.u64(PF_OFF_ROUND);
+  U.aunts[0] = here();
   L.bytes(PF_OFF_AUNTS + 128 * 0, 128);   // chain_id_proof.proof
+  U.cid_len = here();
   L.u32(PF_OFF_CIDLEN);                   // enc_chain_id_byte_length
+  U.cid = here();
   L.bytes(PF_OFF_CID52, 52);              // chain_id
+  U.aunts[1] = here();
   L.bytes(PF_OFF_AUNTS + 128 * 1, 128);   // height_proof.proof
+  U.h_len = here();
   L.u32(PF_OFF_HLEN);                     // enc_height_byte_length
   L.u64(PF_OFF_HEIGHT);                   // height
-  emit_inclusion_proof(L, 2, PF_OFF_LEAFV, 34);
+  emit_inclusion_proof(L, 2, PF_OFF_LEAFV, 34, &U.aunts[2], &U.leaf[2]);
+  U.leaf_bytes[0] = 52; U.leaf_bytes[1] = 11; U.leaf_bytes[2] = 34; U.leaf_bytes[3] = skip ? 34 : 72; U.leaf_bytes[4] = 34;
   if (skip) {
     L.u32(PF_OFF_NB_B);
-    emit_inclusion_proof(L, 3, PF_OFF_LEAFX, 34);
+    emit_inclusion_proof(L, 3, PF_OFF_LEAFX, 34, &U.aunts[3], &U.leaf[3]);
   } else {
-    emit_inclusion_proof(L, 3, PF_OFF_LEAFX, 72);
-    emit_inclusion_proof(L, 4, PF_OFF_LEAFY, 34);
+    emit_inclusion_proof(L, 3, PF_OFF_LEAFX, 72, &U.aunts[3], &U.leaf[3]);
+    emit_inclusion_proof(L, 4, PF_OFF_LEAFY, 34, &U.aunts[4], &U.leaf[4]);
   }
+  // (table positions -> elements inside H.3)
+  for (uint32_t* at : {&U.cid_len, &U.cid, &U.h_len}) *at -= mark;
+  for (int q = 0; q < 5; q++) { U.aunts[q] = q < (skip ? 4 : 5) ? U.aunts[q] - mark : 0; U.leaf[q] = (q >= 2 && q < (skip ? 4 : 5)) ? U.leaf[q] - mark : 0; }
+  U.h3 = elem;
   add_section((uint32_t)L.v.size() - mark, 1, mark, SEC_LUT, SRC_PF, 1);
 
   // H.4 skip: trusted_header_validator_hash_fields[N] : ValidatorHashFieldVariable (variables.rs:82-88)
@@ -169,7 +187,9 @@ Program build_program(int kind, uint32_t n) {
     mark = (uint32_t)L.v.size();
     L.bytes(HR_OFF_PK, 32);
     L.u64(HR_OFF_POWER);
+    P.pub.h4_vlen = (uint32_t)L.v.size() - mark;
     L.u8(HR_OFF_VLEN);
+    P.pub.h4 = elem; P.pub.h4_lane = (uint32_t)L.v.size() - mark;
     add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_TRUSTED, 0);
   }
   P.hint_elems = elem;
@@ -178,8 +198,10 @@ Program build_program(int kind, uint32_t n) {
   // they are written while the table walk runs; only D.1b waits for k_ed_fin.
   mark = (uint32_t)L.v.size();
   L.bytes(TL_OFF_LT + LN_OFF_MARSHAL, 46);
+  P.pub.lane_leaf = (uint32_t)L.v.size() - mark;  // (the marshalled validator first, then the leaf hash: D.2a the same)
   L.bytes(TL_OFF_LT + LN_OFF_LEAF, 32);
   L.bytes(TL_OFF_ED + ED_OFF_DIGEST, 64);
+  P.pub.d1a = elem; P.pub.d1a_lane = (uint32_t)L.v.size() - mark;
   add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_TL, 4);
   // D.1b per target lane: h, the ten coordinates, the EdDSA verdict, the six flags, the two prefix sums
   mark = (uint32_t)L.v.size();
@@ -198,6 +220,7 @@ Program build_program(int kind, uint32_t n) {
     mark = (uint32_t)L.v.size();
     L.bytes(LN_OFF_MARSHAL, 46);
     L.bytes(LN_OFF_LEAF, 32);
+    P.pub.d2a = elem; P.pub.d2a_lane = (uint32_t)L.v.size() - mark;
     add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_LR, 5);
     mark = (uint32_t)L.v.size();
     L.u8(LN_OFF_FLAGS);
@@ -208,17 +231,20 @@ Program build_program(int kind, uint32_t n) {
   }
   // D.3 / D.4 tree nodes
   if (tn) {
+    P.pub.d3 = elem;
     add_section(tn * 256, 1, 0, SEC_LINEAR_T, SRC_PF, 1);
-    if (skip) add_section(tn * 256, 1, 0, SEC_LINEAR_R, SRC_PF, 1);
+    if (skip) { P.pub.d4 = elem; add_section(tn * 256, 1, 0, SEC_LINEAR_R, SRC_PF, 1); }
   }
   // D.5 header proofs, tallies, checks, verdict
   mark = (uint32_t)L.v.size();
+  P.pub.d5 = elem;
   emit_proof_d(L, 0);
+  P.pub.d5_hleaf = (uint32_t)L.v.size() - mark;
   L.bytes(PF_OFF_HLEAF, 11);
-  emit_proof_d(L, 1);
-  emit_proof_d(L, 2);
-  emit_proof_d(L, 3);
-  if (!skip) emit_proof_d(L, 4);
+  for (int q = 1; q < (skip ? 4 : 5); q++) {
+    P.pub.d5_proof[q] = (uint32_t)L.v.size() - mark;
+    emit_proof_d(L, q);
+  }
   for (int k = 0; k < 4; k++) L.u64(PF_OFF_TALLY_T + 8 * k);
   P.tail_dep_elem = elem + ((uint32_t)L.v.size() - mark);
   L.u32(PF_OFF_VERDICTS);
@@ -442,12 +468,14 @@ struct tmx_ctx {
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
   // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
-  void* d_set_sha[3][3] = {};
-  size_t set_sha_bytes[3][3] = {};
+  void* d_set_sha[4][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6)
+  size_t set_sha_bytes[4][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
   size_t air2_bytes = 0;
+  void* d_air6 = nullptr;  // constraint set 6's caller-level scratch (AIR6_OFF_*)
+  size_t air6_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1445,6 +1473,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
       if (b) (void)hipFree(b);
   if (c->d_air) (void)hipFree(c->d_air);
   if (c->d_air2) (void)hipFree(c->d_air2);
+  if (c->d_air6) (void)hipFree(c->d_air6);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -5123,6 +5152,340 @@ int32_t tmx_air_sha256_init_quotient_range_device(tmx_ctx* c, uint32_t log_n, ui
                                                   uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_range_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols,
                                  d_cap, d_cap_helper, d_quot, hip_stream);
+}
+
+}  // extern "C"
+
+// ---- constraint set 6: the SHA-256 tables' link to Level-1 (include/tmx.h).  A host path of its own beside sets 3 - 5: the same argument
+// checks but for the block count, set 3's geometry, a scratch of its own (words at d_air6):
+//   tables (air.h AIR6_TAB_*) | twiddles [K] | V of the prover [17][K][2] | V of the verifier | coefficients [2 K] | the public digest's
+//   levels, prover and verifier | one extended public polynomial (2 M) | PQ (2 M)
+// The challenge words are where set 1 keeps its own (d_air).
+constexpr uint64_t AIR6_K_MAX = 1ull << AIR_SHA_PUBLIC_MAX_LOG_K;
+constexpr uint64_t AIR6_OFF_TW = AIR6_TAB_WORDS, AIR6_OFF_VP = AIR6_OFF_TW + AIR6_K_MAX, AIR6_OFF_VV = AIR6_OFF_VP + 34 * AIR6_K_MAX,
+                   AIR6_OFF_COEF = AIR6_OFF_VV + 34 * AIR6_K_MAX, AIR6_OFF_LEVP = AIR6_OFF_COEF + 2 * AIR6_K_MAX,
+                   AIR6_OFF_LEVV = AIR6_OFF_LEVP + 8 * AIR6_K_MAX, AIR6_OFF_EXT = AIR6_OFF_LEVV + 8 * AIR6_K_MAX;
+
+static int32_t link_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
+  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
+  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
+  if (log_n - log_blowup < 6 + AIR_SHA_PUBLIC_MIN_LOG_K || log_n - log_blowup > 6 + AIR_SHA_PUBLIC_MAX_LOG_K)
+    return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * AIR_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "33 n_proofs must be at most 2^24");
+  return TMX_OK;
+}
+
+// s, w the coset; om = omega_N = w^B, om_k = omega_K = om^64, om64 = omega_64 = om^K, k_inv = 1 / K
+struct LinkGeo { uint32_t log_k; uint64_t s, w, om, om_k, om64, k_inv; };
+static void link_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, LinkGeo& B) {
+  const uint64_t P = 0xffffffff00000001ull;
+  B.log_k = log_n - log_blowup - 6;
+  B.s = shift % P;
+  B.w = gl_pow_host(root_2_32, 1ull << (32 - log_n));
+  B.om = gl_pow_host(B.w, 1ull << log_blowup);
+  B.om_k = gl_pow_host(B.om, 64);
+  B.om64 = gl_pow_host(B.om, 1ull << B.log_k);
+  B.k_inv = gl_pow_host(1ull << B.log_k, P - 2);
+}
+
+// the set-6 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
+static int32_t link_scratch(tmx_ctx* c, uint32_t log_m) {
+  const size_t want = (AIR6_OFF_EXT + (log_m ? (size_t)4 << log_m : 0)) * 8;
+  if (c->air6_bytes < want) {
+    if (c->d_air6) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air6)); c->d_air6 = nullptr; c->air6_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air6, want));
+    c->air6_bytes = want;
+  }
+  return TMX_OK;
+}
+
+// gamma of set 6: the public table's digest (its Poseidon Merkle root), then the lone-lane kernel over the two caps and the digest
+static int32_t link_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t log_k, const uint64_t* d_cap,
+                          const uint64_t* d_cap_helper, const uint64_t* d_pub, bool verifier, void* hip_stream) {
+  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air6) + (verifier ? AIR6_OFF_LEVV : AIR6_OFF_LEVP);
+  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_SHA_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, hip_stream);
+  if (st) return st;
+  const uint32_t obs[5] = {6 /* the constraint-set id */, log_n, log_blowup, cap_height, n_proofs};
+  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
+  const int rc = launch_air_link_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper,
+                                       lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32, reinterpret_cast<hipStream_t>(hip_stream));
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_gamma launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// PQ on the coset from the public table and the prover's gamma: V, then per coset the coefficients, the extension and its fold.  The
+// tables (first = 0) are written first: the fold reads 1 / S and 1 / D_t
+static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, const ShaGeo& A, const LinkGeo& B, uint32_t n_proofs, const uint64_t* d_pub,
+                           hipStream_t s) {
+  const uint64_t P = 0xffffffff00000001ull;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  int rc = launch_air_link_tables(log_blowup, 0, A.s_n, A.w_n, A.s_sel, A.w_sel, B.om64, gamma, X, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR6_OFF_VP, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR6_OFF_TW, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
+  uint64_t* ext = X + AIR6_OFF_EXT;
+  uint64_t* pq = ext + ((size_t)2 << log_m);
+  for (uint32_t k = 0; k < 17; k++) {
+    const uint32_t off = k ? k - 1 : 63;
+    const uint64_t off_inv = gl_pow_host(gl_pow_host(B.om, off), P - 2);
+    rc = launch_air_public_coefs(B.log_k, B.k_inv, off_inv, X + AIR6_OFF_VP + ((uint64_t)k << (B.log_k + 1)), X + AIR6_OFF_TW, X + AIR6_OFF_COEF, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR6_OFF_COEF, X + AIR6_OFF_TW, ext, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = launch_air_link_fold(log_m, log_blowup, k, k == 0, ext, X, pq, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_fold launch: ") + hipGetErrorString((hipError_t)rc));
+  }
+  return TMX_OK;
+}
+
+// form as in sha_quotient_call; the piece with proof_lo = 0 carries - PQ
+static int32_t link_quotient_call(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t proof_lo,
+                                  uint32_t proof_hi, int form, const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                  const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = link_check(c, log_n, log_blowup, n_proofs);
+  if (st) return st;
+  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
+  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_pub || !d_quot)
+    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub and d_quot must be set");
+  ShaGeo A;
+  if ((st = sha_geo(c, log_n, log_blowup, 0, c->ntt_root, c->ntt_shift, A))) return st;
+  LinkGeo B;
+  link_geo(log_n, log_blowup, c->ntt_root, c->ntt_shift, B);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if ((st = link_scratch(c, log_n))) return st;
+  if ((st = link_gamma(c, log_n, log_blowup, cap_height, n_proofs, B.log_k, d_cap, d_cap_helper, d_pub, false, hip_stream))) return st;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  if (proof_lo == 0 && (st = link_public(c, log_n, log_blowup, A, B, n_proofs, d_pub, s))) return st;
+  if (proof_lo != 0) {
+    const int rc = launch_air_link_tables(log_blowup, proof_lo, A.s_n, A.w_n, A.s_sel, A.w_sel, B.om64, gamma, X, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  }
+  const int rc = launch_air_link_quotient(log_n, log_blowup, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_SHA_WIDTH) << log_n),
+                                          d_helper_cols, X, proof_lo == 0 ? X + AIR6_OFF_EXT + ((size_t)2 << log_n) : nullptr, form, d_quot, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  return TMX_OK;
+}
+
+// The set-level call of set 6 on a resident member: sha_set_call's resident path with the public table in gamma and in the pass.  The pair
+// goes behind every pair of sets 3 - 5 that follows the table (their calls, unchanged, insert in front of later members: every order ends
+// as table, H3, Q3, H4, Q4, H5, Q5, H6, Q6).  The scratch of the section is sets 3 - 5's layout with 33 columns per proof (row 3 of
+// d_set_sha); one extended public polynomial and PQ (4 M words) live in the context's set-6 scratch d_air6, not per section.
+static const ShaSet LINK_SET = {6, AIR_LINK_HELPER_COLS, false, TMX_TRACE_SHA256_LINK_HELPER, TMX_TRACE_SHA256_LINK_QUOTIENT, 3, "link", "link helper",
+                                "the commit set already holds the link helper and quotient of that section", "k_helper", "k_helper + 1",
+                                "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr};
+
+static int32_t link_set_call(tmx_ctx* c, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  const ShaSet& d = LINK_SET;
+  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
+  if (st) return st;
+  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
+  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
+  if (!d_pub || !d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_pub, d_cap_h and d_cap_q must be set");
+  tmx_ctx::SetRec r = c->set;
+  uint32_t kt = r.n_oracles;
+  for (uint32_t k = 0; k < r.n_oracles; k++)
+    if (r.o[k].section == section) kt = k;
+  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
+  uint32_t at = kt + 1;
+  for (const ShaSet& lower : SHA_SETS)
+    if (at < r.n_oracles && r.o[at].section == lower.helper_section) at += 2;
+  if (at < r.n_oracles && r.o[at].section == d.helper_section) return fail(c, TMX_ERR_BAD_ARG, d.already);
+  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
+  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
+  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
+  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
+  if ((st = link_check(c, log_m, r.log_blowup, n_proofs))) return st;
+  ShaGeo A;
+  if ((st = sha_geo(c, log_m, r.log_blowup, 0, r.root, r.shift, A))) return st;
+  LinkGeo B;
+  link_geo(log_m, r.log_blowup, r.root, r.shift, B);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, r.log_blowup))) return st;
+  if ((st = link_scratch(c, log_m))) return st;
+  const uint32_t n_hcols = n_proofs * d.helper_cols;
+  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
+  const ShaScratch SP = sha_scratch_plan(d, log_m, r.log_blowup, h, n_proofs, n_proofs);
+  void*& d_scratch = c->d_set_sha[d.scratch][slot];
+  size_t& scratch_bytes = c->set_sha_bytes[d.scratch][slot];
+  if (scratch_bytes < SP.want) {
+    if (d_scratch) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(d_scratch)); d_scratch = nullptr; scratch_bytes = 0; }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && SP.want > free_b)
+      return fail(c, TMX_ERR_CAPACITY, "the link helper member needs " + std::to_string(SP.want >> 20) + " MiB of scratch, " +
+                                           std::to_string(free_b >> 20) + " MiB free");
+    HIPCK(c, hipMalloc(&d_scratch, SP.want));
+    scratch_bytes = SP.want;
+  }
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
+  uint8_t* sb = reinterpret_cast<uint8_t*>(d_scratch);
+  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
+  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + SP.pre_b);
+  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b);
+  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b + SP.lev_b);
+  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b + SP.lev_b + SP.quot_b);
+  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
+  int rc = launch_air_link_helper(log_sub, n_proofs, base + tabm.cols_off, d_pub, hpre, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_helper launch: ") + hipGetErrorString((hipError_t)rc));
+  // the helper extended under the set's domain, one proof's columns at a time (the LDE's own scratch is twice what it extends at once)
+  const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+  const bool moved = root != r.root || shift != r.shift;
+  if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
+  for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += d.helper_cols)
+    st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, d.helper_cols, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
+  if (moved) {
+    const int32_t back = tmx_ntt_set_domain(c, root, shift);
+    if (!st) st = back;
+  }
+  if (st) return st;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  if ((st = link_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, B.log_k, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), d_pub, false,
+                       hip_stream)))
+    return st;
+  if ((st = link_public(c, log_m, r.log_blowup, A, B, n_proofs, d_pub, s))) return st;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+  rc = launch_air_link_quotient(log_m, r.log_blowup, n_proofs, base + tabm.lde_off, hext, X, X + AIR6_OFF_EXT + ((size_t)2 << log_m), AIR_FORM_WHOLE, quot, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
+  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
+  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
+  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
+  r.o[at] = {d.helper_section, log_m, n_hcols, 0, SP.pre_b, SP.pre_b + SP.ext_b, false, false, sb};
+  r.o[at + 1] = {d.quotient_section, log_m, 2, 0, SP.pre_b + SP.ext_b + SP.lev_b, SP.pre_b + SP.ext_b + SP.lev_b + SP.quot_b, false, true, sb};
+  r.n_oracles += 2;
+  c->set = r;
+  return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* c, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
+                                                    void* hip_stream) {
+  return link_set_call(c, section, d_pub, d_cap_h, d_cap_q, hip_stream);
+}
+
+int32_t tmx_air_sha256_link_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  return link_quotient_call(c, log_n, log_blowup, cap_height, n_proofs, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub,
+                            d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha256_link_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
+  return link_quotient_call(c, log_n, log_blowup, cap_height, n_proofs, proof_lo, proof_hi, accumulate ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE, d_cols,
+                            d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha256_link_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = batch_check(c, p);
+  if (st) return st;
+  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles)
+    return fail(c, TMX_ERR_BAD_ARG, "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof");
+  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
+  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)AIR_LINK_HELPER_COLS * n_proofs)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper must be the helper: the log_n of oracle k_trace and 33 columns per proof");
+  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
+  if ((st = link_check(c, log_n, p->log_blowup, n_proofs))) return st;
+  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
+  ShaGeo A;
+  if ((st = sha_geo(c, log_n, p->log_blowup, 0, c->ntt_root, c->ntt_shift, A))) return st;
+  LinkGeo B;
+  link_geo(log_n, p->log_blowup, c->ntt_root, c->ntt_shift, B);
+  if (!d_caps || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_caps, d_proof and d_ok must be set");
+  if ((st = air_scratch(c, p->log_blowup))) return st;
+  if ((st = link_scratch(c, 0))) return st;
+  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  tmx_batch_layout L;
+  batch_layout(*p, L);
+  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
+  // zeta as the batch transcript draws it, gamma from the two caps and the verifier's own digest of d_pub, V from d_pub, then the identity
+  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = link_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, B.log_k, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], d_pub, true,
+                       hip_stream)))
+    return st;
+  rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, X + AIR6_OFF_VV, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, B.om64, B.om, B.om_k, B.k_inv,
+                             d_proof + L.off_open[k_trace], d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT,
+                             V + 32 + FRI_GAMMA_AT, X + AIR6_OFF_VV, p->n_queries, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_check launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// ---- the public table of a SHA-256 table from element rows, and the helper oracle over it
+int32_t tmx_air_sha256_public_shape(int32_t kind, uint32_t section, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols) {
+  uint32_t log_rows = 0, width = 0;
+  if (section != TMX_TRACE_SHA256 && section != TMX_TRACE_TREE && section != TMX_TRACE_HEADER) return TMX_ERR_BAD_ARG;
+  if (n_proofs < 1 || tmx_trace_commit_shape(kind, n_max, section, &log_rows, &width) != TMX_OK) return TMX_ERR_BAD_ARG;
+  if (log_rows < 6 + AIR_SHA_PUBLIC_MIN_LOG_K || log_rows > 6 + AIR_SHA_PUBLIC_MAX_LOG_K) return TMX_ERR_BAD_ARG;
+  if ((uint64_t)n_proofs * AIR_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return TMX_ERR_BAD_ARG;
+  if (log_k) *log_k = log_rows - 6;
+  if (n_cols) *n_cols = AIR_SHA_PUBLIC_WIDTH * n_proofs;
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha256_public_device(tmx_ctx* c, int32_t kind, uint32_t section, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub,
+                                     void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (kind != TMX_KIND_SKIP && kind != TMX_KIND_STEP) return fail(c, TMX_ERR_BAD_ARG, "kind must be TMX_KIND_SKIP or TMX_KIND_STEP");
+  if (section != TMX_TRACE_SHA256 && section != TMX_TRACE_TREE && section != TMX_TRACE_HEADER)
+    return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
+  uint32_t log_k = 0;
+  if (tmx_air_sha256_public_shape(kind, section, c->cfg.n_max, n_proofs, &log_k, nullptr))
+    return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1 (33 n_proofs at most 2^24) and the table 2 .. 2^12 blocks");
+  if (!d_elems || !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_elems and d_pub must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const Program& prog = c->prog[kind];
+  const SerializeProgram& sp = prog.sp;
+  AirShaPublicGeom G = prog.pub;  // (every offset as build_program recorded it)
+  G.elem_stride = sp.elem_stride; G.kind = (uint32_t)kind; G.section = section; G.n = c->cfg.n_max; G.tn = sp.tree_nodes;
+  const int rc = launch_air_sha_public_gather(d_elems, G, log_k, n_proofs, d_pub, hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_public_gather launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha256_link_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, const uint64_t* d_pub,
+                                          uint64_t* d_helper, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (log_rows < 6 + AIR_SHA_PUBLIC_MIN_LOG_K || log_rows > 6 + AIR_SHA_PUBLIC_MAX_LOG_K)
+    return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows");
+  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
+  if ((uint64_t)n_proofs * AIR_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "33 n_proofs must be at most 2^24");
+  if (!d_table || !d_pub || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table, d_pub and d_helper must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const int rc = launch_air_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_helper launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
 }
 
 uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,

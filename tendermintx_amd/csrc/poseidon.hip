@@ -579,6 +579,32 @@ __global__ __launch_bounds__(64) void k_air_sha_gamma(const uint64_t* __restrict
   chal_store(c, state);
 }
 
+// The constraint challenge of set 6 (include/tmx.h "the SHA-256 tables' link to Level-1"): k_air_sha_gamma's form with a third span, the
+// four words of the public table's digest.  A kernel of its own beside it: k_air_sha_gamma and k_fri_transcript stay as they are.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_air_link_gamma(const uint64_t* __restrict__ consts, AirShaObs obs, uint32_t cap_words,
+                                                       const uint64_t* __restrict__ cap, const uint64_t* __restrict__ cap_helper,
+                                                       const uint64_t* __restrict__ digest, uint64_t* __restrict__ state,
+                                                       uint64_t* __restrict__ chal) {
+  if (threadIdx.x) return;
+  const PosConsts K = pos_consts(consts);
+  FriChal c;
+  chal_init(c);
+  chal_observe<MODE>(c, K, 1ull << 33);
+  for (int k = 0; k < 5; k++) chal_observe<MODE>(c, K, obs.v[k]);
+  chal_observe_span<MODE>(c, K, cap, cap_words);
+  chal_observe_span<MODE>(c, K, cap_helper, cap_words);
+  chal_observe_span<MODE>(c, K, digest, 4);
+  gl2 g;
+  do {
+    g.c0 = chal_challenge<MODE>(c, K);
+    g.c1 = chal_challenge<MODE>(c, K);
+  } while (g.c1 == 0);
+  chal[FRI_GAMMA_AT] = g.c0;
+  chal[FRI_GAMMA_AT + 1] = g.c1;
+  chal_store(c, state);
+}
+
 // The proof-of-work search (include/tmx.h "proof of work"), the one wide piece of the transcript: every candidate is one permutation of the
 // duplex phase 5 left in `state` (12 words and the n_in <= 7 pending input words, uniform across the grid: scalar loads) with the
 // candidate as the next input word; it satisfies the condition if output word 7, the one challenge() pops, has pow_bits leading zero bits.
@@ -950,6 +976,21 @@ int launch_air_sha_gamma(const void* d_consts, int mode, const uint32_t obs[5], 
   if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL(k_air_sha_gamma<POS_MODE_MERGE3>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, st, ch);
   else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL(k_air_sha_gamma<POS_MODE_SMALL>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, st, ch);
   else hipLaunchKernelGGL(k_air_sha_gamma<POS_MODE_GENERAL>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, st, ch);
+  return (int)hipGetLastError();
+}
+int launch_air_link_gamma(const void* d_consts, int mode, const uint32_t obs[5], uint32_t cap_words, const void* d_cap, const void* d_cap_helper,
+                          const void* d_digest, void* d_state, void* d_chal, void* stream) {
+  const uint64_t* K = reinterpret_cast<const uint64_t*>(d_consts);
+  const uint64_t* cap = reinterpret_cast<const uint64_t*>(d_cap);
+  const uint64_t* cap_h = reinterpret_cast<const uint64_t*>(d_cap_helper);
+  const uint64_t* dg = reinterpret_cast<const uint64_t*>(d_digest);
+  uint64_t* st = reinterpret_cast<uint64_t*>(d_state);
+  uint64_t* ch = reinterpret_cast<uint64_t*>(d_chal);
+  AirShaObs o;
+  for (int k = 0; k < 5; k++) o.v[k] = obs[k];
+  if (mode == POS_MODE_MERGE3) hipLaunchKernelGGL(k_air_link_gamma<POS_MODE_MERGE3>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, dg, st, ch);
+  else if (mode == POS_MODE_SMALL) hipLaunchKernelGGL(k_air_link_gamma<POS_MODE_SMALL>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, dg, st, ch);
+  else hipLaunchKernelGGL(k_air_link_gamma<POS_MODE_GENERAL>, dim3(1), dim3(64), 0, S_(stream), K, o, cap_words, cap, cap_h, dg, st, ch);
   return (int)hipGetLastError();
 }
 // The grid of the search: one lane per expected candidate (2^pow_bits: a 4-bit search is one workgroup), at most four 256-thread workgroups

@@ -29,7 +29,8 @@
            SHA_SET_P proofs at N = n (skip), alternating, with the prove and the three verifiers over the set of seven oracles.
   parent   the set commit + prove WITHOUT any air call, then the set-3 and set-4 set-level calls on HEADER (MODE=set_plain,sets34), for library
            builds named in LIBS (comma separated), one subprocess per measurement, alternating under TMX_LIB (differences between boxes exceed
-           most changes: compare inside one call).
+           most changes: compare inside one call).  PARENT_MODES names other modes for the subprocesses: `init,set_plain` adds the set-5
+           set-level call (a parent that has set 5).
   sha_streamed  the streamed helpers of constraint sets 3 - 5 (tmx_trace_commit_set_air_sha256_streamed_device) on a set SHA256 | SECTION
            of SHA_SET_P proofs at N = n (skip), the sets named in SETS (3 by default; 3,4,5), CHUNK_PROOFS proofs per chunk (8).  SECTION=
            HEADER (default): the resident and the streamed set-level calls, alternating in one process after a warm call, with the prove
@@ -37,6 +38,15 @@
            helper-LDE share of the streamed call.  SECTION=TREE or SHA256: the streamed calls only, once (the resident helper does not
            fit at full size): the bytes from tmx_trace_commit_set_air_sha256_streamed_bytes, free memory before and after, digests of
            both caps per set, the times, and the verdicts of the three verifiers on one proof over the set.
+  link     the public table and the helper of constraint set 6 (tmx_air_sha256_public_device, tmx_air_sha256_link_helper_device): the gather
+           of T.3, T.5 and T.6 from the element rows of P proofs at N = n (skip), one time per section, and k_air_link_helper over
+           SHA_PROOFS proofs x 9 random table columns of 2^LOG_ROWS words (13 by default) under random public flags, with the bytes it moves
+           and link_helper_sha256, the SHA-256 of the words it leaves; then the quotient call (the public digest, gamma, the tables, the
+           public side, k_air_link_quotient) over random extended columns of the same shape beside a plain FRI prove over the SAME helper
+           columns, alternating.  Under `rocprofv3 --kernel-trace --stats` (MODE=link) k_air_sha_public_gather, k_air_link_helper,
+           k_air_link_quotient and k_fri_combine show in ONE trace.  Between the two: the set-level call
+           (tmx_trace_commit_set_air_sha256_link_device) on the HEADER member of a set SHA256 | HEADER of the same P proofs beside set 5's
+           call on the same set, alternating, with the prove over table, H5, Q5, H6, Q6 and both verifiers.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -62,7 +72,7 @@ if "parent" in modes:
     res = {os.path.basename(os.path.dirname(l)) + "/" + os.path.basename(l): [] for l in libs}
     for _ in range(rounds):
         for l, key in zip(libs, res):
-            o = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, MODE="sets34,set_plain", TMX_LIB=l), capture_output=True, text=True)
+            o = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, MODE=os.environ.get("PARENT_MODES", "sets34,set_plain"), TMX_LIB=l), capture_output=True, text=True)
             line = [json.loads(x) for x in o.stdout.splitlines() if x.startswith("{")]
             res[key].append(line if line else {"failed": o.stderr[-300:]})
     print(json.dumps({"mode": "parent", "proofs": P, "n": n, "runs": res}), flush=True)
@@ -630,5 +640,87 @@ if "set" in modes or "set_plain" in modes:
             del proof
         res.update(order=params()[1], log_n=bp["log_n"], columns=bp["n_cols"])
         res["re_lde_share_of_streamed"] = round(1 - min(res["air_resident_ms"]) / min(res["air_streamed_ms"]), 3)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+
+if "link" in modes:
+    from tendermintx_amd.synth import bench_workload
+    SHA256_T, TREE_T, HEADER_T = 4, 16, 32
+    w = bench_workload("survey8d", n, P, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=P)
+    out = torch.empty(P * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(P * 64, dtype=torch.uint8, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, P, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    torch.cuda.synchronize(dev)
+    res = {"mode": "link", "proofs": P, "n": n, "reps": reps, "gather_ms": {}, "public_words": {}}
+    for name, sec in (("sha256", SHA256_T), ("tree", TREE_T), ("header", HEADER_T)):
+        log_k, pub_cols = ctx.air_sha256_public_shape(KIND_SKIP, sec, P)
+        pub = torch.empty(pub_cols << log_k, dtype=torch.int64, device=dev)
+        res["gather_ms"][name] = r4(timed(lambda: ctx.air_sha256_public_device(KIND_SKIP, sec, P, out.data_ptr(), pub.data_ptr(), 0), reps))
+        res["public_words"][name] = pub_cols << log_k
+    # the set-level call on HEADER (pub is HEADER's table now) beside set 5's on the same set, alternating; the prove and both verifiers
+    tr = torch.empty(P * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.trace_rows_device(KIND_SKIP, P, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    cw = 4 << cap_h
+    scaps, c5, c6 = (torch.zeros(2 * cw, dtype=torch.int64, device=dev) for _ in range(3))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    hpub = pub
+    commit6 = lambda: ctx.trace_commit_set_device(KIND_SKIP, P, SHA256_T | HEADER_T, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    air5 = lambda: ctx.trace_commit_set_air_sha256_init_device(HEADER_T, c5[:cw].data_ptr(), c5[cw:].data_ptr(), 0)
+    air6 = lambda: ctx.trace_commit_set_air_sha256_link_device(HEADER_T, hpub.data_ptr(), c6[:cw].data_ptr(), c6[cw:].data_ptr(), 0)
+    res.update(air_sha256_link_header_ms=[], air_sha256_init_header_ms=[], prove_with_sets_5_6_ms=[])
+    for _ in range(rounds):
+        res["air_sha256_link_header_ms"].append(r4(timed(air6, reps, before=commit6)))
+        res["air_sha256_init_header_ms"].append(r4(timed(air5, reps, before=commit6)))
+        air6()  # (the set now holds table, H5, Q5, H6, Q6)
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_sets_5_6_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(HEADER_T)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], c5, c6, scaps[(kt + 1) * cw:]])
+        res["verify_link_ms"] = r4(timed(lambda: ctx.air_sha256_link_verify_device(bp, kt, kt + 3, all_caps.data_ptr(), proof.data_ptr(), hpub.data_ptr(),
+                                                                                  ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        ctx.air_sha256_init_verify_device(bp, kt, kt + 1, 1, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+        res["all_ok_set5"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
+    del tr
+    log_rows, sp_ = int(os.environ.get("LOG_ROWS", "13")), int(os.environ.get("SHA_PROOFS", "64"))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    table = torch.randint(0, 2**62, ((9 * sp_) << log_rows,), dtype=torch.int64, device=dev, generator=g)
+    pub = torch.randint(0, 2, ((26 * sp_) << (log_rows - 6),), dtype=torch.int64, device=dev, generator=g)
+    helper = torch.empty((33 * sp_) << log_rows, dtype=torch.int64, device=dev)
+    call = lambda: ctx.air_sha256_link_helper_device(log_rows, sp_, table.data_ptr(), pub.data_ptr(), helper.data_ptr(), 0)
+    res.update(helper_proofs=sp_, helper_log_rows=log_rows, helper_ms=[r4(timed(call, reps)) for _ in range(rounds)])
+    res["helper_gb_per_s"] = round((33 + 8) * sp_ * 8 * 2**log_rows / min(res["helper_ms"]) / 1e6, 1)
+    res["link_helper_sha256"] = words_digest(call, helper)
+    # the quotient call (digest, gamma, tables, the public side, k_air_link_quotient) over random extended columns, beside a plain FRI prove
+    # over the SAME helper columns: its combine stage is k_fri_combine over 33 of the 50 columns the pass reads per proof
+    log_m = log_rows + log_blowup
+    cols = torch.randint(0, 2**62, ((9 * sp_) << log_m,), dtype=torch.int64, device=dev, generator=g)
+    hcols = torch.randint(0, 2**62, ((33 * sp_) << log_m,), dtype=torch.int64, device=dev, generator=g)
+    caps = []
+    for c_, k_ in ((cols, 9 * sp_), (hcols, 33 * sp_)):
+        lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+        ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+        caps.append(lv)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    qcall = lambda: ctx.air_sha256_link_quotient_device(log_m, log_blowup, cap_h, sp_, cols.data_ptr(), hcols.data_ptr(), caps[0][-(4 << cap_h):].data_ptr(),
+                                                        caps[1][-(4 << cap_h):].data_ptr(), pub.data_ptr(), quot.data_ptr(), 0)
+    fp = dict(log_n=log_m, n_cols=33 * sp_, cap_height=cap_h, log_blowup=log_blowup, arity_bits=arity, final_log_max=final_max, n_queries=nq)
+    proof = torch.empty(ctx.fri_layout(fp)["words"], dtype=torch.int64, device=dev)
+    res.update(log_m=log_m, link_quotient_call_ms=[], fri_prove_helper_ms=[], fri_combine_stage_ms=[])
+    for _ in range(rounds):
+        res["link_quotient_call_ms"].append(r4(timed(qcall, reps)))
+        res["fri_prove_helper_ms"].append(r4(timed(lambda: ctx.fri_prove_device(fp, hcols.data_ptr(), caps[1].data_ptr(), proof.data_ptr(), 0), reps)))
+        res["fri_combine_stage_ms"].append(r4(ctx.fri_last_ms()["combine"]))
+    res["quotient_read_gib"] = round((50 * sp_ << log_m) * 8 / 2**30, 2)
+    res["combine_read_gib"] = round((33 * sp_ << log_m) * 8 / 2**30, 2)
+    res["quotient_sha256"] = words_digest(qcall, quot)
     print(json.dumps(res), flush=True)
     ctx.close()
