@@ -4205,20 +4205,35 @@ int32_t tmx_trace_commit_set_prove_device(tmx_ctx* c, const tmx_batch_params* p,
 
 }  // extern "C"
 
-// ---- the constraint quotient of the ladder rows (include/tmx.h "the constraint quotient of the ladder rows") -------------------------------
-// The domain constants of one quotient: x_i = s w^i over M = 2^log_n points, N = M >> log_blowup
-struct AirGeo { uint64_t s_n, w_n, s_n256, w_n256, om256_inv; };
+// ---- the constraint quotient of the ladder rows: constraint set 1 (include/tmx.h "the constraint quotient of the ladder rows") and set 2,
+// set 1 plus the boundary constraints against a public table ("the boundary constraints of the ladder rows") ---------------------------------
+// One host path drives both.  `boundary` selects set 2: two more row bounds, a scratch of its own (d_air2) beside set 1's, the public
+// table's digest in gamma (phase 10 of the transcript), Pub_gamma ahead of the first piece, and the boundary tables, quotient and check
+// launches with d_pub and V.  d_pub is null under set 1.  K = N / 256 ladders; the public table is 17 n_proofs columns of K words.
+// The domain constants of one quotient: x_i = s w^i over M = 2^log_n points, N = M >> log_blowup; from log_k on, set 2's alone
+struct AirGeo {
+  uint64_t s_n, w_n, s_n256, w_n256, om256_inv;
+  uint32_t log_k;
+  uint64_t s, w, om_k, om255, om255_inv, k_inv, bary_inv;
+};
+constexpr uint64_t AIR2_K_MAX = 1ull << AIR_PUBLIC_MAX_LOG_K;
+constexpr uint64_t AIR2_OFF_TW = AIR2_TAB_WORDS, AIR2_OFF_VP = AIR2_OFF_TW + AIR2_K_MAX, AIR2_OFF_VV = AIR2_OFF_VP + 2 * AIR2_K_MAX,
+                   AIR2_OFF_COEF = AIR2_OFF_VV + 2 * AIR2_K_MAX, AIR2_OFF_LEVP = AIR2_OFF_COEF + 2 * AIR2_K_MAX,
+                   AIR2_OFF_LEVV = AIR2_OFF_LEVP + 8 * AIR2_K_MAX, AIR2_OFF_EXT = AIR2_OFF_LEVV + 8 * AIR2_K_MAX;
 
-static int32_t air_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
+static int32_t air_check(tmx_ctx* c, bool boundary, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
   if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
   if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
   if (log_n - log_blowup < 8) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 8: a ladder is 256 rows");
   if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
   if ((uint64_t)n_proofs * AIR_LADDER_WIDTH > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "65 n_proofs must be at most 2^24");
+  if (!boundary) return TMX_OK;
+  if (log_n - log_blowup < 9) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 9: the boundary constraints need two ladders");
+  if (log_n - log_blowup > 8 + AIR_PUBLIC_MAX_LOG_K) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at most 20: at most 2^12 ladders");
   return TMX_OK;
 }
 
-static int32_t air_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, AirGeo& A) {
+static int32_t air_geo(tmx_ctx* c, bool boundary, uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, AirGeo& A) {
   const uint64_t P = 0xffffffff00000001ull;
   const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
   A.s_n = gl_pow_host(s, n); A.w_n = gl_pow_host(w, n);
@@ -4227,6 +4242,14 @@ static int32_t air_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint64_t
   uint64_t x = A.s_n;
   for (uint32_t k = 0; k < (1u << log_blowup); k++, x = (uint64_t)(((unsigned __int128)x * A.w_n) % P))
     if (x == 1) return fail(c, TMX_ERR_BAD_ARG, "x^N - 1 vanishes on the evaluation domain: the coset shift lies in the trace domain");
+  if (!boundary) return TMX_OK;
+  A.log_k = log_n - log_blowup - 8;
+  A.s = s; A.w = w;
+  A.om_k = gl_pow_host(w, 1ull << (8 + log_blowup));  // omega_N^256 = w^(256 B)
+  A.om255 = gl_pow_host(w, 255ull << log_blowup);
+  A.om255_inv = gl_pow_host(A.om255, P - 2);
+  A.k_inv = gl_pow_host(1ull << A.log_k, P - 2);
+  A.bary_inv = (uint64_t)(((unsigned __int128)A.k_inv * gl_pow_host(A.om256_inv, P - 2)) % P);  // 1 / (K omega_256^-1)
   return TMX_OK;
 }
 
@@ -4242,29 +4265,102 @@ static int32_t air_scratch(tmx_ctx* c, uint32_t log_blowup) {
   return TMX_OK;
 }
 
-// gamma from the trace cap, into the prover's (verifier = false) or the verifier's challenge words of d_air
-static int32_t air_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cap, bool verifier,
-                         hipStream_t s) {
+// the set-2 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
+static int32_t air2_scratch(tmx_ctx* c, uint32_t log_m) {
+  const size_t want = (AIR2_OFF_EXT + (log_m ? (size_t)2 << log_m : 0)) * 8;
+  if (c->air2_bytes < want) {
+    if (c->d_air2) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air2)); c->d_air2 = nullptr; c->air2_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air2, want));
+    c->air2_bytes = want;
+  }
+  return TMX_OK;
+}
+
+// gamma into the prover's (verifier = false) or the verifier's challenge words of d_air.  Set 1: phase 9 over the trace cap.  Set 2: the
+// public table's digest (its Poseidon Merkle root) first, then phase 10 over the trace cap and the digest
+static int32_t air_gamma(tmx_ctx* c, bool boundary, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cap,
+                         const uint64_t* d_pub, bool verifier, hipStream_t s) {
+  uint64_t* digest = nullptr;
+  if (boundary) {
+    const uint32_t log_k = log_n - log_blowup - 8;
+    uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air2) + (verifier ? AIR2_OFF_LEVV : AIR2_OFF_LEVP);
+    const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, s);
+    if (st) return st;
+    digest = lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1);
+  }
   FriGeom G;
   std::memset(&G, 0, sizeof G);
-  const uint32_t obs[5] = {1 /* the constraint-set id: the ladder rows */, log_n, log_blowup, cap_height, n_proofs};
+  const uint32_t obs[5] = {boundary ? 2u : 1u /* the constraint-set id: the ladder rows, with their boundaries */, log_n, log_blowup, cap_height, n_proofs};
   std::memcpy(G.params, obs, sizeof obs);
   G.cap_height = std::min(cap_height, log_n);
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 9, 0, d_cap, nullptr, W, W + 32, nullptr, s);
+  const int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, boundary ? 10 : 9, 0, d_cap, digest, W, W + 32, nullptr, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
   return TMX_OK;
 }
 
-// one piece of the table: n proofs whose first is proof `first` of the table, their extended columns at cols
-static int32_t air_piece(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo& A, uint32_t first, uint32_t n, const uint64_t* cols,
-                         bool accumulate, uint64_t* d_quot, hipStream_t s) {
+// Pub_gamma on the coset from the public table and the prover's gamma: V, the coefficients, the extension
+static int32_t air2_public(tmx_ctx* c, uint32_t log_m, const AirGeo& B, uint32_t n_proofs, const uint64_t* d_pub, hipStream_t s) {
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  int rc = launch_air_public_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR2_OFF_VP, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR2_OFF_TW, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_coefs(B.log_k, B.k_inv, B.om255_inv, X + AIR2_OFF_VP, X + AIR2_OFF_TW, X + AIR2_OFF_COEF, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR2_OFF_COEF, X + AIR2_OFF_TW, X + AIR2_OFF_EXT, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+// one piece of the table: n proofs whose first is proof `first` of the table, their extended columns at cols.  Set 2 keeps its tables in
+// its own scratch, and the piece whose first proof is proof 0 carries - Pub_gamma / S
+static int32_t air_piece(tmx_ctx* c, bool boundary, uint32_t log_n, uint32_t log_blowup, const AirGeo& A, uint32_t first, uint32_t n,
+                         const uint64_t* cols, bool accumulate, uint64_t* d_quot, hipStream_t s) {
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
+  const uint64_t* gamma = W + 32 + FRI_GAMMA_AT;
+  if (boundary) {
+    uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
+    int rc = launch_air_boundary_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, gamma, X, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_boundary_tables launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = launch_air_ladder_boundary_quotient(log_n, log_blowup, n, cols, X, first == 0 ? X + AIR2_OFF_EXT : nullptr, accumulate ? 1 : 0, d_quot, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+    return TMX_OK;
+  }
   uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = launch_air_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, W + 32 + FRI_GAMMA_AT, tab, s);
+  int rc = launch_air_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, gamma, tab, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_tables launch: ") + hipGetErrorString((hipError_t)rc));
   rc = launch_air_ladder_quotient(log_n, log_blowup, n, cols, tab, accumulate ? 1 : 0, d_quot, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_quotient launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+static int32_t air_quotient_range_call(tmx_ctx* c, bool boundary, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                       uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_cap,
+                                       const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  int32_t st = air_check(c, boundary, log_n, log_blowup, n_proofs);
+  if (st) return st;
+  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
+  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
+  if (!d_cols || !d_cap || (boundary && !d_pub) || !d_quot)
+    return fail(c, TMX_ERR_BAD_ARG, boundary ? "d_cols, d_cap, d_pub and d_quot must be set" : "d_cols, d_cap and d_quot must be set");
+  AirGeo A;
+  if ((st = air_geo(c, boundary, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  if ((st = poseidon_ready(c, s))) return st;
+  c->air_valid = false;
+  if ((st = air_scratch(c, log_blowup))) return st;
+  if (boundary && (st = air2_scratch(c, log_n))) return st;
+  if ((st = air_gamma(c, boundary, log_n, log_blowup, cap_height, n_proofs, d_cap, d_pub, false, s))) return st;
+  if (boundary && proof_lo == 0 && (st = air2_public(c, log_n, A, n_proofs, d_pub, s))) return st;
+  if ((st = air_piece(c, boundary, log_n, log_blowup, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_LADDER_WIDTH) << log_n),
+                      accumulate != 0, d_quot, s)))
+    return st;
+  HIPCK(c, hipEventRecord(c->ev_air, s));
+  c->air_valid = true;
   return TMX_OK;
 }
 
@@ -4273,26 +4369,8 @@ extern "C" {
 int32_t tmx_air_ladder_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                              uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_cap,
                                              uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = air_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
-  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
-  if (!d_cols || !d_cap || !d_quot) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_cap and d_quot must be set");
-  AirGeo A;
-  if ((st = air_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = air_gamma(c, log_n, log_blowup, cap_height, n_proofs, d_cap, false, s))) return st;
-  if ((st = air_piece(c, log_n, log_blowup, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_LADDER_WIDTH) << log_n),
-                      accumulate != 0, d_quot, s)))
-    return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
+  return air_quotient_range_call(c, false, log_n, log_blowup, cap_height, n_proofs, proof_lo, proof_hi, accumulate, d_cols, d_cap, nullptr, d_quot,
+                                 hip_stream);
 }
 
 int32_t tmx_air_ladder_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
@@ -4309,8 +4387,10 @@ int32_t tmx_air_last_gamma(tmx_ctx* c, uint64_t g[2]) {
   return TMX_OK;
 }
 
-int32_t tmx_air_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok,
-                              void* hip_stream) {
+}  // extern "C"
+
+static int32_t air_verify_call(tmx_ctx* c, bool boundary, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                               const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = batch_check(c, p);
   if (st) return st;
@@ -4319,30 +4399,44 @@ int32_t tmx_air_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_
   if (p->log_n[k_trace + 1] != p->log_n[k_trace] || p->n_cols[k_trace + 1] != 2)
     return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
   const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_LADDER_WIDTH;
-  if ((st = air_check(c, log_n, p->log_blowup, n_proofs))) return st;
+  if ((st = air_check(c, boundary, log_n, p->log_blowup, n_proofs))) return st;
+  if (boundary && !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
   AirGeo A;
-  if ((st = air_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
+  if ((st = air_geo(c, boundary, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
   if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   if ((st = air_scratch(c, p->log_blowup))) return st;
+  if (boundary && (st = air2_scratch(c, 0))) return st;
   tmx_batch_layout L;
   batch_layout(*p, L);
   const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the trace cap: both into the verifier's words of d_air, then the identity
+  // zeta as the batch transcript draws it, gamma from the trace cap (set 2: and the verifier's own digest of d_pub): both into the
+  // verifier's words of d_air, then the identity (set 2: V from d_pub first)
   uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
   int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = air_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, d_caps + G.o_cap_at[k_trace], true, s))) return st;
-  rc = launch_air_ladder_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, d_proof + L.off_open[k_trace],
-                               d_proof + L.off_open[k_trace + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_check launch: ") + hipGetErrorString((hipError_t)rc));
+  if ((st = air_gamma(c, boundary, log_n, p->log_blowup, p->cap_height, n_proofs, d_caps + G.o_cap_at[k_trace], d_pub, true, s))) return st;
+  const uint64_t *open_t = d_proof + L.off_open[k_trace], *open_q = d_proof + L.off_open[k_trace + 1];
+  if (!boundary) {
+    rc = launch_air_ladder_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, open_t, open_q, V + 32 + FRI_ZETA_AT,
+                                 V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_check launch: ") + hipGetErrorString((hipError_t)rc));
+    return TMX_OK;
+  }
+  uint64_t* vv = reinterpret_cast<uint64_t*>(c->d_air2) + AIR2_OFF_VV;
+  rc = launch_air_public_combine(A.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, vv, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_ladder_boundary_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, A.om255, A.om_k, A.bary_inv, open_t, open_q,
+                                        V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, vv, p->n_queries, d_ok, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_check launch: ") + hipGetErrorString((hipError_t)rc));
   return TMX_OK;
 }
 
-int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip_stream) {
+static int32_t air_set_call(tmx_ctx* c, bool boundary, const uint64_t* d_pub, uint64_t* d_cap_q, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
   if (st) return st;
+  if (boundary && !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
   if (!d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_q is null");
   tmx_ctx::SetRec r = c->set;
   uint32_t kt = r.n_oracles;
@@ -4354,16 +4448,17 @@ int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip
   if (r.n_oracles >= TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for one more oracle");
   const tmx_ctx::SetRec::Oracle lad = r.o[kt];
   const uint32_t log_m = lad.log_m, log_sub = log_m - r.log_blowup, n_proofs = lad.n_cols / AIR_LADDER_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = air_check(c, log_m, r.log_blowup, n_proofs))) return st;
+  if ((st = air_check(c, boundary, log_m, r.log_blowup, n_proofs))) return st;
   if (lad.streamed && r.chunk_cols < AIR_LADDER_WIDTH)
     return fail(c, TMX_ERR_BAD_ARG, "a streamed ladders member is fed in chunks of whole proofs: chunk_cols must be at least 65");
   AirGeo A;
-  if ((st = air_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
+  if ((st = air_geo(c, boundary, log_m, r.log_blowup, r.root, r.shift, A))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCK(c, hipSetDevice(c->cfg.device));
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
+  if (boundary && (st = air2_scratch(c, log_m))) return st;
   const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
   const size_t quot_b = ((size_t)2 << log_m) * 8, want = quot_b + (size_t)n_dig * 32;
   if (c->set_air_bytes < want) {
@@ -4375,9 +4470,12 @@ int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip
   uint64_t* quot = reinterpret_cast<uint64_t*>(c->d_set_air);
   uint64_t* lev_q = quot + ((size_t)2 << log_m);
   const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + lad.lev_off);
-  if ((st = air_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, lev_t + 4 * (n_dig - n_cap), false, s))) return st;
+  if ((st = air_gamma(c, boundary, log_m, r.log_blowup, r.cap_height, n_proofs, lev_t + 4 * (n_dig - n_cap), d_pub, false, s))) return st;
+  // Pub_gamma is extended by kernels of its own from the set's root and shift: the context's NTT domain plays no part in it
+  if (boundary && (st = air2_public(c, log_m, A, n_proofs, d_pub, s))) return st;
   if (!lad.streamed) {
-    if ((st = air_piece(c, log_m, r.log_blowup, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + lad.lde_off), false, quot, s))) return st;
+    if ((st = air_piece(c, boundary, log_m, r.log_blowup, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + lad.lde_off), false, quot, s)))
+      return st;
   } else {
     // chunks of whole proofs, each extended once more into the set's chunk buffer under the set's domain (as the streamed prove does: if
     // tmx_ntt_set_domain has changed the context's since, it is put back for this call and restored after it)
@@ -4390,7 +4488,7 @@ int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip
     for (uint32_t p0 = 0; p0 < n_proofs && !st; p0 += per) {
       const uint32_t n = std::min(per, n_proofs - p0);
       st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * AIR_LADDER_WIDTH, cols + (((uint64_t)p0 * AIR_LADDER_WIDTH) << log_sub), chunk, hip_stream);
-      if (!st) st = air_piece(c, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
+      if (!st) st = air_piece(c, boundary, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
     }
     if (moved) {
       const int32_t back = tmx_ntt_set_domain(c, root, shift);
@@ -4409,94 +4507,18 @@ int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip
   return TMX_OK;
 }
 
-}  // extern "C"
-
-// ---- constraint set 2: the boundary constraints of the ladder rows (include/tmx.h "the boundary constraints of the ladder rows") ----------
-// Beside set 1: the functions above are not touched.  K = N / 256 ladders; the public table is 17 n_proofs columns of K words.
-struct AirGeo2 { uint32_t log_k; uint64_t s, w, om_k, om255, om255_inv, k_inv, bary_inv; };
-constexpr uint64_t AIR2_K_MAX = 1ull << AIR_PUBLIC_MAX_LOG_K;
-constexpr uint64_t AIR2_OFF_TW = AIR2_TAB_WORDS, AIR2_OFF_VP = AIR2_OFF_TW + AIR2_K_MAX, AIR2_OFF_VV = AIR2_OFF_VP + 2 * AIR2_K_MAX,
-                   AIR2_OFF_COEF = AIR2_OFF_VV + 2 * AIR2_K_MAX, AIR2_OFF_LEVP = AIR2_OFF_COEF + 2 * AIR2_K_MAX,
-                   AIR2_OFF_LEVV = AIR2_OFF_LEVP + 8 * AIR2_K_MAX, AIR2_OFF_EXT = AIR2_OFF_LEVV + 8 * AIR2_K_MAX;
-
-static int32_t air2_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
-  const int32_t st = air_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (log_n - log_blowup < 9) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 9: the boundary constraints need two ladders");
-  if (log_n - log_blowup > 8 + AIR_PUBLIC_MAX_LOG_K) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at most 20: at most 2^12 ladders");
-  return TMX_OK;
-}
-
-static void air2_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, const AirGeo& A, AirGeo2& B) {
-  const uint64_t P = 0xffffffff00000001ull;
-  B.log_k = log_n - log_blowup - 8;
-  B.s = shift % P;
-  B.w = gl_pow_host(root_2_32, 1ull << (32 - log_n));
-  B.om_k = gl_pow_host(B.w, 1ull << (8 + log_blowup));  // omega_N^256 = w^(256 B)
-  B.om255 = gl_pow_host(B.w, 255ull << log_blowup);
-  B.om255_inv = gl_pow_host(B.om255, P - 2);
-  B.k_inv = gl_pow_host(1ull << B.log_k, P - 2);
-  B.bary_inv = (uint64_t)(((unsigned __int128)B.k_inv * gl_pow_host(A.om256_inv, P - 2)) % P);  // 1 / (K omega_256^-1)
-}
-
-// the set-2 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
-static int32_t air2_scratch(tmx_ctx* c, uint32_t log_m) {
-  const size_t want = (AIR2_OFF_EXT + (log_m ? (size_t)2 << log_m : 0)) * 8;
-  if (c->air2_bytes < want) {
-    if (c->d_air2) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air2)); c->d_air2 = nullptr; c->air2_bytes = 0; }
-    HIPCK(c, hipMalloc(&c->d_air2, want));
-    c->air2_bytes = want;
-  }
-  return TMX_OK;
-}
-
-// gamma of set 2: the public table's digest (its Poseidon Merkle root), then phase 10 over the trace cap and the digest
-static int32_t air2_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t log_k, const uint64_t* d_cap,
-                          const uint64_t* d_pub, bool verifier, void* hip_stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air2) + (verifier ? AIR2_OFF_LEVV : AIR2_OFF_LEVP);
-  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, hip_stream);
-  if (st) return st;
-  FriGeom G;
-  std::memset(&G, 0, sizeof G);
-  const uint32_t obs[5] = {2 /* the constraint-set id: the ladder rows with their boundaries */, log_n, log_blowup, cap_height, n_proofs};
-  std::memcpy(G.params, obs, sizeof obs);
-  G.cap_height = std::min(cap_height, log_n);
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 10, 0, d_cap, lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32,
-                                       nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-// Pub_gamma on the coset from the public table and the prover's gamma: V, the coefficients, the extension
-static int32_t air2_public(tmx_ctx* c, uint32_t log_m, const AirGeo2& B, uint32_t n_proofs, const uint64_t* d_pub, hipStream_t s) {
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
-  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
-  int rc = launch_air_public_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR2_OFF_VP, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR2_OFF_TW, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_public_coefs(B.log_k, B.k_inv, B.om255_inv, X + AIR2_OFF_VP, X + AIR2_OFF_TW, X + AIR2_OFF_COEF, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR2_OFF_COEF, X + AIR2_OFF_TW, X + AIR2_OFF_EXT, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-// one piece of the table, as air_piece; the piece whose first proof is proof 0 carries - Pub_gamma / S
-static int32_t air2_piece(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, const AirGeo& A, uint32_t first, uint32_t n, const uint64_t* cols,
-                          bool accumulate, uint64_t* d_quot, hipStream_t s) {
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
-  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
-  int rc = launch_air_boundary_tables(log_blowup, first, A.s_n, A.w_n, A.s_n256, A.w_n256, A.om256_inv, gamma, X, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_boundary_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_ladder_boundary_quotient(log_n, log_blowup, n, cols, X, first == 0 ? X + AIR2_OFF_EXT : nullptr, accumulate ? 1 : 0, d_quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_quotient launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
 extern "C" {
+
+int32_t tmx_air_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok,
+                              void* hip_stream) {
+  return air_verify_call(c, false, p, k_trace, d_caps, d_proof, nullptr, d_ok, hip_stream);
+}
+
+int32_t tmx_trace_commit_set_air_device(tmx_ctx* c, uint64_t* d_cap_q, void* hip_stream) {
+  return air_set_call(c, false, nullptr, d_cap_q, hip_stream);
+}
+
+// ---- the public table of the ladder rows from element rows, and set 2's entry points
 
 int32_t tmx_air_ladder_public_shape(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols) {
   uint32_t log_rows = 0, width = 0;
@@ -4526,30 +4548,8 @@ int32_t tmx_air_ladder_public_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs
 int32_t tmx_air_ladder_boundary_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                                       uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
                                                       const uint64_t* d_cap, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = air2_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
-  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
-  if (!d_cols || !d_cap || !d_pub || !d_quot) return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_cap, d_pub and d_quot must be set");
-  AirGeo A;
-  if ((st = air_geo(c, log_n, log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  AirGeo2 B;
-  air2_geo(log_n, log_blowup, c->ntt_root, c->ntt_shift, A, B);
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = air2_scratch(c, log_n))) return st;
-  if ((st = air2_gamma(c, log_n, log_blowup, cap_height, n_proofs, B.log_k, d_cap, d_pub, false, hip_stream))) return st;
-  if (proof_lo == 0 && (st = air2_public(c, log_n, B, n_proofs, d_pub, s))) return st;
-  if ((st = air2_piece(c, log_n, log_blowup, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_LADDER_WIDTH) << log_n),
-                       accumulate != 0, d_quot, s)))
-    return st;
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
+  return air_quotient_range_call(c, true, log_n, log_blowup, cap_height, n_proofs, proof_lo, proof_hi, accumulate, d_cols, d_cap, d_pub, d_quot,
+                                 hip_stream);
 }
 
 int32_t tmx_air_ladder_boundary_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
@@ -4561,133 +4561,35 @@ int32_t tmx_air_ladder_boundary_quotient_device(tmx_ctx* c, uint32_t log_n, uint
 
 int32_t tmx_air_boundary_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
                                        const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = batch_check(c, p);
-  if (st) return st;
-  if (k_trace + 1 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, "k_trace and k_trace + 1 must both be oracles of the proof");
-  if (p->n_cols[k_trace] % AIR_LADDER_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 65 columns");
-  if (p->log_n[k_trace + 1] != p->log_n[k_trace] || p->n_cols[k_trace + 1] != 2)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_LADDER_WIDTH;
-  if ((st = air2_check(c, log_n, p->log_blowup, n_proofs))) return st;
-  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
-  AirGeo A;
-  if ((st = air_geo(c, log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A))) return st;
-  AirGeo2 B;
-  air2_geo(log_n, p->log_blowup, c->ntt_root, c->ntt_shift, A, B);
-  if (!d_caps || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_caps, d_proof and d_ok must be set");
-  if ((st = air_scratch(c, p->log_blowup))) return st;
-  if ((st = air2_scratch(c, 0))) return st;
-  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  tmx_batch_layout L;
-  batch_layout(*p, L);
-  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the trace cap and the verifier's own digest of d_pub, V from d_pub, then the identity
-  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air2);
-  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = air2_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, B.log_k, d_caps + G.o_cap_at[k_trace], d_pub, true, hip_stream))) return st;
-  rc = launch_air_public_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, X + AIR2_OFF_VV, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_combine launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_ladder_boundary_check(n_proofs, G.o_log_r[k_trace], log_n - p->log_blowup, A.om256_inv, B.om255, B.om_k, B.bary_inv,
-                                        d_proof + L.off_open[k_trace], d_proof + L.off_open[k_trace + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT,
-                                        X + AIR2_OFF_VV, p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_ladder_boundary_check launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return air_verify_call(c, true, p, k_trace, d_caps, d_proof, d_pub, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_pub, uint64_t* d_cap_q, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
-  if (st) return st;
-  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
-  if (!d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_q is null");
-  tmx_ctx::SetRec r = c->set;
-  uint32_t kt = r.n_oracles;
-  for (uint32_t k = 0; k < r.n_oracles; k++) {
-    if (r.o[k].section == TMX_TRACE_LADDERS_QUOTIENT) return fail(c, TMX_ERR_BAD_ARG, "the commit set already holds the ladders' constraint quotient");
-    if (r.o[k].section == TMX_TRACE_LADDERS) kt = k;
-  }
-  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold TMX_TRACE_LADDERS");
-  if (r.n_oracles >= TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for one more oracle");
-  const tmx_ctx::SetRec::Oracle lad = r.o[kt];
-  const uint32_t log_m = lad.log_m, log_sub = log_m - r.log_blowup, n_proofs = lad.n_cols / AIR_LADDER_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = air2_check(c, log_m, r.log_blowup, n_proofs))) return st;
-  if (lad.streamed && r.chunk_cols < AIR_LADDER_WIDTH)
-    return fail(c, TMX_ERR_BAD_ARG, "a streamed ladders member is fed in chunks of whole proofs: chunk_cols must be at least 65");
-  AirGeo A;
-  if ((st = air_geo(c, log_m, r.log_blowup, r.root, r.shift, A))) return st;
-  AirGeo2 B;
-  air2_geo(log_m, r.log_blowup, r.root, r.shift, A, B);
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, r.log_blowup))) return st;
-  if ((st = air2_scratch(c, log_m))) return st;
-  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const size_t quot_b = ((size_t)2 << log_m) * 8, want = quot_b + (size_t)n_dig * 32;
-  if (c->set_air_bytes < want) {
-    if (c->d_set_air) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(c->d_set_air)); c->d_set_air = nullptr; c->set_air_bytes = 0; }
-    HIPCK(c, hipMalloc(&c->d_set_air, want));
-    c->set_air_bytes = want;
-  }
-  uint8_t* base = reinterpret_cast<uint8_t*>(c->d_set);
-  uint64_t* quot = reinterpret_cast<uint64_t*>(c->d_set_air);
-  uint64_t* lev_q = quot + ((size_t)2 << log_m);
-  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + lad.lev_off);
-  if ((st = air2_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, B.log_k, lev_t + 4 * (n_dig - n_cap), d_pub, false, hip_stream))) return st;
-  // Pub_gamma is extended by kernels of its own from the set's root and shift: the context's NTT domain plays no part in it
-  if ((st = air2_public(c, log_m, B, n_proofs, d_pub, s))) return st;
-  if (!lad.streamed) {
-    if ((st = air2_piece(c, log_m, r.log_blowup, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + lad.lde_off), false, quot, s))) return st;
-  } else {
-    // chunks of whole proofs, as tmx_trace_commit_set_air_device feeds them
-    const uint64_t root = c->ntt_root, shift = c->ntt_shift;
-    const bool moved = root != r.root || shift != r.shift;
-    if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
-    const uint64_t* cols = reinterpret_cast<const uint64_t*>(base + lad.cols_off);
-    uint64_t* chunk = reinterpret_cast<uint64_t*>(base + r.chunk_off);
-    const uint32_t per = r.chunk_cols / AIR_LADDER_WIDTH;
-    for (uint32_t p0 = 0; p0 < n_proofs && !st; p0 += per) {
-      const uint32_t n = std::min(per, n_proofs - p0);
-      st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, n * AIR_LADDER_WIDTH, cols + (((uint64_t)p0 * AIR_LADDER_WIDTH) << log_sub), chunk, hip_stream);
-      if (!st) st = air2_piece(c, log_m, r.log_blowup, A, p0, n, chunk, p0 != 0, quot, s);
-    }
-    if (moved) {
-      const int32_t back = tmx_ntt_set_domain(c, root, shift);
-      if (!st) st = back;
-    }
-    if (st) return st;
-  }
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  for (uint32_t k = r.n_oracles; k > kt + 1; k--) r.o[k] = r.o[k - 1];
-  r.o[kt + 1] = {TMX_TRACE_LADDERS_QUOTIENT, log_m, 2, 0, 0, quot_b, false, true};
-  r.n_oracles++;
-  c->set = r;
-  return TMX_OK;
+  return air_set_call(c, true, d_pub, d_cap_q, hip_stream);
 }
 
 }  // extern "C"
 
-// ---- constraint sets 3, 4 and 5 on the SHA-256 tables: the round constraints, the message schedule and the block starts (include/tmx.h
-// "the round constraints of the SHA-256 tables", "the message schedule ...", "the block starts ...") ----------------------------------------
-// One host path drives all three: the same argument checks, the same geometry, the gamma kernel (the set id, and set 5's mode, in obs[0]),
-// the same tables-then-quotient pass and the same scratch layout.  The tables of a quotient launch sit in the table part of d_air (air.h
-// AIR3_TAB_*, AIR4_TAB_*, AIR5_TAB_*), the challenge words where set 1 keeps its own.  What differs between the sets is a ShaSet: the id,
-// the helper's column count, whether the set has a chain mode, the two section ids, the row of tmx_ctx::d_set_sha, the words its messages
-// differ in, and its four launches under set 5's signatures (sets 3 and 4 have no mode: their adapters drop `chain`).
+// ---- constraint sets 3, 4, 5 and 6 on the SHA-256 tables: the round constraints, the message schedule, the block starts and the link to
+// Level-1 (include/tmx.h "the round constraints of the SHA-256 tables", "the message schedule ...", "the block starts ...", "the SHA-256
+// tables' link to Level-1") -----------------------------------------------------------------------------------------------------------------
+// One host path drives all four: the same argument checks, the same geometry, the same tables-then-quotient pass, the same scratch layout
+// and the same placement in the commit set.  The tables of a quotient launch of sets 3 - 5 sit in the table part of d_air (air.h
+// AIR3_TAB_*, AIR4_TAB_*, AIR5_TAB_*), the challenge words of all four where set 1 keeps its own.  What differs between the sets is a
+// ShaSet: the id, the helper's column count, whether the set has a chain mode, whether it has a public table, the rows it accepts, the two
+// section ids, the row of tmx_ctx::d_set_sha, the words its messages differ in, and the four launches of a set without a public table
+// under set 5's signatures (sets 3 and 4 have no mode: their adapters drop `chain`).  A set with a public table (set 6) takes d_pub, null
+// for the others, and does its public step at four places, each a branch on has_public: gamma observes the table's digest (sha_gamma), the
+// pass writes its tables to d_air6 and the piece that starts at proof 0 carries - PQ (sha_pass), the verifier forms V before its check
+// (sha_verify_call), and the helper kernel reads d_pub (sha_helper_launch).  Its helper is resident only: the streamed calls take sets 3 - 5.
 struct ShaSet {
   uint32_t id, helper_cols;
-  bool has_chain;
+  bool has_chain, has_public;
+  uint32_t rows_lo, rows_hi;  // log2 of the pre-LDE rows it accepts
   uint32_t helper_section, quotient_section;
   int scratch;
-  const char *stem, *word, *already;           // k_air_<stem>_*, "the <word> member", the refusal of a second set-level call
+  const char *bad_sub, *bad_rows;               // the refusals of log_n - log_blowup and of log_rows outside rows_lo .. rows_hi
+  const char *stem, *word, *already;            // k_air_<stem>_*, "the <word> member", the refusal of a second set-level call
   const char *at_helper, *at_quot, *bad_index;  // how the verifier's messages name the helper's and the quotient's oracle index
   int (*helper)(uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, void* d_helper, void* stream);
   int (*tables)(uint32_t log_blowup, uint32_t chain, uint64_t first_proof, uint64_t s_n, uint64_t w_n, uint64_t s_sel, uint64_t w_sel, uint64_t rho,
@@ -4732,17 +4634,24 @@ static int sha4_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uin
 }
 
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
-static const ShaSet SHA_SETS[3] = {
-    {3, AIR_SHA_HELPER_COLS, false, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, "sha", "helper",
+static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
+static const char SHA_BAD_ROWS[] = "log_rows must be 6 .. 27: a SHA-256 block is 64 rows";
+static const ShaSet SHA_SETS[4] = {
+    {3, AIR_SHA_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, SHA_BAD_SUB, SHA_BAD_ROWS, "sha", "helper",
      "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
      "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check},
-    {4, AIR_SCHED_HELPER_COLS, false, TMX_TRACE_SHA256_SCHED_HELPER, TMX_TRACE_SHA256_SCHED_QUOTIENT, 1, "sched", "schedule helper",
-     "the commit set already holds the schedule helper and quotient of that section", "k_helper", "k_helper + 1",
+    {4, AIR_SCHED_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_SCHED_HELPER, TMX_TRACE_SHA256_SCHED_QUOTIENT, 1, SHA_BAD_SUB, SHA_BAD_ROWS,
+     "sched", "schedule helper", "the commit set already holds the schedule helper and quotient of that section", "k_helper", "k_helper + 1",
      "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check},
-    {5, AIR_INIT_HELPER_COLS, true, TMX_TRACE_SHA256_INIT_HELPER, TMX_TRACE_SHA256_INIT_QUOTIENT, 2, "init", "block-start helper",
-     "the commit set already holds the block-start helper and quotient of that section", "k_helper", "k_helper + 1",
+    {5, AIR_INIT_HELPER_COLS, true, false, 6, 27, TMX_TRACE_SHA256_INIT_HELPER, TMX_TRACE_SHA256_INIT_QUOTIENT, 2, SHA_BAD_SUB, SHA_BAD_ROWS, "init",
+     "block-start helper", "the commit set already holds the block-start helper and quotient of that section", "k_helper", "k_helper + 1",
      "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", launch_air_init_helper, launch_air_init_tables,
      launch_air_init_quotient, launch_air_init_check},
+    {6, AIR_LINK_HELPER_COLS, false, true, 6 + AIR_SHA_PUBLIC_MIN_LOG_K, 6 + AIR_SHA_PUBLIC_MAX_LOG_K, TMX_TRACE_SHA256_LINK_HELPER,
+     TMX_TRACE_SHA256_LINK_QUOTIENT, 3, "log_n - log_blowup must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows",
+     "log_rows must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows", "link", "link helper",
+     "the commit set already holds the link helper and quotient of that section", "k_helper", "k_helper + 1",
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr},
 };
 
 static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
@@ -4755,7 +4664,7 @@ static std::string sha_too_many_cols(const ShaSet& d) { return std::to_string(d.
 static int32_t sha_check(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs, uint32_t chain) {
   if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
   if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
-  if (log_n - log_blowup < 6) return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows");
+  if (log_n - log_blowup < d.rows_lo || log_n - log_blowup > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_sub);
   if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
   if ((uint64_t)n_proofs * d.helper_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, sha_too_many_cols(d));
   if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
@@ -4763,12 +4672,26 @@ static int32_t sha_check(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t l
   return TMX_OK;
 }
 
-// s_n = s^N, w_n = w^N; the selector's period is 64 << chain rows: s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0,
-// s^(N/128), w^(N/128), omega_128^-1 under chain = 1
-struct ShaGeo { uint64_t s_n, w_n, s_sel, w_sel, rho; };
-
-static int32_t sha_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, ShaGeo& A) {
+// s, w the coset; om = omega_N = w^B, om_k = omega_K = om^64, om64 = omega_64 = om^K, k_inv = 1 / K
+struct LinkGeo { uint32_t log_k; uint64_t s, w, om, om_k, om64, k_inv; };
+static void link_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, LinkGeo& B) {
   const uint64_t P = 0xffffffff00000001ull;
+  B.log_k = log_n - log_blowup - 6;
+  B.s = shift % P;
+  B.w = gl_pow_host(root_2_32, 1ull << (32 - log_n));
+  B.om = gl_pow_host(B.w, 1ull << log_blowup);
+  B.om_k = gl_pow_host(B.om, 64);
+  B.om64 = gl_pow_host(B.om, 1ull << B.log_k);
+  B.k_inv = gl_pow_host(1ull << B.log_k, P - 2);
+}
+
+// s_n = s^N, w_n = w^N; the selector's period is 64 << chain rows: s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0,
+// s^(N/128), w^(N/128), omega_128^-1 under chain = 1; link: filled for a set with a public table
+struct ShaGeo { uint64_t s_n, w_n, s_sel, w_sel, rho; LinkGeo link; };
+
+static int32_t sha_geo(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, ShaGeo& A) {
+  const uint64_t P = 0xffffffff00000001ull;
+  if (d.has_public) link_geo(log_n, log_blowup, root_2_32, shift, A.link);
   const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
   const uint32_t log_per = 6 + chain;
   A.s_n = gl_pow_host(s, n); A.w_n = gl_pow_host(w, n);
@@ -4780,40 +4703,123 @@ static int32_t sha_geo(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t
   return TMX_OK;
 }
 
-// gamma from the table cap and the helper cap, into the prover's (verifier = false) or the verifier's challenge words of d_air
+// What set 6 has of its own inside that path: the public side.  Set 3's geometry and LinkGeo, and a scratch of its own (words at d_air6):
+//   tables (air.h AIR6_TAB_*) | twiddles [K] | V of the prover [17][K][2] | V of the verifier | coefficients [2 K] | the public digest's
+//   levels, prover and verifier | one extended public polynomial (2 M) | PQ (2 M)
+// One extended public polynomial and PQ live here per context, not per section; the scratch of a section is sets 3 - 5's layout with 33
+// columns per proof (row 3 of d_set_sha).
+constexpr uint64_t AIR6_K_MAX = 1ull << AIR_SHA_PUBLIC_MAX_LOG_K;
+constexpr uint64_t AIR6_OFF_TW = AIR6_TAB_WORDS, AIR6_OFF_VP = AIR6_OFF_TW + AIR6_K_MAX, AIR6_OFF_VV = AIR6_OFF_VP + 34 * AIR6_K_MAX,
+                   AIR6_OFF_COEF = AIR6_OFF_VV + 34 * AIR6_K_MAX, AIR6_OFF_LEVP = AIR6_OFF_COEF + 2 * AIR6_K_MAX,
+                   AIR6_OFF_LEVV = AIR6_OFF_LEVP + 8 * AIR6_K_MAX, AIR6_OFF_EXT = AIR6_OFF_LEVV + 8 * AIR6_K_MAX;
+
+// the set-6 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
+static int32_t link_scratch(tmx_ctx* c, uint32_t log_m) {
+  const size_t want = (AIR6_OFF_EXT + (log_m ? (size_t)4 << log_m : 0)) * 8;
+  if (c->air6_bytes < want) {
+    if (c->d_air6) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air6)); c->d_air6 = nullptr; c->air6_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air6, want));
+    c->air6_bytes = want;
+  }
+  return TMX_OK;
+}
+
+// PQ on the coset from the public table and the prover's gamma: V, then per coset the coefficients, the extension and its fold.  The
+// tables (first = 0) are written first: the fold reads 1 / S and 1 / D_t
+static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, const ShaGeo& A, uint32_t n_proofs, const uint64_t* d_pub, hipStream_t s) {
+  const uint64_t P = 0xffffffff00000001ull;
+  const LinkGeo& B = A.link;
+  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
+  int rc = launch_air_link_tables(log_blowup, 0, A.s_n, A.w_n, A.s_sel, A.w_sel, B.om64, gamma, X, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_tables launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR6_OFF_VP, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_combine launch: ") + hipGetErrorString((hipError_t)rc));
+  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR6_OFF_TW, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
+  uint64_t* ext = X + AIR6_OFF_EXT;
+  uint64_t* pq = ext + ((size_t)2 << log_m);
+  for (uint32_t k = 0; k < 17; k++) {
+    const uint32_t off = k ? k - 1 : 63;
+    const uint64_t off_inv = gl_pow_host(gl_pow_host(B.om, off), P - 2);
+    rc = launch_air_public_coefs(B.log_k, B.k_inv, off_inv, X + AIR6_OFF_VP + ((uint64_t)k << (B.log_k + 1)), X + AIR6_OFF_TW, X + AIR6_OFF_COEF, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR6_OFF_COEF, X + AIR6_OFF_TW, ext, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = launch_air_link_fold(log_m, log_blowup, k, k == 0, ext, X, pq, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_fold launch: ") + hipGetErrorString((hipError_t)rc));
+  }
+  return TMX_OK;
+}
+
+// gamma from the table cap and the helper cap, into the prover's (verifier = false) or the verifier's challenge words of d_air.  A set with
+// a public table: the table's digest (its Poseidon Merkle root) first, then the lone-lane kernel over the two caps and the digest
 static int32_t sha_gamma(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
-                         const uint64_t* d_cap, const uint64_t* d_cap_helper, bool verifier, hipStream_t s) {
+                         const uint64_t* d_cap, const uint64_t* d_cap_helper, const uint64_t* d_pub, bool verifier, hipStream_t s) {
   const uint32_t obs[5] = {d.id | chain << 8 /* the constraint-set id, and set 5's mode */, log_n, log_blowup, cap_height, n_proofs};
+  const uint32_t cap_words = 4u << std::min(cap_height, log_n);
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper, W, W + 32, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
+  if (!d.has_public) {
+    const int rc = launch_air_sha_gamma(c->d_pos_consts, c->pos_mode, obs, cap_words, d_cap, d_cap_helper, W, W + 32, s);
+    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
+    return TMX_OK;
+  }
+  const uint32_t log_k = log_n - log_blowup - 6;
+  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air6) + (verifier ? AIR6_OFF_LEVV : AIR6_OFF_LEVP);
+  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_SHA_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, s);
+  if (st) return st;
+  const int rc = launch_air_link_gamma(c->d_pos_consts, c->pos_mode, obs, cap_words, d_cap, d_cap_helper,
+                                       lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32, s);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_gamma launch: ") + hipGetErrorString((hipError_t)rc));
   return TMX_OK;
 }
 
 // the tables from the prover's gamma, then the pass.  form = AIR_FORM_WHOLE: the whole table (first = 0).  A piece: n_proofs proofs whose
-// first is proof `first` of the table, cols that proof's table column 0 and hcols the piece's own helper columns
+// first is proof `first` of the table, cols that proof's table column 0 and hcols the piece's own helper columns.  A set with a public
+// table (d_pub, of n_all proofs): the piece that starts at proof 0 first forms PQ, which writes the tables too, and carries - PQ
 static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, const ShaGeo& A, uint32_t first,
-                        uint32_t n_proofs, const uint64_t* cols, const uint64_t* hcols, int form, uint64_t* d_quot, hipStream_t s) {
+                        uint32_t n_proofs, const uint64_t* cols, const uint64_t* hcols, const uint64_t* d_pub, uint32_t n_all, int form,
+                        uint64_t* d_quot, hipStream_t s) {
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
-  uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-  int rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s);
-  if (rc) return sha_launch_failed(c, d, "tables", rc);
-  rc = d.quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, form, d_quot, s);
+  int rc;
+  if (d.has_public) {
+    uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
+    if (first == 0) {
+      const int32_t st = link_public(c, log_n, log_blowup, A, n_all, d_pub, s);
+      if (st) return st;
+    } else if ((rc = launch_air_link_tables(log_blowup, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.link.om64, W + 32 + FRI_GAMMA_AT, X, s))) {
+      return sha_launch_failed(c, d, "tables", rc);
+    }
+    rc = launch_air_link_quotient(log_n, log_blowup, n_proofs, cols, hcols, X, first == 0 ? X + AIR6_OFF_EXT + ((size_t)2 << log_n) : nullptr, form,
+                                  d_quot, s);
+  } else {
+    uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
+    if ((rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s)))
+      return sha_launch_failed(c, d, "tables", rc);
+    rc = d.quotient(log_n, log_blowup, n_proofs, chain, cols, hcols, tab, form, d_quot, s);
+  }
   if (rc) return sha_launch_failed(c, d, "quotient", rc);
   return TMX_OK;
 }
 
+static int sha_helper_launch(const ShaSet& d, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, const void* d_pub,
+                             void* d_helper, void* stream) {
+  return d.has_public ? launch_air_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, stream)
+                      : d.helper(log_rows, n_proofs, chain, d_table, d_helper, stream);
+}
+
 static int32_t sha_helper_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
-                               uint64_t* d_helper, void* hip_stream) {
+                               const uint64_t* d_pub, uint64_t* d_helper, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
-  if (log_rows < 6 || log_rows > 27) return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 6 .. 27: a SHA-256 block is 64 rows");
+  if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
   if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
   if ((uint64_t)n_proofs * d.helper_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, sha_too_many_cols(d));
   if (chain > 1) return fail(c, TMX_ERR_BAD_ARG, "chain must be 0 or 1");
   if (chain && log_rows < 7) return fail(c, TMX_ERR_BAD_ARG, "chain = 1 needs at least 128 rows: a chained hash is two blocks");
-  if (!d_table || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table and d_helper must be set");
+  if (!d_table || (d.has_public && !d_pub) || !d_helper)
+    return fail(c, TMX_ERR_BAD_ARG, d.has_public ? "d_table, d_pub and d_helper must be set" : "d_table and d_helper must be set");
   HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = d.helper(log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
+  const int rc = sha_helper_launch(d, log_rows, n_proofs, chain, d_table, d_pub, d_helper, hip_stream);
   if (rc) return sha_launch_failed(c, d, "helper", rc);
   return TMX_OK;
 }
@@ -4822,24 +4828,26 @@ static int32_t sha_helper_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, u
 // helper columns alone are at d_helper_cols; gamma is drawn over n_proofs either way
 static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                  uint32_t chain, uint32_t proof_lo, uint32_t proof_hi, int form, const uint64_t* d_cols,
-                                 const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
-                                 void* hip_stream) {
+                                 const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, const uint64_t* d_pub,
+                                 uint64_t* d_quot, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = sha_check(c, d, log_n, log_blowup, n_proofs, chain);
   if (st) return st;
   if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
-  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_quot)
-    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
+  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || (d.has_public && !d_pub) || !d_quot)
+    return fail(c, TMX_ERR_BAD_ARG, d.has_public ? "d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub and d_quot must be set"
+                                                 : "d_cols, d_helper_cols, d_cap, d_cap_helper and d_quot must be set");
   ShaGeo A;
-  if ((st = sha_geo(c, log_n, log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
+  if ((st = sha_geo(c, d, log_n, log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCK(c, hipSetDevice(c->cfg.device));
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, false, s))) return st;
+  if (d.has_public && (st = link_scratch(c, log_n))) return st;
+  if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, d_pub, false, s))) return st;
   if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_SHA_WIDTH) << log_n),
-                     d_helper_cols, form, d_quot, s)))
+                     d_helper_cols, d_pub, n_proofs, form, d_quot, s)))
     return st;
   HIPCK(c, hipEventRecord(c->ev_air, s));
   c->air_valid = true;
@@ -4848,16 +4856,16 @@ static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, ui
 
 static int32_t sha_quotient_range_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                        uint32_t chain, uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
-                                       const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
-                                       void* hip_stream) {
+                                       const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, const uint64_t* d_pub,
+                                       uint64_t* d_quot, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
   return sha_quotient_call(c, d, log_n, log_blowup, cap_height, n_proofs, chain, proof_lo, proof_hi, accumulate ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE,
-                           d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot, hip_stream);
+                           d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot, hip_stream);
 }
 
 static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
-                               const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+                               const uint64_t* d_caps, const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = batch_check(c, p);
   if (st) return st;
@@ -4870,22 +4878,36 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
     return fail(c, TMX_ERR_BAD_ARG, std::string("oracle ") + d.at_quot + " must be the quotient: the log_n of oracle k_trace and 2 columns");
   if ((st = sha_check(c, d, log_n, p->log_blowup, n_proofs, chain))) return st;
+  if (d.has_public && !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
   ShaGeo A;
-  if ((st = sha_geo(c, log_n, p->log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
+  if ((st = sha_geo(c, d, log_n, p->log_blowup, chain, c->ntt_root, c->ntt_shift, A))) return st;
   if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   if ((st = air_scratch(c, p->log_blowup))) return st;
+  if (d.has_public && (st = link_scratch(c, 0))) return st;
   tmx_batch_layout L;
   batch_layout(*p, L);
   const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the two caps: both into the verifier's words of d_air, then the identity
+  // zeta as the batch transcript draws it, gamma from the two caps (and the verifier's own digest of d_pub): both into the verifier's words
+  // of d_air, then the identity (a set with a public table: V from d_pub first)
   uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
   int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
   if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = sha_gamma(c, d, log_n, p->log_blowup, p->cap_height, n_proofs, chain, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], true, s)))
+  if ((st = sha_gamma(c, d, log_n, p->log_blowup, p->cap_height, n_proofs, chain, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], d_pub,
+                      true, s)))
     return st;
-  rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, d_proof + L.off_open[k_trace],
-               d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+  const uint64_t *open_t = d_proof + L.off_open[k_trace], *open_h = d_proof + L.off_open[k_helper], *open_q = d_proof + L.off_open[k_helper + 1];
+  if (d.has_public) {
+    const LinkGeo& B = A.link;
+    uint64_t* vv = reinterpret_cast<uint64_t*>(c->d_air6) + AIR6_OFF_VV;
+    rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, vv, s);
+    if (rc) return sha_launch_failed(c, d, "combine", rc);
+    rc = launch_air_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, B.om64, B.om, B.om_k, B.k_inv, open_t, open_h,
+                               open_q, V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, vv, p->n_queries, d_ok, s);
+  } else {
+    rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
+                 V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+  }
   if (rc) return sha_launch_failed(c, d, "check", rc);
   return TMX_OK;
 }
@@ -4920,9 +4942,10 @@ static const char* sha_chunk_refusal(const ShaSet& d, uint32_t chunk_proofs) {
 }
 
 // chunk_proofs = 0: the resident calls.  Else tmx_trace_commit_set_air_sha256_streamed_device: the helper streamed in chunks of chunk_proofs
-// whole proofs, or resident exactly as from the resident calls if one chunk holds it all.
-static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint32_t chunk_proofs, bool by_chunks, uint64_t* d_cap_h, uint64_t* d_cap_q,
-                            void* hip_stream) {
+// whole proofs, or resident exactly as from the resident calls if one chunk holds it all.  The pair goes behind every pair of a lower set
+// that follows the table, and the calls of lower sets insert in front of later members: every order ends as table, H3, Q3, ..., H6, Q6.
+static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint32_t chunk_proofs, bool by_chunks, const uint64_t* d_pub,
+                            uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
   if (st) return st;
@@ -4930,7 +4953,8 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
     if (const char* why = sha_chunk_refusal(d, chunk_proofs)) return fail(c, TMX_ERR_BAD_ARG, why);
   const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
   if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
-  if (!d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_cap_h and d_cap_q must be set");
+  if ((d.has_public && !d_pub) || !d_cap_h || !d_cap_q)
+    return fail(c, TMX_ERR_BAD_ARG, d.has_public ? "d_pub, d_cap_h and d_cap_q must be set" : "d_cap_h and d_cap_q must be set");
   const uint32_t chain = d.has_chain && section != TMX_TRACE_SHA256;  // T.3 hashes are single blocks, T.5 and T.6 hashes pairs of blocks
   tmx_ctx::SetRec r = c->set;
   uint32_t kt = r.n_oracles;
@@ -4948,12 +4972,13 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
   if ((st = sha_check(c, d, log_m, r.log_blowup, n_proofs, chain))) return st;
   ShaGeo A;
-  if ((st = sha_geo(c, log_m, r.log_blowup, chain, r.root, r.shift, A))) return st;
+  if ((st = sha_geo(c, d, log_m, r.log_blowup, chain, r.root, r.shift, A))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCK(c, hipSetDevice(c->cfg.device));
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
+  if (d.has_public && (st = link_scratch(c, log_m))) return st;
   // the scratch of this set and section (ShaScratch)
   const bool streamed = by_chunks && chunk_proofs < n_proofs;
   const uint32_t n_hcols = n_proofs * d.helper_cols;
@@ -4983,7 +5008,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   uint64_t* quot = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b);
   uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + pre_b + ext_b + lev_b + quot_b);
   const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
-  const int rc = d.helper(log_sub, n_proofs, chain, base + tabm.cols_off, hpre, s);
+  const int rc = sha_helper_launch(d, log_sub, n_proofs, chain, base + tabm.cols_off, d_pub, hpre, s);
   if (rc) return sha_launch_failed(c, d, "helper", rc);
   if (streamed) {
     // The helper never exists extended.  Sweep 1: chunk by chunk, extended into the chunk buffer and absorbed into the rows' sponge states;
@@ -5013,12 +5038,13 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
         cur += 4 * cnt;
       }
       HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-      if ((e = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s)))
+      if ((e = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), d_pub, false,
+                         s)))
         return e;
       for (uint32_t p0 = 0; p0 < n_proofs; p0 += chunk_proofs) {
         const uint32_t n = std::min(chunk_proofs, n_proofs - p0);
         if ((e = extend(p0, n))) return e;
-        if ((e = sha_pass(c, d, log_m, r.log_blowup, chain, A, p0, n, tcols + (((uint64_t)p0 * AIR_SHA_WIDTH) << log_m), chunk,
+        if ((e = sha_pass(c, d, log_m, r.log_blowup, chain, A, p0, n, tcols + (((uint64_t)p0 * AIR_SHA_WIDTH) << log_m), chunk, d_pub, n_proofs,
                           p0 ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE, quot, s)))
           return e;
       }
@@ -5047,10 +5073,11 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
     if (st) return st;
     if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
     HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-    if ((st = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), false, s)))
+    if ((st = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), d_pub, false,
+                        s)))
       return st;
-    if ((st = sha_pass(c, d, log_m, r.log_blowup, chain, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, AIR_FORM_WHOLE,
-                       quot, s)))
+    if ((st = sha_pass(c, d, log_m, r.log_blowup, chain, A, 0, n_proofs, reinterpret_cast<const uint64_t*>(base + tabm.lde_off), hext, d_pub, n_proofs,
+                       AIR_FORM_WHOLE, quot, s)))
       return st;
   }
   HIPCK(c, hipEventRecord(c->ev_air, s));
@@ -5069,73 +5096,73 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
 extern "C" {
 
 int32_t tmx_air_sha256_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper, void* hip_stream) {
-  return sha_helper_call(c, SHA_SETS[0], log_rows, n_proofs, 0, d_table, d_helper, hip_stream);
+  return sha_helper_call(c, SHA_SETS[0], log_rows, n_proofs, 0, d_table, nullptr, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
                                        const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
                                        void* hip_stream) {
   return sha_quotient_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
-                           d_cap_helper, d_quot, hip_stream);
+                           d_cap_helper, nullptr, d_quot, hip_stream);
 }
 
 // (the helper sits directly behind the table; a k_trace + 1 that wraps to 0 fails the index rule as it should)
 int32_t tmx_air_sha256_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
                                      uint32_t* d_ok, void* hip_stream) {
-  return sha_verify_call(c, SHA_SETS[0], p, k_trace, k_trace + 1, 0, d_caps, d_proof, d_ok, hip_stream);
+  return sha_verify_call(c, SHA_SETS[0], p, k_trace, k_trace + 1, 0, d_caps, d_proof, nullptr, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[0], section, 0, false, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[0], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
                                            void* hip_stream) {
-  return sha_helper_call(c, SHA_SETS[1], log_rows, n_proofs, 0, d_table, d_helper, hip_stream);
+  return sha_helper_call(c, SHA_SETS[1], log_rows, n_proofs, 0, d_table, nullptr, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                              const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                              const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
-                           d_cap_helper, d_quot, hip_stream);
+                           d_cap_helper, nullptr, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
                                            const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
-  return sha_verify_call(c, SHA_SETS[1], p, k_trace, k_helper, 0, d_caps, d_proof, d_ok, hip_stream);
+  return sha_verify_call(c, SHA_SETS[1], p, k_trace, k_helper, 0, d_caps, d_proof, nullptr, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[1], section, 0, false, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[1], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const uint64_t* d_table,
                                           uint64_t* d_helper, void* hip_stream) {
-  return sha_helper_call(c, SHA_SETS[2], log_rows, n_proofs, chain, d_table, d_helper, hip_stream);
+  return sha_helper_call(c, SHA_SETS[2], log_rows, n_proofs, chain, d_table, nullptr, d_helper, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                             const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
-                           d_cap_helper, d_quot, hip_stream);
+                           d_cap_helper, nullptr, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, uint32_t chain,
                                           const uint64_t* d_caps, const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
-  return sha_verify_call(c, SHA_SETS[2], p, k_trace, k_helper, chain, d_caps, d_proof, d_ok, hip_stream);
+  return sha_verify_call(c, SHA_SETS[2], p, k_trace, k_helper, chain, d_caps, d_proof, nullptr, d_ok, hip_stream);
 }
 
 int32_t tmx_trace_commit_set_air_sha256_init_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  return sha_set_call(c, SHA_SETS[2], section, 0, false, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[2], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t proof_lo,
                                              uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_helper_cols,
                                              const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_range_call(c, SHA_SETS[0], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
-                                 d_cap_helper, d_quot, hip_stream);
+                                 d_cap_helper, nullptr, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_sched_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
@@ -5143,7 +5170,7 @@ int32_t tmx_air_sha256_sched_quotient_range_device(tmx_ctx* c, uint32_t log_n, u
                                                    const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
                                                    uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_range_call(c, SHA_SETS[1], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
-                                 d_cap_helper, d_quot, hip_stream);
+                                 d_cap_helper, nullptr, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_init_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
@@ -5151,295 +5178,32 @@ int32_t tmx_air_sha256_init_quotient_range_device(tmx_ctx* c, uint32_t log_n, ui
                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
                                                   uint64_t* d_quot, void* hip_stream) {
   return sha_quotient_range_call(c, SHA_SETS[2], log_n, log_blowup, cap_height, n_proofs, chain, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols,
-                                 d_cap, d_cap_helper, d_quot, hip_stream);
+                                 d_cap, d_cap_helper, nullptr, d_quot, hip_stream);
 }
-
-}  // extern "C"
-
-// ---- constraint set 6: the SHA-256 tables' link to Level-1 (include/tmx.h).  A host path of its own beside sets 3 - 5: the same argument
-// checks but for the block count, set 3's geometry, a scratch of its own (words at d_air6):
-//   tables (air.h AIR6_TAB_*) | twiddles [K] | V of the prover [17][K][2] | V of the verifier | coefficients [2 K] | the public digest's
-//   levels, prover and verifier | one extended public polynomial (2 M) | PQ (2 M)
-// The challenge words are where set 1 keeps its own (d_air).
-constexpr uint64_t AIR6_K_MAX = 1ull << AIR_SHA_PUBLIC_MAX_LOG_K;
-constexpr uint64_t AIR6_OFF_TW = AIR6_TAB_WORDS, AIR6_OFF_VP = AIR6_OFF_TW + AIR6_K_MAX, AIR6_OFF_VV = AIR6_OFF_VP + 34 * AIR6_K_MAX,
-                   AIR6_OFF_COEF = AIR6_OFF_VV + 34 * AIR6_K_MAX, AIR6_OFF_LEVP = AIR6_OFF_COEF + 2 * AIR6_K_MAX,
-                   AIR6_OFF_LEVV = AIR6_OFF_LEVP + 8 * AIR6_K_MAX, AIR6_OFF_EXT = AIR6_OFF_LEVV + 8 * AIR6_K_MAX;
-
-static int32_t link_check(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t n_proofs) {
-  if (log_blowup < 1 || log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be 1 .. 6");
-  if (log_n <= log_blowup || log_n > 28) return fail(c, TMX_ERR_BAD_ARG, "log_n must exceed log_blowup and be at most 28");
-  if (log_n - log_blowup < 6 + AIR_SHA_PUBLIC_MIN_LOG_K || log_n - log_blowup > 6 + AIR_SHA_PUBLIC_MAX_LOG_K)
-    return fail(c, TMX_ERR_BAD_ARG, "log_n - log_blowup must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "33 n_proofs must be at most 2^24");
-  return TMX_OK;
-}
-
-// s, w the coset; om = omega_N = w^B, om_k = omega_K = om^64, om64 = omega_64 = om^K, k_inv = 1 / K
-struct LinkGeo { uint32_t log_k; uint64_t s, w, om, om_k, om64, k_inv; };
-static void link_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, uint64_t shift, LinkGeo& B) {
-  const uint64_t P = 0xffffffff00000001ull;
-  B.log_k = log_n - log_blowup - 6;
-  B.s = shift % P;
-  B.w = gl_pow_host(root_2_32, 1ull << (32 - log_n));
-  B.om = gl_pow_host(B.w, 1ull << log_blowup);
-  B.om_k = gl_pow_host(B.om, 64);
-  B.om64 = gl_pow_host(B.om, 1ull << B.log_k);
-  B.k_inv = gl_pow_host(1ull << B.log_k, P - 2);
-}
-
-// the set-6 scratch, for a coset of 2^log_m points (log_m = 0: the verifier, which extends nothing)
-static int32_t link_scratch(tmx_ctx* c, uint32_t log_m) {
-  const size_t want = (AIR6_OFF_EXT + (log_m ? (size_t)4 << log_m : 0)) * 8;
-  if (c->air6_bytes < want) {
-    if (c->d_air6) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air6)); c->d_air6 = nullptr; c->air6_bytes = 0; }
-    HIPCK(c, hipMalloc(&c->d_air6, want));
-    c->air6_bytes = want;
-  }
-  return TMX_OK;
-}
-
-// gamma of set 6: the public table's digest (its Poseidon Merkle root), then the lone-lane kernel over the two caps and the digest
-static int32_t link_gamma(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t log_k, const uint64_t* d_cap,
-                          const uint64_t* d_cap_helper, const uint64_t* d_pub, bool verifier, void* hip_stream) {
-  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air6) + (verifier ? AIR6_OFF_LEVV : AIR6_OFF_LEVP);
-  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_SHA_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, hip_stream);
-  if (st) return st;
-  const uint32_t obs[5] = {6 /* the constraint-set id */, log_n, log_blowup, cap_height, n_proofs};
-  uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air) + (verifier ? 32 + AIR_CHAL_WORDS : 0);
-  const int rc = launch_air_link_gamma(c->d_pos_consts, c->pos_mode, obs, 4u << std::min(cap_height, log_n), d_cap, d_cap_helper,
-                                       lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32, reinterpret_cast<hipStream_t>(hip_stream));
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_gamma launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
-}
-
-// PQ on the coset from the public table and the prover's gamma: V, then per coset the coefficients, the extension and its fold.  The
-// tables (first = 0) are written first: the fold reads 1 / S and 1 / D_t
-static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, const ShaGeo& A, const LinkGeo& B, uint32_t n_proofs, const uint64_t* d_pub,
-                           hipStream_t s) {
-  const uint64_t P = 0xffffffff00000001ull;
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
-  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
-  int rc = launch_air_link_tables(log_blowup, 0, A.s_n, A.w_n, A.s_sel, A.w_sel, B.om64, gamma, X, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, gamma, X + AIR6_OFF_VP, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_combine launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_public_twiddles(B.log_k, B.om_k, X + AIR6_OFF_TW, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_twiddles launch: ") + hipGetErrorString((hipError_t)rc));
-  uint64_t* ext = X + AIR6_OFF_EXT;
-  uint64_t* pq = ext + ((size_t)2 << log_m);
-  for (uint32_t k = 0; k < 17; k++) {
-    const uint32_t off = k ? k - 1 : 63;
-    const uint64_t off_inv = gl_pow_host(gl_pow_host(B.om, off), P - 2);
-    rc = launch_air_public_coefs(B.log_k, B.k_inv, off_inv, X + AIR6_OFF_VP + ((uint64_t)k << (B.log_k + 1)), X + AIR6_OFF_TW, X + AIR6_OFF_COEF, s);
-    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_coefs launch: ") + hipGetErrorString((hipError_t)rc));
-    rc = launch_air_public_extend(log_m, B.log_k, B.s, B.w, X + AIR6_OFF_COEF, X + AIR6_OFF_TW, ext, s);
-    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_public_extend launch: ") + hipGetErrorString((hipError_t)rc));
-    rc = launch_air_link_fold(log_m, log_blowup, k, k == 0, ext, X, pq, s);
-    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_fold launch: ") + hipGetErrorString((hipError_t)rc));
-  }
-  return TMX_OK;
-}
-
-// form as in sha_quotient_call; the piece with proof_lo = 0 carries - PQ
-static int32_t link_quotient_call(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t proof_lo,
-                                  uint32_t proof_hi, int form, const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
-                                  const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = link_check(c, log_n, log_blowup, n_proofs);
-  if (st) return st;
-  if (proof_lo >= proof_hi || proof_hi > n_proofs) return fail(c, TMX_ERR_BAD_ARG, "the proof range must be non-empty and lie within n_proofs");
-  if (!d_cols || !d_helper_cols || !d_cap || !d_cap_helper || !d_pub || !d_quot)
-    return fail(c, TMX_ERR_BAD_ARG, "d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub and d_quot must be set");
-  ShaGeo A;
-  if ((st = sha_geo(c, log_n, log_blowup, 0, c->ntt_root, c->ntt_shift, A))) return st;
-  LinkGeo B;
-  link_geo(log_n, log_blowup, c->ntt_root, c->ntt_shift, B);
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, log_blowup))) return st;
-  if ((st = link_scratch(c, log_n))) return st;
-  if ((st = link_gamma(c, log_n, log_blowup, cap_height, n_proofs, B.log_k, d_cap, d_cap_helper, d_pub, false, hip_stream))) return st;
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
-  const uint64_t* gamma = reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT;
-  if (proof_lo == 0 && (st = link_public(c, log_n, log_blowup, A, B, n_proofs, d_pub, s))) return st;
-  if (proof_lo != 0) {
-    const int rc = launch_air_link_tables(log_blowup, proof_lo, A.s_n, A.w_n, A.s_sel, A.w_sel, B.om64, gamma, X, s);
-    if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_tables launch: ") + hipGetErrorString((hipError_t)rc));
-  }
-  const int rc = launch_air_link_quotient(log_n, log_blowup, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_SHA_WIDTH) << log_n),
-                                          d_helper_cols, X, proof_lo == 0 ? X + AIR6_OFF_EXT + ((size_t)2 << log_n) : nullptr, form, d_quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_quotient launch: ") + hipGetErrorString((hipError_t)rc));
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  return TMX_OK;
-}
-
-// The set-level call of set 6 on a resident member: sha_set_call's resident path with the public table in gamma and in the pass.  The pair
-// goes behind every pair of sets 3 - 5 that follows the table (their calls, unchanged, insert in front of later members: every order ends
-// as table, H3, Q3, H4, Q4, H5, Q5, H6, Q6).  The scratch of the section is sets 3 - 5's layout with 33 columns per proof (row 3 of
-// d_set_sha); one extended public polynomial and PQ (4 M words) live in the context's set-6 scratch d_air6, not per section.
-static const ShaSet LINK_SET = {6, AIR_LINK_HELPER_COLS, false, TMX_TRACE_SHA256_LINK_HELPER, TMX_TRACE_SHA256_LINK_QUOTIENT, 3, "link", "link helper",
-                                "the commit set already holds the link helper and quotient of that section", "k_helper", "k_helper + 1",
-                                "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr};
-
-static int32_t link_set_call(tmx_ctx* c, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  const ShaSet& d = LINK_SET;
-  int32_t st = tmx_trace_commit_set_shape(c, nullptr, nullptr);
-  if (st) return st;
-  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
-  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
-  if (!d_pub || !d_cap_h || !d_cap_q) return fail(c, TMX_ERR_BAD_ARG, "d_pub, d_cap_h and d_cap_q must be set");
-  tmx_ctx::SetRec r = c->set;
-  uint32_t kt = r.n_oracles;
-  for (uint32_t k = 0; k < r.n_oracles; k++)
-    if (r.o[k].section == section) kt = k;
-  if (kt == r.n_oracles) return fail(c, TMX_ERR_BAD_ARG, "the commit set does not hold that section");
-  uint32_t at = kt + 1;
-  for (const ShaSet& lower : SHA_SETS)
-    if (at < r.n_oracles && r.o[at].section == lower.helper_section) at += 2;
-  if (at < r.n_oracles && r.o[at].section == d.helper_section) return fail(c, TMX_ERR_BAD_ARG, d.already);
-  const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
-  if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
-  if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
-  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
-  if ((st = link_check(c, log_m, r.log_blowup, n_proofs))) return st;
-  ShaGeo A;
-  if ((st = sha_geo(c, log_m, r.log_blowup, 0, r.root, r.shift, A))) return st;
-  LinkGeo B;
-  link_geo(log_m, r.log_blowup, r.root, r.shift, B);
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  if ((st = poseidon_ready(c, s))) return st;
-  c->air_valid = false;
-  if ((st = air_scratch(c, r.log_blowup))) return st;
-  if ((st = link_scratch(c, log_m))) return st;
-  const uint32_t n_hcols = n_proofs * d.helper_cols;
-  const uint64_t n_dig = tmx_poseidon_merkle_digests(log_m, h), n_cap = 1ull << h;
-  const ShaScratch SP = sha_scratch_plan(d, log_m, r.log_blowup, h, n_proofs, n_proofs);
-  void*& d_scratch = c->d_set_sha[d.scratch][slot];
-  size_t& scratch_bytes = c->set_sha_bytes[d.scratch][slot];
-  if (scratch_bytes < SP.want) {
-    if (d_scratch) { HIPCK(c, hipStreamSynchronize(s)); HIPCK(c, hipFree(d_scratch)); d_scratch = nullptr; scratch_bytes = 0; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && SP.want > free_b)
-      return fail(c, TMX_ERR_CAPACITY, "the link helper member needs " + std::to_string(SP.want >> 20) + " MiB of scratch, " +
-                                           std::to_string(free_b >> 20) + " MiB free");
-    HIPCK(c, hipMalloc(&d_scratch, SP.want));
-    scratch_bytes = SP.want;
-  }
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(c->d_set);
-  uint8_t* sb = reinterpret_cast<uint8_t*>(d_scratch);
-  uint64_t* hpre = reinterpret_cast<uint64_t*>(sb);
-  uint64_t* hext = reinterpret_cast<uint64_t*>(sb + SP.pre_b);
-  uint64_t* lev_h = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b);
-  uint64_t* quot = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b + SP.lev_b);
-  uint64_t* lev_q = reinterpret_cast<uint64_t*>(sb + SP.pre_b + SP.ext_b + SP.lev_b + SP.quot_b);
-  const uint64_t* lev_t = reinterpret_cast<const uint64_t*>(base + tabm.lev_off);
-  int rc = launch_air_link_helper(log_sub, n_proofs, base + tabm.cols_off, d_pub, hpre, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  // the helper extended under the set's domain, one proof's columns at a time (the LDE's own scratch is twice what it extends at once)
-  const uint64_t root = c->ntt_root, shift = c->ntt_shift;
-  const bool moved = root != r.root || shift != r.shift;
-  if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
-  for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += d.helper_cols)
-    st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, d.helper_cols, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
-  if (moved) {
-    const int32_t back = tmx_ntt_set_domain(c, root, shift);
-    if (!st) st = back;
-  }
-  if (st) return st;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, n_hcols, hext, h, lev_h, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_h, lev_h + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  if ((st = link_gamma(c, log_m, r.log_blowup, r.cap_height, n_proofs, B.log_k, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), d_pub, false,
-                       hip_stream)))
-    return st;
-  if ((st = link_public(c, log_m, r.log_blowup, A, B, n_proofs, d_pub, s))) return st;
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
-  rc = launch_air_link_quotient(log_m, r.log_blowup, n_proofs, base + tabm.lde_off, hext, X, X + AIR6_OFF_EXT + ((size_t)2 << log_m), AIR_FORM_WHOLE, quot, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_quotient launch: ") + hipGetErrorString((hipError_t)rc));
-  HIPCK(c, hipEventRecord(c->ev_air, s));
-  c->air_valid = true;
-  if ((st = tmx_poseidon_merkle_device(c, log_m, 2, quot, h, lev_q, hip_stream))) return st;
-  HIPCK(c, hipMemcpyAsync(d_cap_q, lev_q + 4 * (n_dig - n_cap), n_cap * 32, hipMemcpyDeviceToDevice, s));
-  for (uint32_t k = r.n_oracles + 1; k >= at + 2; k--) r.o[k] = r.o[k - 2];
-  r.o[at] = {d.helper_section, log_m, n_hcols, 0, SP.pre_b, SP.pre_b + SP.ext_b, false, false, sb};
-  r.o[at + 1] = {d.quotient_section, log_m, 2, 0, SP.pre_b + SP.ext_b + SP.lev_b, SP.pre_b + SP.ext_b + SP.lev_b + SP.quot_b, false, true, sb};
-  r.n_oracles += 2;
-  c->set = r;
-  return TMX_OK;
-}
-
-extern "C" {
 
 int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* c, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
                                                     void* hip_stream) {
-  return link_set_call(c, section, d_pub, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[3], section, 0, false, d_pub, d_cap_h, d_cap_q, hip_stream);
 }
 
 int32_t tmx_air_sha256_link_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
                                             const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
-  return link_quotient_call(c, log_n, log_blowup, cap_height, n_proofs, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub,
-                            d_quot, hip_stream);
+  return sha_quotient_call(c, SHA_SETS[3], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, d_pub, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_link_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
                                                   uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
                                                   const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  if (accumulate > 1) return fail(c, TMX_ERR_BAD_ARG, "accumulate must be 0 or 1");
-  return link_quotient_call(c, log_n, log_blowup, cap_height, n_proofs, proof_lo, proof_hi, accumulate ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE, d_cols,
-                            d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot, hip_stream);
+  return sha_quotient_range_call(c, SHA_SETS[3], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, d_pub, d_quot, hip_stream);
 }
 
 int32_t tmx_air_sha256_link_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
                                           const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  int32_t st = batch_check(c, p);
-  if (st) return st;
-  if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles)
-    return fail(c, TMX_ERR_BAD_ARG, "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof");
-  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
-  if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)AIR_LINK_HELPER_COLS * n_proofs)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper must be the helper: the log_n of oracle k_trace and 33 columns per proof");
-  if (p->log_n[k_helper + 1] != log_n || p->n_cols[k_helper + 1] != 2)
-    return fail(c, TMX_ERR_BAD_ARG, "oracle k_helper + 1 must be the quotient: the log_n of oracle k_trace and 2 columns");
-  if ((st = link_check(c, log_n, p->log_blowup, n_proofs))) return st;
-  if (!d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_pub is null");
-  ShaGeo A;
-  if ((st = sha_geo(c, log_n, p->log_blowup, 0, c->ntt_root, c->ntt_shift, A))) return st;
-  LinkGeo B;
-  link_geo(log_n, p->log_blowup, c->ntt_root, c->ntt_shift, B);
-  if (!d_caps || !d_proof || !d_ok) return fail(c, TMX_ERR_BAD_ARG, "d_caps, d_proof and d_ok must be set");
-  if ((st = air_scratch(c, p->log_blowup))) return st;
-  if ((st = link_scratch(c, 0))) return st;
-  if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  tmx_batch_layout L;
-  batch_layout(*p, L);
-  const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
-  // zeta as the batch transcript draws it, gamma from the two caps and the verifier's own digest of d_pub, V from d_pub, then the identity
-  uint64_t* V = reinterpret_cast<uint64_t*>(c->d_air) + 32 + AIR_CHAL_WORDS;
-  uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
-  int rc = launch_fri_transcript(c->d_pos_consts, c->pos_mode, G, 7, 0, d_caps, nullptr, V, V + 32, nullptr, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_fri_transcript launch: ") + hipGetErrorString((hipError_t)rc));
-  if ((st = link_gamma(c, log_n, p->log_blowup, p->cap_height, n_proofs, B.log_k, d_caps + G.o_cap_at[k_trace], d_caps + G.o_cap_at[k_helper], d_pub, true,
-                       hip_stream)))
-    return st;
-  rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, X + AIR6_OFF_VV, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_combine launch: ") + hipGetErrorString((hipError_t)rc));
-  rc = launch_air_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, B.om64, B.om, B.om_k, B.k_inv,
-                             d_proof + L.off_open[k_trace], d_proof + L.off_open[k_helper], d_proof + L.off_open[k_helper + 1], V + 32 + FRI_ZETA_AT,
-                             V + 32 + FRI_GAMMA_AT, X + AIR6_OFF_VV, p->n_queries, d_ok, s);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_check launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_verify_call(c, SHA_SETS[3], p, k_trace, k_helper, 0, d_caps, d_proof, d_pub, d_ok, hip_stream);
 }
 
 // ---- the public table of a SHA-256 table from element rows, and the helper oracle over it
@@ -5476,16 +5240,7 @@ int32_t tmx_air_sha256_public_device(tmx_ctx* c, int32_t kind, uint32_t section,
 
 int32_t tmx_air_sha256_link_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, const uint64_t* d_pub,
                                           uint64_t* d_helper, void* hip_stream) {
-  if (!c) return TMX_ERR_BAD_ARG;
-  if (log_rows < 6 + AIR_SHA_PUBLIC_MIN_LOG_K || log_rows > 6 + AIR_SHA_PUBLIC_MAX_LOG_K)
-    return fail(c, TMX_ERR_BAD_ARG, "log_rows must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows");
-  if (n_proofs < 1) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1");
-  if ((uint64_t)n_proofs * AIR_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "33 n_proofs must be at most 2^24");
-  if (!d_table || !d_pub || !d_helper) return fail(c, TMX_ERR_BAD_ARG, "d_table, d_pub and d_helper must be set");
-  HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = launch_air_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, hip_stream);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_link_helper launch: ") + hipGetErrorString((hipError_t)rc));
-  return TMX_OK;
+  return sha_helper_call(c, SHA_SETS[3], log_rows, n_proofs, 0, d_table, d_pub, d_helper, hip_stream);
 }
 
 uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
@@ -5503,7 +5258,7 @@ int32_t tmx_trace_commit_set_air_sha256_streamed_device(tmx_ctx* c, uint32_t con
                                                         uint64_t* d_cap_q, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   if (constraint_set < 3 || constraint_set > 5) return fail(c, TMX_ERR_BAD_ARG, "constraint_set must be 3, 4 or 5");
-  return sha_set_call(c, SHA_SETS[constraint_set - 3], section, chunk_proofs, true, d_cap_h, d_cap_q, hip_stream);
+  return sha_set_call(c, SHA_SETS[constraint_set - 3], section, chunk_proofs, true, nullptr, d_cap_h, d_cap_q, hip_stream);
 }
 
 uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* c, uint32_t constraint_set, uint32_t section) {

@@ -6,16 +6,19 @@ oracles satisfies all three device verifiers and all three model identities; a b
 third round equals the first word for word.  The buffers of an earlier table stay allocated while a later one is proved, so two
 (set, table) pairs that shared a buffer would show as a changed proof or a rejected query.  What the helpers, caps, gammas and quotients
 ARE is compared against the models in tests/test_sha_air.py, tests/test_sha_sched.py and tests/test_sha_init.py, whose plumbing this
-file uses."""
+file uses.  Row 3 of the same table, constraint set 6's (tmx_trace_commit_set_air_sha256_link_device), goes through the same three commits
+beside set 5 on a context of its own, under the public tables the device gathers (tests/test_sha_public.py)."""
 import numpy as np
 import pytest
 
 import batch_model as bm
 import sha_air_model as sm
 import sha_init_model as si
+import sha_public_model as sl
 import sha_sched_model as ss
 import test_sha_air as tsa
 import test_sha_init as tsi
+import test_sha_public as tsl
 import test_sha_sched as tss
 from test_fri import _down, _sentinel, _shift
 
@@ -81,3 +84,68 @@ def test_three_commits_per_table_on_one_context(shared, oracle, section):
     _round(c, oracle, tr, section, 2, "345")
     caps3, proof3 = _round(c, oracle, tr, section, 1, "453")
     assert np.array_equal(caps1, caps3) and np.array_equal(proof1, proof3)
+
+
+# ---- row 3 of the same scratch table: constraint set 6 (tmx_trace_commit_set_air_sha256_link_device), beside set 5
+H6, Q6 = 8192, 16384
+
+
+@pytest.fixture(scope="module")
+def linked(built_lib):
+    """one more context of the same shape with two proofs' element and trace rows, and the public tables the device gathers from the
+    element rows: {(section, n_proofs): (device table, host table)} (the one-proof table is that of the first proof)"""
+    import tendermintx_amd as tmx
+    with tmx.Context(N, tsl.CID, max_batch=MAX_BATCH) as c:
+        d_rows, tr = tsl._device_rows(c, KIND, N, MAX_BATCH, 9600)
+        pubs = {(sec, k): tsl._gather(c, KIND, sec, k, d_rows) for sec in (SHA256, TREE, HEADER) for k in (1, 2)}
+        yield c, tr, pubs
+
+
+def _round_6(c, oracle, tr, pubs, section, n_proofs, way):
+    """commit `section` alone, the calls of `way` ("5" and "6") in that order, one proof; set 6's part as _set_6_holds of
+    tests/test_sha_public_shapes.py has it; returns (set 6's two caps, its gamma)"""
+    import torch
+    cw = 4 << CAP_H
+    d_pub, pub = pubs[section, n_proofs]
+    calls = {"5": lambda h, q: c.trace_commit_set_air_sha256_init_device(section, h, q, 0),
+             "6": lambda h, q: c.trace_commit_set_air_sha256_link_device(section, d_pub.data_ptr(), h, q, 0)}
+    d_cap_t = _sentinel(cw)
+    c.trace_commit_set_device(KIND, n_proofs, section, LB, CAP_H, tr.data_ptr(), d_cap_t.data_ptr(), 0)
+    pair, gamma = {}, None
+    for s in way:
+        pair[s] = (_sentinel(cw), _sentinel(cw))
+        calls[s](pair[s][0].data_ptr(), pair[s][1].data_ptr())
+        if s == "6":
+            gamma = c.air_last_gamma()
+    shape, order = c.trace_commit_set_shape()
+    assert order == [section] + ([H5, Q5] if "5" in way else []) + [H6, Q6], (section, n_proofs, way)
+    k6 = order.index(H6)
+    assert shape["n_cols"][k6:] == [n_proofs * sl.HELPER_COLS, 2] and shape["log_n"] == [shape["log_n"][0]] * len(order)
+    p = dict(shape, arity_bits=2, final_log_max=2, n_queries=3, pow_bits=0)
+    proof = _down(tsa._guarded(bm.layout(p)["words"], lambda out: c.trace_commit_set_prove_device(p, out, 0)))
+    assert c.fri_last_degree_ok() is True
+    d_caps = torch.cat([d_cap_t] + [x for s in sorted(way) for x in pair[s]])
+    caps = _down(d_caps)
+    cap_h6, cap_q6 = caps[k6 * cw:(k6 + 1) * cw], caps[(k6 + 1) * cw:]
+    assert gamma == sl.gamma(oracle, p["log_n"][0], LB, CAP_H, n_proofs, caps[:cw], cap_h6, pub), (section, n_proofs, way)
+    batch = bm.verify(oracle, p, caps, proof, _shift())
+    assert tsa._verdicts(c, p, 0, d_caps, proof, batch_only=True) == [bool(x) for x in batch] and all(batch)
+    assert sl.identity(oracle, p, 0, k6, caps, proof, pub), (section, n_proofs, way)
+    assert tsl._verdicts(c, p, 0, k6, d_caps, proof, pub) == [True] * p["n_queries"], (section, n_proofs, way)
+    bad = tsi._bumped(proof, bm.layout(p)["off_open"][k6 + 1])
+    assert not any(tsl._verdicts(c, p, 0, k6, d_caps, bad, pub)), (section, n_proofs, way)
+    return cap_h6.copy(), cap_q6.copy(), gamma
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("section", [SHA256, TREE, HEADER])
+def test_three_commits_of_set_6_per_table_on_one_context(linked, oracle, section):
+    """one proof with the calls in the order 6, 5 (the row-3 buffer of this table is allocated); two proofs in the order 5, 6 (it grows);
+    one proof with set 6 alone (it is larger than needed and reused).  Every round's proof satisfies set 6's device verifier and the
+    model identity under the gathered public table and is rejected on a bumped quotient opening; set 6's two caps and gamma in the third
+    round equal the first round's word for word"""
+    c, tr, pubs = linked
+    first = _round_6(c, oracle, tr, pubs, section, 1, "65")
+    _round_6(c, oracle, tr, pubs, section, 2, "56")
+    third = _round_6(c, oracle, tr, pubs, section, 1, "6")
+    assert np.array_equal(first[0], third[0]) and np.array_equal(first[1], third[1]) and first[2] == third[2]
