@@ -1077,7 +1077,7 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d
  *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; row 0 of a block against the IV or
  *              the chaining value and the feed-forward between the two blocks of T.5 / T.6 hashes, which constraint set 5 below proves;
  *              the digest's link to Level-1, which constraint set 6 below proves; and, still open (the follow-ups): LIVE against anything
- *              public (set 6's flags); SHA-512.  Under set 3 ALONE a
+ *              public (set 6's flags); SHA-512 beyond its round function (constraint set 7 below).  Under set 3 ALONE a
  *              block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
  *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
@@ -1151,7 +1151,7 @@ int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, u
  *              and zero padding satisfy all 117 without a LIVE column.
  *   NOT PROVED by sets 3 and 4: row 0 of a block against the IV or the chaining value and the feed-forward between the two blocks of
  *              T.5 / T.6 hashes, which constraint set 5 below proves; the first sixteen W of a block against Level-1, which constraint
- *              set 6 below proves; and, still open (the follow-ups): LIVE against anything public (set 6's flags); SHA-512.  Under sets
+ *              set 6 below proves; and, still open (the follow-ups): LIVE against anything public (set 6's flags); SHA-512 beyond its round function (constraint set 7 below).  Under sets
  *              3 and 4 ALONE a block re-run consistently (schedule
  *              and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected (tests/test_sha_sched.py records it).
  *   challenge  as set 3 with the set id 4: a fresh duplex observes 2^33, then 4, log_n, log_blowup, cap_height, n_proofs, then the table cap,
@@ -1245,7 +1245,7 @@ int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* ctx, uint32_t sect
  *              multiplied by LV' and why PZ carries LV'.
  *   NOT PROVED by sets 3 + 4 + 5 (the follow-ups): the first sixteen W of a block against Level-1; the digest (IV or chaining value plus
  *              the state after the last round) against Level-1; LV against anything public -- a hash whose live second block is replaced
- *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512; the ladders' curve arithmetic
+ *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512 beyond its round function (constraint set 7 below); the ladders' curve arithmetic
  *              and limb ranges (tests/test_sha_init.py records the first and the third).  Constraint set 6 below ("the SHA-256 tables'
  *              link to Level-1") closes the first three: it pins the first sixteen W, the digest and the block structure to Level-1.
  *   challenge  set 3's lone-lane kernel: a fresh duplex observes 2^33, then 5 | chain << 8, log_n, log_blowup, cap_height, n_proofs, then the
@@ -1421,7 +1421,7 @@ uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* ctx, uint3
  *              own V63 and V^t, and evaluates the seventeen polynomials barycentrically, set 2's form with K <= 2^12 per coset:
  *              P_c(zeta) / D_c(zeta) = 1 / (K y_0^K) sum_k V_k y_k / (zeta - y_k).  A failed identity, or a zero denominator, clears
  *              every query's verdict.
- *   NOT PROVED by sets 3 + 4 + 5 + 6: LIVE / LV of sets 3 and 5 against set 6's public flags; SHA-512; the ladders' curve arithmetic and
+ *   NOT PROVED by sets 3 + 4 + 5 + 6: LIVE / LV of sets 3 and 5 against set 6's public flags; SHA-512 beyond its round function (constraint set 7 below); the ladders' curve arithmetic and
  *              limb ranges; a T.5 slot whose right child is not enabled (above); and there is no range argument for DG on chain rows --
  *              the identities are integer identities far below p and the digest is pinned to a public word below 2^32, so the digest is
  *              right mod 2^32 provided set 3 range-checks s_j.  TMX_BATCH_MAX_ORACLES stays 8: a section that already carries sets 3 + 4 + 5 has seven oracles
@@ -1495,6 +1495,100 @@ int32_t tmx_air_sha256_link_verify_device(tmx_ctx* ctx, const tmx_batch_params* 
                                           const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream);
 int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
                                                     void* hip_stream);
+
+/* ---- the round constraints of the SHA-512 table (constraint set 7) ----------------------------------------------------------------------
+ * Sets 3 - 6 argue about the three SHA-256 tables.  The fifth committed row table, T.2 (TMX_TRACE_SHA512), holds the SHA-512 rows of every
+ * lane's SHA-512(R || A || M), the hash that yields the scalar h of h A.  Set 7 proves the SHA-512 ROUND FUNCTION on it: the sibling of
+ * set 3, with the same machinery -- a helper oracle behind the table, one two-column quotient oracle behind the helper, the identity at
+ * zeta -- and no change to any existing kernel, transcript phase, proof word, call, refusal or scratch; the batch prover, its proof format
+ * and tmx_batch_verify_device are used UNCHANGED.  Same field, extension, duplex and caveats as the blocks above (PARITY UNPINNED).
+ *   table      18 n_proofs columns of 32-bit limbs; inside a proof W lo 0, W hi 1, a lo 2, a hi 3, ... h lo 16, h hi 17; row
+ *              (2 i + b) 80 + t holds W_t and the state after round t of block b of lane i (docs/level2_rows.md).  Of the N = 2^log_rows
+ *              rows the first 160 lanes are live or zero, the rest zero padding; N is never a multiple of 80.
+ *   preprocessed columns  A block is 80 rows, and no power-of-two subgroup has a coset structure of period 80: a selector x^(N/80) - c
+ *              does not exist.  Three PUBLIC columns that depend on N alone take its place, each a polynomial of degree <= N - 1:
+ *                SEL_r = 1, but 0 where r mod 80 = 79 and at r = N - 1 (the wrap row must be off: (N - 1) mod 80 != 79)
+ *                KLO_r, KHI_r = the low and the high 32 bits of K512[r mod 80], on every row r < N
+ *              The prover fills them (k_air_sha512_periodic) and extends them exactly as helper columns are extended.  The verifier
+ *              commits to nothing: it computes SEL(zeta), KLO(zeta), KHI(zeta) itself, barycentrically over the N rows,
+ *                P(zeta) = (zeta^N - 1) / N  sum_r v_r omega^r / (zeta - omega^r)
+ *              in a multi-workgroup kernel (k_air_sha512_periodic_eval, one batched inversion per four rows of a thread).  A zero
+ *              denominator clears every verdict.  This O(N) work bounds the rows set 7 accepts to log_rows 7 .. 18 (the full size is 15).
+ *   helper     599 columns per proof, the table's rows, bits LSB first, bit 32 limb + i in limb `limb`, bit indices mod 64:
+ *                0 .. 63  A      128 .. 191  C      256 .. 319  F      384 .. 447  U0_i = A_(i+28) xor A_(i+34)     512 .. 575  V_i = A_i B_i
+ *               64 .. 127 B      192 .. 255  E      320 .. 383  G      448 .. 511  U1_i = E_(i+14) xor E_(i+18)
+ *               576 / 577 Sigma0 lo / hi   578 / 579 Sigma1   580 / 581 Ch   582 / 583 Maj   584 LIVE   585 / 586 KL = LIVE K512[r mod 80]
+ *               587 .. 589 CAL   590 .. 592 CAH  (carry bits of the a update, low and high limb)   593 .. 595 CEL   596 .. 598 CEH  (e update)
+ *              LIVE = 1 iff row r - r mod 80 of the proof's table has a word whose low 32 bits are not zero.  Defined for ANY input: the
+ *              operands are the low 32 bits of each table word; carries are 0 where SEL = 0; elsewhere, primes from row r + 1,
+ *              CAL = ((h + Sigma1 + Ch + KL' + W' + Sigma0 + Maj)_lo >> 32) & 7, CAH the same over the high limbs plus the value of CAL;
+ *              CEL, CEH the same over d + h + Sigma1 + Ch + KL' + W'.  Seven summands: the a carries are <= 6; six: the e carries <= 5; every
+ *              identity is an integer identity below 2^35.
+ *   constraints  628 per proof, at index j; a prime is the value at omega x:
+ *                0 .. 383   X^2 - X for helper columns 0 .. 383          384 .. 395  X^2 - X for helper columns 587 .. 598
+ *              396          LIVE^2 - LIVE
+ *              397 .. 408   limb - sum_(i < 32) 2^i bit_(32 limb + i) for (a, A) lo, hi, then b, c, e, f, g
+ *              409 + i      U0_i - (A_(i+28) + A_(i+34) - 2 A_(i+28) A_(i+34))       473 + i   U1_i - (E_(i+14) + E_(i+18) - 2 E_(i+14) E_(i+18))
+ *              537 + i      V_i - A_i B_i
+ *              601 .. 608   Sigma0, Sigma1, Ch, Maj, lo then hi each, against sum 2^i of U0_j + A_(j+39) - 2 U0_j A_(j+39),
+ *                           U1_j + E_(j+41) - 2 U1_j E_(j+41), G_j + E_j (F_j - G_j), V_j + C_j (A_j + B_j - 2 V_j), j = 32 limb + i
+ *              609, 610     KL_lo - LIVE KLO(x), KL_hi - LIVE KHI(x)
+ *              611 .. 622   SEL(x) (b' - a), (c' - b), (d' - c), (f' - e), (g' - f), (h' - g), lo then hi each      623   SEL(x) (LIVE' - LIVE)
+ *              624          SEL(x) (a'_lo + 2^32 (CAL_0 + 2 CAL_1 + 4 CAL_2) - h_lo - Sigma1_lo - Ch_lo - KL'_lo - W'_lo - Sigma0_lo - Maj_lo)
+ *              625          the same over the high limbs with CAH, minus (CAL_0 + 2 CAL_1 + 4 CAL_2)
+ *              626, 627     the e update: d + h + Sigma1 + Ch + KL' + W', with CEL / CEH
+ *              Every nonlinear constraint has degree 2 in the columns and no selector, every selected one is SEL (linear), the K constraint
+ *              KL - LIVE K(x): every constraint has degree <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient
+ *              oracle still suffices.  Zero blocks and zero padding satisfy all 628 with LIVE = 0.
+ *   NOT PROVED by set 7: the message schedule (W_t for t >= 16); the IV and the feed-forward of the two blocks; W's limb range; the link of
+ *              message and digest to Level-1, and so of h; LIVE against anything public.  Under set 7 alone a block re-run consistently
+ *              from a changed W_t goes undetected (tests/test_sha512_air.py records it).
+ *   challenge  a fresh duplex, as set 3: observe 2^33, then the set id 7, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
+ *              the helper cap.  The preprocessed columns are a function of log_n - log_blowup and are not observed.
+ *   quotient   q(x_i) = sum_p sum_(j < 628) gamma^(628 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical as in set 1; pointwise.
+ *   identity   as set 3's, with SEL(zeta), KLO(zeta), KHI(zeta) from the barycentric kernel.  A failed identity clears every verdict.
+ *   tmx_air_sha512_helper_device        the helper (599 n_proofs columns at d_helper) from PRE-LDE table columns (18 n_proofs at d_table).
+ *                                       TMX_ERR_BAD_ARG: log_rows outside 7 .. 18, n_proofs = 0, 599 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_quotient_device      fills and extends the preprocessed columns under the context's CURRENT NTT domain, draws gamma from
+ *                                       d_cap and d_cap_helper, then the quotient of the EXTENDED columns into d_quot (2 << log_n words).
+ *                                       TMX_ERR_BAD_ARG: FRI's rules on log_n and log_blowup, log_n - log_blowup outside 7 .. 18,
+ *                                       n_proofs = 0, 599 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_quotient_range_device   set 3's range call: the piece [proof_lo, proof_hi), d_helper_cols that piece's own columns,
+ *                                       written or (accumulate = 1) added; also refused: an empty or overhanging range, accumulate > 1.
+ *   tmx_air_sha512_verify_device        tmx_batch_verify_device, the barycentric kernel, then the identity for the oracles k_trace (18 k
+ *                                       columns), k_trace + 1 (599 k) and k_trace + 2 (2).  TMX_ERR_BAD_ARG unless the column counts are these
+ *                                       and the three log_n equal (and the rules above).
+ *   tmx_trace_commit_set_air_sha512_device   set 3's set-level call for `section` = TMX_TRACE_SHA512, a RESIDENT member only: the pair goes
+ *                                       directly behind the table; tmx_trace_commit_set_shape reports TMX_TRACE_SHA512_HELPER and
+ *                                       TMX_TRACE_SHA512_QUOTIENT.  Refused: any other section, an absent or streamed section, a second
+ *                                       call on the section, a set with no room for two more oracles.
+ *   tmx_air_sha512_periodic_device      the three preprocessed columns on their own: 3 << log_rows words at d_pre and, extended under the
+ *                                       current NTT domain, 3 << (log_rows + log_blowup) words at d_ext (log_blowup = 0: d_pre alone).
+ *   tmx_air_sha512_periodic_eval_device d_out[0 .. 6) = SEL(zeta), KLO(zeta), KHI(zeta) for the two words at d_zeta, d_out[6] = 1 if a
+ *                                       denominator was zero (d_out: 7 words).  Both refuse log_rows outside 7 .. 18 and null pointers.
+ * Scratch: per section set 3's formula with 599 columns -- (599 n_proofs (N + M) + 2 M) 8 bytes plus two trees and the LDE scratch of 599
+ * columns -- and once per context (3 (N + M) + 512) 8 bytes for the preprocessed columns and the barycentric kernel's rows.  At 256 proofs,
+ * N = 2^15 and blow-up 8 the helper alone is 599 256 2^15 9 8 bytes, about 360 GB: it CANNOT be resident on one card.  The streamed call
+ * keeps refusing every constraint_set but 3, 4 and 5; a streamed form of this helper is a follow-up.  Every refusal comes before anything
+ * is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers the quotient calls and the set-level call. */
+#define TMX_AIR_SHA512_HELPER_COLS 599
+#define TMX_AIR_SHA512_CONSTRAINTS 628
+#define TMX_TRACE_SHA512_HELPER 32768u
+#define TMX_TRACE_SHA512_QUOTIENT 65536u
+int32_t tmx_air_sha512_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                     void* hip_stream);
+int32_t tmx_air_sha512_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                       const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                       uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                             const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                             void* hip_stream);
+int32_t tmx_air_sha512_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                                     uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha512_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+int32_t tmx_air_sha512_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
+int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

@@ -1891,4 +1891,387 @@ int launch_air_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_t
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 7: the round constraints of the SHA-512 table (include/tmx.h "the round constraints of the SHA-512 table") -------------
+// A sibling of set 3 on T.2: 64-bit words as lo / hi limbs, 80-row blocks.  No power-of-two subgroup fits 80 rows, so the selector and the
+// round constants are three preprocessed columns of full degree (SEL, KLO, KHI): the prover fills and extends them like helper columns, the
+// verifier evaluates them at zeta barycentrically over the N rows.  Nothing above changes.
+// Helper column offsets inside a proof's 599, table columns inside its 18 (the low limb; the high limb is the next one), constraint indices
+// inside its 628.
+constexpr uint32_t Q_A = 0, Q_B = 64, Q_C = 128, Q_E = 192, Q_F = 256, Q_G = 320, Q_U0 = 384, Q_U1 = 448, Q_V = 512, Q_S0 = 576, Q_S1 = 578,
+                   Q_CH = 580, Q_MAJ = 582, Q_LIVE = 584, Q_KL = 585, Q_CAL = 587, Q_CAH = 590, Q_CEL = 593, Q_CEH = 596;
+constexpr uint32_t R_W = 0, R_A = 2, R_B = 4, R_C = 6, R_D = 8, R_E = 10, R_F = 12, R_G = 14, R_H = 16;
+constexpr uint32_t JQ_CARRY = 384, JQ_LIVE = 396, JQ_WORD = 397, JQ_U0 = 409, JQ_U1 = 473, JQ_V = 537, JQ_S0 = 601, JQ_S1 = 603, JQ_CH = 605,
+                   JQ_MAJ = 607, JQ_KL = 609, JQ_SHIFT = 611, JQ_LIVEN = 623, JQ_NA = 624, JQ_NE = 626;
+constexpr uint32_t SHA512_BLOCK = 80;
+
+// SEL at row r of N: off on the last row of every block and on the wrap row N - 1 (N is no multiple of 80, so the latter is a row of its own)
+__device__ __forceinline__ bool sha512_sel(uint32_t r, uint32_t n) { return r % SHA512_BLOCK != SHA512_BLOCK - 1 && r != n - 1; }
+
+// One lane per row: the three preprocessed columns before the LDE, planar (3 << log_rows words)
+__global__ __launch_bounds__(256) void k_air_sha512_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
+  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= N) return;
+  const uint64_t k = K_SHA512[r % SHA512_BLOCK];
+  pre[r] = sha512_sel(r, N) ? 1 : 0;
+  pre[N + r] = (uint32_t)k;
+  pre[2 * (size_t)N + r] = k >> 32;
+}
+
+// One lane per (proof, row) of the pre-LDE table, k_air_sha_helper's shape: the eighteen limbs of the row, the block's first row (LIVE)
+// and W of the next row (the carries), then 599 stores, each of them consecutive words of one column across the wave.  Operands are the
+// low 32 bits of the words.  Where SEL = 1 the next row lies in the lane's own block, so KL' = LIVE K512[rnd + 1].
+__global__ __launch_bounds__(256) void k_air_sha512_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                           uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows), N = 1u << log_rows;
+  const uint32_t r = (uint32_t)(idx & (N - 1)), rnd = r % SHA512_BLOCK, r0 = r - rnd;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA512_WIDTH) << log_rows);
+  uint32_t w[AIR_SHA512_WIDTH], any = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < AIR_SHA512_WIDTH; c++) {
+    w[c] = (uint32_t)t[((uint64_t)c << log_rows) + r];
+    any |= (uint32_t)t[((uint64_t)c << log_rows) + r0];
+  }
+  const uint32_t live = any ? 1u : 0u;
+  auto word = [&](uint32_t c) { return (uint64_t)w[c] | (uint64_t)w[c + 1] << 32; };
+  const uint64_t a = word(R_A), b = word(R_B), c = word(R_C), e = word(R_E), f = word(R_F), g = word(R_G);
+  const uint64_t u0 = rotr64(a, 28) ^ rotr64(a, 34), u1 = rotr64(e, 14) ^ rotr64(e, 18), v = a & b;
+  const uint64_t s0 = u0 ^ rotr64(a, 39), s1 = u1 ^ rotr64(e, 41);
+  const uint64_t chv = (e & f) ^ (~e & g), mjv = (a & b) ^ (a & c) ^ (b & c);
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA512_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 64; i++) {
+    put(Q_A + i, (a >> i) & 1);
+    put(Q_B + i, (b >> i) & 1);
+    put(Q_C + i, (c >> i) & 1);
+    put(Q_E + i, (e >> i) & 1);
+    put(Q_F + i, (f >> i) & 1);
+    put(Q_G + i, (g >> i) & 1);
+    put(Q_U0 + i, (u0 >> i) & 1);
+    put(Q_U1 + i, (u1 >> i) & 1);
+    put(Q_V + i, (v >> i) & 1);
+  }
+  auto put2 = [&](uint32_t col, uint64_t x) {
+    put(col, (uint32_t)x);
+    put(col + 1, x >> 32);
+  };
+  put2(Q_S0, s0);
+  put2(Q_S1, s1);
+  put2(Q_CH, chv);
+  put2(Q_MAJ, mjv);
+  put(Q_LIVE, live);
+  put2(Q_KL, live ? K_SHA512[rnd] : 0);
+  uint32_t cal = 0, cah = 0, cel = 0, ceh = 0;
+  if (sha512_sel(r, N)) {
+    const uint64_t kn = live ? K_SHA512[rnd + 1] : 0;
+    const uint32_t wn_lo = (uint32_t)t[((uint64_t)R_W << log_rows) + r + 1], wn_hi = (uint32_t)t[((uint64_t)(R_W + 1) << log_rows) + r + 1];
+    const uint64_t t1_lo = (uint64_t)w[R_H] + (uint32_t)s1 + (uint32_t)chv + (uint32_t)kn + wn_lo;
+    const uint64_t t1_hi = (uint64_t)w[R_H + 1] + (s1 >> 32) + (chv >> 32) + (kn >> 32) + wn_hi;
+    cal = (uint32_t)((t1_lo + (uint32_t)s0 + (uint32_t)mjv) >> 32) & 7;
+    cah = (uint32_t)((t1_hi + (s0 >> 32) + (mjv >> 32) + cal) >> 32) & 7;
+    cel = (uint32_t)((t1_lo + w[R_D]) >> 32) & 7;
+    ceh = (uint32_t)((t1_hi + w[R_D + 1] + cel) >> 32) & 7;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 3; k++) {
+    put(Q_CAL + k, (cal >> k) & 1);
+    put(Q_CAH + k, (cah >> k) & 1);
+    put(Q_CEL + k, (cel >> k) & 1);
+    put(Q_CEH + k, (ceh >> k) & 1);
+  }
+}
+
+// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^628, gamma^(628 first); the selector and the round constants
+// are columns, not tables
+__global__ __launch_bounds__(256) void k_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
+                                                           const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_CONSTRAINTS, tab + AIR7_TAB_ZINV, tab + AIR7_TAB_GPOW);
+}
+
+// The 628 constraints of one proof at one point; klo and khi are KLO and KHI at the point.  The bit loop is set 3's (air_round_bits) per
+// 32-bit limb, the high limb first, with the rotations of SHA-512 taken mod 64 across both limbs: per bit index the nine bit words and the
+// six rotated ones (A_(i+28), A_(i+34), A_(i+39), E_(i+14), E_(i+18), E_(i+41)), re-read through the cache; nine constraints and one Horner
+// step by 2 of the ten word sums.  The ten sums of a limb go into its word constraints before the other limb starts, so no more than ten
+// are ever live.  Behind the loops the words are read again for the two-limb updates; the thirteen selected constraints go to a gamma sum
+// of their own: SEL(x) is factored out of it, the kernel applies it once.
+template <class F, class View>
+__device__ __forceinline__ void air_sha512_constraints(View& at, typename F::T klo, typename F::T khi) {
+  using A = Forms<F>;
+  using T = typename F::T;
+#pragma unroll 1
+  for (uint32_t l = 2; l-- > 0;) {
+    RoundWords<F> w = {F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero()};
+#pragma unroll View::BITS
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint32_t i = 32 * l + b;
+      const T A_ = at.again(Q_A + i), B = at.once(Q_B + i), C = at.once(Q_C + i), E = at.again(Q_E + i), F_ = at.once(Q_F + i), G = at.once(Q_G + i);
+      const T U0 = at.once(Q_U0 + i), U1 = at.once(Q_U1 + i), V = at.once(Q_V + i);
+      const T A28 = at.again(Q_A + ((i + 28) & 63)), A34 = at.again(Q_A + ((i + 34) & 63)), A39 = at.again(Q_A + ((i + 39) & 63));
+      const T E14 = at.again(Q_E + ((i + 14) & 63)), E18 = at.again(Q_E + ((i + 18) & 63)), E41 = at.again(Q_E + ((i + 41) & 63));
+      at.plain(Q_A + i, A::boolean(A_));
+      at.plain(Q_B + i, A::boolean(B));
+      at.plain(Q_C + i, A::boolean(C));
+      at.plain(Q_E + i, A::boolean(E));
+      at.plain(Q_F + i, A::boolean(F_));
+      at.plain(Q_G + i, A::boolean(G));
+      at.plain(JQ_U0 + i, A::sub(U0, A::exor(A28, A34)));
+      at.plain(JQ_U1 + i, A::sub(U1, A::exor(E14, E18)));
+      at.plain(JQ_V + i, A::sub(V, A::mul(A_, B)));
+      w.a = A::dbl_add(w.a, A_);
+      w.b = A::dbl_add(w.b, B);
+      w.c = A::dbl_add(w.c, C);
+      w.e = A::dbl_add(w.e, E);
+      w.f = A::dbl_add(w.f, F_);
+      w.g = A::dbl_add(w.g, G);
+      w.s0 = A::dbl_add(w.s0, A::exor(U0, A39));
+      w.s1 = A::dbl_add(w.s1, A::exor(U1, E41));
+      w.ch = A::dbl_add(w.ch, A::add(G, A::mul(E, A::sub(F_, G))));
+      w.maj = A::dbl_add(w.maj, A::add(V, A::mul(C, A::sub(A::add(A_, B), A::add(V, V)))));
+    }
+    at.plain(JQ_WORD + 0 + l, A::sub(at.tbl(R_A + l), w.a));
+    at.plain(JQ_WORD + 2 + l, A::sub(at.tbl(R_B + l), w.b));
+    at.plain(JQ_WORD + 4 + l, A::sub(at.tbl(R_C + l), w.c));
+    at.plain(JQ_WORD + 6 + l, A::sub(at.tbl(R_E + l), w.e));
+    at.plain(JQ_WORD + 8 + l, A::sub(at.tbl(R_F + l), w.f));
+    at.plain(JQ_WORD + 10 + l, A::sub(at.tbl(R_G + l), w.g));
+    at.plain(JQ_S0 + l, A::sub(at.again(Q_S0 + l), w.s0));
+    at.plain(JQ_S1 + l, A::sub(at.again(Q_S1 + l), w.s1));
+    at.plain(JQ_CH + l, A::sub(at.again(Q_CH + l), w.ch));
+    at.plain(JQ_MAJ + l, A::sub(at.again(Q_MAJ + l), w.maj));
+  }
+  const T LIVE = at.again(Q_LIVE);
+  at.plain(JQ_LIVE, A::boolean(LIVE));
+  at.plain(JQ_KL, A::sub(at.again(Q_KL), A::mul(LIVE, klo)));
+  at.plain(JQ_KL + 1, A::sub(at.again(Q_KL + 1), A::mul(LIVE, khi)));
+  at.selected(JQ_LIVEN, A::sub(at.next(Q_LIVE), LIVE));
+  T carry[4];  // the values CAL, CAH, CEL, CEH (both loops in full under either view: carry stays in registers)
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    const T x0 = at.once(Q_CAL + 3 * k), x1 = at.once(Q_CAL + 3 * k + 1), x2 = at.once(Q_CAL + 3 * k + 2);
+    at.plain(JQ_CARRY + 3 * k, A::boolean(x0));
+    at.plain(JQ_CARRY + 3 * k + 1, A::boolean(x1));
+    at.plain(JQ_CARRY + 3 * k + 2, A::boolean(x2));
+    carry[k] = A::add(x0, A::add(A::add(x1, x1), A::scale(x2, 4)));
+  }
+#pragma unroll
+  for (uint32_t l = 0; l < 2; l++) {
+    const T ta = at.tbl(R_A + l), tb = at.tbl(R_B + l), tc = at.tbl(R_C + l), td = at.tbl(R_D + l), te = at.tbl(R_E + l), tf = at.tbl(R_F + l),
+            tg = at.tbl(R_G + l), th = at.tbl(R_H + l);
+    at.selected(JQ_SHIFT + 0 + l, A::sub(at.tbl_next(R_B + l), ta));
+    at.selected(JQ_SHIFT + 2 + l, A::sub(at.tbl_next(R_C + l), tb));
+    at.selected(JQ_SHIFT + 4 + l, A::sub(at.tbl_next(R_D + l), tc));
+    at.selected(JQ_SHIFT + 6 + l, A::sub(at.tbl_next(R_F + l), te));
+    at.selected(JQ_SHIFT + 8 + l, A::sub(at.tbl_next(R_G + l), tf));
+    at.selected(JQ_SHIFT + 10 + l, A::sub(at.tbl_next(R_H + l), tg));
+    const T t1 = A::add(A::add(A::add(th, at.again(Q_S1 + l)), A::add(at.again(Q_CH + l), at.next(Q_KL + l))), at.tbl_next(R_W + l));
+    T na = A::sub(A::add(at.tbl_next(R_A + l), A::scale(carry[l], 1ull << 32)), A::add(t1, A::add(at.again(Q_S0 + l), at.again(Q_MAJ + l))));
+    T ne = A::sub(A::add(at.tbl_next(R_E + l), A::scale(carry[2 + l], 1ull << 32)), A::add(td, t1));
+    if (l) {  // the carry out of the low limb comes in
+      na = A::sub(na, carry[0]);
+      ne = A::sub(ne, carry[2]);
+    }
+    at.selected(JQ_NA + l, na);
+    at.selected(JQ_NE + l, ne);
+  }
+}
+
+// The set-7 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^628), the eighteen table columns and the 599 helper columns read once from HBM.  pre: the three extended preprocessed planes (SEL,
+// KLO, KHI; 3 << log_m words), one word each per lane.  Per proof  v = a + SEL(x) b; at the end 1 / (x^N - 1).  FORM as in set 3.
+template <int FORM>
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                     const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                     const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
+                                                                     uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR7_TAB_GPOW;
+  const uint64_t sel = gl_canon(pre[i]), klo = gl_canon(pre[M + i]), khi = gl_canon(pre[2 * M + i]);
+  const uint64_t zinv = tab[AIR7_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g628 = {gp[2 * AIR_SHA512_CONSTRAINTS], gp[2 * AIR_SHA512_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_sha512_constraints<FieldP>(at, klo, khi);
+    const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sel, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sel, at.b1))};
+    t = gl2_add(gl2_mul(t, g628), v);
+  }
+  gl2 q = gl2_scale(t, zinv);
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
+  out[i] = q.c0;
+  out[M + i] = q.c1;
+}
+
+// The three preprocessed columns at zeta, barycentric over the N rows: P(zeta) = (zeta^N - 1) / N  sum_r v_r omega^r / (zeta - omega^r).
+// Several workgroups; thread g of T takes the rows g, g + T, ... four at a time, inverting its four zeta - omega^r with one F_p^2 inversion
+// (prefix products, one Fermat chain, back-substitution); v_r comes from r itself (SEL, K512[r mod 80]).  A workgroup's three sums meet in
+// LDS and go to its row of `part`: [6] words of sums, then 1 if a denominator was zero (such a term is left out).  air_sha512_periodic_at
+// folds the rows.
+constexpr int AIR7_EVAL_PER = 4;
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
+                                                                                 uint64_t* __restrict__ part) {
+  __shared__ uint64_t red[6][AIR_CHECK_THREADS];
+  __shared__ uint32_t bad;
+  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
+  const uint64_t stride = gl_pow(om, T);
+  uint64_t y = gl_pow(om, g);
+  gl2 ssel = {0, 0}, sklo = {0, 0}, skhi = {0, 0};
+  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
+    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
+    uint64_t yk[AIR7_EVAL_PER];
+    gl2 run = {1, 0};
+#pragma unroll
+    for (int m = 0; m < AIR7_EVAL_PER; m++) {
+      const bool in = r0 + m * T < N;
+      yk[m] = y;
+      den[m] = {gl_sub(z.c0, y), z.c1};
+      pre[m] = run;
+      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
+        bad = 1;
+        den[m] = {1, 0};
+      }
+      if (in) run = gl2_mul(run, den[m]);
+      y = gl_mul(y, stride);
+    }
+    gl2 inv = gl2_inv(run);
+#pragma unroll
+    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
+      const uint32_t r = r0 + m * T;
+      if (r < N) {
+        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
+        inv = gl2_mul(inv, den[m]);
+        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
+        const uint64_t k = K_SHA512[r % SHA512_BLOCK];
+        if (sha512_sel(r, N)) ssel = gl2_add(ssel, term);
+        sklo = gl2_add(sklo, gl2_scale(term, (uint32_t)k));
+        skhi = gl2_add(skhi, gl2_scale(term, k >> 32));
+      }
+    }
+  }
+  const uint32_t t = threadIdx.x;
+  red[0][t] = ssel.c0, red[1][t] = ssel.c1, red[2][t] = sklo.c0, red[3][t] = sklo.c1, red[4][t] = skhi.c0, red[5][t] = skhi.c1;
+  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h)
+      for (uint32_t k = 0; k < 6; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+  }
+  __syncthreads();
+  if (t < 6) part[(size_t)blockIdx.x * AIR7_PART_WORDS + t] = red[t][0];
+  if (t == 6) part[(size_t)blockIdx.x * AIR7_PART_WORDS + 6] = bad;
+}
+
+// SEL(zeta), KLO(zeta), KHI(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
+__device__ __forceinline__ bool air_sha512_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2 v[3]) {
+  uint64_t s[6] = {0, 0, 0, 0, 0, 0}, bad = 0;
+  for (uint32_t k = 0; k < n_parts; k++) {
+    for (uint32_t j = 0; j < 6; j++) s[j] = gl_add(s[j], part[(size_t)k * AIR7_PART_WORDS + j]);
+    bad |= part[(size_t)k * AIR7_PART_WORDS + 6];
+  }
+  const gl2 lead = gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv);
+  for (uint32_t j = 0; j < 3; j++) v[j] = gl2_mul(lead, {s[2 * j], s[2 * j + 1]});
+  return bad == 0;
+}
+
+// One thread: the three values (six words), then 1 if a denominator was zero, at out[0 .. 7)
+__global__ void k_air_sha512_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                           const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
+  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v[3];
+  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_periodic_at(part, n_parts, zn, n_inv, v);
+  for (uint32_t j = 0; j < 3; j++) {
+    out[2 * j] = v[j].c0;
+    out[2 * j + 1] = v[j].c1;
+  }
+  out[6] = fine ? 0 : 1;
+}
+
+// The set-7 identity at zeta, one workgroup: gamma^0 .. gamma^628 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
+// their 628 constraints over F_p^2 from the table's and the helper's openings, with SEL, KLO and KHI at zeta from the barycentric kernel's
+// rows.  A proof contributes gamma^(628 p) (a + SEL(zeta) b); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero denominator in
+// the barycentric sums clears every verdict.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                         uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                                         const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
+                                                                         const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
+                                                                         const uint64_t* __restrict__ gamma, uint32_t n_queries,
+                                                                         uint32_t* __restrict__ ok) {
+  __shared__ uint64_t gpw[2 * (AIR_SHA512_CONSTRAINTS + 1)];
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_SHA512_CONSTRAINTS, gpw);
+  __syncthreads();
+  gl2 zn = {zeta[0], zeta[1]}, pv[3];
+  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_periodic_at(part, n_parts, zn, n_inv, pv);
+  gl2 sum = {0, 0};
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_sha512_constraints<FieldP2>(at, pv[1], pv[2]);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_CONSTRAINTS * p), gl2_add(at.a, gl2_mul(pv[0], at.b))));
+  }
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
+  if (!fine)
+    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_sha512_periodic(uint32_t log_rows, void* d_pre, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows, reinterpret_cast<uint64_t*>(d_pre));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sha512_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
+  // (three workgroups: the 630 gamma powers; 2^log_blowup <= 64 inverses)
+  hipLaunchKernelGGL(k_air_sha512_tables, dim3((AIR_SHA512_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n,
+                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
+                               const void* d_tab, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* pre = reinterpret_cast<const uint64_t*>(d_pre);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
+                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                            const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                            uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
+                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
+                     reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
+                     reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx

@@ -468,14 +468,18 @@ struct tmx_ctx {
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
   // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
-  void* d_set_sha[4][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6)
-  size_t set_sha_bytes[4][3] = {};
+  void* d_set_sha[5][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; row 4: set 7, whose one section uses slot 0)
+  size_t set_sha_bytes[5][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
   size_t air2_bytes = 0;
   void* d_air6 = nullptr;  // constraint set 6's caller-level scratch (AIR6_OFF_*)
   size_t air6_bytes = 0;
+  // constraint set 7 (tmx_air_sha512_*): the barycentric kernel's rows (prover-free: the verifier's) | SEL, KLO, KHI before the LDE (3 N)
+  // | the three extended planes (3 M: the part that grows)
+  void* d_air7 = nullptr;
+  size_t air7_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1474,6 +1478,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_air) (void)hipFree(c->d_air);
   if (c->d_air2) (void)hipFree(c->d_air2);
   if (c->d_air6) (void)hipFree(c->d_air6);
+  if (c->d_air7) (void)hipFree(c->d_air7);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -4582,6 +4587,10 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // for the others, and does its public step at four places, each a branch on has_public: gamma observes the table's digest (sha_gamma), the
 // pass writes its tables to d_air6 and the piece that starts at proof 0 carries - PQ (sha_pass), the verifier forms V before its check
 // (sha_verify_call), and the helper kernel reads d_pub (sha_helper_launch).  Its helper is resident only: the streamed calls take sets 3 - 5.
+// Set 7 (the SHA-512 table: 18 columns per proof, 80-row blocks) is the fifth row.  Where it differs is a branch on has_periodic: the pass
+// reads the three extended preprocessed planes of d_air7 instead of period-64 tables (sha_pass; sha512_periodic fills and extends them in
+// front of it), the verifier runs the barycentric kernel in front of its check (sha_verify_call), and the set-level call takes
+// TMX_TRACE_SHA512 alone.  Rows 3 - 6 take none of these branches: they enqueue what they enqueued before the row existed.
 struct ShaSet {
   uint32_t id, helper_cols;
   bool has_chain, has_public;
@@ -4598,6 +4607,8 @@ struct ShaSet {
                   const void* d_tab, int form, void* d_quot, void* stream);
   int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho, const void* d_open_t,
                const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
+  uint32_t width;     // the table's columns per proof
+  bool has_periodic;  // set 7: preprocessed columns of full degree in place of the period-64 tables
 };
 
 static int sha3_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
@@ -4633,25 +4644,34 @@ static int sha4_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uin
   return launch_air_sched_check(n_proofs, log_r_t, log_r_h, log_sub, om64_inv, d_open_t, d_open_h, d_open_q, d_zeta, d_gamma, n_queries, d_ok, stream);
 }
 
+static int sha7_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
+  return launch_air_sha512_helper(log_rows, n_proofs, d_table, d_helper, stream);
+}
+
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
 static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
 static const char SHA_BAD_ROWS[] = "log_rows must be 6 .. 27: a SHA-256 block is 64 rows";
-static const ShaSet SHA_SETS[4] = {
+static const ShaSet SHA_SETS[5] = {
     {3, AIR_SHA_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, SHA_BAD_SUB, SHA_BAD_ROWS, "sha", "helper",
      "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
-     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check},
+     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check, AIR_SHA_WIDTH, false},
     {4, AIR_SCHED_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_SCHED_HELPER, TMX_TRACE_SHA256_SCHED_QUOTIENT, 1, SHA_BAD_SUB, SHA_BAD_ROWS,
      "sched", "schedule helper", "the commit set already holds the schedule helper and quotient of that section", "k_helper", "k_helper + 1",
-     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check},
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check, AIR_SHA_WIDTH, false},
     {5, AIR_INIT_HELPER_COLS, true, false, 6, 27, TMX_TRACE_SHA256_INIT_HELPER, TMX_TRACE_SHA256_INIT_QUOTIENT, 2, SHA_BAD_SUB, SHA_BAD_ROWS, "init",
      "block-start helper", "the commit set already holds the block-start helper and quotient of that section", "k_helper", "k_helper + 1",
      "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", launch_air_init_helper, launch_air_init_tables,
-     launch_air_init_quotient, launch_air_init_check},
+     launch_air_init_quotient, launch_air_init_check, AIR_SHA_WIDTH, false},
     {6, AIR_LINK_HELPER_COLS, false, true, 6 + AIR_SHA_PUBLIC_MIN_LOG_K, 6 + AIR_SHA_PUBLIC_MAX_LOG_K, TMX_TRACE_SHA256_LINK_HELPER,
      TMX_TRACE_SHA256_LINK_QUOTIENT, 3, "log_n - log_blowup must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows",
      "log_rows must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows", "link", "link helper",
      "the commit set already holds the link helper and quotient of that section", "k_helper", "k_helper + 1",
-     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr},
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr, AIR_SHA_WIDTH, false},
+    {7, AIR_SHA512_HELPER_COLS, false, false, 7, 18, TMX_TRACE_SHA512_HELPER, TMX_TRACE_SHA512_QUOTIENT, 4,
+     "log_n - log_blowup must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them",
+     "log_rows must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them", "sha512",
+     "SHA-512 helper", "the commit set already holds the SHA-512 helper and quotient of that section", "k_trace + 1", "k_trace + 2",
+     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha7_helper, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true},
 };
 
 static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
@@ -4752,6 +4772,34 @@ static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, cons
   return TMX_OK;
 }
 
+// What set 7 has of its own inside that path: the preprocessed columns.  A scratch of its own (words at d_air7): the barycentric kernel's
+// rows | SEL, KLO, KHI before the LDE [3][N] | the three extended planes [3][M].  One per context, not per section.
+constexpr uint64_t AIR7_OFF_PRE = (uint64_t)AIR7_MAX_PARTS * AIR7_PART_WORDS;
+
+// the set-7 scratch, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
+static int32_t sha512_scratch(tmx_ctx* c, uint32_t log_m, uint32_t log_sub) {
+  const size_t want = (AIR7_OFF_PRE + (log_m ? ((size_t)3 << log_sub) + ((size_t)3 << log_m) : 0)) * 8;
+  if (c->air7_bytes < want) {
+    if (c->d_air7) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air7)); c->d_air7 = nullptr; c->air7_bytes = 0; }
+    HIPCK(c, hipMalloc(&c->d_air7, want));
+    c->air7_bytes = want;
+  }
+  return TMX_OK;
+}
+static const uint64_t* sha512_planes(const tmx_ctx* c, uint32_t log_sub) {
+  return reinterpret_cast<const uint64_t*>(c->d_air7) + AIR7_OFF_PRE + ((size_t)3 << log_sub);
+}
+
+// SEL, KLO and KHI filled and extended exactly as helper columns are: under the context's current NTT domain (the set-level call has put
+// the set's domain there)
+static int32_t sha512_periodic(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, void* hip_stream) {
+  const uint32_t log_sub = log_m - log_blowup;
+  uint64_t* pre = reinterpret_cast<uint64_t*>(c->d_air7) + AIR7_OFF_PRE;
+  const int rc = launch_air_sha512_periodic(log_sub, pre, hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha512_periodic launch: ") + hipGetErrorString((hipError_t)rc));
+  return tmx_lde_goldilocks_device(c, log_sub, log_blowup, 3, pre, pre + ((size_t)3 << log_sub), hip_stream);
+}
+
 // gamma from the table cap and the helper cap, into the prover's (verifier = false) or the verifier's challenge words of d_air.  A set with
 // a public table: the table's digest (its Poseidon Merkle root) first, then the lone-lane kernel over the two caps and the digest
 static int32_t sha_gamma(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t chain,
@@ -4792,6 +4840,10 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
     }
     rc = launch_air_link_quotient(log_n, log_blowup, n_proofs, cols, hcols, X, first == 0 ? X + AIR6_OFF_EXT + ((size_t)2 << log_n) : nullptr, form,
                                   d_quot, s);
+  } else if (d.has_periodic) {  // the extended planes (sha512_periodic, in front of this call) instead of the period-64 tables
+    uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
+    if ((rc = launch_air_sha512_tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
+    rc = launch_air_sha512_quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, log_n - log_blowup), tab, form, d_quot, s);
   } else {
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
     if ((rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s)))
@@ -4845,8 +4897,9 @@ static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, ui
   c->air_valid = false;
   if ((st = air_scratch(c, log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, log_n))) return st;
+  if (d.has_periodic && ((st = sha512_scratch(c, log_n, log_n - log_blowup)) || (st = sha512_periodic(c, log_n, log_blowup, hip_stream)))) return st;
   if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, d_pub, false, s))) return st;
-  if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * AIR_SHA_WIDTH) << log_n),
+  if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * d.width) << log_n),
                      d_helper_cols, d_pub, n_proofs, form, d_quot, s)))
     return st;
   HIPCK(c, hipEventRecord(c->ev_air, s));
@@ -4870,8 +4923,9 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   int32_t st = batch_check(c, p);
   if (st) return st;
   if (k_helper <= k_trace || (uint64_t)k_helper + 1 >= p->n_oracles) return fail(c, TMX_ERR_BAD_ARG, d.bad_index);
-  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % AIR_SHA_WIDTH) return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of 9 columns");
-  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / AIR_SHA_WIDTH;
+  if (p->n_cols[k_trace] == 0 || p->n_cols[k_trace] % d.width)
+    return fail(c, TMX_ERR_BAD_ARG, "oracle k_trace must have a multiple of " + std::to_string(d.width) + " columns");
+  const uint32_t log_n = p->log_n[k_trace], n_proofs = p->n_cols[k_trace] / d.width;
   if (p->log_n[k_helper] != log_n || (uint64_t)p->n_cols[k_helper] != (uint64_t)d.helper_cols * n_proofs)
     return fail(c, TMX_ERR_BAD_ARG, std::string("oracle ") + d.at_helper + " must be the helper: the log_n of oracle k_trace and " +
                                         std::to_string(d.helper_cols) + " columns per proof");
@@ -4885,6 +4939,7 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   if ((st = air_scratch(c, p->log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, 0))) return st;
+  if (d.has_periodic && (st = sha512_scratch(c, 0, 0))) return st;
   tmx_batch_layout L;
   batch_layout(*p, L);
   const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
@@ -4904,6 +4959,13 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
     if (rc) return sha_launch_failed(c, d, "combine", rc);
     rc = launch_air_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, B.om64, B.om, B.om_k, B.k_inv, open_t, open_h,
                                open_q, V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, vv, p->n_queries, d_ok, s);
+  } else if (d.has_periodic) {  // the barycentric kernel in front of the check: SEL, KLO, KHI at zeta over the N rows
+    const uint32_t log_sub = log_n - p->log_blowup;
+    const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_sub)), n_inv = gl_pow_host(1ull << log_sub, P - 2);
+    rc = launch_air_sha512_periodic_eval(log_sub, om, V + 32 + FRI_ZETA_AT, c->d_air7, s);
+    if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
+    rc = launch_air_sha512_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, c->d_air7, open_t, open_h, open_q,
+                                 V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
   } else {
     rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
                  V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
@@ -4951,8 +5013,10 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   if (st) return st;
   if (by_chunks)
     if (const char* why = sha_chunk_refusal(d, chunk_proofs)) return fail(c, TMX_ERR_BAD_ARG, why);
-  const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
-  if (slot < 0) return fail(c, TMX_ERR_BAD_ARG, "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
+  const int slot = d.has_periodic ? (section == TMX_TRACE_SHA512 ? 0 : -1)
+                                  : section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
+  if (slot < 0)
+    return fail(c, TMX_ERR_BAD_ARG, d.has_periodic ? "section must be TMX_TRACE_SHA512" : "section must be TMX_TRACE_SHA256, TMX_TRACE_TREE or TMX_TRACE_HEADER");
   if ((d.has_public && !d_pub) || !d_cap_h || !d_cap_q)
     return fail(c, TMX_ERR_BAD_ARG, d.has_public ? "d_pub, d_cap_h and d_cap_q must be set" : "d_cap_h and d_cap_q must be set");
   const uint32_t chain = d.has_chain && section != TMX_TRACE_SHA256;  // T.3 hashes are single blocks, T.5 and T.6 hashes pairs of blocks
@@ -4969,7 +5033,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   const tmx_ctx::SetRec::Oracle tabm = r.o[kt];
   if (tabm.streamed) return fail(c, TMX_ERR_BAD_ARG, "a streamed member has no resident extended columns: the helper is not streamed");
   if (r.n_oracles + 2 > TMX_BATCH_MAX_ORACLES) return fail(c, TMX_ERR_BAD_ARG, "the commit set has no room for two more oracles");
-  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / AIR_SHA_WIDTH, h = std::min(r.cap_height, log_m);
+  const uint32_t log_m = tabm.log_m, log_sub = log_m - r.log_blowup, n_proofs = tabm.n_cols / d.width, h = std::min(r.cap_height, log_m);
   if ((st = sha_check(c, d, log_m, r.log_blowup, n_proofs, chain))) return st;
   ShaGeo A;
   if ((st = sha_geo(c, d, log_m, r.log_blowup, chain, r.root, r.shift, A))) return st;
@@ -4979,6 +5043,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, log_m))) return st;
+  if (d.has_periodic && (st = sha512_scratch(c, log_m, log_sub))) return st;
   // the scratch of this set and section (ShaScratch)
   const bool streamed = by_chunks && chunk_proofs < n_proofs;
   const uint32_t n_hcols = n_proofs * d.helper_cols;
@@ -5066,6 +5131,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
     if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
     for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += d.helper_cols)
       st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, d.helper_cols, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
+    if (!st && d.has_periodic) st = sha512_periodic(c, log_m, r.log_blowup, hip_stream);
     if (moved) {
       const int32_t back = tmx_ntt_set_domain(c, root, shift);
       if (!st) st = back;
@@ -5266,6 +5332,63 @@ uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* c, uint32_
   const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
   if (slot < 0) return 0;
   return c->set_sha_bytes[SHA_SETS[constraint_set - 3].scratch][slot];
+}
+
+// ---- constraint set 7: the round constraints of the SHA-512 table, through row 4 of the host path above
+int32_t tmx_air_sha512_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper, void* hip_stream) {
+  return sha_helper_call(c, SHA_SETS[4], log_rows, n_proofs, 0, d_table, nullptr, d_helper, hip_stream);
+}
+
+int32_t tmx_air_sha512_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, const uint64_t* d_cols,
+                                       const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                       void* hip_stream) {
+  return sha_quotient_call(c, SHA_SETS[4], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs, uint32_t proof_lo,
+                                             uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols, const uint64_t* d_helper_cols,
+                                             const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[4], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, const uint64_t* d_caps, const uint64_t* d_proof,
+                                     uint32_t* d_ok, void* hip_stream) {
+  return sha_verify_call(c, SHA_SETS[4], p, k_trace, k_trace + 1, 0, d_caps, d_proof, nullptr, d_ok, hip_stream);
+}
+
+int32_t tmx_trace_commit_set_air_sha512_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  return sha_set_call(c, SHA_SETS[4], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
+}
+
+// the preprocessed columns on their own: what the quotient call fills and extends, and what the verifier evaluates
+int32_t tmx_air_sha512_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  const ShaSet& d = SHA_SETS[4];
+  if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
+  if (log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be at most 6");
+  if (!d_pre || (log_blowup && !d_ext)) return fail(c, TMX_ERR_BAD_ARG, "d_pre must be set, and d_ext unless log_blowup is 0");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const int rc = launch_air_sha512_periodic(log_rows, d_pre, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "periodic", rc);
+  return log_blowup ? tmx_lde_goldilocks_device(c, log_rows, log_blowup, 3, d_pre, d_ext, hip_stream) : TMX_OK;
+}
+
+int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  const ShaSet& d = SHA_SETS[4];
+  if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
+  if (!d_zeta || !d_out) return fail(c, TMX_ERR_BAD_ARG, "d_zeta and d_out must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  int32_t st = sha512_scratch(c, 0, 0);
+  if (st) return st;
+  const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_rows)), n_inv = gl_pow_host(1ull << log_rows, P - 2);
+  int rc = launch_air_sha512_periodic_eval(log_rows, om, d_zeta, c->d_air7, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
+  rc = launch_air_sha512_periodic_fold(log_rows, n_inv, c->d_air7, d_zeta, d_out, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "periodic_fold", rc);
+  return TMX_OK;
 }
 
 }  // extern "C"

@@ -47,6 +47,12 @@
            k_air_link_quotient and k_fri_combine show in ONE trace.  Between the two: the set-level call
            (tmx_trace_commit_set_air_sha256_link_device) on the HEADER member of a set SHA256 | HEADER of the same P proofs beside set 5's
            call on the same set, alternating, with the prove over table, H5, Q5, H6, Q6 and both verifiers.
+  sha512   constraint set 7 (tmx_air_sha512_*) beside set 3, its yardstick: k_air_sha512_helper over S512_PROOFS proofs (16) x 18 random table
+           columns, then the quotient call of set 7 (the preprocessed columns filled and extended, gamma, the tables, k_air_sha512_quotient)
+           and of set 3 (SHA_PROOFS proofs, 32) over random extended columns at M = 2^LOG_M (16), and a plain FRI prove over set 7's table
+           columns, alternating; ns_per_helper_word_set7 / _set3 and their ratio.  Under `rocprofv3 --kernel-trace --stats` (MODE=sha512) the
+           helper kernel, both hot passes and k_fri_combine show in ONE trace.  Then the set-level call on the SHA512 member of a set
+           SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove over table, helper, quotient and HEADER, and the verifier.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -722,5 +728,91 @@ if "link" in modes:
     res["quotient_read_gib"] = round((50 * sp_ << log_m) * 8 / 2**30, 2)
     res["combine_read_gib"] = round((33 * sp_ << log_m) * 8 / 2**30, 2)
     res["quotient_sha256"] = words_digest(qcall, quot)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+
+if "sha512" in modes:
+    # constraint set 7 beside set 3, its yardstick: the helper kernel, the caller-level quotient call of each set over random extended columns
+    # (S512_PROOFS proofs of 18 + 599 columns against SHA_PROOFS proofs of 9 + 300, M = 2^LOG_M each) and a plain FRI prove over set 7's table
+    # columns, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512) k_air_sha512_helper, k_air_sha512_quotient,
+    # k_air_sha_quotient and k_fri_combine show in ONE trace.  ns_per_helper_word: the call's time per helper word read, the figure the two
+    # passes are compared on.  Then the set-level call on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
+    log_m, cp, cp3 = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16")), int(os.environ.get("SHA_PROOFS", "32"))
+    log_rows = log_m - log_blowup
+    torch.manual_seed(seed)
+    ctx = Context(4, b"celestia", device=0)
+
+    def columns(width, helper, proofs):
+        cols = torch.randint(0, 2**62, ((width * proofs) << log_m,), dtype=torch.int64, device=dev)
+        hcols = torch.randint(0, 2**62, ((helper * proofs) << log_m,), dtype=torch.int64, device=dev)
+        caps = []
+        for c_, k_ in ((cols, width * proofs), (hcols, helper * proofs)):
+            lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+            ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+            caps.append(lv)
+        return cols, hcols, caps
+
+    cols7, hcols7, caps7 = columns(18, 599, cp)
+    cols3, hcols3, caps3 = columns(9, 300, cp3)
+    table = torch.randint(0, 2**62, ((18 * cp) << log_rows,), dtype=torch.int64, device=dev)
+    pre = torch.empty((599 * cp) << log_rows, dtype=torch.int64, device=dev)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    fp = dict(log_n=log_m, n_cols=18 * cp, cap_height=cap_h, log_blowup=log_blowup, arity_bits=arity, final_log_max=final_max, n_queries=nq)
+    proof = torch.empty(ctx.fri_layout(fp)["words"], dtype=torch.int64, device=dev)
+    q7 = lambda: ctx.air_sha512_quotient_device(log_m, log_blowup, cap_h, cp, cols7.data_ptr(), hcols7.data_ptr(), caps7[0][-(4 << cap_h):].data_ptr(),
+                                                caps7[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0)
+    q3 = lambda: ctx.air_sha256_quotient_device(log_m, log_blowup, cap_h, cp3, cols3.data_ptr(), hcols3.data_ptr(), caps3[0][-(4 << cap_h):].data_ptr(),
+                                                caps3[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0)
+    res = {"mode": "sha512", "log_m": log_m, "proofs_set7": cp, "proofs_set3": cp3, "read_gib_set7": round(((617 * cp) << log_m) * 8 / 2**30, 2),
+           "read_gib_set3": round(((309 * cp3) << log_m) * 8 / 2**30, 2), "reps": reps, "helper_kernel_ms": [], "sha512_quotient_call_ms": [],
+           "sha256_quotient_call_ms": [], "fri_prove_table_ms": [], "fri_combine_stage_ms": []}
+    for _ in range(rounds):
+        res["helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha512_helper_device(log_rows, cp, table.data_ptr(), pre.data_ptr(), 0), reps)))
+        res["sha512_quotient_call_ms"].append(r4(timed(q7, reps)))
+        res["sha256_quotient_call_ms"].append(r4(timed(q3, reps)))
+        res["fri_prove_table_ms"].append(r4(timed(lambda: ctx.fri_prove_device(fp, cols7.data_ptr(), caps7[0].data_ptr(), proof.data_ptr(), 0), reps)))
+        res["fri_combine_stage_ms"].append(r4(ctx.fri_last_ms()["combine"]))
+    res["quotient_sha256"] = words_digest(q7, quot)
+    ns7 = min(res["sha512_quotient_call_ms"]) * 1e6 / ((599 * cp) << log_m)
+    ns3 = min(res["sha256_quotient_call_ms"]) * 1e6 / ((300 * cp3) << log_m)
+    res.update(ns_per_helper_word_set7=round(ns7, 4), ns_per_helper_word_set3=round(ns3, 4), ratio_set7_over_set3=round(ns7 / ns3, 3),
+               helper_store_gb_per_s=round(((599 * cp) << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e6, 1))
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols7, hcols7, caps7, cols3, hcols3, caps3, table, pre, quot, proof
+    torch.cuda.empty_cache()
+    # the set-level call on SHA512
+    from tendermintx_amd.synth import bench_workload
+    sp = int(os.environ.get("S512_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    SHA512, HEADER = 2, 32
+    cw = 4 << cap_h
+    scaps, cap_h_, cap_q = (torch.zeros(k * cw, dtype=torch.int64, device=dev) for k in (2, 1, 1))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA512 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    res = {"mode": "sha512_set", "proofs": sp, "n": n, "reps": reps, "commit_ms": r4(timed(commit, 2)), "air_sha512_ms": [], "prove_with_ms": []}
+    for _ in range(rounds):
+        res["air_sha512_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_sha512_device(SHA512, cap_h_.data_ptr(), cap_q.data_ptr(), 0), reps,
+                                             before=commit)))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(SHA512)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
+        res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
     print(json.dumps(res), flush=True)
     ctx.close()
