@@ -7,7 +7,8 @@ third round equals the first word for word.  The buffers of an earlier table sta
 (set, table) pairs that shared a buffer would show as a changed proof or a rejected query.  What the helpers, caps, gammas and quotients
 ARE is compared against the models in tests/test_sha_air.py, tests/test_sha_sched.py and tests/test_sha_init.py, whose plumbing this
 file uses.  Row 3 of the same table, constraint set 6's (tmx_trace_commit_set_air_sha256_link_device), goes through the same three commits
-beside set 5 on a context of its own, under the public tables the device gathers (tests/test_sha_public.py)."""
+beside set 5 on a context of its own, under the public tables the device gathers (tests/test_sha_public.py).
+Row 4, constraint set 7's, and its d_air7: tests/test_sha512_air_shapes.py test_growth_and_reuse_of_the_scratch_on_one_context."""
 import numpy as np
 import pytest
 
