@@ -1077,7 +1077,7 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* ctx, const uint64_t* d
  *   NOT PROVED by set 3: the message schedule (W_t for t >= 16), which constraint set 4 below proves; row 0 of a block against the IV or
  *              the chaining value and the feed-forward between the two blocks of T.5 / T.6 hashes, which constraint set 5 below proves;
  *              the digest's link to Level-1, which constraint set 6 below proves; and, still open (the follow-ups): LIVE against anything
- *              public (set 6's flags); SHA-512 beyond its round function (constraint set 7 below).  Under set 3 ALONE a
+ *              public (set 6's flags); SHA-512 beyond its round function and message schedule (constraint sets 7 and 8 below).  Under set 3 ALONE a
  *              block re-run consistently from a changed W_t or a changed row-0 state goes undetected (tests/test_sha_air.py records it).
  *   challenge  a fresh duplex, as set 1: observe 2^33, then the set id 3, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap (4 << min(cap_height, log_n) words each); gamma drawn as in set 1.
@@ -1151,7 +1151,7 @@ int32_t tmx_trace_commit_set_air_sha256_device(tmx_ctx* ctx, uint32_t section, u
  *              and zero padding satisfy all 117 without a LIVE column.
  *   NOT PROVED by sets 3 and 4: row 0 of a block against the IV or the chaining value and the feed-forward between the two blocks of
  *              T.5 / T.6 hashes, which constraint set 5 below proves; the first sixteen W of a block against Level-1, which constraint
- *              set 6 below proves; and, still open (the follow-ups): LIVE against anything public (set 6's flags); SHA-512 beyond its round function (constraint set 7 below).  Under sets
+ *              set 6 below proves; and, still open (the follow-ups): LIVE against anything public (set 6's flags); SHA-512 beyond its round function and message schedule (constraint sets 7 and 8 below).  Under sets
  *              3 and 4 ALONE a block re-run consistently (schedule
  *              and rounds) from a changed W_t, t < 16, or from a changed row-0 state goes undetected (tests/test_sha_sched.py records it).
  *   challenge  as set 3 with the set id 4: a fresh duplex observes 2^33, then 4, log_n, log_blowup, cap_height, n_proofs, then the table cap,
@@ -1245,7 +1245,7 @@ int32_t tmx_trace_commit_set_air_sha256_sched_device(tmx_ctx* ctx, uint32_t sect
  *              multiplied by LV' and why PZ carries LV'.
  *   NOT PROVED by sets 3 + 4 + 5 (the follow-ups): the first sixteen W of a block against Level-1; the digest (IV or chaining value plus
  *              the state after the last round) against Level-1; LV against anything public -- a hash whose live second block is replaced
- *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512 beyond its round function (constraint set 7 below); the ladders' curve arithmetic
+ *              by a zero block goes unseen, because the set cannot know that a second block was due; SHA-512 beyond its round function and message schedule (constraint sets 7 and 8 below); the ladders' curve arithmetic
  *              and limb ranges (tests/test_sha_init.py records the first and the third).  Constraint set 6 below ("the SHA-256 tables'
  *              link to Level-1") closes the first three: it pins the first sixteen W, the digest and the block structure to Level-1.
  *   challenge  set 3's lone-lane kernel: a fresh duplex observes 2^33, then 5 | chain << 8, log_n, log_blowup, cap_height, n_proofs, then the
@@ -1421,7 +1421,7 @@ uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* ctx, uint3
  *              own V63 and V^t, and evaluates the seventeen polynomials barycentrically, set 2's form with K <= 2^12 per coset:
  *              P_c(zeta) / D_c(zeta) = 1 / (K y_0^K) sum_k V_k y_k / (zeta - y_k).  A failed identity, or a zero denominator, clears
  *              every query's verdict.
- *   NOT PROVED by sets 3 + 4 + 5 + 6: LIVE / LV of sets 3 and 5 against set 6's public flags; SHA-512 beyond its round function (constraint set 7 below); the ladders' curve arithmetic and
+ *   NOT PROVED by sets 3 + 4 + 5 + 6: LIVE / LV of sets 3 and 5 against set 6's public flags; SHA-512 beyond its round function and message schedule (constraint sets 7 and 8 below); the ladders' curve arithmetic and
  *              limb ranges; a T.5 slot whose right child is not enabled (above); and there is no range argument for DG on chain rows --
  *              the identities are integer identities far below p and the digest is pinned to a public word below 2^32, so the digest is
  *              right mod 2^32 provided set 3 range-checks s_j.  TMX_BATCH_MAX_ORACLES stays 8: a section that already carries sets 3 + 4 + 5 has seven oracles
@@ -1540,9 +1540,10 @@ int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t secti
  *              Every nonlinear constraint has degree 2 in the columns and no selector, every selected one is SEL (linear), the K constraint
  *              KL - LIVE K(x): every constraint has degree <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient
  *              oracle still suffices.  Zero blocks and zero padding satisfy all 628 with LIVE = 0.
- *   NOT PROVED by set 7: the message schedule (W_t for t >= 16); the IV and the feed-forward of the two blocks; W's limb range; the link of
- *              message and digest to Level-1, and so of h; LIVE against anything public.  Under set 7 alone a block re-run consistently
- *              from a changed W_t goes undetected (tests/test_sha512_air.py records it).
+ *   NOT PROVED by set 7: the message schedule (W_t for t >= 16) and W's limb range -- both are constraint set 8 below --; the IV and the
+ *              feed-forward of the two blocks; the link of message and digest to Level-1, and so of h; LIVE against anything public.
+ *              Under set 7 ALONE a block re-run consistently from a changed W_t goes undetected (tests/test_sha512_air.py records it;
+ *              set 8 rejects it, tests/test_sha512_sched.py).
  *   challenge  a fresh duplex, as set 3: observe 2^33, then the set id 7, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
  *              the helper cap.  The preprocessed columns are a function of log_n - log_blowup and are not observed.
  *   quotient   q(x_i) = sum_p sum_(j < 628) gamma^(628 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical as in set 1; pointwise.
@@ -1589,6 +1590,101 @@ int32_t tmx_air_sha512_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, ui
 int32_t tmx_trace_commit_set_air_sha512_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 int32_t tmx_air_sha512_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
 int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
+
+/* ---- the message schedule of the SHA-512 table (constraint set 8) ------------------------------------------------------------------------
+ * Set 7 proves the round function on T.2 and leaves W free from row 16 of each block on.  Set 8 is the SCHEDULE: the sibling of set 4 on
+ * 64-bit words in lo / hi limbs, with set 7's preprocessed-column mechanism for the period 80.  Sets 7 + 8 together state that every live
+ * block of T.2 is a real SHA-512 compression of its first sixteen W words from the state in front of it, and W's limbs are range-checked
+ * by their bits.  Everything is additive: no existing kernel, launch, transcript word, refusal, scratch layout or proof word changes; the
+ * batch prover, its proof format and tmx_batch_verify_device are used UNCHANGED.  Same field, extension, duplex and caveats as above.
+ *   table      T.2 as in set 7: 18 n_proofs columns of 32-bit limbs, W lo at 0 and W hi at 1 inside a proof; row (2 i + b) 80 + t holds W_t.
+ *   schedule   W_t = sigma1(W_(t-2)) + W_(t-7) + sigma0(W_(t-15)) + W_(t-16) mod 2^64 for t = 16 .. 79, with
+ *              sigma0(x) = x >>> 1 xor x >>> 8 xor x >> 7 and sigma1(x) = x >>> 19 xor x >>> 61 xor x >> 6 (>>> rotates, >> shifts).
+ *   preprocessed column  ONE more public column of full degree N - 1 that depends on N alone:
+ *                SCH_r = 1 where the NEXT row is a schedule row of the same block, 15 <= r mod 80 <= 78, and r != N - 1; 0 elsewhere.
+ *              The wrap row must be switched off explicitly: (2^k - 1) mod 80 is 47, 15, 31, 63 for k = 3, 0, 1, 2 mod 4, always inside
+ *              15 .. 78, while row 0 is W_0 of a block.  The prover fills it (k_air_sha512_sched_periodic) and extends it exactly as helper
+ *              columns are extended; the verifier commits to nothing and computes SCH(zeta) itself, barycentrically over the N rows
+ *              (k_air_sha512_sched_periodic_eval, set 7's batching: four rows per F_p^2 inversion, up to 64 workgroups).  It is not observed
+ *              by gamma, as SEL, KLO and KHI are not.  A zero denominator clears every verdict.  log_rows 7 .. 18, set 7's range, for the
+ *              same reason.
+ *   helper     230 columns per proof (twice set 4's 115), bits LSB first, bit indices mod 64; defined for ANY input: the operands are the
+ *              low 32 bits of each table word.  Offsets inside a proof:
+ *                0 .. 63    WB_i, the bits of W (0 .. 31 the low limb, 32 .. 63 the high limb)
+ *               64 .. 127   X0_i = WB_(i+1) xor WB_(i+8)              128 .. 191   X1_i = WB_(i+19) xor WB_(i+61)
+ *              192, 193     sigma0(W) lo, hi (G0)                     194, 195     sigma1(W) lo, hi (G1)
+ *              195 + k      QL_k, k = 1 .. 15, the low-limb pipeline of the schedule sum      210 + k   QH_k, the same over the high limbs
+ *              226, 227     the two bits of CL, the low limb's carry                          228, 229  the two bits of CH
+ *              The pipelines are per limb and WITHOUT carries, set 4's pipeline twice, rows cyclic inside one proof:
+ *              QL_1(r+1) = W_lo(r) + G0_lo(r+1); QL_k(r+1) = QL_(k-1)(r), plus W_lo(r+1) for k = 9, plus G1_lo(r+1) for k = 14; so
+ *              QL_15(r) = W_lo(r-15) + sigma0_lo(r-14) + W_lo(r-6) + sigma1_lo(r-1).  QH the same over the high limbs.  Four summands
+ *              below 2^32: a limb sum stays below 2^34.  CL = (QL_15 >> 32) & 3 and CH = ((QH_15 + CL) >> 32) & 3, both 0 where
+ *              SCH = 0: every carry is at most 3 and every identity is an integer identity below 2^35.
+ *   constraints  234 per proof (twice set 4's 117), at index j; a prime is the value at omega x:
+ *                0 .. 63    X^2 - X for WB                               64 .. 67   X^2 - X for the four carry bits (CL_0, CL_1, CH_0, CH_1)
+ *               68, 69      W_lo, W_hi - sum_(i < 32) 2^i WB_(32 limb + i)
+ *               70 + i      X0_i - (WB_(i+1) + WB_(i+8) - 2 WB_(i+1) WB_(i+8))      134 + i   the same for X1 with 19 and 61
+ *              198, 199     sigma0 lo, hi - sum 2^i of X0_j xor WB_(j+7) for j < 57 and X0_j for j >= 57, j = 32 limb + i (the shift by 7
+ *                           brings nothing in)                          200, 201   sigma1 the same, with WB_(j+6) for j < 58
+ *              201 + k      QL_k' - (W_lo + G0_lo') for k = 1, QL_k' - QL_(k-1) - [k = 9] W_lo' - [k = 14] G1_lo' (linear, unselected)
+ *              216 + k      the same for QH over the high limbs
+ *              232          SCH(x) (W_lo' + 2^32 (CL_0 + 2 CL_1) - QL_15)
+ *              233          SCH(x) (W_hi' + 2^32 (CH_0 + 2 CH_1) - QH_15 - (CL_0 + 2 CL_1))
+ *              Every nonlinear constraint has degree 2 and no selector, the two selected ones are SCH (linear): every constraint has degree
+ *              <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient oracle suffices, as in set 7.  Zero blocks and
+ *              zero padding satisfy all 234.
+ *   NOT PROVED by sets 7 + 8: the IV and the feed-forward of the two blocks; the link of message and digest to Level-1, and so of h; LIVE
+ *              against anything public; and so a message word W_t, t < 16, changed with the schedule recomputed from it goes undetected
+ *              (tests/test_sha512_sched.py records it).
+ *   challenge  word for word set 7's with the set id 8: a fresh duplex observes 2^33, then 8, log_n, log_blowup, cap_height, n_proofs, then
+ *              the table cap, then THIS helper's cap; gamma drawn again while gamma.c1 == 0.
+ *   quotient   q(x_i) = sum_p sum_(j < 234) gamma^(234 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical; pointwise.
+ *   identity   sum_p gamma^(234 p) (a_p + SCH(zeta) b_p) == (u_0 + X u_1) (zeta^N - 1), a the gamma sum of constraints 0 .. 231, b of 232
+ *              and 233 without SCH.  The helper's oracle index is explicit, k_helper with the quotient at k_helper + 1, as in set 4: set 7's
+ *              pair and set 8's pair can both sit behind one table in one proof.
+ *   tmx_air_sha512_sched_helper_device     the helper (230 n_proofs columns at d_helper) from PRE-LDE table columns (18 n_proofs at d_table).
+ *                                          TMX_ERR_BAD_ARG: log_rows outside 7 .. 18, n_proofs = 0, 230 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_sched_quotient_device   fills and extends SCH under the context's CURRENT NTT domain, draws gamma from d_cap and
+ *                                          d_cap_helper, then the quotient of the EXTENDED columns into d_quot (2 << log_n words).
+ *                                          TMX_ERR_BAD_ARG: FRI's rules on log_n and log_blowup, log_n - log_blowup outside 7 .. 18,
+ *                                          n_proofs = 0, 230 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_sched_quotient_range_device   set 3's range call: the piece [proof_lo, proof_hi), d_helper_cols that piece's own columns,
+ *                                          written or (accumulate = 1) added; also refused: an empty or overhanging range, accumulate > 1.
+ *   tmx_air_sha512_sched_verify_device     tmx_batch_verify_device, the barycentric kernel, then the identity for the oracles k_trace (18 k
+ *                                          columns), k_helper (230 k) and k_helper + 1 (2).  TMX_ERR_BAD_ARG unless the column counts are
+ *                                          these, the three log_n equal, k_helper > k_trace, k_helper + 1 < n_oracles (and the rules above).
+ *   tmx_trace_commit_set_air_sha512_sched_device   set 7's set-level call for this set: `section` = TMX_TRACE_SHA512 alone, a RESIDENT member
+ *                                          only; the pair goes behind set 7's pair if that follows the table, and set 7's call inserts in
+ *                                          front of it: either order ends as table, H7, Q7, H8, Q8 with the same caps and the same proof.
+ *                                          tmx_trace_commit_set_shape reports TMX_TRACE_SHA512_SCHED_HELPER and _SCHED_QUOTIENT.  Refused:
+ *                                          any other section, an absent or streamed section, a second call on the section, a set with no
+ *                                          room for two more oracles.
+ *   tmx_air_sha512_sched_periodic_device   SCH on its own: 1 << log_rows words at d_pre and, extended under the current NTT domain,
+ *                                          1 << (log_rows + log_blowup) words at d_ext (log_blowup = 0: d_pre alone).
+ *   tmx_air_sha512_sched_periodic_eval_device   d_out[0 .. 2) = SCH(zeta) for the two words at d_zeta, d_out[2] = 1 if a denominator was zero
+ *                                          (d_out: 3 words).  Both refuse log_rows outside 7 .. 18 and null pointers.
+ * Scratch: per section set 3's formula with 230 columns, and once per context ((N + M) + 256) 8 bytes of its own for SCH and the
+ * barycentric kernel's rows (set 7's context scratch is not touched).  The streamed call keeps refusing every constraint_set but 3, 4 and 5.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers the quotient calls
+ * and the set-level call.  Follow-ups: the block starts of T.2 (IV, feed-forward), its link to Level-1, a streamed form of the helper. */
+#define TMX_AIR_SHA512_SCHED_HELPER_COLS 230
+#define TMX_AIR_SHA512_SCHED_CONSTRAINTS 234
+#define TMX_TRACE_SHA512_SCHED_HELPER 131072u
+#define TMX_TRACE_SHA512_SCHED_QUOTIENT 262144u
+int32_t tmx_air_sha512_sched_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                           void* hip_stream);
+int32_t tmx_air_sha512_sched_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                             const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_sched_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                   uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                   uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_sched_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                           const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha512_sched_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+int32_t tmx_air_sha512_sched_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
+int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

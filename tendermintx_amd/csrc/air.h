@@ -247,4 +247,40 @@ int launch_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_
                             const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
                             uint32_t n_queries, void* d_ok, void* stream);
 
+// ---- constraint set 8: the message schedule of the SHA-512 table (include/tmx.h "the message schedule of the SHA-512 table").  Set 7's table,
+// a helper oracle of 230 columns per proof (set 4's 115 twice: lo / hi limbs), 234 constraints per proof; gamma comes from set 3's lone-lane
+// kernel with the set id 8 in obs[0] (launch_air_sha_gamma: the same code object).  The selector "the next row is a schedule row" has the
+// period 80: one more preprocessed column of full degree (SCH), filled, extended and evaluated as set 7's three are.
+constexpr uint32_t AIR_SHA512_SCHED_HELPER_COLS = 230, AIR_SHA512_SCHED_CONSTRAINTS = 234;
+// The tables one set-8 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
+//   gpow  [236][2]               gamma^0 .. gamma^234, then gamma^(234 first)
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+constexpr uint32_t AIR8_TAB_GPOW = 0, AIR8_TAB_ZINV = 512;
+constexpr uint64_t AIR8_TAB_WORDS = AIR8_TAB_ZINV + 64;
+static_assert(2 * (AIR_SHA512_SCHED_CONSTRAINTS + 2) <= AIR8_TAB_ZINV && AIR8_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-8 tables live in the table part of set 1's scratch");
+// The barycentric kernel's output: one row of AIR8_PART_WORDS words per workgroup (two words of the sum, a zero-denominator flag, one
+// unused); the workgroups are set 7's (air_sha512_eval_parts: 1024 rows each, at most AIR7_MAX_PARTS)
+constexpr uint32_t AIR8_PART_WORDS = 4;
+// SCH before the LDE (1 << log_rows words at d_pre): one lane per row
+int launch_air_sha512_sched_periodic(uint32_t log_rows, void* d_pre, void* stream);
+// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 230 n_proofs
+int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
+// s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
+int launch_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(234 p + j) C_(p,j) / (x^N - 1); d_pre the extended SCH
+// plane (1 << log_m words); form as in launch_air_sha_quotient
+int launch_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                                     const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream);
+// The barycentric sum of SCH at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N: air_sha512_eval_parts(log_rows) rows
+// at d_part
+int launch_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
+// d_out[0 .. 2) = SCH(zeta), d_out[2] = 1 if a denominator was zero; n_inv = 1 / N
+int launch_air_sha512_sched_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
+// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with
+// SCH at zeta from the barycentric kernel's rows at d_part
+int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                  const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                                  uint32_t n_queries, void* d_ok, void* stream);
+
 }  // namespace tmx

@@ -2274,4 +2274,339 @@ int launch_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 8: the message schedule of the SHA-512 table (include/tmx.h "the message schedule of the SHA-512 table") ----------------
+// A sibling of set 4 on T.2: W as lo / hi limbs, the schedule sum as one carry-free pipeline per limb, 80-row blocks.  The selector "the
+// next row is a schedule row" has the period 80: one more preprocessed column of full degree (SCH), filled, extended and evaluated at zeta
+// as set 7's three are.  Nothing above changes.
+// Helper column offsets inside a proof's 230 (QL_k at Z_QL + k, QH_k at Z_QH + k), constraint indices inside its 234 (the pipelines' at
+// JZ_QL + k and JZ_QH + k).  The low limb's column or index first; the high limb's is the next one.
+constexpr uint32_t Z_WB = 0, Z_X0 = 64, Z_X1 = 128, Z_G0 = 192, Z_G1 = 194, Z_QL = 195, Z_QH = 210, Z_CL = 226, Z_CH = 228;
+constexpr uint32_t JZ_CARRY = 64, JZ_WORD = 68, JZ_X0 = 70, JZ_X1 = 134, JZ_G0 = 198, JZ_G1 = 200, JZ_QL = 201, JZ_QH = 216, JZ_NEXT = 232;
+
+__device__ __forceinline__ uint64_t sched512_s0(uint64_t w) { return rotr64(w, 1) ^ rotr64(w, 8) ^ (w >> 7); }
+__device__ __forceinline__ uint64_t sched512_s1(uint64_t w) { return rotr64(w, 19) ^ rotr64(w, 61) ^ (w >> 6); }
+
+// SCH at row r of N: on where the NEXT row is a schedule row of the same block, off on the wrap row N - 1 ((N - 1) mod 80 always lies in
+// 15 .. 78, while row 0 is W_0 of a block)
+__device__ __forceinline__ bool sha512_sch(uint32_t r, uint32_t n) {
+  const uint32_t t = r % SHA512_BLOCK;
+  return t >= 15 && t <= SHA512_BLOCK - 2 && r != n - 1;
+}
+
+// One lane per row: SCH before the LDE (1 << log_rows words)
+__global__ __launch_bounds__(256) void k_air_sha512_sched_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
+  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= N) return;
+  pre[r] = sha512_sch(r, N) ? 1 : 0;
+}
+
+// One lane per (proof, row) of the pre-LDE table, k_air_sched_helper's shape: 230 stores, each of them consecutive words of one column
+// across the wave.  Both pipelines unrolled: Q_k(r) = W(r-k) + sigma0(W(r-k+1)) + [k >= 9] W(r-k+9) + [k >= 14] sigma1(W(r-k+14)) per limb
+// and without carries, rows cyclic inside the proof, so the lane reads W of the sixteen rows r - 15 .. r and recomputes sigma0 / sigma1
+// instead of exchanging them.  The operands are the low 32 bits of the two W columns.
+__global__ __launch_bounds__(256) void k_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                                 uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows);
+  const uint64_t mask = (1ull << log_rows) - 1, r = idx & mask;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA512_WIDTH) << log_rows);  // (W lo is column 0, W hi column 1)
+  uint64_t w[16];  // w[d] = W(r - d)
+#pragma unroll
+  for (uint32_t d = 0; d < 16; d++) w[d] = (uint64_t)(uint32_t)t[(r - d) & mask] | (uint64_t)(uint32_t)t[(mask + 1) + ((r - d) & mask)] << 32;
+  const uint64_t w0 = w[0], x0 = rotr64(w0, 1) ^ rotr64(w0, 8), x1 = rotr64(w0, 19) ^ rotr64(w0, 61);
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA512_SCHED_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 64; i++) {
+    put(Z_WB + i, (w0 >> i) & 1);
+    put(Z_X0 + i, (x0 >> i) & 1);
+    put(Z_X1 + i, (x1 >> i) & 1);
+  }
+  const uint64_t g0 = sched512_s0(w0), g1 = sched512_s1(w0);
+  put(Z_G0, (uint32_t)g0);
+  put(Z_G0 + 1, g0 >> 32);
+  put(Z_G1, (uint32_t)g1);
+  put(Z_G1 + 1, g1 >> 32);
+  uint64_t ql15 = 0, qh15 = 0;
+#pragma unroll
+  for (uint32_t k = 1; k <= 15; k++) {
+    const uint64_t s0 = sched512_s0(w[k - 1]);
+    uint64_t ql = (uint64_t)(uint32_t)w[k] + (uint32_t)s0, qh = (w[k] >> 32) + (s0 >> 32);
+    if (k >= 9) ql += (uint32_t)w[k - 9], qh += w[k - 9] >> 32;
+    if (k >= 14) {
+      const uint64_t s1 = sched512_s1(w[k - 14]);
+      ql += (uint32_t)s1, qh += s1 >> 32;
+    }
+    put(Z_QL + k, ql);
+    put(Z_QH + k, qh);
+    ql15 = ql, qh15 = qh;
+  }
+  uint32_t cl = 0, ch = 0;
+  if (sha512_sch((uint32_t)r, (uint32_t)(mask + 1))) {
+    cl = (uint32_t)(ql15 >> 32) & 3;
+    ch = (uint32_t)((qh15 + cl) >> 32) & 3;
+  }
+  put(Z_CL, cl & 1);
+  put(Z_CL + 1, cl >> 1);
+  put(Z_CH, ch & 1);
+  put(Z_CH + 1, ch >> 1);
+}
+
+// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^234, gamma^(234 first); the selector is a column, not a table
+__global__ __launch_bounds__(256) void k_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
+                                                                 const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_SCHED_CONSTRAINTS, tab + AIR8_TAB_ZINV, tab + AIR8_TAB_GPOW);
+}
+
+// The 234 constraints of one proof at one point.  The bit loop is set 4's (air_sched_constraints) per 32-bit limb, the high limb first, with
+// the rotations of SHA-512 taken mod 64 across both limbs as column offsets: per bit index i the pass holds WB_i, X0_i, X1_i and the rotated
+// or shifted bit words (WB_(i+1), WB_(i+8), WB_(i+19), WB_(i+61), and WB_(i+7) for i < 57, WB_(i+6) for i < 58), re-read through the cache.
+// Per i: three constraints (X^2 - X, X0, X1) and one Horner step by 2 of the limb's three word sums: 5 reduced column products and 6 gamma
+// weights, as in set 4.  A limb's three sums go into its word constraints before the other limb starts, so no more than three are ever
+// live.  Behind the loops the four carry bits, the two pipelines (linear) and the two selected constraints, which go to a gamma sum of
+// their own: SCH(x) is factored out of it, the kernel applies it once.
+template <class F, class View>
+__device__ __forceinline__ void air_sha512_sched_constraints(View& at) {
+  using A = Forms<F>;
+  using T = typename F::T;
+#pragma unroll 1
+  for (uint32_t l = 2; l-- > 0;) {
+    T ww = F::zero(), wg0 = F::zero(), wg1 = F::zero();
+#pragma unroll View::BITS
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint32_t i = 32 * l + b;
+      const T WB = at.again(Z_WB + i), X0 = at.once(Z_X0 + i), X1 = at.once(Z_X1 + i);
+      const T W1 = at.again(Z_WB + ((i + 1) & 63)), W8 = at.again(Z_WB + ((i + 8) & 63));
+      const T W19 = at.again(Z_WB + ((i + 19) & 63)), W61 = at.again(Z_WB + ((i + 61) & 63));
+      at.plain(Z_WB + i, A::boolean(WB));
+      at.plain(JZ_X0 + i, A::sub(X0, A::exor(W1, W8)));
+      at.plain(JZ_X1 + i, A::sub(X1, A::exor(W19, W61)));
+      ww = A::dbl_add(ww, WB);
+      wg0 = A::dbl_add(wg0, i < 57 ? A::exor(X0, at.again(Z_WB + i + 7)) : X0);  // (i is uniform: a scalar branch)
+      wg1 = A::dbl_add(wg1, i < 58 ? A::exor(X1, at.again(Z_WB + i + 6)) : X1);
+    }
+    at.plain(JZ_WORD + l, A::sub(at.tbl(R_W + l), ww));
+    at.plain(JZ_G0 + l, A::sub(at.again(Z_G0 + l), wg0));
+    at.plain(JZ_G1 + l, A::sub(at.again(Z_G1 + l), wg1));
+  }
+  // the values CL, CH (two scalars, not an array: the limb loop below is not unrolled)
+  const T cl0 = at.once(Z_CL), cl1 = at.once(Z_CL + 1), ch0 = at.once(Z_CH), ch1 = at.once(Z_CH + 1);
+  at.plain(JZ_CARRY, A::boolean(cl0));
+  at.plain(JZ_CARRY + 1, A::boolean(cl1));
+  at.plain(JZ_CARRY + 2, A::boolean(ch0));
+  at.plain(JZ_CARRY + 3, A::boolean(ch1));
+  const T CL = A::add(cl0, A::add(cl1, cl1)), CH = A::add(ch0, A::add(ch1, ch1));
+  // one pipeline at a time, as the bit loop takes one limb at a time: the fifteen Q_k and Q_k' of a limb are spent before the other starts
+#pragma unroll 1
+  for (uint32_t l = 0; l < 2; l++) {
+    const uint32_t zq = l ? Z_QH : Z_QL, jq = l ? JZ_QH : JZ_QL;  // (l is uniform: scalar selects)
+    const T Wn = at.tbl_next(R_W + l);
+    T prev = A::add(at.tbl(R_W + l), at.next(Z_G0 + l));  // what Q_k' must equal: W + G0' for k = 1, then Q_(k-1) (+ W' for k = 9, + G1' for k = 14)
+#pragma unroll View::SHORT
+    for (uint32_t k = 1; k <= 15; k++) {
+      at.plain(jq + k, A::sub(at.next(zq + k), prev));
+      prev = at.again(zq + k);
+      if (k + 1 == 9) prev = A::add(prev, Wn);
+      if (k + 1 == 14) prev = A::add(prev, at.next(Z_G1 + l));
+    }
+    // (prev = Q_15)  W' + 2^32 C - Q_15, and in the high limb the carry out of the low limb comes in
+    T nw = A::sub(A::add(Wn, A::scale(l ? CH : CL, 1ull << 32)), prev);
+    if (l) nw = A::sub(nw, CL);
+    at.selected(JZ_NEXT + l, nw);
+  }
+}
+
+// The set-8 hot pass, k_air_sha512_quotient's frame: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^234), W's two columns and the 230 helper columns.  pre: the extended SCH plane (1 << log_m words), one word per lane.  Per proof
+// v = a + SCH(x) b; at the end 1 / (x^N - 1).  FORM as in set 3.
+template <int FORM>
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                           const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                           const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
+                                                                           uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR8_TAB_GPOW;
+  const uint64_t sch = gl_canon(pre[i]);
+  const uint64_t zinv = tab[AIR8_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g234 = {gp[2 * AIR_SHA512_SCHED_CONSTRAINTS], gp[2 * AIR_SHA512_SCHED_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_SCHED_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_sha512_sched_constraints<FieldP>(at);
+    const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sch, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sch, at.b1))};
+    t = gl2_add(gl2_mul(t, g234), v);
+  }
+  gl2 q = gl2_scale(t, zinv);
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
+  out[i] = q.c0;
+  out[M + i] = q.c1;
+}
+
+// SCH at zeta, barycentric over the N rows: k_air_sha512_periodic_eval's batching (thread g of T takes the rows g, g + T, ... four at a
+// time, one F_p^2 inversion per four denominators; up to AIR7_MAX_PARTS workgroups) with one sum, v_r = SCH_r from r itself.  A
+// workgroup's sum meets in LDS and goes to its row of `part`: [2] words of the sum, then 1 if a denominator was zero (such a term is left
+// out).  air_sha512_sched_periodic_at folds the rows.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
+                                                                                       uint64_t* __restrict__ part) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint32_t bad;
+  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
+  const uint64_t stride = gl_pow(om, T);
+  uint64_t y = gl_pow(om, g);
+  gl2 ssch = {0, 0};
+  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
+    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
+    uint64_t yk[AIR7_EVAL_PER];
+    gl2 run = {1, 0};
+#pragma unroll
+    for (int m = 0; m < AIR7_EVAL_PER; m++) {
+      const bool in = r0 + m * T < N;
+      yk[m] = y;
+      den[m] = {gl_sub(z.c0, y), z.c1};
+      pre[m] = run;
+      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
+        bad = 1;
+        den[m] = {1, 0};
+      }
+      if (in) run = gl2_mul(run, den[m]);
+      y = gl_mul(y, stride);
+    }
+    gl2 inv = gl2_inv(run);
+#pragma unroll
+    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
+      const uint32_t r = r0 + m * T;
+      if (r < N) {
+        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
+        inv = gl2_mul(inv, den[m]);
+        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
+        if (sha512_sch(r, N)) ssch = gl2_add(ssch, term);
+      }
+    }
+  }
+  const uint32_t t = threadIdx.x;
+  red[0][t] = ssch.c0, red[1][t] = ssch.c1;
+  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h)
+      for (uint32_t k = 0; k < 2; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+  }
+  __syncthreads();
+  if (t < 2) part[(size_t)blockIdx.x * AIR8_PART_WORDS + t] = red[t][0];
+  if (t == 2) part[(size_t)blockIdx.x * AIR8_PART_WORDS + 2] = bad;
+}
+
+// SCH(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
+__device__ __forceinline__ bool air_sha512_sched_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2& v) {
+  uint64_t s0 = 0, s1 = 0, bad = 0;
+  for (uint32_t k = 0; k < n_parts; k++) {
+    s0 = gl_add(s0, part[(size_t)k * AIR8_PART_WORDS]);
+    s1 = gl_add(s1, part[(size_t)k * AIR8_PART_WORDS + 1]);
+    bad |= part[(size_t)k * AIR8_PART_WORDS + 2];
+  }
+  v = gl2_mul(gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv), {s0, s1});
+  return bad == 0;
+}
+
+// One thread: the value (two words), then 1 if a denominator was zero, at out[0 .. 3)
+__global__ void k_air_sha512_sched_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                 const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
+  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v;
+  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_sched_periodic_at(part, n_parts, zn, n_inv, v);
+  out[0] = v.c0;
+  out[1] = v.c1;
+  out[2] = fine ? 0 : 1;
+}
+
+// The set-8 identity at zeta, one workgroup: gamma^0 .. gamma^234 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
+// their 234 constraints over F_p^2 from the table's and the helper's openings, with SCH at zeta from the barycentric kernel's rows.  A
+// proof contributes gamma^(234 p) (a + SCH(zeta) b); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero denominator in the
+// barycentric sum clears every verdict.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                               uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                                               const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
+                                                                               const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
+                                                                               const uint64_t* __restrict__ gamma, uint32_t n_queries,
+                                                                               uint32_t* __restrict__ ok) {
+  __shared__ uint64_t gpw[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1)];
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_SHA512_SCHED_CONSTRAINTS, gpw);
+  __syncthreads();
+  gl2 zn = {zeta[0], zeta[1]}, sch;
+  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_sched_periodic_at(part, n_parts, zn, n_inv, sch);
+  gl2 sum = {0, 0};
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_SCHED_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_sha512_sched_constraints<FieldP2>(at);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_SCHED_CONSTRAINTS * p), gl2_add(at.a, gl2_mul(sch, at.b))));
+  }
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
+  if (!fine)
+    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_sha512_sched_periodic(uint32_t log_rows, void* d_pre, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_sched_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
+                     reinterpret_cast<uint64_t*>(d_pre));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sha512_sched_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
+  // (one workgroup: the 236 gamma powers; 2^log_blowup <= 64 inverses)
+  hipLaunchKernelGGL(k_air_sha512_sched_tables, dim3((AIR_SHA512_SCHED_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof,
+                     s_n, w_n, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                                     const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* pre = reinterpret_cast<const uint64_t*>(d_pre);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab,
+                       out);
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_sched_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_sched_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
+                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                  const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                                  uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_sched_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
+                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
+                     reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
+                     reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx

@@ -468,8 +468,8 @@ struct tmx_ctx {
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
   // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
-  void* d_set_sha[5][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; row 4: set 7, whose one section uses slot 0)
-  size_t set_sha_bytes[5][3] = {};
+  void* d_set_sha[6][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4, 5: sets 7 and 8, whose one section uses slot 0)
+  size_t set_sha_bytes[6][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
@@ -480,6 +480,10 @@ struct tmx_ctx {
   // | the three extended planes (3 M: the part that grows)
   void* d_air7 = nullptr;
   size_t air7_bytes = 0;
+  // constraint set 8 (tmx_air_sha512_sched_*), a scratch of its own so that set 7's stays as it is: the barycentric kernel's rows | SCH
+  // before the LDE (N) | the extended plane (M: the part that grows)
+  void* d_air8 = nullptr;
+  size_t air8_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1479,6 +1483,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_air2) (void)hipFree(c->d_air2);
   if (c->d_air6) (void)hipFree(c->d_air6);
   if (c->d_air7) (void)hipFree(c->d_air7);
+  if (c->d_air8) (void)hipFree(c->d_air8);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -4591,6 +4596,22 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // reads the three extended preprocessed planes of d_air7 instead of period-64 tables (sha_pass; sha512_periodic fills and extends them in
 // front of it), the verifier runs the barycentric kernel in front of its check (sha_verify_call), and the set-level call takes
 // TMX_TRACE_SHA512 alone.  Rows 3 - 6 take none of these branches: they enqueue what they enqueued before the row existed.
+// Set 8 (the SHA-512 message schedule) is the sixth row and takes set 7's branches.  What the two differ in there is a ShaPeriodic the row
+// carries: how many preprocessed planes there are, the context scratch that holds them, and the launches that fill them, read them in the
+// pass and evaluate them at zeta.  Set 7's row names d_air7 and its own launches: it enqueues what it enqueued before.
+struct ShaPeriodic {
+  uint32_t planes, part_words;  // the preprocessed columns; the words of one workgroup's row of the barycentric kernel
+  void* tmx_ctx::*scratch;      // rows of the barycentric kernel | the planes before the LDE [planes][N] | extended [planes][M]
+  size_t tmx_ctx::*bytes;
+  int (*fill)(uint32_t log_rows, void* d_pre, void* stream);
+  int (*tables)(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
+  int (*quotient)(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
+                  const void* d_tab, int form, void* d_quot, void* stream);
+  int (*eval)(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
+  int (*fold)(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
+  int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part, const void* d_open_t,
+               const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
+};
 struct ShaSet {
   uint32_t id, helper_cols;
   bool has_chain, has_public;
@@ -4608,7 +4629,8 @@ struct ShaSet {
   int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho, const void* d_open_t,
                const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
   uint32_t width;     // the table's columns per proof
-  bool has_periodic;  // set 7: preprocessed columns of full degree in place of the period-64 tables
+  bool has_periodic;  // sets 7 and 8: preprocessed columns of full degree in place of the period-64 tables
+  const ShaPeriodic* per;  // what such a set's preprocessed columns are; null without has_periodic
 };
 
 static int sha3_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
@@ -4647,31 +4669,49 @@ static int sha4_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uin
 static int sha7_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
   return launch_air_sha512_helper(log_rows, n_proofs, d_table, d_helper, stream);
 }
+static int sha8_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
+  return launch_air_sha512_sched_helper(log_rows, n_proofs, d_table, d_helper, stream);
+}
+static const ShaPeriodic SHA7_PERIODIC = {3, AIR7_PART_WORDS, &tmx_ctx::d_air7, &tmx_ctx::air7_bytes, launch_air_sha512_periodic,
+                                          launch_air_sha512_tables, launch_air_sha512_quotient, launch_air_sha512_periodic_eval,
+                                          launch_air_sha512_periodic_fold, launch_air_sha512_check};
+static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, &tmx_ctx::air8_bytes, launch_air_sha512_sched_periodic,
+                                          launch_air_sha512_sched_tables, launch_air_sha512_sched_quotient, launch_air_sha512_sched_periodic_eval,
+                                          launch_air_sha512_sched_periodic_fold, launch_air_sha512_sched_check};
 
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
 static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
 static const char SHA_BAD_ROWS[] = "log_rows must be 6 .. 27: a SHA-256 block is 64 rows";
-static const ShaSet SHA_SETS[5] = {
+static const ShaSet SHA_SETS[6] = {
     {3, AIR_SHA_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, SHA_BAD_SUB, SHA_BAD_ROWS, "sha", "helper",
      "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
-     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check, AIR_SHA_WIDTH, false},
+     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check, AIR_SHA_WIDTH, false, nullptr},
     {4, AIR_SCHED_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_SCHED_HELPER, TMX_TRACE_SHA256_SCHED_QUOTIENT, 1, SHA_BAD_SUB, SHA_BAD_ROWS,
      "sched", "schedule helper", "the commit set already holds the schedule helper and quotient of that section", "k_helper", "k_helper + 1",
-     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check, AIR_SHA_WIDTH, false},
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha4_helper, sha4_tables, sha4_quotient, sha4_check, AIR_SHA_WIDTH, false,
+     nullptr},
     {5, AIR_INIT_HELPER_COLS, true, false, 6, 27, TMX_TRACE_SHA256_INIT_HELPER, TMX_TRACE_SHA256_INIT_QUOTIENT, 2, SHA_BAD_SUB, SHA_BAD_ROWS, "init",
      "block-start helper", "the commit set already holds the block-start helper and quotient of that section", "k_helper", "k_helper + 1",
      "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", launch_air_init_helper, launch_air_init_tables,
-     launch_air_init_quotient, launch_air_init_check, AIR_SHA_WIDTH, false},
+     launch_air_init_quotient, launch_air_init_check, AIR_SHA_WIDTH, false, nullptr},
     {6, AIR_LINK_HELPER_COLS, false, true, 6 + AIR_SHA_PUBLIC_MIN_LOG_K, 6 + AIR_SHA_PUBLIC_MAX_LOG_K, TMX_TRACE_SHA256_LINK_HELPER,
      TMX_TRACE_SHA256_LINK_QUOTIENT, 3, "log_n - log_blowup must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows",
      "log_rows must be 7 .. 18: the public table has 2 .. 2^12 blocks of 64 rows", "link", "link helper",
      "the commit set already holds the link helper and quotient of that section", "k_helper", "k_helper + 1",
-     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr, AIR_SHA_WIDTH, false},
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr, AIR_SHA_WIDTH, false,
+     nullptr},
     {7, AIR_SHA512_HELPER_COLS, false, false, 7, 18, TMX_TRACE_SHA512_HELPER, TMX_TRACE_SHA512_QUOTIENT, 4,
      "log_n - log_blowup must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them",
      "log_rows must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them", "sha512",
      "SHA-512 helper", "the commit set already holds the SHA-512 helper and quotient of that section", "k_trace + 1", "k_trace + 2",
-     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha7_helper, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true},
+     "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha7_helper, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true,
+     &SHA7_PERIODIC},
+    {8, AIR_SHA512_SCHED_HELPER_COLS, false, false, 7, 18, TMX_TRACE_SHA512_SCHED_HELPER, TMX_TRACE_SHA512_SCHED_QUOTIENT, 5,
+     "log_n - log_blowup must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed column over all of them",
+     "log_rows must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed column over all of them", "sha512_sched",
+     "SHA-512 schedule helper", "the commit set already holds the SHA-512 schedule helper and quotient of that section", "k_helper", "k_helper + 1",
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha8_helper, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true,
+     &SHA8_PERIODIC},
 };
 
 static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
@@ -4774,30 +4814,34 @@ static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, cons
 
 // What set 7 has of its own inside that path: the preprocessed columns.  A scratch of its own (words at d_air7): the barycentric kernel's
 // rows | SEL, KLO, KHI before the LDE [3][N] | the three extended planes [3][M].  One per context, not per section.
-constexpr uint64_t AIR7_OFF_PRE = (uint64_t)AIR7_MAX_PARTS * AIR7_PART_WORDS;
+// Set 8 has the same of its own (words at d_air8) with one plane, SCH: d_air7 does not grow for it.
+static uint64_t sha512_off_pre(const ShaSet& d) { return (uint64_t)AIR7_MAX_PARTS * d.per->part_words; }
+static_assert(AIR7_MAX_PARTS * AIR7_PART_WORDS == 512, "set 7's scratch layout stays as it is");
 
-// the set-7 scratch, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
-static int32_t sha512_scratch(tmx_ctx* c, uint32_t log_m, uint32_t log_sub) {
-  const size_t want = (AIR7_OFF_PRE + (log_m ? ((size_t)3 << log_sub) + ((size_t)3 << log_m) : 0)) * 8;
-  if (c->air7_bytes < want) {
-    if (c->d_air7) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(c->d_air7)); c->d_air7 = nullptr; c->air7_bytes = 0; }
-    HIPCK(c, hipMalloc(&c->d_air7, want));
-    c->air7_bytes = want;
+// the scratch of set 7 or 8, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
+static int32_t sha512_scratch(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_sub) {
+  const size_t planes = d.per->planes, want = (sha512_off_pre(d) + (log_m ? (planes << log_sub) + (planes << log_m) : 0)) * 8;
+  void*& buf = c->*(d.per->scratch);
+  size_t& bytes = c->*(d.per->bytes);
+  if (bytes < want) {
+    if (buf) { HIPCK(c, hipDeviceSynchronize()); HIPCK(c, hipFree(buf)); buf = nullptr; bytes = 0; }
+    HIPCK(c, hipMalloc(&buf, want));
+    bytes = want;
   }
   return TMX_OK;
 }
-static const uint64_t* sha512_planes(const tmx_ctx* c, uint32_t log_sub) {
-  return reinterpret_cast<const uint64_t*>(c->d_air7) + AIR7_OFF_PRE + ((size_t)3 << log_sub);
+static const uint64_t* sha512_planes(const tmx_ctx* c, const ShaSet& d, uint32_t log_sub) {
+  return reinterpret_cast<const uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d) + ((size_t)d.per->planes << log_sub);
 }
 
-// SEL, KLO and KHI filled and extended exactly as helper columns are: under the context's current NTT domain (the set-level call has put
-// the set's domain there)
-static int32_t sha512_periodic(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, void* hip_stream) {
+// The preprocessed columns (SEL, KLO and KHI; SCH) filled and extended exactly as helper columns are: under the context's current NTT
+// domain (the set-level call has put the set's domain there)
+static int32_t sha512_periodic(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_blowup, void* hip_stream) {
   const uint32_t log_sub = log_m - log_blowup;
-  uint64_t* pre = reinterpret_cast<uint64_t*>(c->d_air7) + AIR7_OFF_PRE;
-  const int rc = launch_air_sha512_periodic(log_sub, pre, hip_stream);
-  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha512_periodic launch: ") + hipGetErrorString((hipError_t)rc));
-  return tmx_lde_goldilocks_device(c, log_sub, log_blowup, 3, pre, pre + ((size_t)3 << log_sub), hip_stream);
+  uint64_t* pre = reinterpret_cast<uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d);
+  const int rc = d.per->fill(log_sub, pre, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "periodic", rc);
+  return tmx_lde_goldilocks_device(c, log_sub, log_blowup, d.per->planes, pre, pre + ((size_t)d.per->planes << log_sub), hip_stream);
 }
 
 // gamma from the table cap and the helper cap, into the prover's (verifier = false) or the verifier's challenge words of d_air.  A set with
@@ -4842,8 +4886,8 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
                                   d_quot, s);
   } else if (d.has_periodic) {  // the extended planes (sha512_periodic, in front of this call) instead of the period-64 tables
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-    if ((rc = launch_air_sha512_tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
-    rc = launch_air_sha512_quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, log_n - log_blowup), tab, form, d_quot, s);
+    if ((rc = d.per->tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
+    rc = d.per->quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, d, log_n - log_blowup), tab, form, d_quot, s);
   } else {
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
     if ((rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s)))
@@ -4897,7 +4941,7 @@ static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, ui
   c->air_valid = false;
   if ((st = air_scratch(c, log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, log_n))) return st;
-  if (d.has_periodic && ((st = sha512_scratch(c, log_n, log_n - log_blowup)) || (st = sha512_periodic(c, log_n, log_blowup, hip_stream)))) return st;
+  if (d.has_periodic && ((st = sha512_scratch(c, d, log_n, log_n - log_blowup)) || (st = sha512_periodic(c, d, log_n, log_blowup, hip_stream)))) return st;
   if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, d_pub, false, s))) return st;
   if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * d.width) << log_n),
                      d_helper_cols, d_pub, n_proofs, form, d_quot, s)))
@@ -4939,7 +4983,7 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   if ((st = air_scratch(c, p->log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, 0))) return st;
-  if (d.has_periodic && (st = sha512_scratch(c, 0, 0))) return st;
+  if (d.has_periodic && (st = sha512_scratch(c, d, 0, 0))) return st;
   tmx_batch_layout L;
   batch_layout(*p, L);
   const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
@@ -4959,13 +5003,14 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
     if (rc) return sha_launch_failed(c, d, "combine", rc);
     rc = launch_air_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, B.om64, B.om, B.om_k, B.k_inv, open_t, open_h,
                                open_q, V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, vv, p->n_queries, d_ok, s);
-  } else if (d.has_periodic) {  // the barycentric kernel in front of the check: SEL, KLO, KHI at zeta over the N rows
+  } else if (d.has_periodic) {  // the barycentric kernel in front of the check: the preprocessed columns at zeta over the N rows
     const uint32_t log_sub = log_n - p->log_blowup;
     const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_sub)), n_inv = gl_pow_host(1ull << log_sub, P - 2);
-    rc = launch_air_sha512_periodic_eval(log_sub, om, V + 32 + FRI_ZETA_AT, c->d_air7, s);
+    void* part = c->*(d.per->scratch);
+    rc = d.per->eval(log_sub, om, V + 32 + FRI_ZETA_AT, part, s);
     if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
-    rc = launch_air_sha512_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, c->d_air7, open_t, open_h, open_q,
-                                 V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+    rc = d.per->check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
+                      V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
   } else {
     rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
                  V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
@@ -5043,7 +5088,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
   if (d.has_public && (st = link_scratch(c, log_m))) return st;
-  if (d.has_periodic && (st = sha512_scratch(c, log_m, log_sub))) return st;
+  if (d.has_periodic && (st = sha512_scratch(c, d, log_m, log_sub))) return st;
   // the scratch of this set and section (ShaScratch)
   const bool streamed = by_chunks && chunk_proofs < n_proofs;
   const uint32_t n_hcols = n_proofs * d.helper_cols;
@@ -5131,7 +5176,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
     if (moved && (st = tmx_ntt_set_domain(c, r.root, r.shift))) return st;
     for (uint32_t c0 = 0; c0 < n_hcols && !st; c0 += d.helper_cols)
       st = tmx_lde_goldilocks_device(c, log_sub, r.log_blowup, d.helper_cols, hpre + ((uint64_t)c0 << log_sub), hext + ((uint64_t)c0 << log_m), hip_stream);
-    if (!st && d.has_periodic) st = sha512_periodic(c, log_m, r.log_blowup, hip_stream);
+    if (!st && d.has_periodic) st = sha512_periodic(c, d, log_m, r.log_blowup, hip_stream);
     if (moved) {
       const int32_t back = tmx_ntt_set_domain(c, root, shift);
       if (!st) st = back;
@@ -5362,33 +5407,82 @@ int32_t tmx_trace_commit_set_air_sha512_device(tmx_ctx* c, uint32_t section, uin
   return sha_set_call(c, SHA_SETS[4], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
 }
 
-// the preprocessed columns on their own: what the quotient call fills and extends, and what the verifier evaluates
-int32_t tmx_air_sha512_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+}  // extern "C"
+
+// the preprocessed columns of set 7 or 8 on their own: what the quotient call fills and extends, and what the verifier evaluates
+static int32_t sha_periodic_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
-  const ShaSet& d = SHA_SETS[4];
   if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
   if (log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be at most 6");
   if (!d_pre || (log_blowup && !d_ext)) return fail(c, TMX_ERR_BAD_ARG, "d_pre must be set, and d_ext unless log_blowup is 0");
   HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = launch_air_sha512_periodic(log_rows, d_pre, hip_stream);
+  const int rc = d.per->fill(log_rows, d_pre, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic", rc);
-  return log_blowup ? tmx_lde_goldilocks_device(c, log_rows, log_blowup, 3, d_pre, d_ext, hip_stream) : TMX_OK;
+  return log_blowup ? tmx_lde_goldilocks_device(c, log_rows, log_blowup, d.per->planes, d_pre, d_ext, hip_stream) : TMX_OK;
 }
 
-int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+static int32_t sha_periodic_eval_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
-  const ShaSet& d = SHA_SETS[4];
   if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
   if (!d_zeta || !d_out) return fail(c, TMX_ERR_BAD_ARG, "d_zeta and d_out must be set");
   HIPCK(c, hipSetDevice(c->cfg.device));
-  int32_t st = sha512_scratch(c, 0, 0);
+  int32_t st = sha512_scratch(c, d, 0, 0);
   if (st) return st;
   const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_rows)), n_inv = gl_pow_host(1ull << log_rows, P - 2);
-  int rc = launch_air_sha512_periodic_eval(log_rows, om, d_zeta, c->d_air7, hip_stream);
+  void* part = c->*(d.per->scratch);
+  int rc = d.per->eval(log_rows, om, d_zeta, part, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
-  rc = launch_air_sha512_periodic_fold(log_rows, n_inv, c->d_air7, d_zeta, d_out, hip_stream);
+  rc = d.per->fold(log_rows, n_inv, part, d_zeta, d_out, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic_fold", rc);
   return TMX_OK;
+}
+
+extern "C" {
+
+int32_t tmx_air_sha512_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+  return sha_periodic_call(c, SHA_SETS[4], log_rows, log_blowup, d_pre, d_ext, hip_stream);
+}
+
+int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+  return sha_periodic_eval_call(c, SHA_SETS[4], log_rows, d_zeta, d_out, hip_stream);
+}
+
+// ---- constraint set 8: the message schedule of the SHA-512 table, through row 5 of the host path above
+int32_t tmx_air_sha512_sched_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                           void* hip_stream) {
+  return sha_helper_call(c, SHA_SETS[5], log_rows, n_proofs, 0, d_table, nullptr, d_helper, hip_stream);
+}
+
+int32_t tmx_air_sha512_sched_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                             const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                             uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_call(c, SHA_SETS[5], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_sched_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                   uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                   const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                                   void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[5], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_sched_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                           const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  return sha_verify_call(c, SHA_SETS[5], p, k_trace, k_helper, 0, d_caps, d_proof, nullptr, d_ok, hip_stream);
+}
+
+int32_t tmx_trace_commit_set_air_sha512_sched_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  return sha_set_call(c, SHA_SETS[5], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
+}
+
+int32_t tmx_air_sha512_sched_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+  return sha_periodic_call(c, SHA_SETS[5], log_rows, log_blowup, d_pre, d_ext, hip_stream);
+}
+
+int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+  return sha_periodic_eval_call(c, SHA_SETS[5], log_rows, d_zeta, d_out, hip_stream);
 }
 
 }  // extern "C"

@@ -53,6 +53,11 @@
            columns, alternating; ns_per_helper_word_set7 / _set3 and their ratio.  Under `rocprofv3 --kernel-trace --stats` (MODE=sha512) the
            helper kernel, both hot passes and k_fri_combine show in ONE trace.  Then the set-level call on the SHA512 member of a set
            SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove over table, helper, quotient and HEADER, and the verifier.
+  sha512_sched   constraint set 8 (tmx_air_sha512_sched_*) beside set 4, its yardstick: k_air_sha512_sched_helper over S512_PROOFS proofs (16)
+           x 18 random table columns, then the quotient call of set 8 (SCH filled and extended, gamma, the tables,
+           k_air_sha512_sched_quotient; 248 columns per proof) and of set 4 (SCHED_PROOFS proofs, 32; 124 columns per proof) over random
+           extended columns at M = 2^LOG_M (16), alternating; ps_per_helper_word_set8 / _set4 and their ratio.  Then the set-level call of
+           set 8 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the verifier.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -811,6 +816,88 @@ if "sha512" in modes:
         kt = order.index(SHA512)
         all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
         res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
+    print(json.dumps(res), flush=True)
+    ctx.close()
+
+if "sha512_sched" in modes:
+    # constraint set 8 beside set 4, its yardstick: the helper kernel, then the caller-level quotient call of each set over random extended
+    # columns (S512_PROOFS proofs of 18 + 230 columns against SCHED_PROOFS proofs of 9 + 115, M = 2^LOG_M each: an equal count of words read),
+    # alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512_sched) k_air_sha512_sched_helper, k_air_sha512_sched_quotient and
+    # k_air_sched_quotient show in ONE trace.  ps_per_helper_word: the call's time per helper word read, the figure the two passes are
+    # compared on.  Then the set-level call of set 8 on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
+    log_m, cp, cp4 = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16")), int(os.environ.get("SCHED_PROOFS", "32"))
+    log_rows = log_m - log_blowup
+    torch.manual_seed(seed)
+    ctx = Context(4, b"celestia", device=0)
+
+    def columns(width, helper, proofs):
+        cols = torch.randint(0, 2**62, ((width * proofs) << log_m,), dtype=torch.int64, device=dev)
+        hcols = torch.randint(0, 2**62, ((helper * proofs) << log_m,), dtype=torch.int64, device=dev)
+        caps = []
+        for c_, k_ in ((cols, width * proofs), (hcols, helper * proofs)):
+            lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+            ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+            caps.append(lv)
+        return cols, hcols, caps
+
+    cols8, hcols8, caps8 = columns(18, 230, cp)
+    cols4, hcols4, caps4 = columns(9, 115, cp4)
+    table = torch.randint(0, 2**62, ((18 * cp) << log_rows,), dtype=torch.int64, device=dev)
+    pre = torch.empty((230 * cp) << log_rows, dtype=torch.int64, device=dev)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    q8 = lambda: ctx.air_sha512_sched_quotient_device(log_m, log_blowup, cap_h, cp, cols8.data_ptr(), hcols8.data_ptr(),
+                                                      caps8[0][-(4 << cap_h):].data_ptr(), caps8[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0)
+    q4 = lambda: ctx.air_sha256_sched_quotient_device(log_m, log_blowup, cap_h, cp4, cols4.data_ptr(), hcols4.data_ptr(),
+                                                      caps4[0][-(4 << cap_h):].data_ptr(), caps4[1][-(4 << cap_h):].data_ptr(), quot.data_ptr(), 0)
+    res = {"mode": "sha512_sched", "log_m": log_m, "proofs_set8": cp, "proofs_set4": cp4, "read_gib_set8": round(((232 * cp) << log_m) * 8 / 2**30, 2),
+           "read_gib_set4": round(((116 * cp4) << log_m) * 8 / 2**30, 2), "reps": reps, "helper_kernel_ms": [], "sha512_sched_quotient_call_ms": [],
+           "sha256_sched_quotient_call_ms": []}
+    for _ in range(rounds):
+        res["helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha512_sched_helper_device(log_rows, cp, table.data_ptr(), pre.data_ptr(), 0), reps)))
+        res["sha512_sched_quotient_call_ms"].append(r4(timed(q8, reps)))
+        res["sha256_sched_quotient_call_ms"].append(r4(timed(q4, reps)))
+    res["quotient_sha256"] = words_digest(q8, quot)
+    ps8 = min(res["sha512_sched_quotient_call_ms"]) * 1e9 / ((230 * cp) << log_m)
+    ps4 = min(res["sha256_sched_quotient_call_ms"]) * 1e9 / ((115 * cp4) << log_m)
+    res.update(ps_per_helper_word_set8=round(ps8, 2), ps_per_helper_word_set4=round(ps4, 2), ratio_set8_over_set4=round(ps8 / ps4, 3),
+               helper_store_gb_per_s=round(((230 * cp) << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e6, 1))
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols8, hcols8, caps8, cols4, hcols4, caps4, table, pre, quot
+    torch.cuda.empty_cache()
+    # the set-level call of set 8 on SHA512
+    from tendermintx_amd.synth import bench_workload
+    sp = int(os.environ.get("S512_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    SHA512, HEADER = 2, 32
+    cw = 4 << cap_h
+    scaps, cap_h_, cap_q = (torch.zeros(k * cw, dtype=torch.int64, device=dev) for k in (2, 1, 1))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA512 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    res = {"mode": "sha512_sched_set", "proofs": sp, "n": n, "reps": reps, "commit_ms": r4(timed(commit, 2)), "air_sha512_sched_ms": [], "prove_with_ms": []}
+    for _ in range(rounds):
+        res["air_sha512_sched_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_sha512_sched_device(SHA512, cap_h_.data_ptr(), cap_q.data_ptr(), 0),
+                                                   reps, before=commit)))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(SHA512)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
+        res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_sched_verify_device(bp, kt, kt + 1, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
         res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
         res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
         del proof
