@@ -1541,7 +1541,8 @@ int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t secti
  *              KL - LIVE K(x): every constraint has degree <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient
  *              oracle still suffices.  Zero blocks and zero padding satisfy all 628 with LIVE = 0.
  *   NOT PROVED by set 7: the message schedule (W_t for t >= 16) and W's limb range -- both are constraint set 8 below --; the IV and the
- *              feed-forward of the two blocks; the link of message and digest to Level-1, and so of h; LIVE against anything public.
+ *              feed-forward of the two blocks -- constraint set 9 below --; the link of message and digest to Level-1, and so of h; LIVE
+ *              against anything public.
  *              Under set 7 ALONE a block re-run consistently from a changed W_t goes undetected (tests/test_sha512_air.py records it;
  *              set 8 rejects it, tests/test_sha512_sched.py).
  *   challenge  a fresh duplex, as set 3: observe 2^33, then the set id 7, log_n, log_blowup, cap_height, n_proofs, then the table cap, then
@@ -1633,7 +1634,8 @@ int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, con
  *              Every nonlinear constraint has degree 2 and no selector, the two selected ones are SCH (linear): every constraint has degree
  *              <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient oracle suffices, as in set 7.  Zero blocks and
  *              zero padding satisfy all 234.
- *   NOT PROVED by sets 7 + 8: the IV and the feed-forward of the two blocks; the link of message and digest to Level-1, and so of h; LIVE
+ *   NOT PROVED by sets 7 + 8: the IV and the feed-forward of the two blocks, which constraint set 9 below proves; the link of message and
+ *              digest to Level-1, and so of h; LIVE
  *              against anything public; and so a message word W_t, t < 16, changed with the schedule recomputed from it goes undetected
  *              (tests/test_sha512_sched.py records it).
  *   challenge  word for word set 7's with the set id 8: a fresh duplex observes 2^33, then 8, log_n, log_blowup, cap_height, n_proofs, then
@@ -1666,7 +1668,8 @@ int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, con
  * Scratch: per section set 3's formula with 230 columns, and once per context ((N + M) + 256) 8 bytes of its own for SCH and the
  * barycentric kernel's rows (set 7's context scratch is not touched).  The streamed call keeps refusing every constraint_set but 3, 4 and 5.
  * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers the quotient calls
- * and the set-level call.  Follow-ups: the block starts of T.2 (IV, feed-forward), its link to Level-1, a streamed form of the helper. */
+ * and the set-level call.  The block starts of T.2 (IV, feed-forward) are constraint set 9 below.  Follow-ups: the link of T.2 to Level-1,
+ * a streamed form of the helper. */
 #define TMX_AIR_SHA512_SCHED_HELPER_COLS 230
 #define TMX_AIR_SHA512_SCHED_CONSTRAINTS 234
 #define TMX_TRACE_SHA512_SCHED_HELPER 131072u
@@ -1685,6 +1688,122 @@ int32_t tmx_air_sha512_sched_verify_device(tmx_ctx* ctx, const tmx_batch_params*
 int32_t tmx_trace_commit_set_air_sha512_sched_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 int32_t tmx_air_sha512_sched_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
 int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
+
+/* ---- the block starts of the SHA-512 table (constraint set 9) ----------------------------------------------------------------------------
+ * Sets 7 and 8 prove that every live 80-row block of T.2 is a real SHA-512 compression FROM THE STATE IN FRONT OF IT, and tie that state
+ * to nothing: SEL is 0 on the last row of every block and on row N - 1, so row 0 of a block is free.  Set 9 is the BLOCK STARTS: the
+ * sibling of set 5 on 64-bit words in lo / hi limbs, with sets 7 and 8's preprocessed columns in the place of set 5's subgroup selectors.
+ * It proves that every live hash starts from the SHA-512 IV and that the second block of a lane starts from IV + (the state after round
+ * 79 of the first block) mod 2^64.  Everything is additive: no existing kernel, launch, transcript word, refusal, scratch layout or proof
+ * word changes; the batch prover, its proof format and tmx_batch_verify_device are used UNCHANGED.  Same field, extension, duplex and
+ * caveats as above.  Notation as in sets 5 and 7: a prime is the value at omega x, rows are cyclic inside a proof, operands are the low
+ * 32 bits of a table word, limb 0 is lo and limb 1 is hi.
+ *   table      T.2 as in set 7: 18 n_proofs columns of 32-bit limbs; inside a proof W at 0, 1 and the state words s_0 .. s_7 = a .. h at
+ *              2 + 2 j + limb.  A lane is two blocks of 80 rows; row t of a block holds W_t and a .. h AFTER round t; the first block
+ *              starts from IV512, an unused second block is zero.
+ *   row 0      of a block that starts from H_0 .. H_7 is round 0 applied to them: b = H_0, c = H_1, d = H_2, f = H_4, g = H_5, h = H_6,
+ *              a = T1 + T2, e = H_3 + T1 mod 2^64 with T1 = H_7 + Sigma1(H_4) + Ch(H_4, H_5, H_6) + K_0 + W_0 and T2 = Sigma0(H_0) +
+ *              Maj(H_0, H_1, H_2); Sigma0(x) = x >>> 28 xor x >>> 34 xor x >>> 39, Sigma1(x) = x >>> 14 xor x >>> 18 xor x >>> 41,
+ *              K_0 = 0x428a2f98d728ae22.  Six of the eight words stand in row 0 itself.
+ *   preprocessed columns  TWO more public columns of full degree N - 1 that depend on N alone:
+ *                STA_r = 1 where the NEXT row is row 0 of a FIRST block: r mod 160 = 159, AND r = N - 1; 0 elsewhere.
+ *                CHN_r = 1 where r mod 160 = 79 (the next row is row 0 of a second block); 0 elsewhere.
+ *              (2^k - 1) mod 160 is 127, 95, 31, 63 for k = 3, 0, 1, 2 mod 4, never 79 or 159: the wrap row is never a chain row, and
+ *              it must be switched ON in STA explicitly, because row 0 is the first row of a hash -- the opposite of SEL and SCH, whose
+ *              wrap row is switched off.  The prover fills them (k_air_sha512_init_periodic) and extends them exactly as helper columns
+ *              are extended; the verifier commits to nothing and computes STA(zeta) and CHN(zeta) itself, barycentrically over the N rows
+ *              (k_air_sha512_init_periodic_eval, set 7's batching: four rows per F_p^2 inversion, up to 64 workgroups).  gamma does not
+ *              observe them.  A zero denominator clears every verdict.  log_rows 7 .. 18, set 7's range, for the same reason.
+ *   helper     629 columns per proof (set 5's 315 in limbs), bits LSB first, bit indices mod 64; defined for ANY input.  Offsets inside
+ *              a proof:
+ *                0 .. 383   the bits B_i, C_i, D_i, F_i, G_i, H_i of b, c, d, f, g, h of the row, 64 each in this order
+ *              384 .. 447   U0_i = B_(i+28) xor B_(i+34)       448 .. 511   U1_i = F_(i+14) xor F_(i+18)       512 .. 575   V_i = B_i C_i
+ *              576 .. 583   Sigma0(b), Sigma1(f), Ch(f, g, h), Maj(b, c, d), each as lo, hi
+ *              584          LV: set 7's LIVE rule, 1 iff row r - r mod 80 of the proof has a nonzero word
+ *              585 + 2 j + limb   PZ_j = LV(r+1) ((IV_j + s_j(r)) mod 2^64), j = 0 .. 7, on every row
+ *              601 + 2 j + limb   CZL_j, CZH_j: the carry bits of that sum's two limbs (CZL out of IV_(j,lo) + s_(j,lo), CZH out of
+ *                                 IV_(j,hi) + s_(j,hi) + CZL), on every row and whatever LV is
+ *              617 .. 628   three bits each of CAL, CAH, CEL, CEH: the limb carries of the a-sum and the e-sum below, masked to three
+ *                           bits; 0 unless STA or CHN is 1 on the row
+ *              With LV' = LV(r+1), S0' .. MAJ' the four helper words of the next row, and X the start word of the row's kind -- on a
+ *              row with STA = 1: H7 = IV_7 LV', H3 = IV_3 LV'; on a row with CHN = 1: H7 = PZ_7, H3 = PZ_3 -- per limb
+ *                a-sum = H7 + K_0 LV' + S1' + CH' + W' + S0' + MAJ' (+ CAL in the high limb) = a' + 2^32 CA
+ *                e-sum = H3 + H7 + K_0 LV' + S1' + CH' + W' (+ CEL in the high limb) = e' + 2^32 CE
+ *              Seven summands below 2^32 and a carry-in of at most 6: CA <= 6.  Six summands: CE <= 5.  Every identity is an integer
+ *              identity below 2^35.
+ *   constraints  673 per proof, at index j:
+ *                0 .. 383   X^2 - X for the bit columns                 384 .. 399   X^2 - X for CZ (at the column's offset - 217)
+ *              400 .. 411   X^2 - X for the twelve carry bits           412          LV^2 - LV
+ *              413 .. 424   word_limb - sum_(i < 32) 2^i bit_(32 limb + i) for b, c, d, f, g, h (413 + 2 k + limb)
+ *              425 + i      U0_i - (B_(i+28) xor B_(i+34))    489 + i   U1_i - (F_(i+14) xor F_(i+18))    553 + i   V_i - B_i C_i
+ *              617, 618     Sigma0 lo, hi - sum 2^i (U0_j xor B_(j+39))                619, 620   Sigma1 with U1_j xor F_(j+41)
+ *              621, 622     Ch - sum 2^i (H_j + F_j (G_j - H_j))                      623, 624   Maj - sum 2^i (V_j + D_j (B_j + C_j - 2 V_j))
+ *              625 + 2 j + limb   PZ_(j,limb) - LV' (IV_(j,limb) + s_(j,limb) [+ CZL_j in the high limb] - 2^32 CZ_(j,limb)): holds on
+ *                                 every row by construction, no selector
+ *              641 .. 656   STA(x) times: 641 + 2 k + limb   x'_limb - IV_(j,limb) LV' for the six words x = b, c, d, f, g, h
+ *                           (j = 0, 1, 2, 4, 5, 6; k counts them); 653, 654   a'_limb + 2^32 CA_limb [- CAL] - ((IV_7 + K_0)_limbwise LV'
+ *                           + S1' + CH' + W' + S0' + MAJ'); 655, 656   e'_limb + 2^32 CE_limb [- CEL] - ((IV_3 + IV_7 + K_0)_limbwise LV' +
+ *                           S1' + CH' + W'), where "limbwise" adds the constants' limbs as integers
+ *              657 .. 672   CHN(x) times: 657 + 2 k + limb   x'_limb - PZ_(j,limb); 669, 670 the a-sum with PZ_7 + K_0 LV'; 671, 672 the
+ *                           e-sum with PZ_3 + PZ_7 + K_0 LV'
+ *              641 carry no selector; every nonlinear one has degree 2; every selected one is a preprocessed column times a linear form:
+ *              every constraint has degree <= 2 N - 2, the honest quotient degree <= N - 2, and ONE two-column quotient oracle suffices,
+ *              divided by x^N - 1 alone (set 5's D_s and D_c have no counterpart).  Zero blocks, unused second blocks and zero padding
+ *              satisfy all 673 with LV = 0.
+ *   NOT PROVED by sets 7 + 8 + 9 (the follow-ups): the first sixteen W of a block and the digest against Level-1, and so h; LV against
+ *              anything public -- a hash whose live second block is replaced by a zero block goes unseen, as in set 5
+ *              (tests/test_sha512_init.py records both).
+ *   challenge  word for word set 7's with the set id 9: a fresh duplex observes 2^33, then 9, log_n, log_blowup, cap_height, n_proofs, then
+ *              the table cap, then THIS helper's cap; gamma drawn again while gamma.c1 == 0.
+ *   quotient   q(x_i) = sum_p sum_(j < 673) gamma^(673 p + j) C_(p,j)(x_i) / (x_i^N - 1), planar and canonical; pointwise.
+ *   identity   sum_p gamma^(673 p) (A_p + STA(zeta) S_p + CHN(zeta) C_p) == (u_0 + X u_1) (zeta^N - 1), A the gamma sum of constraints
+ *              0 .. 640, S of 641 .. 656 without STA, C of 657 .. 672 without CHN.  The helper's oracle index is explicit, k_helper with
+ *              the quotient at k_helper + 1: [table, H7, Q7, H8, Q8, H9, Q9] is one proof of seven oracles.
+ *   tmx_air_sha512_init_helper_device      the helper (629 n_proofs columns at d_helper) from PRE-LDE table columns (18 n_proofs at d_table).
+ *                                          TMX_ERR_BAD_ARG: log_rows outside 7 .. 18, n_proofs = 0, 629 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_init_quotient_device    fills and extends STA and CHN under the context's CURRENT NTT domain, draws gamma from d_cap
+ *                                          and d_cap_helper, then the quotient of the EXTENDED columns into d_quot (2 << log_n words).
+ *                                          TMX_ERR_BAD_ARG: FRI's rules on log_n and log_blowup, log_n - log_blowup outside 7 .. 18,
+ *                                          n_proofs = 0, 629 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_init_quotient_range_device   set 3's range call: the piece [proof_lo, proof_hi), d_helper_cols that piece's own columns,
+ *                                          written or (accumulate = 1) added; also refused: an empty or overhanging range, accumulate > 1.
+ *   tmx_air_sha512_init_verify_device      tmx_batch_verify_device, the barycentric kernel, then the identity for the oracles k_trace (18 k
+ *                                          columns), k_helper (629 k) and k_helper + 1 (2).  TMX_ERR_BAD_ARG unless the column counts are
+ *                                          these, the three log_n equal, k_helper > k_trace, k_helper + 1 < n_oracles (and the rules above).
+ *   tmx_trace_commit_set_air_sha512_init_device   the set-level call: `section` = TMX_TRACE_SHA512 alone, a RESIDENT member only; the pair
+ *                                          goes behind the pairs of sets 7 and 8 where they follow the table, and their calls insert in front
+ *                                          of it: every call order ends as table, H7, Q7, H8, Q8, H9, Q9 with the same caps and the same
+ *                                          proof.  tmx_trace_commit_set_shape reports TMX_TRACE_SHA512_INIT_HELPER and _INIT_QUOTIENT.
+ *                                          Refused: any other section, an absent or streamed section, a second call on the section, a set
+ *                                          with no room for two more oracles (TMX_BATCH_MAX_ORACLES = 8: the three pairs leave room for one
+ *                                          more table).
+ *   tmx_air_sha512_init_periodic_device    STA and CHN on their own: planar, 2 << log_rows words at d_pre and, extended under the current
+ *                                          NTT domain, 2 << (log_rows + log_blowup) words at d_ext (log_blowup = 0: d_pre alone).
+ *   tmx_air_sha512_init_periodic_eval_device   d_out[0 .. 4) = STA(zeta), CHN(zeta) for the two words at d_zeta, d_out[4] = 1 if a
+ *                                          denominator was zero (d_out: 5 words).  Both refuse log_rows outside 7 .. 18 and null pointers.
+ * Scratch: per section set 3's formula with 629 columns, and once per context (2 (N + M) + 512) 8 bytes of its own for STA, CHN and the
+ * barycentric kernel's rows (the context scratch of sets 7 and 8 is not touched).  The streamed call keeps refusing every constraint_set
+ * but 3, 4 and 5.  Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers
+ * the quotient calls and the set-level call.  Follow-ups: the link of T.2 to Level-1, a streamed form of the helpers of sets 7 - 9 (at
+ * 629 columns the full 256-proof T.2 cannot be resident). */
+#define TMX_AIR_SHA512_INIT_HELPER_COLS 629
+#define TMX_AIR_SHA512_INIT_CONSTRAINTS 673
+#define TMX_TRACE_SHA512_INIT_HELPER 524288u
+#define TMX_TRACE_SHA512_INIT_QUOTIENT 1048576u
+int32_t tmx_air_sha512_init_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                          void* hip_stream);
+int32_t tmx_air_sha512_init_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_init_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_init_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha512_init_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+int32_t tmx_air_sha512_init_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
+int32_t tmx_air_sha512_init_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

@@ -29,6 +29,8 @@ AIR_SHA512_HELPER_COLS, AIR_SHA512_CONSTRAINTS = 599, 628   # TMX_AIR_SHA512_*: 
 TRACE_SHA512_HELPER, TRACE_SHA512_QUOTIENT = 32768, 65536   # TMX_TRACE_SHA512_*: the helper and the quotient of set 7
 AIR_SHA512_SCHED_HELPER_COLS, AIR_SHA512_SCHED_CONSTRAINTS = 230, 234   # TMX_AIR_SHA512_SCHED_*: constraint set 8, the SHA-512 message schedule
 TRACE_SHA512_SCHED_HELPER, TRACE_SHA512_SCHED_QUOTIENT = 131072, 262144   # TMX_TRACE_SHA512_SCHED_*: the helper and the quotient of set 8
+AIR_SHA512_INIT_HELPER_COLS, AIR_SHA512_INIT_CONSTRAINTS = 629, 673   # TMX_AIR_SHA512_INIT_*: constraint set 9, the SHA-512 block starts
+TRACE_SHA512_INIT_HELPER, TRACE_SHA512_INIT_QUOTIENT = 524288, 1048576   # TMX_TRACE_SHA512_INIT_*: the helper and the quotient of set 9
 AIR_SHA256_PUBLIC_WIDTH, AIR_SHA256_LINK_HELPER_COLS, AIR_SHA256_LINK_CONSTRAINTS = 26, 33, 50   # constraint set 6, the link to Level-1
 
 
@@ -434,6 +436,18 @@ def lib():
         L.tmx_trace_commit_set_air_sha512_sched_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_air_sha512_sched_periodic_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_air_sha512_sched_periodic_eval_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
+    try:   # constraint set 9: the block starts of the SHA-512 table
+        L.tmx_air_sha512_init_helper_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_init_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 6
+        L.tmx_air_sha512_init_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 6
+        L.tmx_air_sha512_init_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha512_init_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_init_periodic_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_init_periodic_eval_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

@@ -685,6 +685,42 @@ class Context:
         """d_out[0 .. 2) = SCH at the F_p^2 point at d_zeta, barycentric over the 2^log_rows rows; d_out[2] = 1 on a zero denominator"""
         check(self._L.tmx_air_sha512_sched_periodic_eval_device(self._h, log_rows, d_zeta, d_out, self._stream(stream)), self._h)
 
+    # ---- constraint set 9: the block starts of the SHA-512 table (include/tmx.h)
+    def air_sha512_init_helper_device(self, log_rows, n_proofs, d_table, d_helper, stream=None):
+        """the block-start helper (629 n_proofs columns of 2^log_rows words at d_helper) from the pre-LDE T.2 columns (18 n_proofs) at d_table"""
+        check(self._L.tmx_air_sha512_init_helper_device(self._h, log_rows, n_proofs, d_table, d_helper, self._stream(stream)), self._h)
+
+    def air_sha512_init_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_quot,
+                                        stream=None, proof_range=None, accumulate=0):
+        """STA and CHN filled and extended, gamma from the table cap and the helper cap, then the quotient of the 673 constraints per proof
+        over the extended table and helper columns into d_quot (planar, 2 << log_n words); proof_range and accumulate as in
+        air_sha256_quotient_device"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha512_init_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                                    d_helper_cols, d_cap, d_cap_helper, d_quot, self._stream(stream)), self._h)
+            return
+        check(self._L.tmx_air_sha512_init_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap,
+                                                          d_cap_helper, d_quot, self._stream(stream)), self._h)
+
+    def air_sha512_init_verify_device(self, params, k_trace, k_helper, d_caps, d_proof, d_ok, stream=None):
+        """batch_verify_device, then the set-9 identity at zeta for the oracles k_trace (table), k_helper (helper), k_helper + 1 (quotient)"""
+        check(self._L.tmx_air_sha512_init_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, k_helper, d_caps, d_proof, d_ok,
+                                                        self._stream(stream)), self._h)
+
+    def trace_commit_set_air_sha512_init_device(self, section, d_cap_h, d_cap_q, stream=None):
+        """adds the SHA-512 block-start helper and quotient of the resident member `section` (SHA512 only) to the commit set, behind the
+        table or behind the pairs of sets 7 and 8"""
+        check(self._L.tmx_trace_commit_set_air_sha512_init_device(self._h, section, d_cap_h, d_cap_q, self._stream(stream)), self._h)
+
+    def air_sha512_init_periodic_device(self, log_rows, log_blowup, d_pre, d_ext, stream=None):
+        """STA, CHN (planar, 2 << log_rows words at d_pre) and, unless log_blowup is 0, their extension under the current NTT domain at d_ext"""
+        check(self._L.tmx_air_sha512_init_periodic_device(self._h, log_rows, log_blowup, d_pre, d_ext, self._stream(stream)), self._h)
+
+    def air_sha512_init_periodic_eval_device(self, log_rows, d_zeta, d_out, stream=None):
+        """d_out[0 .. 4) = STA, CHN at the F_p^2 point at d_zeta, barycentric over the 2^log_rows rows; d_out[4] = 1 on a zero denominator"""
+        check(self._L.tmx_air_sha512_init_periodic_eval_device(self._h, log_rows, d_zeta, d_out, self._stream(stream)), self._h)
+
     # ---- streamed helpers of constraint sets 3 - 5 (include/tmx.h "streamed helpers of the SHA-256 sets")
     def trace_commit_set_air_sha256_streamed_device(self, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q, stream=None):
         """the set-level call of constraint set 3, 4 or 5 with the helper fed in chunks of chunk_proofs whole proofs and never resident

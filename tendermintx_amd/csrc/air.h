@@ -283,4 +283,41 @@ int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t 
                                   const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
                                   uint32_t n_queries, void* d_ok, void* stream);
 
+// ---- constraint set 9: the block starts of the SHA-512 table (include/tmx.h "the block starts of the SHA-512 table").  Set 7's table, a
+// helper oracle of 629 columns per proof (set 5's 315 in lo / hi limbs), 673 constraints per proof; gamma comes from set 3's lone-lane
+// kernel with the set id 9 in obs[0] (launch_air_sha_gamma: the same code object).  The selectors "the next row starts a hash" and "the
+// next row starts a second block" have the period 160 with a wrap row of their own: two more preprocessed columns of full degree (STA,
+// CHN), filled, extended and evaluated as set 7's three are.
+constexpr uint32_t AIR_SHA512_INIT_HELPER_COLS = 629, AIR_SHA512_INIT_CONSTRAINTS = 673;
+// The tables one set-9 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
+//   gpow  [675][2]               gamma^0 .. gamma^673, then gamma^(673 first)
+//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
+constexpr uint32_t AIR9_TAB_GPOW = 0, AIR9_TAB_ZINV = 1408;
+constexpr uint64_t AIR9_TAB_WORDS = AIR9_TAB_ZINV + 64;
+static_assert(2 * (AIR_SHA512_INIT_CONSTRAINTS + 2) <= AIR9_TAB_ZINV && AIR9_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-9 tables live in the table part of set 1's scratch");
+// The barycentric kernel's output: one row of AIR9_PART_WORDS words per workgroup (four words of the two sums, a zero-denominator flag,
+// three unused); the workgroups are set 7's (air_sha512_eval_parts: 1024 rows each, at most AIR7_MAX_PARTS)
+constexpr uint32_t AIR9_PART_WORDS = 8;
+// STA and CHN before the LDE (planar, 2 << log_rows words at d_pre): one lane per row
+int launch_air_sha512_init_periodic(uint32_t log_rows, void* d_pre, void* stream);
+// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 629 n_proofs
+int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
+// s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
+int launch_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
+// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(673 p + j) C_(p,j) / (x^N - 1); d_pre the two extended
+// preprocessed planes (STA, CHN; 2 << log_m words); form as in launch_air_sha_quotient
+int launch_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                                    const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream);
+// The barycentric sums of STA and CHN at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N:
+// air_sha512_eval_parts(log_rows) rows at d_part
+int launch_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
+// d_out[0 .. 4) = STA(zeta), CHN(zeta), d_out[4] = 1 if a denominator was zero; n_inv = 1 / N
+int launch_air_sha512_init_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
+// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with
+// STA and CHN at zeta from the barycentric kernel's rows at d_part
+int launch_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                 const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                                 uint32_t n_queries, void* d_ok, void* stream);
+
 }  // namespace tmx

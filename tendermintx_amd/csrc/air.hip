@@ -2609,4 +2609,434 @@ int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t 
   return (int)hipGetLastError();
 }
 
+// ---- constraint set 9: the block starts of the SHA-512 table (include/tmx.h "the block starts of the SHA-512 table") ------------------------
+// A sibling of set 5 on T.2: row 0 of a block is round 0 applied to the eight words the block starts from, so six of them stand in row 0
+// itself (b, c, d, f, g, h) and set 7's bit loop runs on them with the register names shifted by one.  A lane is two blocks of 80 rows:
+// the selectors "the next row starts a hash" and "the next row starts a second block" are two more preprocessed columns of full degree
+// (STA, CHN), filled, extended and evaluated at zeta as set 7's three are.  Nothing above changes.
+// Helper column offsets inside a proof's 629 (a word's low limb first; PZ_j and CZ_j at + 2 j), constraint indices inside its 673.
+constexpr uint32_t Y_B = 0, Y_C = 64, Y_D = 128, Y_F = 192, Y_G = 256, Y_H = 320, Y_U0 = 384, Y_U1 = 448, Y_V = 512, Y_S0 = 576, Y_S1 = 578,
+                   Y_CH = 580, Y_MAJ = 582, Y_LV = 584, Y_PZ = 585, Y_CZ = 601, Y_CAL = 617, Y_CAH = 620, Y_CEL = 623, Y_CEH = 626;
+constexpr uint32_t JY_CZ = 384, JY_CARRY = 400, JY_LV = 412, JY_WORD = 413, JY_U0 = 425, JY_U1 = 489, JY_V = 553, JY_S0 = 617, JY_S1 = 619,
+                   JY_CH = 621, JY_MAJ = 623, JY_PZ = 625, JY_START = 641, JY_CHAIN = 657;
+constexpr uint32_t SHA512_LANE = 2 * SHA512_BLOCK;
+__device__ __constant__ const uint64_t IV_SHA512[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                                       0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+constexpr uint64_t INIT512_IV3 = 0xa54ff53a5f1d36f1ull, INIT512_IV7 = 0x5be0cd19137e2179ull, INIT512_K0 = 0x428a2f98d728ae22ull;
+// limb l of a 64-bit constant
+__host__ __device__ constexpr uint64_t limb_of(uint64_t x, uint32_t l) { return l ? x >> 32 : x & 0xffffffffull; }
+
+// STA at row r of N: on where the NEXT row is row 0 of a first block.  The wrap row N - 1 is switched on explicitly: row 0 starts a hash,
+// and (N - 1) mod 160 is 127, 95, 31 or 63, never 159.  CHN: on where the next row is row 0 of a second block (never the wrap row).
+__device__ __forceinline__ bool sha512_sta(uint32_t r, uint32_t n) { return r % SHA512_LANE == SHA512_LANE - 1 || r == n - 1; }
+__device__ __forceinline__ bool sha512_chn(uint32_t r) { return r % SHA512_LANE == SHA512_BLOCK - 1; }
+
+// One lane per row: STA and CHN before the LDE, planar (2 << log_rows words)
+__global__ __launch_bounds__(256) void k_air_sha512_init_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
+  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= N) return;
+  pre[r] = sha512_sta(r, N) ? 1 : 0;
+  pre[(size_t)N + r] = sha512_chn(r) ? 1 : 0;
+}
+
+// One lane per (proof, row) of the pre-LDE table, k_air_sha512_helper's shape: the eighteen limbs of the row and the block's first row
+// (LV), then 629 stores, each of them consecutive words of one column across the wave.  The next row (cyclic inside the proof) is loaded
+// only where STA or CHN is on: there it is row 0 of its block, so it gives LV' and the two round-0 sums; on every other row the next row
+// lies in the lane's own block and LV' = LV.  Operands are the low 32 bits of the words.
+__global__ __launch_bounds__(256) void k_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                                uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows), N = 1u << log_rows;
+  const uint32_t r = (uint32_t)(idx & (N - 1)), r0 = r - r % SHA512_BLOCK;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA512_WIDTH) << log_rows);
+  uint32_t w[AIR_SHA512_WIDTH], any = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < AIR_SHA512_WIDTH; c++) {
+    w[c] = (uint32_t)t[((uint64_t)c << log_rows) + r];
+    any |= (uint32_t)t[((uint64_t)c << log_rows) + r0];
+  }
+  const uint32_t live = any ? 1u : 0u;
+  const bool chn = sha512_chn(r), edge = chn || sha512_sta(r, N);
+  uint32_t n[AIR_SHA512_WIDTH] = {}, live_next = live;
+  if (edge) {
+    const uint32_t rn = (r + 1) & (N - 1);
+    uint32_t any_next = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < AIR_SHA512_WIDTH; c++) {
+      n[c] = (uint32_t)t[((uint64_t)c << log_rows) + rn];
+      any_next |= n[c];
+    }
+    live_next = any_next ? 1u : 0u;
+  }
+  auto word = [&](const uint32_t* x, uint32_t c) { return (uint64_t)x[c] | (uint64_t)x[c + 1] << 32; };
+  const uint64_t b = word(w, R_B), c = word(w, R_C), d = word(w, R_D), f = word(w, R_F), g = word(w, R_G), hh = word(w, R_H);
+  const uint64_t u0 = rotr64(b, 28) ^ rotr64(b, 34), u1 = rotr64(f, 14) ^ rotr64(f, 18), v = b & c;
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA512_INIT_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll 4
+  for (uint32_t i = 0; i < 64; i++) {
+    put(Y_B + i, (b >> i) & 1);
+    put(Y_C + i, (c >> i) & 1);
+    put(Y_D + i, (d >> i) & 1);
+    put(Y_F + i, (f >> i) & 1);
+    put(Y_G + i, (g >> i) & 1);
+    put(Y_H + i, (hh >> i) & 1);
+    put(Y_U0 + i, (u0 >> i) & 1);
+    put(Y_U1 + i, (u1 >> i) & 1);
+    put(Y_V + i, (v >> i) & 1);
+  }
+  auto put2 = [&](uint32_t col, uint64_t x) {
+    put(col, (uint32_t)x);
+    put(col + 1, x >> 32);
+  };
+  put2(Y_S0, u0 ^ rotr64(b, 39));
+  put2(Y_S1, u1 ^ rotr64(f, 41));
+  put2(Y_CH, (f & g) ^ (~f & hh));
+  put2(Y_MAJ, (b & c) ^ (b & d) ^ (c & d));
+  put(Y_LV, live);
+  uint64_t pz3 = 0, pz7 = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t lo = limb_of(IV_SHA512[j], 0) + w[R_A + 2 * j], czl = lo >> 32;
+    const uint64_t hi = limb_of(IV_SHA512[j], 1) + w[R_A + 2 * j + 1] + czl, czh = hi >> 32;
+    const uint64_t pz = live_next ? (uint64_t)(uint32_t)lo | hi << 32 : 0;
+    put2(Y_PZ + 2 * j, pz);
+    put(Y_CZ + 2 * j, czl);
+    put(Y_CZ + 2 * j + 1, czh);
+    if (j == 3) pz3 = pz;
+    if (j == 7) pz7 = pz;
+  }
+  uint32_t cal = 0, cah = 0, cel = 0, ceh = 0;
+  if (edge) {  // round 0 of the next row's block, from the IV (a start row) or from PZ (a chain row)
+    const uint64_t nb = word(n, R_B), nc = word(n, R_C), nd = word(n, R_D), nf = word(n, R_F), ng = word(n, R_G), nh = word(n, R_H);
+    const uint64_t s0 = rotr64(nb, 28) ^ rotr64(nb, 34) ^ rotr64(nb, 39), s1 = rotr64(nf, 14) ^ rotr64(nf, 18) ^ rotr64(nf, 41);
+    const uint64_t chv = (nf & ng) ^ (~nf & nh), mjv = (nb & nc) ^ (nb & nd) ^ (nc & nd);
+    const uint64_t k0 = live_next ? INIT512_K0 : 0;
+    const uint64_t h7 = chn ? pz7 : live_next ? INIT512_IV7 : 0, h3 = chn ? pz3 : live_next ? INIT512_IV3 : 0;
+    const uint64_t t1_lo = limb_of(s1, 0) + limb_of(chv, 0) + n[R_W] + limb_of(k0, 0);
+    const uint64_t t1_hi = limb_of(s1, 1) + limb_of(chv, 1) + n[R_W + 1] + limb_of(k0, 1);
+    cal = (uint32_t)((limb_of(h7, 0) + t1_lo + limb_of(s0, 0) + limb_of(mjv, 0)) >> 32) & 7;
+    cah = (uint32_t)((limb_of(h7, 1) + t1_hi + limb_of(s0, 1) + limb_of(mjv, 1) + cal) >> 32) & 7;
+    cel = (uint32_t)((limb_of(h3, 0) + limb_of(h7, 0) + t1_lo) >> 32) & 7;
+    ceh = (uint32_t)((limb_of(h3, 1) + limb_of(h7, 1) + t1_hi + cel) >> 32) & 7;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 3; k++) {
+    put(Y_CAL + k, (cal >> k) & 1);
+    put(Y_CAH + k, (cah >> k) & 1);
+    put(Y_CEL + k, (cel >> k) & 1);
+    put(Y_CEH + k, (ceh >> k) & 1);
+  }
+}
+
+// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^673, gamma^(673 first); the selectors are columns, not tables
+__global__ __launch_bounds__(256) void k_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
+                                                                const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_INIT_CONSTRAINTS, tab + AIR9_TAB_ZINV, tab + AIR9_TAB_GPOW);
+}
+
+// The 673 constraints of one proof at one point.  The bit loop is set 7's (air_sha512_constraints) on b, c, d, f, g, h in the roles a, b,
+// c, e, f, g: per 32-bit limb, the high limb first, the rotations of SHA-512 taken mod 64 across both limbs as column offsets, a limb's
+// ten word sums spent on its word constraints before the other limb starts.  Behind it LV, the twelve carry bits, and one rolled loop
+// over the eight words the next block starts from: per word and limb the CZ bit, the PZ constraint (it holds on every row: no selector)
+// and, for the six words that stand in row 0, the two selected linear forms at the next row.  The selected forms go to two gamma sums
+// of their own (started, chained): STA(x) and CHN(x) are factored out of them, the kernel applies each once.
+template <class F, class View>
+__device__ __forceinline__ void air_sha512_init_constraints(View& at) {
+  using A = Forms<F>;
+  using T = typename F::T;
+#pragma unroll 1
+  for (uint32_t l = 2; l-- > 0;) {
+    RoundWords<F> w = {F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero()};
+#pragma unroll View::BITS
+    for (uint32_t b = 32; b-- > 0;) {
+      const uint32_t i = 32 * l + b;
+      const T B = at.again(Y_B + i), C = at.once(Y_C + i), D = at.once(Y_D + i), F_ = at.again(Y_F + i), G = at.once(Y_G + i), H = at.once(Y_H + i);
+      const T U0 = at.once(Y_U0 + i), U1 = at.once(Y_U1 + i), V = at.once(Y_V + i);
+      const T B28 = at.again(Y_B + ((i + 28) & 63)), B34 = at.again(Y_B + ((i + 34) & 63)), B39 = at.again(Y_B + ((i + 39) & 63));
+      const T F14 = at.again(Y_F + ((i + 14) & 63)), F18 = at.again(Y_F + ((i + 18) & 63)), F41 = at.again(Y_F + ((i + 41) & 63));
+      at.plain(Y_B + i, A::boolean(B));
+      at.plain(Y_C + i, A::boolean(C));
+      at.plain(Y_D + i, A::boolean(D));
+      at.plain(Y_F + i, A::boolean(F_));
+      at.plain(Y_G + i, A::boolean(G));
+      at.plain(Y_H + i, A::boolean(H));
+      at.plain(JY_U0 + i, A::sub(U0, A::exor(B28, B34)));
+      at.plain(JY_U1 + i, A::sub(U1, A::exor(F14, F18)));
+      at.plain(JY_V + i, A::sub(V, A::mul(B, C)));
+      w.a = A::dbl_add(w.a, B);
+      w.b = A::dbl_add(w.b, C);
+      w.c = A::dbl_add(w.c, D);
+      w.e = A::dbl_add(w.e, F_);
+      w.f = A::dbl_add(w.f, G);
+      w.g = A::dbl_add(w.g, H);
+      w.s0 = A::dbl_add(w.s0, A::exor(U0, B39));
+      w.s1 = A::dbl_add(w.s1, A::exor(U1, F41));
+      w.ch = A::dbl_add(w.ch, A::add(H, A::mul(F_, A::sub(G, H))));
+      w.maj = A::dbl_add(w.maj, A::add(V, A::mul(D, A::sub(A::add(B, C), A::add(V, V)))));
+    }
+    at.plain(JY_WORD + 0 + l, A::sub(at.tbl(R_B + l), w.a));
+    at.plain(JY_WORD + 2 + l, A::sub(at.tbl(R_C + l), w.b));
+    at.plain(JY_WORD + 4 + l, A::sub(at.tbl(R_D + l), w.c));
+    at.plain(JY_WORD + 6 + l, A::sub(at.tbl(R_F + l), w.e));
+    at.plain(JY_WORD + 8 + l, A::sub(at.tbl(R_G + l), w.f));
+    at.plain(JY_WORD + 10 + l, A::sub(at.tbl(R_H + l), w.g));
+    at.plain(JY_S0 + l, A::sub(at.again(Y_S0 + l), w.s0));
+    at.plain(JY_S1 + l, A::sub(at.again(Y_S1 + l), w.s1));
+    at.plain(JY_CH + l, A::sub(at.again(Y_CH + l), w.ch));
+    at.plain(JY_MAJ + l, A::sub(at.again(Y_MAJ + l), w.maj));
+  }
+  at.plain(JY_LV, A::boolean(at.again(Y_LV)));
+  T carry[4];  // the values CAL, CAH, CEL, CEH (this loop in full under either view: carry stays in registers)
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    const T x0 = at.once(Y_CAL + 3 * k), x1 = at.once(Y_CAL + 3 * k + 1), x2 = at.once(Y_CAL + 3 * k + 2);
+    at.plain(JY_CARRY + 3 * k, A::boolean(x0));
+    at.plain(JY_CARRY + 3 * k + 1, A::boolean(x1));
+    at.plain(JY_CARRY + 3 * k + 2, A::boolean(x2));
+    carry[k] = A::add(x0, A::add(A::add(x1, x1), A::scale(x2, 4)));
+  }
+  // PZ_(j,l) - LV' (IV_(j,l) + s_(j,l) [+ CZL_j] - 2^32 CZ_(j,l)), and with each of the six words that stand in row 0 its two selected
+  // linear forms per limb: the next row's limb against IV_(j,l) LV' (start rows) and against PZ_(j,l) (chain rows).  Rolled over j.
+  const T LVn = at.next(Y_LV);
+  T pz3[2] = {F::zero(), F::zero()}, pz7[2] = {F::zero(), F::zero()};
+#pragma unroll 1
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t iv = IV_SHA512[j];  // (j is uniform: a scalar load)
+    T czl = F::zero();
+#pragma unroll
+    for (uint32_t l = 0; l < 2; l++) {
+      const T CZ = at.once(Y_CZ + 2 * j + l), PZ = at.once(Y_PZ + 2 * j + l);
+      at.plain(JY_CZ + 2 * j + l, A::boolean(CZ));
+      T s = A::sub(A::add_const(at.tbl(R_A + 2 * j + l), limb_of(iv, l)), A::scale(CZ, 1ull << 32));
+      if (l) s = A::add(s, czl);  // the carry out of the low limb comes in
+      else czl = CZ;
+      at.plain(JY_PZ + 2 * j + l, A::sub(PZ, A::mul(LVn, s)));
+      if (j == 3) pz3[l] = PZ;
+      if (j == 7) pz7[l] = PZ;
+      if (j != 3 && j != 7) {
+        const uint32_t k = j < 3 ? j : j - 1;
+        const T xn = at.tbl_next(R_B + 2 * j + l);
+        at.started(JY_START + 2 * k + l, A::sub(xn, A::scale(LVn, limb_of(iv, l))));
+        at.chained(JY_CHAIN + 2 * k + l, A::sub(xn, PZ));
+      }
+    }
+  }
+  // round 0 of the next row's block: a' and e' per limb against the two sums, the low limb's carry entering the high limb
+#pragma unroll
+  for (uint32_t l = 0; l < 2; l++) {
+    const T t1 = A::add(A::add(at.next(Y_S1 + l), at.next(Y_CH + l)), at.tbl_next(R_W + l));
+    const T t12 = A::add(t1, A::add(at.next(Y_S0 + l), at.next(Y_MAJ + l)));
+    T an = A::add(at.tbl_next(R_A + l), A::scale(carry[l], 1ull << 32)), en = A::add(at.tbl_next(R_E + l), A::scale(carry[2 + l], 1ull << 32));
+    if (l) {
+      an = A::sub(an, carry[0]);
+      en = A::sub(en, carry[2]);
+    }
+    const T kl = A::scale(LVn, limb_of(INIT512_K0, l));
+    at.started(JY_START + 12 + l, A::sub(an, A::add(A::scale(LVn, limb_of(INIT512_IV7, l) + limb_of(INIT512_K0, l)), t12)));
+    at.started(JY_START + 14 + l,
+               A::sub(en, A::add(A::scale(LVn, limb_of(INIT512_IV3, l) + limb_of(INIT512_IV7, l) + limb_of(INIT512_K0, l)), t1)));
+    at.chained(JY_CHAIN + 12 + l, A::sub(an, A::add(A::add(pz7[l], kl), t12)));
+    at.chained(JY_CHAIN + 14 + l, A::sub(en, A::add(A::add(pz3[l], pz7[l]), A::add(kl, t1))));
+  }
+}
+
+// The set-9 hot pass, k_air_sha512_quotient's frame: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^673), the eighteen table columns and the 629 helper columns.  pre: the two extended preprocessed planes (STA, CHN; 2 << log_m
+// words), one word each per lane, read once per point.  Per proof v = a + STA(x) b + CHN(x) c; at the end 1 / (x^N - 1).  FORM as in set 3.
+template <int FORM>
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                          const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                          const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
+                                                                          uint64_t* __restrict__ out) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
+  const uint64_t* __restrict__ gp = tab + AIR9_TAB_GPOW;
+  const uint64_t sta = gl_canon(pre[i]), chn = gl_canon(pre[M + i]);
+  const uint64_t zinv = tab[AIR9_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 g673 = {gp[2 * AIR_SHA512_INIT_CONSTRAINTS], gp[2 * AIR_SHA512_INIT_CONSTRAINTS + 1]};
+  gl2 t = {0, 0};
+  for (uint32_t p = n_proofs; p-- > 0;) {
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_INIT_HELPER_COLS) << log_m), gp, log_m, i, nx};
+    air_sha512_init_constraints<FieldP>(at);
+    const gl2 v = {gl_add(gl_add(gl_canon(at.a0), gl_mul(sta, at.b0)), gl_mul(chn, at.c0)),
+                   gl_add(gl_add(gl_canon(at.a1), gl_mul(sta, at.b1)), gl_mul(chn, at.c1))};
+    t = gl2_add(gl2_mul(t, g673), v);
+  }
+  gl2 q = gl2_scale(t, zinv);
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1) + 1]});
+  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
+  out[i] = q.c0;
+  out[M + i] = q.c1;
+}
+
+// STA and CHN at zeta, barycentric over the N rows: k_air_sha512_periodic_eval's batching (thread g of T takes the rows g, g + T, ... four
+// at a time, one F_p^2 inversion per four denominators; up to AIR7_MAX_PARTS workgroups) with two sums, v_r from r itself.  A workgroup's
+// sums meet in LDS and go to its row of `part`: [4] words of the two sums, then 1 if a denominator was zero (such a term is left out).
+// air_sha512_init_periodic_at folds the rows.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
+                                                                                      uint64_t* __restrict__ part) {
+  __shared__ uint64_t red[4][AIR_CHECK_THREADS];
+  __shared__ uint32_t bad;
+  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
+  const uint64_t stride = gl_pow(om, T);
+  uint64_t y = gl_pow(om, g);
+  gl2 ssta = {0, 0}, schn = {0, 0};
+  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
+    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
+    uint64_t yk[AIR7_EVAL_PER];
+    gl2 run = {1, 0};
+#pragma unroll
+    for (int m = 0; m < AIR7_EVAL_PER; m++) {
+      const bool in = r0 + m * T < N;
+      yk[m] = y;
+      den[m] = {gl_sub(z.c0, y), z.c1};
+      pre[m] = run;
+      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
+        bad = 1;
+        den[m] = {1, 0};
+      }
+      if (in) run = gl2_mul(run, den[m]);
+      y = gl_mul(y, stride);
+    }
+    gl2 inv = gl2_inv(run);
+#pragma unroll
+    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
+      const uint32_t r = r0 + m * T;
+      if (r < N) {
+        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
+        inv = gl2_mul(inv, den[m]);
+        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
+        if (sha512_sta(r, N)) ssta = gl2_add(ssta, term);
+        if (sha512_chn(r)) schn = gl2_add(schn, term);
+      }
+    }
+  }
+  const uint32_t t = threadIdx.x;
+  red[0][t] = ssta.c0, red[1][t] = ssta.c1, red[2][t] = schn.c0, red[3][t] = schn.c1;
+  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h)
+      for (uint32_t k = 0; k < 4; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+  }
+  __syncthreads();
+  if (t < 4) part[(size_t)blockIdx.x * AIR9_PART_WORDS + t] = red[t][0];
+  if (t == 4) part[(size_t)blockIdx.x * AIR9_PART_WORDS + 4] = bad;
+}
+
+// STA(zeta), CHN(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
+__device__ __forceinline__ bool air_sha512_init_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2 v[2]) {
+  uint64_t s[4] = {0, 0, 0, 0}, bad = 0;
+  for (uint32_t k = 0; k < n_parts; k++) {
+    for (uint32_t j = 0; j < 4; j++) s[j] = gl_add(s[j], part[(size_t)k * AIR9_PART_WORDS + j]);
+    bad |= part[(size_t)k * AIR9_PART_WORDS + 4];
+  }
+  const gl2 lead = gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv);
+  for (uint32_t j = 0; j < 2; j++) v[j] = gl2_mul(lead, {s[2 * j], s[2 * j + 1]});
+  return bad == 0;
+}
+
+// One thread: the two values (four words), then 1 if a denominator was zero, at out[0 .. 5)
+__global__ void k_air_sha512_init_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
+  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v[2];
+  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_init_periodic_at(part, n_parts, zn, n_inv, v);
+  for (uint32_t j = 0; j < 2; j++) {
+    out[2 * j] = v[j].c0;
+    out[2 * j + 1] = v[j].c1;
+  }
+  out[4] = fine ? 0 : 1;
+}
+
+// The set-9 identity at zeta, one workgroup: gamma^0 .. gamma^673 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
+// their 673 constraints over F_p^2 from the table's and the helper's openings, with STA and CHN at zeta from the barycentric kernel's
+// rows.  A proof contributes gamma^(673 p) (a + STA(zeta) b + CHN(zeta) c); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero
+// denominator in the barycentric sums clears every verdict.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                              uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                                              const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
+                                                                              const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
+                                                                              const uint64_t* __restrict__ gamma, uint32_t n_queries,
+                                                                              uint32_t* __restrict__ ok) {
+  __shared__ uint64_t gpw[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1)];
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, AIR_SHA512_INIT_CONSTRAINTS, gpw);
+  __syncthreads();
+  gl2 zn = {zeta[0], zeta[1]}, pv[2];
+  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
+  const bool fine = air_sha512_init_periodic_at(part, n_parts, zn, n_inv, pv);
+  gl2 sum = {0, 0};
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_INIT_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    air_sha512_init_constraints<FieldP2>(at);
+    const gl2 v = gl2_add(at.a, gl2_add(gl2_mul(pv[0], at.b), gl2_mul(pv[1], at.c)));
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_INIT_CONSTRAINTS * p), v));
+  }
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
+  if (!fine)
+    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+int launch_air_sha512_init_periodic(uint32_t log_rows, void* d_pre, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_init_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
+                     reinterpret_cast<uint64_t*>(d_pre));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sha512_init_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
+                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
+  // (three workgroups: the 675 gamma powers; 2^log_blowup <= 64 inverses)
+  hipLaunchKernelGGL(k_air_sha512_init_tables, dim3((AIR_SHA512_INIT_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof,
+                     s_n, w_n, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                                    const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream) {
+  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
+  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
+  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
+  const uint64_t* pre = reinterpret_cast<const uint64_t*>(d_pre);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
+  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
+  if (form == AIR_FORM_WHOLE)
+    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else if (form == AIR_FORM_PIECE)
+    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+  else
+    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab,
+                       out);
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_init_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_init_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
+                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                 const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                                 uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_init_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
+                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
+                     reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
+                     reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+
 }  // namespace tmx

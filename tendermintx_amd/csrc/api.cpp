@@ -468,8 +468,8 @@ struct tmx_ctx {
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
   // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
-  void* d_set_sha[6][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4, 5: sets 7 and 8, whose one section uses slot 0)
-  size_t set_sha_bytes[6][3] = {};
+  void* d_set_sha[7][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4 .. 6: sets 7, 8 and 9, whose one section uses slot 0)
+  size_t set_sha_bytes[7][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
@@ -484,6 +484,10 @@ struct tmx_ctx {
   // before the LDE (N) | the extended plane (M: the part that grows)
   void* d_air8 = nullptr;
   size_t air8_bytes = 0;
+  // constraint set 9 (tmx_air_sha512_init_*), again a scratch of its own: the barycentric kernel's rows | STA, CHN before the LDE (2 N) |
+  // the two extended planes (2 M: the part that grows)
+  void* d_air9 = nullptr;
+  size_t air9_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1484,6 +1488,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_air6) (void)hipFree(c->d_air6);
   if (c->d_air7) (void)hipFree(c->d_air7);
   if (c->d_air8) (void)hipFree(c->d_air8);
+  if (c->d_air9) (void)hipFree(c->d_air9);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -4599,6 +4604,7 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // Set 8 (the SHA-512 message schedule) is the sixth row and takes set 7's branches.  What the two differ in there is a ShaPeriodic the row
 // carries: how many preprocessed planes there are, the context scratch that holds them, and the launches that fill them, read them in the
 // pass and evaluate them at zeta.  Set 7's row names d_air7 and its own launches: it enqueues what it enqueued before.
+// Set 9 (the SHA-512 block starts) is the seventh row: two planes (STA, CHN) in d_air9, and the same branches.
 struct ShaPeriodic {
   uint32_t planes, part_words;  // the preprocessed columns; the words of one workgroup's row of the barycentric kernel
   void* tmx_ctx::*scratch;      // rows of the barycentric kernel | the planes before the LDE [planes][N] | extended [planes][M]
@@ -4629,7 +4635,7 @@ struct ShaSet {
   int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint32_t chain, uint64_t rho, const void* d_open_t,
                const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
   uint32_t width;     // the table's columns per proof
-  bool has_periodic;  // sets 7 and 8: preprocessed columns of full degree in place of the period-64 tables
+  bool has_periodic;  // sets 7, 8 and 9: preprocessed columns of full degree in place of the period-64 tables
   const ShaPeriodic* per;  // what such a set's preprocessed columns are; null without has_periodic
 };
 
@@ -4675,6 +4681,12 @@ static int sha8_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const voi
 static const ShaPeriodic SHA7_PERIODIC = {3, AIR7_PART_WORDS, &tmx_ctx::d_air7, &tmx_ctx::air7_bytes, launch_air_sha512_periodic,
                                           launch_air_sha512_tables, launch_air_sha512_quotient, launch_air_sha512_periodic_eval,
                                           launch_air_sha512_periodic_fold, launch_air_sha512_check};
+static int sha9_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
+  return launch_air_sha512_init_helper(log_rows, n_proofs, d_table, d_helper, stream);
+}
+static const ShaPeriodic SHA9_PERIODIC = {2, AIR9_PART_WORDS, &tmx_ctx::d_air9, &tmx_ctx::air9_bytes, launch_air_sha512_init_periodic,
+                                          launch_air_sha512_init_tables, launch_air_sha512_init_quotient, launch_air_sha512_init_periodic_eval,
+                                          launch_air_sha512_init_periodic_fold, launch_air_sha512_init_check};
 static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, &tmx_ctx::air8_bytes, launch_air_sha512_sched_periodic,
                                           launch_air_sha512_sched_tables, launch_air_sha512_sched_quotient, launch_air_sha512_sched_periodic_eval,
                                           launch_air_sha512_sched_periodic_fold, launch_air_sha512_sched_check};
@@ -4682,7 +4694,7 @@ static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, 
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
 static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
 static const char SHA_BAD_ROWS[] = "log_rows must be 6 .. 27: a SHA-256 block is 64 rows";
-static const ShaSet SHA_SETS[6] = {
+static const ShaSet SHA_SETS[7] = {
     {3, AIR_SHA_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, SHA_BAD_SUB, SHA_BAD_ROWS, "sha", "helper",
      "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
      "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check, AIR_SHA_WIDTH, false, nullptr},
@@ -4712,6 +4724,12 @@ static const ShaSet SHA_SETS[6] = {
      "SHA-512 schedule helper", "the commit set already holds the SHA-512 schedule helper and quotient of that section", "k_helper", "k_helper + 1",
      "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha8_helper, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true,
      &SHA8_PERIODIC},
+    {9, AIR_SHA512_INIT_HELPER_COLS, false, false, 7, 18, TMX_TRACE_SHA512_INIT_HELPER, TMX_TRACE_SHA512_INIT_QUOTIENT, 6,
+     "log_n - log_blowup must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them",
+     "log_rows must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them", "sha512_init",
+     "SHA-512 block-start helper", "the commit set already holds the SHA-512 block-start helper and quotient of that section", "k_helper",
+     "k_helper + 1", "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha9_helper, nullptr, nullptr, nullptr,
+     AIR_SHA512_WIDTH, true, &SHA9_PERIODIC},
 };
 
 static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
@@ -4814,11 +4832,11 @@ static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, cons
 
 // What set 7 has of its own inside that path: the preprocessed columns.  A scratch of its own (words at d_air7): the barycentric kernel's
 // rows | SEL, KLO, KHI before the LDE [3][N] | the three extended planes [3][M].  One per context, not per section.
-// Set 8 has the same of its own (words at d_air8) with one plane, SCH: d_air7 does not grow for it.
+// Set 8 has the same of its own (words at d_air8) with one plane, SCH: d_air7 does not grow for it.  Set 9 likewise (d_air9; STA, CHN).
 static uint64_t sha512_off_pre(const ShaSet& d) { return (uint64_t)AIR7_MAX_PARTS * d.per->part_words; }
 static_assert(AIR7_MAX_PARTS * AIR7_PART_WORDS == 512, "set 7's scratch layout stays as it is");
 
-// the scratch of set 7 or 8, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
+// the scratch of set 7, 8 or 9, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
 static int32_t sha512_scratch(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_sub) {
   const size_t planes = d.per->planes, want = (sha512_off_pre(d) + (log_m ? (planes << log_sub) + (planes << log_m) : 0)) * 8;
   void*& buf = c->*(d.per->scratch);
@@ -5409,7 +5427,7 @@ int32_t tmx_trace_commit_set_air_sha512_device(tmx_ctx* c, uint32_t section, uin
 
 }  // extern "C"
 
-// the preprocessed columns of set 7 or 8 on their own: what the quotient call fills and extends, and what the verifier evaluates
+// the preprocessed columns of set 7, 8 or 9 on their own: what the quotient call fills and extends, and what the verifier evaluates
 static int32_t sha_periodic_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
   if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
@@ -5483,6 +5501,44 @@ int32_t tmx_air_sha512_sched_periodic_device(tmx_ctx* c, uint32_t log_rows, uint
 
 int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
   return sha_periodic_eval_call(c, SHA_SETS[5], log_rows, d_zeta, d_out, hip_stream);
+}
+
+// ---- constraint set 9: the block starts of the SHA-512 table, through row 6 of the host path above
+int32_t tmx_air_sha512_init_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, uint64_t* d_helper,
+                                          void* hip_stream) {
+  return sha_helper_call(c, SHA_SETS[6], log_rows, n_proofs, 0, d_table, nullptr, d_helper, hip_stream);
+}
+
+int32_t tmx_air_sha512_init_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                            uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_call(c, SHA_SETS[6], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_init_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper, uint64_t* d_quot,
+                                                  void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[6], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, nullptr, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_init_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, uint32_t* d_ok, void* hip_stream) {
+  return sha_verify_call(c, SHA_SETS[6], p, k_trace, k_helper, 0, d_caps, d_proof, nullptr, d_ok, hip_stream);
+}
+
+int32_t tmx_trace_commit_set_air_sha512_init_device(tmx_ctx* c, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
+  return sha_set_call(c, SHA_SETS[6], section, 0, false, nullptr, d_cap_h, d_cap_q, hip_stream);
+}
+
+int32_t tmx_air_sha512_init_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+  return sha_periodic_call(c, SHA_SETS[6], log_rows, log_blowup, d_pre, d_ext, hip_stream);
+}
+
+int32_t tmx_air_sha512_init_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+  return sha_periodic_eval_call(c, SHA_SETS[6], log_rows, d_zeta, d_out, hip_stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,836 @@
+"""The block starts of the SHA-512 table (include/tmx.h "the block starts of the SHA-512 table", constraint set 9):
+tmx_air_sha512_init_helper_device, tmx_air_sha512_init_quotient_device and its range form, tmx_air_sha512_init_verify_device,
+tmx_trace_commit_set_air_sha512_init_device, and the two calls that show the preprocessed columns STA and CHN on their own.  The yardstick
+is tests/sha512_init_model.py on top of tests/batch_model.py: device words must equal the model's word for word and every verdict of the
+device verifier must equal the model verifier's; there are no tolerances.  The CPU part ties the model itself to the claim: on the CPU
+oracle's T.2 rows all 673 constraints hold as integer identities and row 0 of every live block is round 0 from the IV or from the chaining
+value, the quotient is a polynomial of degree N - 2, one change of a detected kind makes it one of degree >= N -- among them the block
+re-run from a changed start state that sets 7 and 8 accept --, and the kinds sets 7 + 8 + 9 do NOT see are recorded next to them."""
+import hashlib
+
+import numpy as np
+import pytest
+
+import air_model as am
+import batch_model as bm
+import deep_model as dm
+import fri_model as fm
+import sha512_air_model as s7
+import sha512_init_model as sm
+import sha512_sched_model as s8
+import test_sha512_air as t7
+import test_sha512_sched as t8
+from batch_model import bparams
+from test_fri import _down, _sentinel, _shift, _up
+from test_sha512_air import _word, device_rows, skip4, step2, step3  # noqa: F401
+from test_sha_air import GUARD, _cap, _degrees, _dev, _guarded, _random_ext, _refused, _tree
+from test_sha_air_shapes import FILLS
+
+P = fm.P
+SHA512, SHA256, HEADER = 2, 4, 32
+H7, Q7, H8, Q8, HELPER, QUOTIENT = 32768, 65536, 131072, 262144, 524288, 1048576
+W, HC, HC7, HC8 = sm.WIDTH, sm.HELPER_COLS, s7.HELPER_COLS, s8.HELPER_COLS
+IV512, M64, M32 = sm.IV512, sm.M64, sm.M32
+CAP_H = 2
+LB = 2  # blow-up 4 in the CPU tests
+
+
+# ---- building and re-running lanes in plain integers
+def _schedule(w16):
+    w = list(w16)
+    for k in range(16, 80):
+        w.append((s8.small_sigma1(w[k - 2]) + w[k - 7] + s8.small_sigma0(w[k - 15]) + w[k - 16]) & M64)
+    return w
+
+
+def _state(t, r):
+    return [_word(t, c, r) for c in range(sm.A_, W, 2)]
+
+
+def _put(t, c, r, x):
+    t[c, r], t[c + 1, r] = x & M32, x >> 32
+
+
+def _run_block(t, r0, start):
+    """rows r0 .. r0 + 79 of the table recomputed from the eight words `start` with the round function, the W column as it stands; returns
+    the state after round 79"""
+    state = list(start)
+    for k in range(80):
+        state = s7.sha_round(state, _word(t, sm.W_, r0 + k), k)
+        for j, x in enumerate(state):
+            _put(t, sm.A_ + 2 * j, r0 + k, x)
+    return state
+
+
+def _run_lane(t, r0, start, second=True):
+    """the lane at r0 re-run consistently from `start`: the first block, and (second) the second block from the chaining value the set
+    states, IV + the state after round 79 mod 2^64"""
+    last = _run_block(t, r0, start)
+    if second:
+        _run_block(t, r0 + 80, [(a + b) & M64 for a, b in zip(IV512, last)])
+
+
+def _hash_lane(msg):
+    """[18][160]: the lane of SHA-512(msg) as tmxo_trace_sha512 lays it out (an unused second block is zero), and the digest"""
+    pad = msg + b"\x80" + bytes(-(len(msg) + 17) % 128) + (8 * len(msg)).to_bytes(16, "big")
+    assert len(pad) in (128, 256)
+    t = np.zeros((W, 160), dtype=np.uint64)
+    start = list(IV512)
+    for b in range(len(pad) // 128):
+        blk = pad[128 * b:128 * b + 128]
+        for k, x in enumerate(_schedule([int.from_bytes(blk[8 * k:8 * k + 8], "big") for k in range(16)])):
+            _put(t, sm.W_, 80 * b + k, x)
+        start = [(a + x) & M64 for a, x in zip(start, _run_block(t, 80 * b, start))]
+    return t, b"".join(x.to_bytes(8, "big") for x in start)
+
+
+def _carries(h):
+    return [int((h[at] + 2 * h[at + 1] + 4 * h[at + 2]).max()) for at in (sm.HCAL, sm.HCAH, sm.HCEL, sm.HCEH)]
+
+
+# ---- CPU
+def test_rows_satisfy_the_constraints_as_integers(skip4, step2, step3):
+    """all 673 constraints hold as integer identities (no reduction mod p) on every row of T.2 of skip N = 4, step N = 2 and step N = 3, with
+    every helper value below 2^32 and every bit column in {0, 1}; on every live boundary round 0 in plain integers, from the IV (first
+    blocks) or from IV + the state after round 79 (second blocks), gives the next row.  The largest carries are printed against their
+    bounds: CAL, CAH <= 6, CEL, CEH <= 5, CZ <= 1"""
+    starts = chains = zero_seconds = 0
+    cmax, czmax = [0, 0, 0, 0], 0
+    bits = list(range(384)) + list(range(sm.HCZ, HC)) + [sm.HLV]
+    for name, table in (("skip4", skip4), ("step2", step2), ("step3", step3)):
+        n_proofs, N = table.shape[0] // W, table.shape[1]
+        help_ = sm.helper(table, n_proofs)
+        assert help_.shape == (n_proofs * HC, N) and int(help_.max()) < 1 << 32
+        for p in range(n_proofs):
+            t, h = table[p * W:(p + 1) * W], help_[p * HC:(p + 1) * HC]
+            assert int(h[bits].max()) <= 1
+            for j, c in enumerate(sm.integer_residuals(t, h)):
+                assert not c.any(), (name, p, j, np.flatnonzero(c)[:4])
+            for lane in range(N // 160):
+                r0 = 160 * lane
+                if t[:, r0].any():
+                    starts += 1
+                    assert _state(t, r0) == sm.round0(IV512, _word(t, sm.W_, r0)), (name, p, lane)
+                    if t[:, r0 + 80].any():
+                        chains += 1
+                        chain = [(a + b) & M64 for a, b in zip(IV512, _state(t, r0 + 79))]
+                        assert _state(t, r0 + 80) == sm.round0(chain, _word(t, sm.W_, r0 + 80)), (name, p, lane)
+                        assert [int(h[sm.HPZ + 2 * j, r0 + 79]) | int(h[sm.HPZ + 2 * j + 1, r0 + 79]) << 32 for j in range(8)] == chain
+                    else:
+                        zero_seconds += 1
+                else:
+                    assert not t[:, r0:r0 + 160].any()
+            cmax = [max(a, b) for a, b in zip(cmax, _carries(h))]
+            czmax = max(czmax, int(h[sm.HCZ:sm.HCZ + 16].max()))
+    print(f"\n[sha512-init] live starts {starts}, live chains {chains}, zero second blocks {zero_seconds}; largest carries CAL {cmax[0]} "
+          f"CAH {cmax[1]} CEL {cmax[2]} CEH {cmax[3]} CZ {czmax}")
+    assert starts and chains and max(cmax[:2]) <= 6 and max(cmax[2:]) <= 5 and czmax <= 1
+
+
+def test_a_one_block_hash_built_in_the_model(oracle):
+    """the real rows have no lane with an unused second block behind a live first one: SHA-512("abc"), one live block and a zero second
+    block, built in plain integers and checked against hashlib, then a two-block message the same way; in a table of N = 512 (the
+    one-block lane at row 0, the two-block lane behind it, zero lanes, padding) all 673 constraints hold as integer identities"""
+    one, d1 = _hash_lane(b"abc")
+    two, d2 = _hash_lane(bytes(range(150)))
+    assert d1 == hashlib.sha512(b"abc").digest() and d2 == hashlib.sha512(bytes(range(150))).digest()
+    assert one[:, :80].any() and not one[:, 80:].any() and two[:, 80].any()
+    t = np.zeros((W, 512), dtype=np.uint64)
+    t[:, :160], t[:, 160:320] = one, two
+    h = sm.helper(t, 1)
+    assert int(h.max()) < 1 << 32 and not h[sm.HLV, 80:160].any() and h[sm.HLV, :80].all()
+    assert not h[sm.HPZ:sm.HPZ + 16, 79].any() and h[sm.HPZ:sm.HPZ + 16, 239].any() and h[sm.HPZ:sm.HPZ + 16, 511].any()
+    for j, c in enumerate(sm.integer_residuals(t, h)):
+        assert not c.any(), (j, np.flatnonzero(c)[:4])
+
+
+def test_sta_and_chn_have_full_degree_and_barycentric_equals_horner(oracle):
+    """STA and CHN interpolate to degree N - 1 = 127 at N = 128, which is why no subgroup selector stands in for them; the model's
+    barycentric values at a zeta outside the base field equal Horner on the interpolated coefficients; the wrap row is ON in STA and off
+    in CHN at every size, and it is never a row with r mod 160 in {79, 159}"""
+    zeta = (0x1234567890ABCDEF % P, 0x0FEDCBA987654321 % P)
+    cols = sm.periodic(128)
+    coefs = [am.coefficients(oracle, c, 1) for c in cols]
+    assert [am.degree(c) for c in coefs] == [127, 127]
+    assert sm.periodic_at(oracle, 7, zeta) == [am.horner(c, zeta) for c in coefs]
+    assert np.flatnonzero(cols[0]).tolist() == [127] and np.flatnonzero(cols[1]).tolist() == [79]
+    assert np.flatnonzero(sm.periodic(256)[0]).tolist() == [159, 255] and np.flatnonzero(sm.periodic(256)[1]).tolist() == [79, 239]
+    for log_rows in range(7, 19):
+        N = 1 << log_rows
+        sta, chn = sm.periodic(N)
+        assert (N - 1) % 160 == {3: 127, 0: 95, 1: 31, 2: 63}[log_rows % 4]
+        assert sta[N - 1] == 1 and chn[N - 1] == 0 and int(sta.sum()) == N // 160 + 1 and int(chn.sum()) == (N + 80) // 160
+        assert not sm.periodic(N, wrap=False)[0][N - 1]
+
+
+def _model_quotient(oracle, table, help_, log_blowup=LB, pre=None):
+    """(extended table, extended helper, gamma, planar quotient) of pre-LDE columns"""
+    n_proofs, log_n = table.shape[0] // W, table.shape[1].bit_length() - 1 + log_blowup
+    ext, hext = oracle.lde(table, log_blowup), oracle.lde(help_, log_blowup)
+    pext = oracle.lde(sm.periodic(table.shape[1]) if pre is None else pre, log_blowup)
+    g = sm.gamma(oracle, log_n, log_blowup, CAP_H, n_proofs, _cap(oracle, ext, log_n), _cap(oracle, hext, log_n))
+    return ext, hext, g, sm.quotient(oracle, log_n, log_blowup, n_proofs, ext, hext, pext, _shift(), g)
+
+
+def _degree9(oracle, t, h=None, pre=None):
+    return max(_degrees(oracle, _model_quotient(oracle, t, sm.helper(t, 1) if h is None else h, pre=pre)[3]))
+
+
+def _degree7(oracle, t):
+    return max(_degrees(oracle, t7._model_quotient(oracle, t, s7.helper(t, 1))[3]))
+
+
+def _degree8(oracle, t):
+    return max(_degrees(oracle, t8._model_quotient(oracle, t, s8.helper(t, 1))[3]))
+
+
+def test_quotient_is_a_polynomial_of_degree_n_minus_2(oracle, step2):
+    """T.2 of step N = 2 (one proof, N = 512: two lanes of two live blocks, padding, a partial block at the end), blow-up 4: the model
+    quotient interpolates to degree exactly N - 2, and the identity holds at a zeta outside the base field -- table, helper and quotient
+    evaluated there by Horner on their coefficients, STA and CHN barycentrically; it fails after bumping u_0, a table opening at zeta and
+    at zeta omega, a helper opening at zeta and at zeta omega, STA(zeta) or CHN(zeta)"""
+    table = step2[:W]
+    N = table.shape[1]
+    assert N == 512
+    log_n, n_proofs = 9 + LB, 1
+    help_ = sm.helper(table, n_proofs)
+    ext, hext, g, quot = _model_quotient(oracle, table, help_)
+    deg = _degrees(oracle, quot)
+    print(f"\n[sha512-init] T.2 of step N = 2: N = {N}, quotient degrees {deg}")
+    assert max(deg) == N - 2 and g[1] != 0
+    M = 1 << log_n
+    zeta = (0x1234567890ABCDEF % P, 0x0FEDCBA987654321 % P)
+    zs = (zeta, fm.e_scale(zeta, oracle.gl_root(log_n - LB)))
+    yt, yh = dm.evaluate(oracle, table, 1, zs), dm.evaluate(oracle, help_, 1, zs)
+    u = [am.horner(am.coefficients(oracle, quot[k * M:(k + 1) * M], _shift()), zeta) for k in (0, 1)]
+    t0, t1, h0, h1 = [tuple(y[0]) for y in yt], [tuple(y[1]) for y in yt], [tuple(y[0]) for y in yh], [tuple(y[1]) for y in yh]
+    pre = sm.periodic_at(oracle, 9, zeta)
+    ident = lambda t0=t0, t1=t1, h0=h0, h1=h1, u0=u[0], pre=pre: sm.identity_at(oracle, log_n, LB, n_proofs, t0, t1, h0, h1, u0, u[1], zeta, g, pre)
+    assert ident()
+    assert not ident(u0=fm.e_add(u[0], (1, 0)))
+    bump = lambda v, at: v[:at] + [fm.e_add(v[at], (0, 1))] + v[at + 1:]
+    assert not ident(t0=bump(t0, sm.H_ + 1)) and not ident(t1=bump(t1, sm.E_))
+    assert not ident(h0=bump(h0, sm.HPZ + 6)) and not ident(h1=bump(h1, sm.HMAJ + 1))
+    assert not ident(pre=bump(pre, 0)) and not ident(pre=bump(pre, 1))
+
+
+def test_model_quotient_in_integers_equals_the_uint64_field(oracle):
+    """the model's two arithmetics agree on random, non-satisfying columns with a few non-canonical words (N = 128, blow-up 2, two
+    proofs): Python integers in object arrays against the vectorised uint64 field the GPU tests are compared with"""
+    log_n, lb, n_proofs = 8, 1, 2
+    rng = np.random.default_rng(11050)
+    ext, hext = _random_ext(rng, n_proofs * W, log_n), _random_ext(rng, n_proofs * HC, log_n)
+    pext = oracle.lde(sm.periodic(128), lb)
+    g = (0x0123456789ABCDEF % P, 0x0FEDCBA987654321 % P)
+    fast = sm.quotient(oracle, log_n, lb, n_proofs, ext, hext, pext, _shift(), g)
+    assert np.array_equal(fast, sm.quotient(oracle, log_n, lb, n_proofs, ext, hext, pext, _shift(), g, ints=True))
+
+
+START_RERUN, CHAIN_RERUN, ROW0_RERUN = "a first block re-run from a changed start state", "a second block re-run from a changed chaining value", \
+    "the lane at row 0 re-run from a changed start state"
+
+
+def _changed(table, kind):
+    """(table, helper) of ONE proof after a single change of `kind`; lane 1 (rows 160 .. 319) of T.2 of step N = 2 has two live blocks"""
+    t = table[:W].copy()
+    r0 = 160
+    assert t[:, r0].any() and t[:, r0 + 80].any()
+    bad_start = [x ^ (1 << (5 + 7 * j)) for j, x in enumerate(IV512)]
+    if kind == START_RERUN:
+        _run_lane(t, r0, bad_start)
+    elif kind == ROW0_RERUN:
+        _run_lane(t, 0, bad_start)
+    elif kind == CHAIN_RERUN:
+        chain = [(a + b) & M64 for a, b in zip(IV512, _state(t, r0 + 79))]
+        _run_block(t, r0 + 80, [x ^ (1 << (9 + 6 * j)) for j, x in enumerate(chain)])
+    elif kind == "d_hi of a row 0 changed alone":
+        t[sm.D_ + 1, r0] ^= np.uint64(1 << 9)
+    elif kind == "f_lo of a chained block's row 0":
+        t[sm.F_, r0 + 80] ^= np.uint64(1 << 9)
+    elif kind == "h of a first block's row 79, the helper regenerated":
+        t[sm.H_, r0 + 79] ^= np.uint64(1 << 9)
+    if kind in (START_RERUN, ROW0_RERUN, CHAIN_RERUN) or kind[1] == "_" or kind.startswith("h of"):
+        return t, sm.helper(t, 1)
+    h = sm.helper(t, 1)
+    if kind == "a flipped CZL bit on a chain row":
+        h[sm.HCZ + 2 * 5, r0 + 79] ^= np.uint64(1)
+    elif kind == "a flipped CZH bit on a chain row":
+        h[sm.HCZ + 2 * 2 + 1, r0 + 79] ^= np.uint64(1)
+    elif kind == "a changed PZ_3 limb on a chain row":
+        h[sm.HPZ + 2 * 3 + 1, r0 + 79] ^= np.uint64(1 << 4)
+    elif kind == "LV cleared on row 0 of a live block":
+        h[sm.HLV, r0] = 0
+    elif kind == "a flipped CAH bit":
+        h[sm.HCAH + 1, r0 + 79] ^= np.uint64(1)
+    else:
+        raise KeyError(kind)
+    return t, h
+
+
+DETECTED = [START_RERUN, CHAIN_RERUN, "d_hi of a row 0 changed alone", "f_lo of a chained block's row 0",
+            "h of a first block's row 79, the helper regenerated", "a flipped CZL bit on a chain row", "a flipped CZH bit on a chain row",
+            "a changed PZ_3 limb on a chain row", "LV cleared on row 0 of a live block", "a flipped CAH bit", ROW0_RERUN]
+
+
+@pytest.mark.parametrize("kind", DETECTED)
+def test_one_change_breaks_the_degree(oracle, step2, kind):
+    """the detected kinds, on T.2 of step N = 2 (one proof): the quotient no longer interpolates to degree < N (set 5 measured 4 N - 1; the
+    degree is printed).  The two re-runs are consistent with the round function and leave W alone, so the model quotients of sets 7 and 8
+    of the SAME tampered table keep degree N - 2: the hole this set closes.  The lane at row 0 is reached through the wrap row alone: with
+    an STA that is 0 on row N - 1 its re-run goes unseen, which pins the explicit wrap"""
+    table = step2[:W]
+    N = table.shape[1]
+    t, h = _changed(table, kind)
+    assert (t != table).sum() + (h != sm.helper(table, 1)).sum() >= 1
+    deg = _degree9(oracle, t, h)
+    print(f"\n[sha512-init] {kind}: quotient degree {deg}, N = {N}")
+    assert deg >= N
+    if kind in (START_RERUN, CHAIN_RERUN):
+        assert (t != table).sum() > 64 and np.array_equal(t[:2], table[:2])
+        d7, d8 = _degree7(oracle, t), _degree8(oracle, t)
+        print(f"[sha512-init] {kind}: set 7's quotient degree {d7}, set 8's {d8}")
+        assert d7 <= N - 2 and d8 <= N - 2
+    if kind == ROW0_RERUN:
+        assert _degree9(oracle, t, h, pre=sm.periodic(N, wrap=False)) <= N - 2
+
+
+def test_kinds_sets_7_8_and_9_do_not_see(oracle, step2):
+    """recorded so that nobody mistakes the claim.  The message is linked to nothing public: W_3 of a live first block changed, with the
+    schedule, the rounds and the following chaining value (the whole second block) re-run from it, keeps all three quotients at degree
+    <= N - 2.  LV is linked to nothing public: a live second block replaced by zeros goes unseen, because the sets cannot know that a
+    second block was due"""
+    table = step2[:W]
+    N = table.shape[1]
+    t = table.copy()
+    r0 = 160
+    w16 = [_word(t, sm.W_, r0 + k) for k in range(16)]
+    w16[3] ^= 1 << 40
+    for k, x in enumerate(_schedule(w16)):
+        _put(t, sm.W_, r0 + k, x)
+    _run_lane(t, r0, IV512)
+    assert (t != table).sum() > 128
+    assert max(_degree9(oracle, t), _degree7(oracle, t), _degree8(oracle, t)) <= N - 2
+    z = table.copy()
+    z[:, r0 + 80:r0 + 160] = 0
+    assert max(_degree9(oracle, z), _degree7(oracle, z), _degree8(oracle, z)) <= N - 2
+
+
+def test_symbols_and_wrappers_exist(built_lib):
+    """the new entry points are in the built library, bound in _lib.py and wrapped in context.py; the four constants are the model's"""
+    from tendermintx_amd import _lib
+    from tendermintx_amd.context import Context
+    for name in ("tmx_air_sha512_init_helper_device", "tmx_air_sha512_init_quotient_device", "tmx_air_sha512_init_quotient_range_device",
+                 "tmx_air_sha512_init_verify_device", "tmx_trace_commit_set_air_sha512_init_device", "tmx_air_sha512_init_periodic_device",
+                 "tmx_air_sha512_init_periodic_eval_device"):
+        assert getattr(built_lib, name).argtypes, name
+    for name in ("air_sha512_init_helper_device", "air_sha512_init_quotient_device", "air_sha512_init_verify_device",
+                 "trace_commit_set_air_sha512_init_device", "air_sha512_init_periodic_device", "air_sha512_init_periodic_eval_device"):
+        assert callable(getattr(Context, name)), name
+    assert (_lib.AIR_SHA512_INIT_HELPER_COLS, _lib.AIR_SHA512_INIT_CONSTRAINTS) == (HC, sm.CONSTRAINTS)
+    assert (_lib.TRACE_SHA512_INIT_HELPER, _lib.TRACE_SHA512_INIT_QUOTIENT) == (HELPER, QUOTIENT)
+
+
+# ---- GPU
+@pytest.fixture(scope="module")
+def ctx(built_lib):
+    import tendermintx_amd as tmx
+    c = tmx.Context(2, b"celestia", max_batch=2)
+    yield c
+    c.close()
+
+
+def _device_helper(ctx, table):
+    n_proofs, log_rows = table.shape[0] // W, table.shape[1].bit_length() - 1
+    d_table = _up(table)
+    return _guarded((n_proofs * HC) << log_rows, lambda out: ctx.air_sha512_init_helper_device(log_rows, n_proofs, d_table.data_ptr(), out, 0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_rows,n_proofs", [(7, 1), (7, 3), (8, 1), (8, 3), (9, 1), (9, 3), (10, 1), (10, 3), (7, 257)])
+def test_helper_of_random_tables_equals_the_model(ctx, log_rows, n_proofs):
+    """random tables of full 64-bit words (the operands are the low 32 bits) at the four residues of (N - 1) mod 160 -- N = 128 has one
+    chain row and only the wrap as a start row, N = 256 the rows 79, 159, 239, 255 --, one and three proofs (3 x 128 lanes end in a partial
+    workgroup) and 257 proofs: the helper equals the model's word for word, so the next row wraps inside its own proof; the carries are
+    zero off the selected rows and nonzero on some of them; guard words intact"""
+    rng = np.random.default_rng(11100 + 10 * log_rows + n_proofs)
+    table = rng.integers(0, 1 << 64, (n_proofs * W, 1 << log_rows), dtype=np.uint64)
+    got = _down(_device_helper(ctx, table)).reshape(n_proofs * HC, -1)
+    want = sm.helper(table, n_proofs)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:10]
+    off = (sm.periodic(1 << log_rows).sum(axis=0) == 0)
+    for p in range(n_proofs):
+        assert not want[p * HC + sm.HCAL:(p + 1) * HC][:, off].any()
+    assert max(_carries(want[p * HC:(p + 1) * HC])[0] for p in range(n_proofs)) >= 1
+
+
+@pytest.mark.gpu
+def test_helper_of_the_devices_own_rows_and_of_the_one_block_hash(ctx, device_rows):
+    """T.2 of two step N = 2 proofs as tmx_trace_rows_device writes it (512 rows: live lanes, padding), and the table of
+    test_a_one_block_hash_built_in_the_model (a zero second block behind a live first one, which the real rows lack)"""
+    table = device_rows[1]
+    assert table.shape == (2 * W, 512) and table.any()
+    got = _down(_device_helper(ctx, table)).reshape(-1, 512)
+    assert np.array_equal(got, sm.helper(table, 2))
+    t = np.zeros((W, 512), dtype=np.uint64)
+    t[:, :160], t[:, 160:320] = _hash_lane(b"abc")[0], _hash_lane(bytes(range(150)))[0]
+    assert np.array_equal(_down(_device_helper(ctx, t)).reshape(-1, 512), sm.helper(t, 1))
+
+
+def _periodic(ctx, log_rows, log_blowup):
+    import torch
+    N, M = 1 << log_rows, 1 << (log_rows + log_blowup)
+    d_pre, d_ext = _sentinel(2 * N + GUARD), _sentinel(2 * M + GUARD)
+    ctx.air_sha512_init_periodic_device(log_rows, log_blowup, d_pre.data_ptr(), d_ext.data_ptr(), 0)
+    torch.cuda.synchronize(_dev())
+    assert torch.equal(d_pre[2 * N:], _sentinel(GUARD)) and torch.equal(d_ext[2 * M:], _sentinel(GUARD))
+    return _down(d_pre[:2 * N]).reshape(2, N), _down(d_ext[:2 * M]).reshape(2, M)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_rows,log_blowup", [(7, 1), (7, 6), (8, 2), (9, 3)])
+def test_sta_chn_and_their_extension(ctx, oracle, log_rows, log_blowup):
+    """STA and CHN before the LDE (planar, 2 << log_rows words, nothing behind them) and extended under the context's domain, against the
+    model and the CPU oracle's LDE"""
+    pre, ext = _periodic(ctx, log_rows, log_blowup)
+    want = sm.periodic(1 << log_rows)
+    assert np.array_equal(pre, want) and np.array_equal(ext, oracle.lde(want, log_blowup))
+
+
+@pytest.mark.gpu
+def test_sta_chn_extend_under_the_current_domain(ctx, oracle):
+    """after tmx_ntt_set_domain (g = 7) the planes are extended under that domain: the CPU oracle's LDE under it, which differs from the
+    default domain's; the columns before the LDE do not depend on the domain"""
+    log_rows, lb = 8, 2
+    want = sm.periodic(1 << log_rows)
+    default = oracle.lde(want, lb)
+    try:
+        ctx.ntt_set_domain(*oracle.G7_DOMAIN)
+        oracle.ntt_set_domain(*oracle.G7_DOMAIN)
+        pre, ext = _periodic(ctx, log_rows, lb)
+        moved = oracle.lde(want, lb)
+    finally:
+        ctx.ntt_set_domain(*oracle.PLONKY2_DOMAIN)
+        oracle.ntt_set_domain(*oracle.PLONKY2_DOMAIN)
+    assert np.array_equal(pre, want) and np.array_equal(ext, moved) and not np.array_equal(moved, default)
+    assert np.array_equal(_periodic(ctx, log_rows, lb)[1], default)
+
+
+def _bary(ctx, log_rows, zeta_words):
+    """the five words of tmx_air_sha512_init_periodic_eval_device at the two words of zeta as given; the words behind them stay untouched"""
+    import torch
+    d_zeta, d_out = _up(np.array(zeta_words, dtype=np.uint64)), _sentinel(5 + GUARD)
+    ctx.air_sha512_init_periodic_eval_device(log_rows, d_zeta.data_ptr(), d_out.data_ptr(), 0)
+    torch.cuda.synchronize(_dev())
+    assert torch.equal(d_out[5:], _sentinel(GUARD))
+    return [int(x) for x in _down(d_out[:5])]
+
+
+def _bary_model(oracle, log_rows, zeta):
+    return [x for v in sm.periodic_at(oracle, log_rows, zeta) for x in v] + [0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_rows", [7, 8, 9, 10, 15, 18])
+def test_sta_chn_at_zeta_equal_the_model(ctx, oracle, log_rows):
+    """STA and CHN at a random zeta of F_p^2 over N = 128 (half a workgroup), 256, 512, 1024 (one), 2^15 (32 workgroups, the full size)
+    and 2^18 (64 workgroups, four batches per thread): the kernel's values equal the model's barycentric sums, no zero denominator"""
+    rng = np.random.default_rng(11500 + log_rows)
+    zeta = tuple(int(x) for x in rng.integers(1, P, 2, dtype=np.uint64))
+    assert _bary(ctx, log_rows, zeta) == _bary_model(oracle, log_rows, zeta)
+
+
+@pytest.mark.gpu
+def test_sta_chn_at_zeta_flags_and_non_canonical_words(ctx, oracle):
+    """N = 4096: four workgroups of 256 threads.  zeta = omega^5 (the first workgroup) and omega^4095 (the last) raise the flag;
+    (omega^5, 1) is no root: no flag; the words (z0 + p, z1 + p) give the words of (z0, z1), at an honest point and at a root; a small
+    evaluation behind a flagged one folds no stale flag"""
+    om = oracle.gl_root(12)
+    assert _bary(ctx, 12, (pow(om, 5, P), 0))[4] == 1 and _bary(ctx, 12, (pow(om, 4095, P), 0))[4] == 1
+    near = (pow(om, 5, P), 1)
+    assert _bary(ctx, 12, near) == _bary_model(oracle, 12, near)
+    z = (0x12345678, 0x7ABCDEF1)
+    want = _bary_model(oracle, 12, z)
+    assert _bary(ctx, 12, z) == want and _bary(ctx, 12, (z[0] + P, z[1] + P)) == want
+    assert _bary(ctx, 12, (1 + P, P))[4] == 1  # (omega^0 = 1, 0) in non-canonical words
+    assert _bary(ctx, 9, z) == _bary_model(oracle, 9, z)
+
+
+def _device_quotient(ctx, log_n, log_blowup, n_proofs, d_cols, d_hcols, d_cap, d_cap_h, cap_height=CAP_H, **kw):
+    return _guarded(2 << log_n, lambda out: ctx.air_sha512_init_quotient_device(log_n, log_blowup, cap_height, n_proofs, d_cols.data_ptr(),
+                                                                               d_hcols.data_ptr(), d_cap.data_ptr(), d_cap_h.data_ptr(), out, 0, **kw))
+
+
+def _quotient_equals_the_model(ctx, oracle, log_n, log_blowup, n_proofs, ext, hext):
+    """uploads, caps, the whole quotient and gamma against the model; returns (device columns, device helper columns, the two caps, the
+    model's quotient)"""
+    d_cols, d_hcols = _up(ext), _up(hext)
+    _, d_cap = _tree(ctx, d_cols, log_n, n_proofs * W)
+    _, d_cap_h = _tree(ctx, d_hcols, log_n, n_proofs * HC)
+    got = _down(_device_quotient(ctx, log_n, log_blowup, n_proofs, d_cols, d_hcols, d_cap, d_cap_h))
+    g = sm.gamma(oracle, log_n, log_blowup, CAP_H, n_proofs, _down(d_cap), _down(d_cap_h))
+    assert ctx.air_last_gamma() == g
+    pext = oracle.lde(sm.periodic(1 << (log_n - log_blowup)), log_blowup)
+    want = sm.quotient(oracle, log_n, log_blowup, n_proofs, ext, hext, pext, _shift(), g)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:10]
+    return d_cols, d_hcols, d_cap, d_cap_h, want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,log_blowup,n_proofs", [(128, 1, 1), (128, 6, 2), (512, 3, 3), (1024, 1, 3)])
+def test_quotient_of_random_columns_equals_the_model(ctx, oracle, N, log_blowup, n_proofs):
+    """random table and helper columns (a few words non-canonical): the definition is pointwise, so gamma and d_quot equal the model word
+    for word -- whole, and through the range call in two pieces in both orders (a written first piece and an accumulated second: [0, 1)
+    then the rest, and the rest then [0, 1)); guard words intact"""
+    import torch
+    log_n = N.bit_length() - 1 + log_blowup
+    rng = np.random.default_rng(11200 + 100 * log_n + 10 * log_blowup + n_proofs)
+    ext, hext = _random_ext(rng, n_proofs * W, log_n), _random_ext(rng, n_proofs * HC, log_n)
+    d_cols, d_hcols, d_cap, d_cap_h, want = _quotient_equals_the_model(ctx, oracle, log_n, log_blowup, n_proofs, ext, hext)
+    pieces, words = ([(0, 1), (1, n_proofs)] if n_proofs > 1 else [(0, 1)]), 2 << log_n
+    for order in (pieces, pieces[::-1]):
+        buf = _sentinel(words + 2 * GUARD)
+        for k, (lo, hi) in enumerate(order):
+            d_piece = d_hcols[(lo * HC) << log_n:]
+            ctx.air_sha512_init_quotient_device(log_n, log_blowup, CAP_H, n_proofs, d_cols.data_ptr(), d_piece.data_ptr(), d_cap.data_ptr(),
+                                                d_cap_h.data_ptr(), buf[GUARD:].data_ptr(), 0, proof_range=(lo, hi), accumulate=int(k > 0))
+        torch.cuda.synchronize(_dev())
+        assert np.array_equal(_down(buf[GUARD:GUARD + words]), want), order
+        assert torch.equal(buf[:GUARD], _sentinel(GUARD)) and torch.equal(buf[GUARD + words:], _sentinel(GUARD)), order
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fill", ["all p - 1", "all 2^64 - 1"])
+def test_quotient_of_extreme_words_equals_the_model(ctx, oracle, fill):
+    """the inputs the NTT's lazy arithmetic is tested with, as table and helper columns of set 9's sums (32-step dbl_add, scale(carry,
+    2^32), 673 accumulated terms in three sums): every word p - 1 and every word 2^64 - 1, at N = 128, blow-up 8, two proofs"""
+    log_n, lb, n_proofs = 10, 3, 2
+    rng = np.random.default_rng(11800)
+    ext, hext = FILLS[fill](rng, (n_proofs * W, 1 << log_n)), FILLS[fill](rng, (n_proofs * HC, 1 << log_n))
+    assert ext.dtype == np.uint64 and int(ext.min()) >= P - 1
+    _quotient_equals_the_model(ctx, oracle, log_n, lb, n_proofs, ext, hext)
+
+
+# ---- GPU: the chain and the verifiers
+SETS = {"7": (HC7, lambda c, t: t7._device_helper(c, t), t7._device_quotient), "8": (HC8, lambda c, t: t8._device_helper(c, t), t8._device_quotient),
+        "9": (HC, _device_helper, _device_quotient)}
+
+
+def _chain(ctx, oracle, table, log_blowup, sets="789", q9_override=None, n_queries=6, others=()):
+    """caller-level chain: the helpers of `sets` -> LDE -> caps -> their quotients -> one batch proof over [table, H7, Q7, H8, Q8, H9, Q9]
+    (or the pairs of `sets` alone).  others: (position, extended columns [n][2^log_n]) of further oracles.  Returns a dict: the params p,
+    the caps on the device, the proof words, kt and k[set] (the helper's oracle index), gamma[set], and set 9's extended helper and
+    quotient words"""
+    import torch
+    n_proofs, log_rows = table.shape[0] // W, table.shape[1].bit_length() - 1
+    log_n = log_rows + log_blowup
+
+    def lde(d_pre, n):
+        d_out = _sentinel(n << log_n)
+        ctx.lde_device(log_rows, log_blowup, n, d_pre.data_ptr(), d_out.data_ptr(), 0)
+        return d_out
+    d_ext = lde(_up(table), n_proofs * W)
+    d_lv_t, d_cap_t = _tree(ctx, d_ext, log_n, n_proofs * W)
+    members, out, gammas = [(d_ext, d_lv_t, d_cap_t, n_proofs * W)], {}, {}
+    for s in sets:
+        hc, helper, quotient = SETS[s]
+        d_h = lde(helper(ctx, table), n_proofs * hc)
+        d_lv, d_cap_h = _tree(ctx, d_h, log_n, n_proofs * hc)
+        if s == "9" and q9_override is not None:
+            d_q = _up(q9_override)
+        else:
+            d_q = quotient(ctx, log_n, log_blowup, n_proofs, d_ext, d_h, d_cap_t, d_cap_h)
+            gammas[s] = ctx.air_last_gamma()
+        d_lv_q, d_cap_q = _tree(ctx, d_q, log_n, 2)
+        members += [(d_h, d_lv, d_cap_h, n_proofs * hc), (d_q, d_lv_q, d_cap_q, 2)]
+        if s == "9":
+            out.update(hext=_down(d_h).reshape(n_proofs * HC, -1), quot=_down(d_q))
+    log_ns = [log_n] * len(members)
+    for at, e in others:
+        d_o, lo = _up(e), e.shape[1].bit_length() - 1
+        d_lv_o, d_cap_o = _tree(ctx, d_o, lo, e.shape[0])
+        members.insert(at, (d_o, d_lv_o, d_cap_o, e.shape[0]))
+        log_ns.insert(at, lo)
+    kt = next(k for k, m in enumerate(members) if m[0] is d_ext)
+    p = bparams(log_ns, [m[3] for m in members], CAP_H, log_blowup, 2, 2, n_queries)
+    proof = _guarded(bm.layout(p)["words"], lambda o: ctx.batch_prove_device(p, [m[0].data_ptr() for m in members], [m[1].data_ptr() for m in members], o, 0))
+    out.update(p=p, d_caps=torch.cat([m[2] for m in members]), proof=_down(proof), kt=kt, k={s: kt + 1 + 2 * i for i, s in enumerate(sets)},
+               gamma=gammas, ext=_down(d_ext).reshape(n_proofs * W, -1))
+    return out
+
+
+def _verdicts(ctx, p, k_trace, k_helper, d_caps, proof, which="9"):
+    import torch
+    ok = torch.full((p["n_queries"],), 7, dtype=torch.int32, device=_dev())
+    args = (d_caps.data_ptr(), _up(proof).data_ptr(), ok.data_ptr(), 0)
+    if which == "9":
+        ctx.air_sha512_init_verify_device(p, k_trace, k_helper, *args)
+    elif which == "8":
+        ctx.air_sha512_sched_verify_device(p, k_trace, k_helper, *args)
+    elif which == "7":
+        ctx.air_sha512_verify_device(p, k_trace, *args)
+    else:
+        ctx.batch_verify_device(p, *args)
+    torch.cuda.synchronize(_dev())
+    out = ok.cpu().numpy()
+    assert ((out == 0) | (out == 1)).all(), out
+    return [bool(x) for x in out]
+
+
+def _bumped(proof, at):
+    bad = proof.copy()
+    bad[at] = np.uint64((int(bad[at]) % P + 1) % P)
+    return bad
+
+
+@pytest.mark.gpu
+def test_real_rows_through_the_caller_level_chain(ctx, oracle, step2):
+    """seven oracles [table, H7, Q7, H8, Q8, H9, Q9] of T.2 of step N = 2 (two proofs, N = 512, blow-up 2) in one batch proof: set 9's
+    helper, gamma and quotient equal the model's and the quotient has degree <= N - 2; all three device verifiers accept every query, as
+    the three models do; set 9's verifier rejects a proof with one bumped table, helper or quotient opening on every query, as the
+    model's identity fails"""
+    table, lb = step2, 1
+    n_proofs = table.shape[0] // W
+    c = _chain(ctx, oracle, table, lb)
+    assert ctx.fri_last_degree_ok() is True
+    p, d_caps, got = c["p"], c["d_caps"], c["proof"]
+    assert p["n_cols"] == [n_proofs * W, n_proofs * HC7, 2, n_proofs * HC8, 2, n_proofs * HC, 2] and (c["kt"], c["k"]) == (0, {"7": 1, "8": 3, "9": 5})
+    log_n, caps, cw = p["log_n"][0], _down(d_caps), 4 << CAP_H
+    assert np.array_equal(c["hext"], oracle.lde(sm.helper(table, n_proofs), lb))
+    g = sm.gamma(oracle, log_n, lb, CAP_H, n_proofs, caps[:cw], caps[5 * cw:6 * cw])
+    assert c["gamma"]["9"] == g and c["gamma"]["7"] == s7.gamma(oracle, log_n, lb, CAP_H, n_proofs, caps[:cw], caps[cw:2 * cw])
+    assert c["gamma"]["8"] == s8.gamma(oracle, log_n, lb, CAP_H, n_proofs, caps[:cw], caps[3 * cw:4 * cw])
+    pext = oracle.lde(sm.periodic(table.shape[1]), lb)
+    assert np.array_equal(c["quot"], sm.quotient(oracle, log_n, lb, n_proofs, c["ext"], c["hext"], pext, _shift(), g))
+    assert max(_degrees(oracle, c["quot"])) <= table.shape[1] - 2
+    model9 = sm.verify(oracle, p, 0, 5, caps, got, _shift())
+    assert all(model9) and s7.identity(oracle, p, 0, caps, got) and s8.identity(oracle, p, 0, 3, caps, got)
+    assert _verdicts(ctx, p, 0, 5, d_caps, got) == model9 and _verdicts(ctx, p, 0, 3, d_caps, got, which="8") == model9
+    assert _verdicts(ctx, p, 0, None, d_caps, got, which="7") == model9 and all(_verdicts(ctx, p, 0, None, d_caps, got, which="0"))
+    L = bm.layout(p)
+    RH = 1 << dm.log_r(p["n_cols"][5])
+    for name, at in (("quotient opening", L["off_open"][6] + 1), ("helper opening at zeta", L["off_open"][5] + sm.HPZ + 5),
+                     ("helper opening at zeta omega", L["off_open"][5] + 2 * RH + HC + sm.HS1 + 1),
+                     ("table opening at zeta", L["off_open"][0] + W + sm.H_ + 1)):
+        bad = _bumped(got, at)
+        assert not sm.identity(oracle, p, 0, 5, caps, bad), name
+        assert _verdicts(ctx, p, 0, 5, d_caps, bad) == [False] * p["n_queries"], name
+
+
+@pytest.mark.gpu
+def test_the_rerun_start_passes_sets_7_and_8_and_fails_set_9_on_the_device(ctx, oracle, step2):
+    """the table whose lane 1 is re-run consistently from a changed start state, with the honest helpers of the changed table, the own
+    quotients of sets 7 and 8 and a zero (low-degree) quotient for set 9: the batch proof is fine, THE DEVICE VERIFIERS OF SETS 7 AND 8
+    ACCEPT every query and SET 9'S REJECTS every one, as the three models do"""
+    t, _ = _changed(step2[:W], START_RERUN)
+    log_n = 9 + 1
+    c = _chain(ctx, oracle, t, 1, q9_override=np.zeros(2 << log_n, dtype=np.uint64))
+    p, d_caps, got, caps = c["p"], c["d_caps"], c["proof"], _down(c["d_caps"])
+    n = p["n_queries"]
+    assert all(_verdicts(ctx, p, 0, None, d_caps, got, which="0"))
+    assert s7.identity(oracle, p, 0, caps, got) and s8.identity(oracle, p, 0, 3, caps, got) and not sm.identity(oracle, p, 0, 5, caps, got)
+    assert _verdicts(ctx, p, 0, None, d_caps, got, which="7") == [True] * n and _verdicts(ctx, p, 0, 3, d_caps, got, which="8") == [True] * n
+    assert _verdicts(ctx, p, 0, 5, d_caps, got) == [False] * n
+
+
+@pytest.mark.gpu
+def test_257_proofs_through_the_check_kernel(ctx, oracle, step2):
+    """N = 128, 257 proofs (one more than k_air_sha512_init_check has threads: thread 0 takes proofs 0 and 256) -- the first 128 rows of
+    the live lanes of T.2 of step N = 2 in turn (a live first block, the chain row 79, a second block cut off at the wrap row, which set 9
+    alone does not mind: it looks at rows 0 and 80), every seventh proof zero --, blow-up 2, two queries, [table, H9, Q9]: the device
+    accepts every query as the model's identity does; a helper opening bumped in proof 256 and a table opening in proof 255 are rejected"""
+    many = 257
+    lanes = [step2[q * W:(q + 1) * W, 160 * b:160 * b + 160] for q in range(step2.shape[0] // W) for b in range(2)]
+    assert all(x[:, 0].any() and x[:, 80].any() for x in lanes)
+    table = np.zeros((many * W, 128), dtype=np.uint64)
+    for q in range(many):
+        if q % 7 != 6:
+            table[q * W:(q + 1) * W] = lanes[q % len(lanes)][:, :128]
+    c = _chain(ctx, oracle, table, 1, sets="9", n_queries=2)
+    assert ctx.fri_last_degree_ok() is True
+    p, d_caps, got, caps = c["p"], c["d_caps"], c["proof"], _down(c["d_caps"])
+    assert sm.identity(oracle, p, 0, 1, caps, got)
+    assert _verdicts(ctx, p, 0, 1, d_caps, got) == [True, True]
+    L = bm.layout(p)
+    for at in (L["off_open"][1] + 256 * HC + sm.HPZ + 3, L["off_open"][0] + 255 * W + sm.D_):
+        bad = _bumped(got, at)
+        assert not sm.identity(oracle, p, 0, 1, caps, bad)
+        assert _verdicts(ctx, p, 0, 1, d_caps, bad) == [False, False]
+
+
+# ---- GPU: the set level
+def _set_round(c, kind, n_proofs, lb, tr, calls, sections=SHA512 | HEADER, queries=6):
+    """commit `sections`, the air calls of `calls` ("7", "8", "9": that set's, on SHA512) in that order, one proof.  Returns (params, the
+    sections in oracle order, the caps in that order on the device, proof words, {set: gamma})"""
+    import torch
+    cw = 4 << CAP_H
+    d_caps = _sentinel(bin(sections).count("1") * cw)
+    own = {s: _sentinel(cw) for s in (H7, Q7, H8, Q8, HELPER, QUOTIENT)}
+    c.trace_commit_set_device(kind, n_proofs, sections, lb, CAP_H, tr.data_ptr(), d_caps.data_ptr(), 0)
+    _, order0 = c.trace_commit_set_shape()
+    gammas = {}
+    for s in calls:
+        call, hs, qs = {"7": (c.trace_commit_set_air_sha512_device, H7, Q7), "8": (c.trace_commit_set_air_sha512_sched_device, H8, Q8),
+                        "9": (c.trace_commit_set_air_sha512_init_device, HELPER, QUOTIENT)}[s]
+        call(SHA512, own[hs].data_ptr(), own[qs].data_ptr(), 0)
+        gammas[s] = c.air_last_gamma()
+    shape, order = c.trace_commit_set_shape()
+    p = dict(shape, arity_bits=2, final_log_max=2, n_queries=queries, pow_bits=0)
+    proof = _down(_guarded(bm.layout(p)["words"], lambda out: c.trace_commit_set_prove_device(p, out, 0)))
+    assert c.fri_last_degree_ok() is True
+    caps_of = {s: d_caps[cw * i:cw * (i + 1)] for i, s in enumerate(order0)}
+    caps_of.update(own)
+    return p, order, torch.cat([caps_of[s] for s in order]), proof, gammas
+
+
+@pytest.mark.gpu
+def test_set_level_in_three_call_orders(ctx, oracle, device_rows):
+    """a set SHA512 | HEADER of two step N = 2 proofs with the calls of sets 7, 8, 9 in the orders 7 8 9, 9 8 7 and 8 9 7.  Every shape ends
+    [HEADER, SHA512, 32768, 65536, 131072, 262144, 524288, 1048576]: eight oracles, the limit; caps, the three gammas and proof words are
+    equal between the orders and equal to the caller-level chain's over the same columns (the header table as one more oracle); all three
+    device verifiers accept, as set 9's model identity holds; the caps of sets 7 and 8 with set 9 present equal those of a set without it"""
+    import torch
+    from test_merkle_open import _oracle_ext
+    c, (tr, table) = ctx, device_rows
+    kind, n, n_proofs, lb = 1, 2, 2, 1
+    cw = 4 << CAP_H
+    a = _set_round(c, kind, n_proofs, lb, tr, "789")
+    p, order, d_caps, proof, gammas = a
+    assert order == [HEADER, SHA512, H7, Q7, H8, Q8, HELPER, QUOTIENT]
+    assert p["log_n"][1:] == [9 + lb] * 7 and p["n_cols"][1:] == [W * n_proofs, HC7 * n_proofs, 2, HC8 * n_proofs, 2, HC * n_proofs, 2]
+    for calls in ("987", "897"):
+        b = _set_round(c, kind, n_proofs, lb, tr, calls)
+        assert b[1] == order and b[0] == p, calls
+        assert torch.equal(b[2], d_caps) and np.array_equal(b[3], proof) and b[4] == gammas, calls
+    e, lm, nc = _oracle_ext(oracle, kind, n, _down(tr), HEADER, lb)
+    ch = _chain(c, oracle, table, lb, others=[(0, e.reshape(nc, -1))])
+    assert {key: ch["p"][key] for key in ("log_n", "n_cols")} == {key: p[key] for key in ("log_n", "n_cols")} and (ch["kt"], ch["k"]["9"]) == (1, 6)
+    assert gammas == ch["gamma"] and torch.equal(d_caps, ch["d_caps"])
+    assert np.array_equal(proof, ch["proof"])
+    caps = _down(d_caps)
+    assert _verdicts(c, p, 1, 6, d_caps, proof) == [True] * 6 and _verdicts(c, p, 1, 4, d_caps, proof, which="8") == [True] * 6
+    assert _verdicts(c, p, 1, None, d_caps, proof, which="7") == [True] * 6
+    assert sm.identity(oracle, p, 1, 6, caps, proof)
+    assert not any(_verdicts(c, p, 1, 6, d_caps, _bumped(proof, bm.layout(p)["off_open"][7])))
+    without = _set_round(c, kind, n_proofs, lb, tr, "78")
+    assert without[1] == order[:6] and torch.equal(without[2], d_caps[:6 * cw]) and without[4] == {s: gammas[s] for s in "78"}
+    only9 = _set_round(c, kind, n_proofs, lb, tr, "9")
+    assert only9[1] == order[:2] + order[6:] and torch.equal(only9[2][2 * cw:], d_caps[6 * cw:]) and only9[4]["9"] == gammas["9"]
+    assert _verdicts(c, only9[0], 1, 2, only9[2], only9[3]) == [True] * 6
+
+
+@pytest.mark.gpu
+def test_set_level_refusals(ctx, device_rows):
+    """the set-level call takes TMX_TRACE_SHA512 alone, a resident member only, refuses a second call on the section and null caps, each
+    with nothing enqueued and the set as it was; the streamed call refuses constraint_set = 9"""
+    c, (tr, _) = ctx, device_rows
+    kind, n_proofs, lb = 1, 2, 1
+    cw = 4 << CAP_H
+    d_caps, d_cap_h, d_cap_q = _sentinel(2 * cw), _sentinel(cw), _sentinel(cw)
+    air = lambda sec: (lambda: c.trace_commit_set_air_sha512_init_device(sec, d_cap_h.data_ptr(), d_cap_q.data_ptr(), 0))
+    commit = lambda secs=SHA512 | HEADER: c.trace_commit_set_device(kind, n_proofs, secs, lb, CAP_H, tr.data_ptr(), d_caps.data_ptr(), 0)
+    commit()
+    before = c.trace_commit_set_shape()
+    for sec in (HEADER, SHA256, 1, H7, H8, HELPER):
+        assert "TMX_TRACE_SHA512" in _refused(air(sec), d_cap_h, d_cap_q)
+    _refused(lambda: c.trace_commit_set_air_sha512_init_device(SHA512, None, d_cap_q.data_ptr(), 0), d_cap_q)
+    _refused(lambda: c.trace_commit_set_air_sha512_init_device(SHA512, d_cap_h.data_ptr(), None, 0), d_cap_h)
+    _refused(lambda: c.trace_commit_set_air_sha256_streamed_device(9, SHA512, 8, d_cap_h.data_ptr(), d_cap_q.data_ptr(), 0), d_cap_h, d_cap_q)
+    assert c.trace_commit_set_shape() == before
+    air(SHA512)()
+    after = c.trace_commit_set_shape()
+    assert after[1] == [HEADER, SHA512, HELPER, QUOTIENT]
+    assert "already" in _refused(air(SHA512), d_cap_h, d_cap_q)
+    assert c.trace_commit_set_shape() == after
+    commit(HEADER)
+    assert "does not hold" in _refused(air(SHA512), d_cap_h, d_cap_q)
+    c.trace_commit_set_streamed_device(kind, n_proofs, SHA512 | HEADER, SHA512, 8, lb, CAP_H, tr.data_ptr(), d_caps.data_ptr(), 0)
+    assert "streamed" in _refused(air(SHA512), d_cap_h, d_cap_q)
+
+
+@pytest.mark.gpu
+def test_a_set_with_no_room_is_refused(ctx, device_rows):
+    """a third table beside sets 7 + 8: SHA512 | SHA256 | HEADER with set 7's and set 8's pairs holds seven oracles, so set 9's pair has no
+    room, and the set stays as it was"""
+    c, (tr, _) = ctx, device_rows
+    cw = 4 << CAP_H
+    d_caps, d_cap_h, d_cap_q = _sentinel(3 * cw), _sentinel(cw), _sentinel(cw)
+    c.trace_commit_set_device(1, 2, SHA512 | SHA256 | HEADER, 1, CAP_H, tr.data_ptr(), d_caps.data_ptr(), 0)
+    c.trace_commit_set_air_sha512_device(SHA512, d_cap_h.data_ptr(), d_cap_q.data_ptr(), 0)
+    c.trace_commit_set_air_sha512_sched_device(SHA512, d_cap_h.data_ptr(), d_cap_q.data_ptr(), 0)
+    before = c.trace_commit_set_shape()
+    assert len(before[1]) == 7
+    assert "room" in _refused(lambda: c.trace_commit_set_air_sha512_init_device(SHA512, d_cap_h.data_ptr(), d_cap_q.data_ptr(), 0), d_cap_h, d_cap_q)
+    assert c.trace_commit_set_shape() == before
+
+
+@pytest.mark.gpu
+def test_each_validation_rule(ctx):
+    """every rule on its own: TMX_ERR_BAD_ARG before anything is enqueued, nothing written.  FRI's rules on log_n and log_blowup;
+    7 <= log_n - log_blowup <= 18; n_proofs >= 1; 629 n_proofs <= 2^24; a range inside n_proofs; accumulate <= 1; no null pointer; the
+    verifier: k_helper > k_trace, column counts 18 k / 629 k / 2, equal log_n, both oracles inside the proof"""
+    import torch
+    log_n, lb = 9, 1
+    d_cols, d_hcols = _sentinel(W << log_n), _sentinel(HC << log_n)
+    d_cap, d_cap_h, d_quot = _sentinel(4 << CAP_H), _sentinel(4 << CAP_H), _sentinel(2 << log_n)
+    ptrs = [d_cols.data_ptr(), d_hcols.data_ptr(), d_cap.data_ptr(), d_cap_h.data_ptr(), d_quot.data_ptr()]
+    q = lambda ln, b, n, a=ptrs, **kw: (lambda: ctx.air_sha512_init_quotient_device(ln, b, CAP_H, n, *a, 0, **kw))
+    for fn in (q(log_n, 0, 1), q(log_n, 7, 1), q(2, 2, 1), q(29, 2, 1), q(7, 1, 1), q(20, 1, 1), q(log_n, lb, 0), q(log_n, lb, (1 << 24) // HC + 1),
+               q(log_n, lb, 2, proof_range=(1, 1)), q(log_n, lb, 2, proof_range=(1, 3)), q(log_n, lb, 2, proof_range=(0, 1), accumulate=2)):
+        _refused(fn, d_quot)
+    for k in range(5):
+        _refused(q(log_n, lb, 1, ptrs[:k] + [None] + ptrs[k + 1:]), d_quot)
+    d_table, d_help = _sentinel(W << 7), _sentinel(HC << 7)
+    hp = lambda lr, n, t=d_table.data_ptr(), o=d_help.data_ptr(): (lambda: ctx.air_sha512_init_helper_device(lr, n, t, o, 0))
+    for fn in (hp(6, 1), hp(19, 1), hp(7, 0), hp(7, (1 << 24) // HC + 1), hp(7, 1, t=None), hp(7, 1, o=None)):
+        _refused(fn, d_help)
+    d_pre, d_out = _sentinel(1 << 9), _sentinel(8)
+    for fn in (lambda: ctx.air_sha512_init_periodic_device(6, 1, d_pre.data_ptr(), d_pre.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_device(19, 1, d_pre.data_ptr(), d_pre.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_device(7, 1, None, d_pre.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_device(7, 1, d_pre.data_ptr(), None, 0),
+               lambda: ctx.air_sha512_init_periodic_eval_device(6, d_pre.data_ptr(), d_out.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_eval_device(19, d_pre.data_ptr(), d_out.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_eval_device(7, None, d_out.data_ptr(), 0),
+               lambda: ctx.air_sha512_init_periodic_eval_device(7, d_pre.data_ptr(), None, 0)):
+        _refused(fn, d_pre, d_out)
+    # the verifier
+    ok, caps, proof = torch.full((4,), 7, dtype=torch.int32, device=_dev()), _sentinel(256), _sentinel(1 << 17)
+    v = lambda p, kt, kh: (lambda: ctx.air_sha512_init_verify_device(p, kt, kh, caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0))
+    good = bparams([9, 9, 9], [W, HC, 2], CAP_H, lb, 2, 2, 4)
+    for p, kt, kh in ((good, 1, 1), (good, 1, 0), (good, 0, 0), (good, 0, 2), (dict(good, n_cols=[W + 1, HC, 2]), 0, 1),
+                      (dict(good, n_cols=[9, HC, 2]), 0, 1), (dict(good, n_cols=[W, HC + 1, 2]), 0, 1), (dict(good, n_cols=[2 * W, HC, 2]), 0, 1),
+                      (dict(good, n_cols=[W, HC, 3]), 0, 1), (dict(good, log_n=[9, 9, 8]), 0, 1), (dict(good, log_n=[9, 8, 9]), 0, 1),
+                      (bparams([7, 7, 7], [W, HC, 2], CAP_H, lb, 2, 2, 4), 0, 1), (dict(good, arity_bits=0), 0, 1),
+                      (bparams([9, 9], [W, HC], CAP_H, lb, 2, 2, 4), 0, 1)):
+        _refused(v(p, kt, kh), ok)
+
+
+# ---- GPU: the scratch
+@pytest.mark.gpu
+def test_growth_and_reuse_of_the_scratch_and_interleaving_with_sets_7_and_8(oracle):
+    """one fresh context (its set-9 scratch starts unallocated): a caller-level set-9 quotient at (N, blow-up) = (128, 2) allocates it, one at
+    (2048, 4) grows it (the scratch is synchronised, freed and allocated anew), a small one after the large one runs in the larger scratch;
+    then quotient calls of sets 7, 8 and 9 interleaved on one stream without a synchronisation between them: each set's words are those
+    of its call alone, all of them the model's"""
+    import torch
+    import tendermintx_amd as tmx
+    import test_sha512_air_shapes as t7s
+    rng = np.random.default_rng(11940)
+    with tmx.Context(2, b"celestia", max_batch=2) as c:
+        small = (8, 1, 1, _random_ext(rng, W, 8), _random_ext(rng, HC, 8))
+        _quotient_equals_the_model(c, oracle, *small)
+        _quotient_equals_the_model(c, oracle, 13, 2, 1, _random_ext(rng, W, 13), _random_ext(rng, HC, 13))
+        d_cols, d_h9, d_cap, d_cap_h9, want9 = _quotient_equals_the_model(c, oracle, *small)
+        _, d_h7, _, d_cap_h7, want7 = t7s._quotient_equals_the_model(c, oracle, 8, 1, 1, CAP_H, small[3], _random_ext(rng, HC7, 8))
+        _, d_h8, _, d_cap_h8, want8 = t8._quotient_equals_the_model(c, oracle, 8, 1, 1, small[3], _random_ext(rng, HC8, 8))
+        words = 2 << 8
+        bufs = [_sentinel(words + 2 * GUARD) for _ in range(6)]
+        trio = ((c.air_sha512_quotient_device, d_h7, d_cap_h7), (c.air_sha512_init_quotient_device, d_h9, d_cap_h9),
+                (c.air_sha512_sched_quotient_device, d_h8, d_cap_h8))
+        for k, buf in enumerate(bufs):
+            call, d_h, d_ch = trio[k % 3]
+            call(8, 1, CAP_H, 1, d_cols.data_ptr(), d_h.data_ptr(), d_cap.data_ptr(), d_ch.data_ptr(), buf[GUARD:].data_ptr(), 0)
+        torch.cuda.synchronize(_dev())
+        for k, buf in enumerate(bufs):
+            assert np.array_equal(_down(buf[GUARD:GUARD + words]), (want7, want9, want8)[k % 3]), k
+            assert torch.equal(buf[:GUARD], _sentinel(GUARD)) and torch.equal(buf[GUARD + words:], _sentinel(GUARD)), k

@@ -58,6 +58,12 @@
            k_air_sha512_sched_quotient; 248 columns per proof) and of set 4 (SCHED_PROOFS proofs, 32; 124 columns per proof) over random
            extended columns at M = 2^LOG_M (16), alternating; ps_per_helper_word_set8 / _set4 and their ratio.  Then the set-level call of
            set 8 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the verifier.
+  sha512_init    constraint set 9 (tmx_air_sha512_init_*) beside set 7, its yardstick: k_air_sha512_init_helper over S512_PROOFS proofs (16)
+           x 18 random table columns of 2^(LOG_M - BLOWUP) rows, then the quotient call of set 9 (STA and CHN filled and extended, gamma, the
+           tables, k_air_sha512_init_quotient; 647 columns per proof) and of set 7 (617 columns per proof) over random extended columns at
+           M = 2^LOG_M (16) and the SAME table, alternating in one process; ps_per_helper_word_set9 / _set7 and their ratio.  Then the
+           set-level call of set 9 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the
+           verifier.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -898,6 +904,85 @@ if "sha512_sched" in modes:
         kt = order.index(SHA512)
         all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
         res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_sched_verify_device(bp, kt, kt + 1, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
+        del proof
+    print(json.dumps(res), flush=True)
+    ctx.close()
+
+if "sha512_init" in modes:
+    # constraint set 9 beside set 7, its yardstick: the helper kernel, then the caller-level quotient call of each set over random extended
+    # columns (S512_PROOFS proofs of the SAME 18 table columns, 629 against 599 helper columns, M = 2^LOG_M), alternating in one process --
+    # under `rocprofv3 --kernel-trace --stats` (MODE=sha512_init) k_air_sha512_init_helper, k_air_sha512_init_quotient and
+    # k_air_sha512_quotient show in ONE trace.  ps_per_helper_word: the call's time per helper word read, the figure the two passes are
+    # compared on.  Then the set-level call of set 9 on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
+    log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16"))
+    log_rows = log_m - log_blowup
+    torch.manual_seed(seed)
+    ctx = Context(4, b"celestia", device=0)
+
+    def capped(words, k_):
+        c_ = torch.randint(0, 2**62, (words,), dtype=torch.int64, device=dev)
+        lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+        ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+        return c_, lv[-(4 << cap_h):]
+
+    cols, cap_t = capped((18 * cp) << log_m, 18 * cp)
+    hcols9, cap9 = capped((629 * cp) << log_m, 629 * cp)
+    hcols7, cap7 = capped((599 * cp) << log_m, 599 * cp)
+    table = torch.randint(0, 2**62, ((18 * cp) << log_rows,), dtype=torch.int64, device=dev)
+    pre = torch.empty((629 * cp) << log_rows, dtype=torch.int64, device=dev)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    q9 = lambda: ctx.air_sha512_init_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols9.data_ptr(), cap_t.data_ptr(),
+                                                     cap9.data_ptr(), quot.data_ptr(), 0)
+    q7 = lambda: ctx.air_sha512_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols7.data_ptr(), cap_t.data_ptr(),
+                                                cap7.data_ptr(), quot.data_ptr(), 0)
+    res = {"mode": "sha512_init", "log_m": log_m, "proofs": cp, "read_gib_set9": round(((647 * cp) << log_m) * 8 / 2**30, 2),
+           "read_gib_set7": round(((617 * cp) << log_m) * 8 / 2**30, 2), "reps": reps, "helper_kernel_ms": [], "sha512_init_quotient_call_ms": [],
+           "sha512_quotient_call_ms": []}
+    for _ in range(rounds):
+        res["helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha512_init_helper_device(log_rows, cp, table.data_ptr(), pre.data_ptr(), 0), reps)))
+        res["sha512_init_quotient_call_ms"].append(r4(timed(q9, reps)))
+        res["sha512_quotient_call_ms"].append(r4(timed(q7, reps)))
+    res["quotient_sha256"] = words_digest(q9, quot)
+    ps9 = min(res["sha512_init_quotient_call_ms"]) * 1e9 / ((629 * cp) << log_m)
+    ps7 = min(res["sha512_quotient_call_ms"]) * 1e9 / ((599 * cp) << log_m)
+    res.update(ps_per_helper_word_set9=round(ps9, 2), ps_per_helper_word_set7=round(ps7, 2), ratio_set9_over_set7=round(ps9 / ps7, 3),
+               helper_rows=1 << log_rows, helper_store_tb_per_s=round(((629 * cp) << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e9, 3))
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols, cap_t, hcols9, cap9, hcols7, cap7, table, pre, quot
+    torch.cuda.empty_cache()
+    # the set-level call of set 9 on SHA512
+    from tendermintx_amd.synth import bench_workload
+    sp = int(os.environ.get("S512_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    SHA512, HEADER = 2, 32
+    cw = 4 << cap_h
+    scaps, cap_h_, cap_q = (torch.zeros(k * cw, dtype=torch.int64, device=dev) for k in (2, 1, 1))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA512 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    res = {"mode": "sha512_init_set", "proofs": sp, "n": n, "reps": reps, "commit_ms": r4(timed(commit, 2)), "air_sha512_init_ms": [], "prove_with_ms": []}
+    for _ in range(rounds):
+        res["air_sha512_init_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_sha512_init_device(SHA512, cap_h_.data_ptr(), cap_q.data_ptr(), 0),
+                                                  reps, before=commit)))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(SHA512)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
+        res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_init_verify_device(bp, kt, kt + 1, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0), 3))
         res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
         res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"])
         del proof
