@@ -1570,8 +1570,9 @@ int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t secti
  *                                       denominator was zero (d_out: 7 words).  Both refuse log_rows outside 7 .. 18 and null pointers.
  * Scratch: per section set 3's formula with 599 columns -- (599 n_proofs (N + M) + 2 M) 8 bytes plus two trees and the LDE scratch of 599
  * columns -- and once per context (3 (N + M) + 512) 8 bytes for the preprocessed columns and the barycentric kernel's rows.  At 256 proofs,
- * N = 2^15 and blow-up 8 the helper alone is 599 256 2^15 9 8 bytes, about 360 GB: it CANNOT be resident on one card.  The streamed call
- * keeps refusing every constraint_set but 3, 4 and 5; a streamed form of this helper is a follow-up.  Every refusal comes before anything
+ * N = 2^15 and blow-up 8 the helper alone is 599 256 2^15 9 8 bytes, about 360 GB: it CANNOT be resident on one card.  The SHA-256-named streamed
+ * call keeps refusing every constraint_set but 3, 4 and 5; the streamed form of this helper is
+ * tmx_trace_commit_set_air_sha512_streamed_device ("streamed helpers of the SHA-512 sets" below).  Every refusal comes before anything
  * is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers the quotient calls and the set-level call. */
 #define TMX_AIR_SHA512_HELPER_COLS 599
 #define TMX_AIR_SHA512_CONSTRAINTS 628
@@ -1668,8 +1669,8 @@ int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, con
  * Scratch: per section set 3's formula with 230 columns, and once per context ((N + M) + 256) 8 bytes of its own for SCH and the
  * barycentric kernel's rows (set 7's context scratch is not touched).  The streamed call keeps refusing every constraint_set but 3, 4 and 5.
  * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers the quotient calls
- * and the set-level call.  The block starts of T.2 (IV, feed-forward) are constraint set 9 below.  Follow-ups: the link of T.2 to Level-1,
- * a streamed form of the helper. */
+ * and the set-level call.  The block starts of T.2 (IV, feed-forward) are constraint set 9 below.  Follow-up: the link of T.2 to Level-1.  The
+ * streamed form of the helper is tmx_trace_commit_set_air_sha512_streamed_device below. */
 #define TMX_AIR_SHA512_SCHED_HELPER_COLS 230
 #define TMX_AIR_SHA512_SCHED_CONSTRAINTS 234
 #define TMX_TRACE_SHA512_SCHED_HELPER 131072u
@@ -1784,8 +1785,8 @@ int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* ctx, uint32_t log_row
  * Scratch: per section set 3's formula with 629 columns, and once per context (2 (N + M) + 512) 8 bytes of its own for STA, CHN and the
  * barycentric kernel's rows (the context scratch of sets 7 and 8 is not touched).  The streamed call keeps refusing every constraint_set
  * but 3, 4 and 5.  Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers
- * the quotient calls and the set-level call.  Follow-ups: the link of T.2 to Level-1, a streamed form of the helpers of sets 7 - 9 (at
- * 629 columns the full 256-proof T.2 cannot be resident). */
+ * the quotient calls and the set-level call.  Follow-up: the link of T.2 to Level-1.  At 629 columns the full 256-proof T.2 cannot be
+ * resident: the streamed form of the helpers of sets 7 - 9 is the block "streamed helpers of the SHA-512 sets" below. */
 #define TMX_AIR_SHA512_INIT_HELPER_COLS 629
 #define TMX_AIR_SHA512_INIT_CONSTRAINTS 673
 #define TMX_TRACE_SHA512_INIT_HELPER 524288u
@@ -1804,6 +1805,50 @@ int32_t tmx_air_sha512_init_verify_device(tmx_ctx* ctx, const tmx_batch_params* 
 int32_t tmx_trace_commit_set_air_sha512_init_device(tmx_ctx* ctx, uint32_t section, uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
 int32_t tmx_air_sha512_init_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
 int32_t tmx_air_sha512_init_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
+
+/* ---- streamed helpers of the SHA-512 sets: constraint sets 7, 8 and 9 on the full-size T.2 ----
+ * The sibling of "streamed helpers of the SHA-256 sets" above, under the same contract.  The helper oracle of a set is 599, 230 or 629
+ * columns per proof, 13 to 35 times the 18 columns of T.2; kept extended it is what bounds the size the three set-level calls above can
+ * run at.  Here the helper is fed in chunks of whole proofs and never exists extended; the table member stays resident, and so do the
+ * helper's PRE-LDE columns (the prove's openings at zeta read them).  Field arithmetic is exact, so the pieces in any order give the
+ * resident call's words: for every valid chunk size d_cap_h, d_cap_q, tmx_air_last_gamma, tmx_trace_commit_set_shape and every word of
+ * tmx_trace_commit_set_prove_device's proof equal the resident call's.  Resident and streamed pairs may be mixed within the section; the
+ * verifiers need nothing.  The pieces of the quotient are those of tmx_air_sha512_quotient_range_device, _sched_quotient_range_device and
+ * _init_quotient_range_device above (C = 628, 234, 673).
+ *   tmx_trace_commit_set_air_sha512_streamed_bytes   host only: the bytes the call below allocates for its scratch -- pre-LDE helper |
+ *                                          helper levels | quotient | quotient levels | sponge states [12][M] | chunk [chunk_proofs
+ *                                          helper_cols][M] -- and, in *lde_scratch_bytes (may be null), the LDE's own scratch: twice what
+ *                                          is extended at once, which is one chunk (ONE transform call per chunk, as the prove's gather
+ *                                          extends a streamed member).  With chunk_proofs >= n_proofs: the resident call's (helper_cols
+ *                                          n_proofs (N + M) + 2 M) 8 bytes plus two trees, and twice one proof's helper columns.  0 on a
+ *                                          refused shape: constraint_set outside 7 .. 9, chunk_proofs = 0, chunk_proofs helper_cols no
+ *                                          multiple of 8 (the sponge absorbs eight columns at a time: a multiple of 8 for sets 7 and 9, of
+ *                                          4 for set 8), log_blowup outside 1 .. 6, log_m - log_blowup outside 7 .. 18, n_proofs = 0,
+ *                                          helper_cols n_proofs > 2^24.
+ *   tmx_trace_commit_set_air_sha512_streamed_device   the set-level call of constraint_set 7, 8 or 9 on TMX_TRACE_SHA512.  chunk_proofs
+ *                                          >= n_proofs takes the resident path exactly.  Else: the helper kernel into the pre-LDE columns;
+ *                                          sweep 1, per chunk the LDE into the chunk buffer and k_poseidon_leaves_chunk, then the levels and
+ *                                          d_cap_h; gamma; the set's preprocessed planes filled and extended once; sweep 2, per chunk the
+ *                                          LDE again and the accumulating piece of the quotient; the quotient's tree and d_cap_q.  All of
+ *                                          it runs under the set's NTT domain: if tmx_ntt_set_domain moved the context's it is put back
+ *                                          for the call and restored after.  The pair is registered by the resident calls' rules (same
+ *                                          place by set id, same refusals); a streamed scratch is sized exactly (a larger one left by a
+ *                                          resident call on that set is released).  TMX_ERR_BAD_ARG: no set, constraint_set outside
+ *                                          7 .. 9, a section other than TMX_TRACE_SHA512 or one that is absent or streamed (the TABLE
+ *                                          member must be resident), null caps, a chunk_proofs _bytes refuses, a second call on the
+ *                                          section in either form, a full set.  TMX_ERR_CAPACITY against free memory, the LDE's scratch
+ *                                          included.  At 256 proofs, N = 2^15, blow-up 8 and chunk_proofs = 8 the three pairs need about
+ *                                          50 + 19 + 53 GB where the resident calls need about 880 GB.
+ * Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream apart from a domain change.
+ * tmx_trace_commit_set_air_sha256_streamed_* keep refusing every constraint_set but 3, 4 and 5: these calls have names of their own. */
+uint64_t tmx_trace_commit_set_air_sha512_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
+                                                        uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes);
+int32_t tmx_trace_commit_set_air_sha512_streamed_device(tmx_ctx* ctx, uint32_t constraint_set, uint32_t section, uint32_t chunk_proofs,
+                                                        uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream);
+/* Host only, for tests and memory accounting: the bytes of the scratch the context holds right now for constraint_set 7, 8 or 9 on
+ * TMX_TRACE_SHA512, as the last resident or streamed set-level call left it (a streamed call leaves exactly what _streamed_bytes returns);
+ * 0 if there is none, for a constraint_set outside 7 .. 9 and for any other section. */
+uint64_t tmx_trace_commit_set_air_sha512_scratch_bytes(const tmx_ctx* ctx, uint32_t constraint_set, uint32_t section);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

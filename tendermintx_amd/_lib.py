@@ -451,6 +451,15 @@ def lib():
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise
+    try:   # the streamed helpers of constraint sets 7 - 9 (include/tmx.h "streamed helpers of the SHA-512 sets")
+        L.tmx_trace_commit_set_air_sha512_streamed_bytes.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint64)]
+        L.tmx_trace_commit_set_air_sha512_streamed_bytes.restype = C.c_uint64
+        L.tmx_trace_commit_set_air_sha512_streamed_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha512_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.tmx_trace_commit_set_air_sha512_scratch_bytes.restype = C.c_uint64
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
     L.tmx_witness_batch_sharded_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_uint32, C.c_void_p]
     L.tmx_witness_validator_sharded_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -732,6 +732,17 @@ class Context:
         """(host only) the bytes of the scratch the context holds for that set and section right now; 0 if none"""
         return int(self._L.tmx_trace_commit_set_air_sha256_scratch_bytes(self._h, constraint_set, section))
 
+    # ---- streamed helpers of constraint sets 7 - 9 (include/tmx.h "streamed helpers of the SHA-512 sets")
+    def trace_commit_set_air_sha512_streamed_device(self, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q, stream=None):
+        """the set-level call of constraint set 7, 8 or 9 on TRACE_SHA512 with the helper fed in chunks of chunk_proofs whole proofs and
+        never resident extended: the same caps, gamma, shape and proof words as the resident call"""
+        check(self._L.tmx_trace_commit_set_air_sha512_streamed_device(self._h, constraint_set, section, chunk_proofs, d_cap_h, d_cap_q,
+                                                                      self._stream(stream)), self._h)
+
+    def trace_commit_set_air_sha512_scratch_bytes(self, constraint_set, section):
+        """(host only) the bytes of the scratch the context holds for set 7, 8 or 9 on that section right now; 0 if none"""
+        return int(self._L.tmx_trace_commit_set_air_sha512_scratch_bytes(self._h, constraint_set, section))
+
     # ---- multi-GPU: the RCCL exchange behind the C ABI (include/tmx.h "multi-GPU")
     def comm_create(self, unique_id, rank, world):
         check(self._L.tmx_comm_create(self._h, bytes(unique_id) if unique_id is not None else None, rank, world), self._h)
@@ -884,6 +895,15 @@ def trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup
     L = L or _lib.lib()
     lde = C.c_uint64(0)
     return int(L.tmx_trace_commit_set_air_sha256_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs,
+                                                                 C.byref(lde))), int(lde.value)
+
+
+def trace_commit_set_air_sha512_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs, L=None):
+    """tmx_trace_commit_set_air_sha512_streamed_bytes (no context, no device): (scratch bytes of the streamed set-level call of set 7, 8 or
+    9, the LDE's own scratch in bytes); (0, 0) for a refused shape"""
+    L = L or _lib.lib()
+    lde = C.c_uint64(0)
+    return int(L.tmx_trace_commit_set_air_sha512_streamed_bytes(constraint_set, log_m, log_blowup, cap_height, n_proofs, chunk_proofs,
                                                                  C.byref(lde))), int(lde.value)
 
 

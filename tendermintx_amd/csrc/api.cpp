@@ -447,7 +447,7 @@ struct tmx_ctx {
   struct SetRec {
     bool valid; uint32_t n_oracles, log_blowup, cap_height; uint64_t root, shift;
     // buf: the scratch the offsets refer to if it is not d_set (ext: d_set_air): a member added by tmx_trace_commit_set_air_sha256_device
-    // chunk_cols != 0: a streamed member with a chunk buffer of its own at chunk_off of buf (a streamed helper of constraint sets 3 - 5)
+    // chunk_cols != 0: a streamed member with a chunk buffer of its own at chunk_off of buf (a streamed helper of constraint sets 3 - 5, 7 - 9)
     struct Oracle {
       uint32_t section, log_m, n_cols; size_t cols_off, lde_off, lev_off; bool streamed, ext; const void* buf = nullptr;
       uint32_t chunk_cols = 0; size_t chunk_off = 0;
@@ -466,7 +466,7 @@ struct tmx_ctx {
   // constraint sets 3, 4 and 5 (tmx_trace_commit_set_air_sha256_device, _sched_device, _init_device), [set (ShaSet.scratch)][section (SHA256,
   // TREE, HEADER)]: one scratch that holds the set's helper member of that section -- pre-LDE columns | extended columns | tree levels --
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
-  // (tmx_trace_commit_set_air_sha256_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
+  // (tmx_trace_commit_set_air_sha256_streamed_device, _sha512_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
   void* d_set_sha[7][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4 .. 6: sets 7, 8 and 9, whose one section uses slot 0)
   size_t set_sha_bytes[7][3] = {};
@@ -3772,7 +3772,7 @@ static FriGeom batch_geom(const tmx_batch_params& p, const tmx_batch_layout& L, 
 // What a batch prove reads: per oracle its extended columns, its tree, and the columns its openings are evaluated from (DeepSrc)
 // A streamed oracle (chunk_cols[k] != 0, a member of a commit set) has no extended columns (cols[k] == nullptr): its deep[k] columns are the
 // set's pre-LDE columns, extended chunk_cols[k] at a time into chunk_buf[k] (chunk_cols[k] << log_n words: the set's shared buffer, or the
-// oracle's own for a streamed helper of constraint sets 3 - 5) when the queried rows are gathered.
+// oracle's own for a streamed helper of constraint sets 3 - 5 and 7 - 9) when the queried rows are gathered.
 struct BatchSrc {
   const uint64_t* cols[TMX_BATCH_MAX_ORACLES]; const uint64_t* levels[TMX_BATCH_MAX_ORACLES]; DeepSrc deep[TMX_BATCH_MAX_ORACLES];
   uint32_t chunk_cols[TMX_BATCH_MAX_ORACLES]; uint64_t* chunk_buf[TMX_BATCH_MAX_ORACLES];
@@ -4596,7 +4596,7 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // under set 5's signatures (sets 3 and 4 have no mode: their adapters drop `chain`).  A set with a public table (set 6) takes d_pub, null
 // for the others, and does its public step at four places, each a branch on has_public: gamma observes the table's digest (sha_gamma), the
 // pass writes its tables to d_air6 and the piece that starts at proof 0 carries - PQ (sha_pass), the verifier forms V before its check
-// (sha_verify_call), and the helper kernel reads d_pub (sha_helper_launch).  Its helper is resident only: the streamed calls take sets 3 - 5.
+// (sha_verify_call), and the helper kernel reads d_pub (sha_helper_launch).  Its helper is resident only: the streamed calls take sets 3 - 5 and 7 - 9.
 // Set 7 (the SHA-512 table: 18 columns per proof, 80-row blocks) is the fifth row.  Where it differs is a branch on has_periodic: the pass
 // reads the three extended preprocessed planes of d_air7 instead of period-64 tables (sha_pass; sha512_periodic fills and extends them in
 // front of it), the verifier runs the barycentric kernel in front of its check (sha_verify_call), and the set-level call takes
@@ -5066,9 +5066,10 @@ static const char* sha_chunk_refusal(const ShaSet& d, uint32_t chunk_proofs) {
   return nullptr;
 }
 
-// chunk_proofs = 0: the resident calls.  Else tmx_trace_commit_set_air_sha256_streamed_device: the helper streamed in chunks of chunk_proofs
-// whole proofs, or resident exactly as from the resident calls if one chunk holds it all.  The pair goes behind every pair of a lower set
-// that follows the table, and the calls of lower sets insert in front of later members: every order ends as table, H3, Q3, ..., H6, Q6.
+// chunk_proofs = 0: the resident calls.  Else tmx_trace_commit_set_air_sha256_streamed_device (sets 3 - 5) or
+// tmx_trace_commit_set_air_sha512_streamed_device (sets 7 - 9): the helper streamed in chunks of chunk_proofs whole proofs, or resident
+// exactly as from the resident calls if one chunk holds it all.  The pair goes behind every pair of a lower set that follows the table,
+// and the calls of lower sets insert in front of later members: every order ends as table, H3, Q3, ..., H6, Q6 (T.2: H7, Q7, ..., H9, Q9).
 static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint32_t chunk_proofs, bool by_chunks, const uint64_t* d_pub,
                             uint64_t* d_cap_h, uint64_t* d_cap_q, void* hip_stream) {
   if (!c) return TMX_ERR_BAD_ARG;
@@ -5169,10 +5170,12 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
       if ((e = sha_gamma(c, d, log_m, r.log_blowup, r.cap_height, n_proofs, chain, lev_t + 4 * (n_dig - n_cap), lev_h + 4 * (n_dig - n_cap), d_pub, false,
                          s)))
         return e;
+      // (sets 7 - 9: the preprocessed planes every piece of sweep 2 reads, filled and extended once, under the set's domain as the chunks are)
+      if (d.has_periodic && (e = sha512_periodic(c, d, log_m, r.log_blowup, hip_stream))) return e;
       for (uint32_t p0 = 0; p0 < n_proofs; p0 += chunk_proofs) {
         const uint32_t n = std::min(chunk_proofs, n_proofs - p0);
         if ((e = extend(p0, n))) return e;
-        if ((e = sha_pass(c, d, log_m, r.log_blowup, chain, A, p0, n, tcols + (((uint64_t)p0 * AIR_SHA_WIDTH) << log_m), chunk, d_pub, n_proofs,
+        if ((e = sha_pass(c, d, log_m, r.log_blowup, chain, A, p0, n, tcols + (((uint64_t)p0 * d.width) << log_m), chunk, d_pub, n_proofs,
                           p0 ? AIR_FORM_PIECE_ACC : AIR_FORM_PIECE, quot, s)))
           return e;
       }
@@ -5395,6 +5398,31 @@ uint64_t tmx_trace_commit_set_air_sha256_scratch_bytes(const tmx_ctx* c, uint32_
   const int slot = section == TMX_TRACE_SHA256 ? 0 : section == TMX_TRACE_TREE ? 1 : section == TMX_TRACE_HEADER ? 2 : -1;
   if (slot < 0) return 0;
   return c->set_sha_bytes[SHA_SETS[constraint_set - 3].scratch][slot];
+}
+
+// ---- streamed helpers of the SHA-512 sets: rows 4 - 6 of the host path above through its streamed branch, under names of their own (the
+// SHA-256 names keep refusing every set but 3, 4 and 5)
+uint64_t tmx_trace_commit_set_air_sha512_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
+                                                        uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes) {
+  if (lde_scratch_bytes) *lde_scratch_bytes = 0;
+  if (constraint_set < 7 || constraint_set > 9) return 0;
+  const ShaSet& d = SHA_SETS[constraint_set - 3];
+  if (sha_chunk_refusal(d, chunk_proofs) || sha_check(nullptr, d, log_m, log_blowup, n_proofs, 0)) return 0;
+  const ShaScratch SP = sha_scratch_plan(d, log_m, log_blowup, std::min(cap_height, log_m), n_proofs, std::min(chunk_proofs, n_proofs));
+  if (lde_scratch_bytes) *lde_scratch_bytes = SP.lde;
+  return SP.want;
+}
+
+int32_t tmx_trace_commit_set_air_sha512_streamed_device(tmx_ctx* c, uint32_t constraint_set, uint32_t section, uint32_t chunk_proofs, uint64_t* d_cap_h,
+                                                        uint64_t* d_cap_q, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (constraint_set < 7 || constraint_set > 9) return fail(c, TMX_ERR_BAD_ARG, "constraint_set must be 7, 8 or 9");
+  return sha_set_call(c, SHA_SETS[constraint_set - 3], section, chunk_proofs, true, nullptr, d_cap_h, d_cap_q, hip_stream);
+}
+
+uint64_t tmx_trace_commit_set_air_sha512_scratch_bytes(const tmx_ctx* c, uint32_t constraint_set, uint32_t section) {
+  if (!c || constraint_set < 7 || constraint_set > 9 || section != TMX_TRACE_SHA512) return 0;
+  return c->set_sha_bytes[SHA_SETS[constraint_set - 3].scratch][0];
 }
 
 // ---- constraint set 7: the round constraints of the SHA-512 table, through row 4 of the host path above

@@ -64,6 +64,14 @@
            M = 2^LOG_M (16) and the SAME table, alternating in one process; ps_per_helper_word_set9 / _set7 and their ratio.  Then the
            set-level call of set 9 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the
            verifier.
+  sha512_streamed  the streamed helpers of constraint sets 7 - 9 (tmx_trace_commit_set_air_sha512_streamed_device), sha_streamed's sibling, on
+           a set SHA512 | HEADER of SHA_SET_P proofs (16) at N = n, the sets named in SETS (7 by default; 7,8,9), CHUNK_PROOFS proofs per
+           chunk (8).  The resident and the streamed set-level calls, alternating in one process after a warm call, every round listed,
+           with the prove after each; cap digests of both forms; and the chunk LDE alone (one sweep's and the two sweeps' transforms over
+           buffers of the same sizes: what the call and the prove have over the resident form).  FULL=1: the streamed calls only, once each
+           (the resident helpers do not fit at full size): the bytes from tmx_trace_commit_set_air_sha512_streamed_bytes, free memory
+           before and after every call, digests of both caps per set, the times, one prove, the degree flag and the verdicts of the sets'
+           verifiers; a refusal (TMX_ERR_CAPACITY on a shared card) is recorded with its text.
 Times per call from HIP events around REPS back-to-back calls after one warm call.  The modes sha, sched and init draw their columns from
 SEED (1 by default) and print quotient_sha256, the SHA-256 of the quotient words their call leaves: equal digests from two library builds
 (one of them named by TMX_LIB) say that both write the same words at the timed size.
@@ -988,3 +996,140 @@ if "sha512_init" in modes:
         del proof
     print(json.dumps(res), flush=True)
     ctx.close()
+    del tr  # (given back so that a mode chained behind this one, such as sha512_streamed, starts from the memory it reports as free)
+    torch.cuda.empty_cache()
+
+if "sha512_streamed" in modes:
+    from tendermintx_amd.synth import bench_workload
+    from tendermintx_amd.context import trace_commit_set_air_sha512_streamed_bytes
+    SHA512, HEADER = 2, 32
+    sets, cpf = [int(x) for x in os.environ.get("SETS", "7").split(",")], int(os.environ.get("CHUNK_PROOFS", "8"))
+    full = os.environ.get("FULL", "0") == "1"
+    hcols = {7: 599, 8: 230, 9: 629}
+    sp = int(os.environ.get("SHA_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    del out
+    cw = 4 << cap_h
+    scaps = torch.zeros(2 * cw, dtype=torch.int64, device=dev)
+    pair = {s_: torch.zeros(2 * cw, dtype=torch.int64, device=dev) for s_ in sets}
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA512 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    resident = {7: ctx.trace_commit_set_air_sha512_device, 8: ctx.trace_commit_set_air_sha512_sched_device,
+                9: ctx.trace_commit_set_air_sha512_init_device}
+
+    def call(s_, streamed):
+        if streamed:
+            ctx.trace_commit_set_air_sha512_streamed_device(s_, SHA512, cpf, pair[s_][:cw].data_ptr(), pair[s_][cw:].data_ptr(), 0)
+        else:
+            resident[s_](SHA512, pair[s_][:cw].data_ptr(), pair[s_][cw:].data_ptr(), 0)
+
+    def calls(streamed):
+        for s_ in sets:
+            call(s_, streamed)
+
+    digests = lambda: {str(s_): [hashlib.sha256(pair[s_][k * cw:(k + 1) * cw].cpu().numpy().tobytes()).hexdigest()[:16] for k in (0, 1)] for s_ in sets}
+    commit()
+    shape0, order0 = ctx.trace_commit_set_shape()
+    log_m = shape0["log_n"][order0.index(SHA512)]
+    res = {"mode": "sha512_streamed", "full": full, "sets": sets, "proofs": sp, "n": n, "log_m": log_m, "chunk_proofs": cpf, "reps": reps,
+           "bytes": {str(s_): list(trace_commit_set_air_sha512_streamed_bytes(s_, log_m, log_blowup, cap_h, sp, cpf)) for s_ in sets},
+           "bytes_resident": {str(s_): list(trace_commit_set_air_sha512_streamed_bytes(s_, log_m, log_blowup, cap_h, sp, sp)) for s_ in sets}}
+
+    def prove_and_verify(k):
+        """k timed proves after a warm one (k = 0: ONE prove, timed cold); the verdicts of the sets' verifiers on the last proof"""
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        if k:
+            ms = r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), k))
+        else:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0)
+            b.record()
+            torch.cuda.synchronize(dev)
+            ms = r4(a.elapsed_time(b))
+        kt = order.index(SHA512)
+        caps, at, where = [scaps[:(kt + 1) * cw]], kt + 1, {}
+        for s_ in sorted(sets):
+            caps.append(pair[s_])
+            where[s_] = at
+            at += 2
+        all_caps = torch.cat(caps + [scaps[(kt + 1) * cw:]])
+        verdicts = {}
+        for s_, kh in where.items():
+            if s_ == 7:
+                ctx.air_sha512_verify_device(bp, kt, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            elif s_ == 8:
+                ctx.air_sha512_sched_verify_device(bp, kt, kh, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            else:
+                ctx.air_sha512_init_verify_device(bp, kt, kh, all_caps.data_ptr(), proof.data_ptr(), ok.data_ptr(), 0)
+            verdicts[str(s_)] = bool((ok.cpu().numpy() == 1).all())
+        return ms, verdicts, ctx.fri_last_degree_ok(), order, bp["n_cols"]
+
+    if not full:
+        res.update(resident_call_ms=[], streamed_call_ms=[], prove_resident_ms=[], prove_streamed_ms=[])
+        calls(False)   # (the warm call: the context's scratches and the LDE's grow here, outside every round)
+        for _ in range(rounds):
+            res["resident_call_ms"].append(r4(timed(lambda: calls(False), reps, before=commit)))
+            ms, res["verdicts_resident"], _, _, _ = prove_and_verify(reps)
+            res["prove_resident_ms"].append(ms)
+            res["caps_resident"] = digests()
+            res["streamed_call_ms"].append(r4(timed(lambda: calls(True), reps, before=commit)))
+            ms, res["verdicts_streamed"], res["degree_ok"], res["order"], res["columns"] = prove_and_verify(reps)
+            res["prove_streamed_ms"].append(ms)
+            res["caps_streamed"] = digests()
+        res["caps_equal"] = res["caps_resident"] == res["caps_streamed"]
+        # the chunk LDE alone: both sweeps' transforms of every set over buffers of the sizes the call uses, and the prove's third
+        log_sub = log_m - log_blowup
+        big = max(hcols[s_] for s_ in sets)
+        pre = torch.randint(0, 2**62, ((big * sp) << log_sub,), dtype=torch.int64, device=dev)
+        chunk_buf = torch.empty((big * cpf) << log_m, dtype=torch.int64, device=dev)
+
+        def lde_alone(sweeps):
+            for s_ in sets:
+                for _sweep in range(sweeps):
+                    for p0 in range(0, sp, cpf):
+                        k_ = min(cpf, sp - p0) * hcols[s_]
+                        ctx.lde_device(log_sub, log_blowup, k_, pre[(p0 * hcols[s_]) << log_sub:].data_ptr(), chunk_buf.data_ptr(), 0)
+
+        res["chunk_lde_two_sweeps_ms"] = [r4(timed(lambda: lde_alone(2), reps)) for _ in range(rounds)]
+        res["chunk_lde_one_sweep_ms"] = [r4(timed(lambda: lde_alone(1), reps)) for _ in range(rounds)]
+        best_s, best_r = min(res["streamed_call_ms"]), min(res["resident_call_ms"])
+        res["ratio_streamed_over_resident_call"] = round(best_s / best_r, 3)
+        res["ratio_streamed_over_resident_prove"] = round(min(res["prove_streamed_ms"]) / min(res["prove_resident_ms"]), 3)
+        res["call_excess_ms"] = r4(best_s - best_r)
+        res["prove_excess_ms"] = r4(min(res["prove_streamed_ms"]) - min(res["prove_resident_ms"]))
+        res["helper_lde_share_of_streamed"] = round(min(res["chunk_lde_two_sweeps_ms"]) / best_s, 3)
+        del pre, chunk_buf
+    else:
+        # the streamed calls only, once each (the resident helpers do not fit): a refusal is recorded as it is worded, not worked around
+        res["free_before_mib"] = torch.cuda.mem_get_info(dev)[0] >> 20
+        res["streamed_call_ms"], res["free_after_mib"] = {}, {}
+        try:
+            for s_ in sets:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                call(s_, True)
+                b.record()
+                torch.cuda.synchronize(dev)
+                res["streamed_call_ms"][str(s_)] = r4(a.elapsed_time(b))
+                res["free_after_mib"][str(s_)] = torch.cuda.mem_get_info(dev)[0] >> 20
+                res["scratch_bytes_" + str(s_)] = ctx.trace_commit_set_air_sha512_scratch_bytes(s_, SHA512)
+            res["caps_streamed"] = digests()
+            res["prove_streamed_ms"], res["verdicts_streamed"], res["degree_ok"], res["order"], res["columns"] = prove_and_verify(0)
+            res["free_after_prove_mib"] = torch.cuda.mem_get_info(dev)[0] >> 20
+        except _lib.TmxError as e:
+            res["refused"] = {"status": e.status, "text": str(e)}
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del tr
+    torch.cuda.empty_cache()
