@@ -1509,10 +1509,10 @@ int32_t tmx_trace_commit_set_air_sha256_link_device(tmx_ctx* ctx, uint32_t secti
  *              does not exist.  Three PUBLIC columns that depend on N alone take its place, each a polynomial of degree <= N - 1:
  *                SEL_r = 1, but 0 where r mod 80 = 79 and at r = N - 1 (the wrap row must be off: (N - 1) mod 80 != 79)
  *                KLO_r, KHI_r = the low and the high 32 bits of K512[r mod 80], on every row r < N
- *              The prover fills them (k_air_sha512_periodic) and extends them exactly as helper columns are extended.  The verifier
+ *              The prover fills them (k_air_sha512_periodic<Sha512Round>) and extends them exactly as helper columns are extended.  The verifier
  *              commits to nothing: it computes SEL(zeta), KLO(zeta), KHI(zeta) itself, barycentrically over the N rows,
  *                P(zeta) = (zeta^N - 1) / N  sum_r v_r omega^r / (zeta - omega^r)
- *              in a multi-workgroup kernel (k_air_sha512_periodic_eval, one batched inversion per four rows of a thread).  A zero
+ *              in a multi-workgroup kernel (k_air_sha512_periodic_eval<Sha512Round>, one batched inversion per four rows of a thread).  A zero
  *              denominator clears every verdict.  This O(N) work bounds the rows set 7 accepts to log_rows 7 .. 18 (the full size is 15).
  *   helper     599 columns per proof, the table's rows, bits LSB first, bit 32 limb + i in limb `limb`, bit indices mod 64:
  *                0 .. 63  A      128 .. 191  C      256 .. 319  F      384 .. 447  U0_i = A_(i+28) xor A_(i+34)     512 .. 575  V_i = A_i B_i
@@ -1605,9 +1605,9 @@ int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, con
  *   preprocessed column  ONE more public column of full degree N - 1 that depends on N alone:
  *                SCH_r = 1 where the NEXT row is a schedule row of the same block, 15 <= r mod 80 <= 78, and r != N - 1; 0 elsewhere.
  *              The wrap row must be switched off explicitly: (2^k - 1) mod 80 is 47, 15, 31, 63 for k = 3, 0, 1, 2 mod 4, always inside
- *              15 .. 78, while row 0 is W_0 of a block.  The prover fills it (k_air_sha512_sched_periodic) and extends it exactly as helper
+ *              15 .. 78, while row 0 is W_0 of a block.  The prover fills it (k_air_sha512_periodic<Sha512Sched>) and extends it exactly as helper
  *              columns are extended; the verifier commits to nothing and computes SCH(zeta) itself, barycentrically over the N rows
- *              (k_air_sha512_sched_periodic_eval, set 7's batching: four rows per F_p^2 inversion, up to 64 workgroups).  It is not observed
+ *              (k_air_sha512_periodic_eval<Sha512Sched>, four rows per F_p^2 inversion, up to 64 workgroups).  It is not observed
  *              by gamma, as SEL, KLO and KHI are not.  A zero denominator clears every verdict.  log_rows 7 .. 18, set 7's range, for the
  *              same reason.
  *   helper     230 columns per proof (twice set 4's 115), bits LSB first, bit indices mod 64; defined for ANY input: the operands are the
@@ -1711,9 +1711,9 @@ int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* ctx, uint32_t log_row
  *                CHN_r = 1 where r mod 160 = 79 (the next row is row 0 of a second block); 0 elsewhere.
  *              (2^k - 1) mod 160 is 127, 95, 31, 63 for k = 3, 0, 1, 2 mod 4, never 79 or 159: the wrap row is never a chain row, and
  *              it must be switched ON in STA explicitly, because row 0 is the first row of a hash -- the opposite of SEL and SCH, whose
- *              wrap row is switched off.  The prover fills them (k_air_sha512_init_periodic) and extends them exactly as helper columns
+ *              wrap row is switched off.  The prover fills them (k_air_sha512_periodic<Sha512Init>) and extends them exactly as helper columns
  *              are extended; the verifier commits to nothing and computes STA(zeta) and CHN(zeta) itself, barycentrically over the N rows
- *              (k_air_sha512_init_periodic_eval, set 7's batching: four rows per F_p^2 inversion, up to 64 workgroups).  gamma does not
+ *              (k_air_sha512_periodic_eval<Sha512Init>, four rows per F_p^2 inversion, up to 64 workgroups).  gamma does not
  *              observe them.  A zero denominator clears every verdict.  log_rows 7 .. 18, set 7's range, for the same reason.
  *   helper     629 columns per proof (set 5's 315 in limbs), bits LSB first, bit indices mod 64; defined for ANY input.  Offsets inside
  *              a proof:

@@ -206,118 +206,63 @@ int launch_air_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h,
                           uint64_t k_inv, const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta,
                           const void* d_gamma, const void* d_v, uint32_t n_queries, void* d_ok, void* stream);
 
-// ---- constraint set 7: the round constraints of the SHA-512 table (include/tmx.h "the round constraints of the SHA-512 table").  A table of
-// 18 columns per proof (T.2: nine 64-bit words as lo, hi), a helper oracle of 599 columns per proof, 628 constraints per proof; gamma comes
-// from set 3's lone-lane kernel with the set id 7 in obs[0] (launch_air_sha_gamma: the same code object).  The selector and the round
-// constants have the period 80, which no power-of-two subgroup fits: they are three preprocessed columns of full degree (SEL, KLO, KHI),
-// filled and extended by the prover like helper columns, and evaluated at zeta by the verifier barycentrically over the N rows.
+// ---- constraint sets 7, 8 and 9: the SHA-512 table (include/tmx.h "the round constraints of the SHA-512 table", "the message schedule of
+// the SHA-512 table", "the block starts of the SHA-512 table").  A table of 18 columns per proof (T.2: nine 64-bit words as lo, hi) and per
+// set a helper oracle and a constraint count:
+//   set 7, the round function   599 helper columns, 628 constraints
+//   set 8, the message schedule 230 helper columns (set 4's 115 twice: lo / hi limbs), 234 constraints
+//   set 9, the block starts     629 helper columns (set 5's 315 in lo / hi limbs), 673 constraints
+// gamma comes from set 3's lone-lane kernel with the set id in obs[0] (launch_air_sha_gamma: the same code object).  The blocks are 80 rows
+// (set 9: lanes of 160 with a wrap row of their own), which no power-of-two subgroup fits, so the selectors and set 7's round constants are
+// preprocessed columns of full degree: SEL, KLO, KHI (set 7), SCH "the next row is a schedule row" (set 8), STA "the next row starts a
+// hash" and CHN "the next row starts a second block" (set 9).  The prover fills and extends them like helper columns, the verifier
+// evaluates them at zeta barycentrically over the N rows.
 constexpr uint32_t AIR_SHA512_WIDTH = 18, AIR_SHA512_HELPER_COLS = 599, AIR_SHA512_CONSTRAINTS = 628;
-// The tables one set-7 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [630][2]               gamma^0 .. gamma^628, then gamma^(628 first)
+constexpr uint32_t AIR_SHA512_SCHED_HELPER_COLS = 230, AIR_SHA512_SCHED_CONSTRAINTS = 234;
+constexpr uint32_t AIR_SHA512_INIT_HELPER_COLS = 629, AIR_SHA512_INIT_CONSTRAINTS = 673;
+// The tables one quotient launch of a set reads (u64 words at d_tab; they fit the table part of set 1's scratch), n its constraint count:
+//   gpow  [n + 2][2]             gamma^0 .. gamma^n, then gamma^(n first)
 //   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
-constexpr uint32_t AIR7_TAB_GPOW = 0, AIR7_TAB_ZINV = 1280;
-constexpr uint64_t AIR7_TAB_WORDS = AIR7_TAB_ZINV + 64;
+constexpr uint32_t AIR7_TAB_GPOW = 0, AIR7_TAB_ZINV = 1280, AIR8_TAB_GPOW = 0, AIR8_TAB_ZINV = 512, AIR9_TAB_GPOW = 0, AIR9_TAB_ZINV = 1408;
+constexpr uint64_t AIR7_TAB_WORDS = AIR7_TAB_ZINV + 64, AIR8_TAB_WORDS = AIR8_TAB_ZINV + 64, AIR9_TAB_WORDS = AIR9_TAB_ZINV + 64;
 static_assert(2 * (AIR_SHA512_CONSTRAINTS + 2) <= AIR7_TAB_ZINV && AIR7_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
               "the set-7 tables live in the table part of set 1's scratch");
-// The barycentric kernel's output: one row of AIR7_PART_WORDS words per workgroup (six words of sums, a zero-denominator flag, one unused),
-// 1024 rows of the table per workgroup, at most AIR7_MAX_PARTS workgroups
-constexpr uint32_t AIR7_PART_WORDS = 8, AIR7_MAX_PARTS = 64;
+static_assert(2 * (AIR_SHA512_SCHED_CONSTRAINTS + 2) <= AIR8_TAB_ZINV && AIR8_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-8 tables live in the table part of set 1's scratch");
+static_assert(2 * (AIR_SHA512_INIT_CONSTRAINTS + 2) <= AIR9_TAB_ZINV && AIR9_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-9 tables live in the table part of set 1's scratch");
+// The barycentric kernel's output: one row of AIR*_PART_WORDS words per workgroup (two words of sum per plane, a zero-denominator flag, the
+// rest unused), 1024 rows of the table per workgroup, at most AIR7_MAX_PARTS workgroups
+constexpr uint32_t AIR7_PART_WORDS = 8, AIR8_PART_WORDS = 4, AIR9_PART_WORDS = 8, AIR7_MAX_PARTS = 64;
 inline uint32_t air_sha512_eval_parts(uint32_t log_rows) {
   const uint32_t n = log_rows > 10 ? 1u << (log_rows - 10) : 1u;
   return n < AIR7_MAX_PARTS ? n : AIR7_MAX_PARTS;
 }
-// SEL, KLO, KHI before the LDE (planar, 3 << log_rows words at d_pre): one lane per row
-int launch_air_sha512_periodic(uint32_t log_rows, void* d_pre, void* stream);
-// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 599 n_proofs
+// The helper oracles from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 599 / 230 /
+// 629 n_proofs
 int launch_air_sha512_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
-// s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
-int launch_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
-// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(628 p + j) C_(p,j) / (x^N - 1); d_pre the three extended
-// preprocessed planes (3 << log_m words); form as in launch_air_sha_quotient
-int launch_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
-                               const void* d_tab, int form, void* d_quot, void* stream);
-// The barycentric sums of SEL, KLO, KHI at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N: air_sha512_eval_parts(log_rows)
-// rows at d_part
-int launch_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
-// d_out[0 .. 6) = SEL(zeta), KLO(zeta), KHI(zeta), d_out[6] = 1 if a denominator was zero; n_inv = 1 / N
-int launch_air_sha512_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
-// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with the
-// three preprocessed columns at zeta from the barycentric kernel's rows at d_part
-int launch_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                            const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                            uint32_t n_queries, void* d_ok, void* stream);
-
-// ---- constraint set 8: the message schedule of the SHA-512 table (include/tmx.h "the message schedule of the SHA-512 table").  Set 7's table,
-// a helper oracle of 230 columns per proof (set 4's 115 twice: lo / hi limbs), 234 constraints per proof; gamma comes from set 3's lone-lane
-// kernel with the set id 8 in obs[0] (launch_air_sha_gamma: the same code object).  The selector "the next row is a schedule row" has the
-// period 80: one more preprocessed column of full degree (SCH), filled, extended and evaluated as set 7's three are.
-constexpr uint32_t AIR_SHA512_SCHED_HELPER_COLS = 230, AIR_SHA512_SCHED_CONSTRAINTS = 234;
-// The tables one set-8 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [236][2]               gamma^0 .. gamma^234, then gamma^(234 first)
-//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
-constexpr uint32_t AIR8_TAB_GPOW = 0, AIR8_TAB_ZINV = 512;
-constexpr uint64_t AIR8_TAB_WORDS = AIR8_TAB_ZINV + 64;
-static_assert(2 * (AIR_SHA512_SCHED_CONSTRAINTS + 2) <= AIR8_TAB_ZINV && AIR8_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
-              "the set-8 tables live in the table part of set 1's scratch");
-// The barycentric kernel's output: one row of AIR8_PART_WORDS words per workgroup (two words of the sum, a zero-denominator flag, one
-// unused); the workgroups are set 7's (air_sha512_eval_parts: 1024 rows each, at most AIR7_MAX_PARTS)
-constexpr uint32_t AIR8_PART_WORDS = 4;
-// SCH before the LDE (1 << log_rows words at d_pre): one lane per row
-int launch_air_sha512_sched_periodic(uint32_t log_rows, void* d_pre, void* stream);
-// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 230 n_proofs
 int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
-// s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
-int launch_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
-// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(234 p + j) C_(p,j) / (x^N - 1); d_pre the extended SCH
-// plane (1 << log_m words); form as in launch_air_sha_quotient
-int launch_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                                     const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream);
-// The barycentric sum of SCH at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N: air_sha512_eval_parts(log_rows) rows
-// at d_part
-int launch_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
-// d_out[0 .. 2) = SCH(zeta), d_out[2] = 1 if a denominator was zero; n_inv = 1 / N
-int launch_air_sha512_sched_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
-// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with
-// SCH at zeta from the barycentric kernel's rows at d_part
-int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                                  const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                                  uint32_t n_queries, void* d_ok, void* stream);
-
-// ---- constraint set 9: the block starts of the SHA-512 table (include/tmx.h "the block starts of the SHA-512 table").  Set 7's table, a
-// helper oracle of 629 columns per proof (set 5's 315 in lo / hi limbs), 673 constraints per proof; gamma comes from set 3's lone-lane
-// kernel with the set id 9 in obs[0] (launch_air_sha_gamma: the same code object).  The selectors "the next row starts a hash" and "the
-// next row starts a second block" have the period 160 with a wrap row of their own: two more preprocessed columns of full degree (STA,
-// CHN), filled, extended and evaluated as set 7's three are.
-constexpr uint32_t AIR_SHA512_INIT_HELPER_COLS = 629, AIR_SHA512_INIT_CONSTRAINTS = 673;
-// The tables one set-9 quotient launch reads (u64 words at d_tab; they fit the table part of set 1's scratch):
-//   gpow  [675][2]               gamma^0 .. gamma^673, then gamma^(673 first)
-//   zinv  [2^log_blowup]         1 / (x_i^N - 1), by i mod 2^log_blowup
-constexpr uint32_t AIR9_TAB_GPOW = 0, AIR9_TAB_ZINV = 1408;
-constexpr uint64_t AIR9_TAB_WORDS = AIR9_TAB_ZINV + 64;
-static_assert(2 * (AIR_SHA512_INIT_CONSTRAINTS + 2) <= AIR9_TAB_ZINV && AIR9_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
-              "the set-9 tables live in the table part of set 1's scratch");
-// The barycentric kernel's output: one row of AIR9_PART_WORDS words per workgroup (four words of the two sums, a zero-denominator flag,
-// three unused); the workgroups are set 7's (air_sha512_eval_parts: 1024 rows each, at most AIR7_MAX_PARTS)
-constexpr uint32_t AIR9_PART_WORDS = 8;
-// STA and CHN before the LDE (planar, 2 << log_rows words at d_pre): one lane per row
-int launch_air_sha512_init_periodic(uint32_t log_rows, void* d_pre, void* stream);
-// The helper oracle from pre-LDE columns: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_helper 629 n_proofs
 int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream);
-// s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
-int launch_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
-// The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(673 p + j) C_(p,j) / (x^N - 1); d_pre the two extended
-// preprocessed planes (STA, CHN; 2 << log_m words); form as in launch_air_sha_quotient
-int launch_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                                    const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream);
-// The barycentric sums of STA and CHN at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N:
-// air_sha512_eval_parts(log_rows) rows at d_part
-int launch_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
-// d_out[0 .. 4) = STA(zeta), CHN(zeta), d_out[4] = 1 if a denominator was zero; n_inv = 1 / N
-int launch_air_sha512_init_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
-// The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with
-// STA and CHN at zeta from the barycentric kernel's rows at d_part
-int launch_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                                 const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                                 uint32_t n_queries, void* d_ok, void* stream);
+// Every other launch is the same code for the three sets, instantiated per set: one table of launchers each.  `planes` below is 3, 1, 2.
+struct AirSha512Launch {
+  // The planes before the LDE (planar, planes << log_rows words at d_pre): one lane per row
+  int (*fill)(uint32_t log_rows, void* d_pre, void* stream);
+  // s_n = s^N, w_n = w^N; gamma at d_gamma (2 words); first_proof = 0 for a whole table
+  int (*tables)(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
+  // The hot pass: d_quot (planar, 2 << log_m words, canonical) = sum_p sum_j gamma^(n p + j) C_(p,j) / (x^N - 1); d_pre the extended
+  // preprocessed planes (planes << log_m words); form as in launch_air_sha_quotient
+  int (*quotient)(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
+                  const void* d_tab, int form, void* d_quot, void* stream);
+  // The barycentric sums of the planes at zeta (2 words at d_zeta) over the N = 2^log_rows rows, om = omega_N: air_sha512_eval_parts(log_rows)
+  // rows at d_part
+  int (*eval)(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
+  // d_out[0 .. 2 planes) = the planes at zeta, d_out[2 planes] = 1 if a denominator was zero; n_inv = 1 / N
+  int (*fold)(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
+  // The identity at zeta from the openings blocks of the table (2^log_r_t rows per plane), the helper (2^log_r_h) and the quotient, with the
+  // planes at zeta from the barycentric kernel's rows at d_part
+  int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part, const void* d_open_t,
+               const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
+};
+const AirSha512Launch* air_sha512_launch(uint32_t set);  // set = 7, 8 or 9
 
 }  // namespace tmx

@@ -551,7 +551,8 @@ int launch_air_ladder_boundary_check(uint32_t n_proofs, uint32_t log_r, uint32_t
 // Siblings of the ladder sets: nothing above changes.  Every constraint of these sets is written once, in an evaluator templated on a field
 // policy and on a view of "one proof at one point".  The hot pass instantiates it over F_p at a coset point (CosetView), the identity check
 // over F_p^2 at zeta (ZetaView): prover and verifier agree term for term and index for index because they are the same source.  How a
-// kernel combines a proof's gamma sums stays in the kernel: there the hot passes and the checks differ on purpose.
+// kernel combines a proof's gamma sums stays in the kernel: there the hot passes and the checks differ on purpose (sets 7 - 9, whose
+// selectors are columns: in the two views' `combined`).
 
 // The two field policies: F_p on canonical words, and F_p^2.  scale and add_const take a base-field constant.
 struct FieldP {
@@ -613,6 +614,13 @@ struct CosetView {
   __device__ __forceinline__ void selected(uint32_t j, uint64_t v) { weigh(b0, b1, j, v); }
   __device__ __forceinline__ void started(uint32_t j, uint64_t v) { weigh(b0, b1, j, v); }
   __device__ __forceinline__ void chained(uint32_t j, uint64_t v) { weigh(c0, c1, j, v); }
+  // A proof's value where the selectors are columns (sets 7 - 9): a + s[0] b, with SUMS = 2 also + s[1] c; s the selectors at the point
+  template <uint32_t SUMS>
+  __device__ __forceinline__ gl2 combined(const uint64_t* s) const {
+    gl2 v = {gl_add(gl_canon(a0), gl_mul(s[0], b0)), gl_add(gl_canon(a1), gl_mul(s[0], b1))};
+    if (SUMS == 2) v = {gl_add(v.c0, gl_mul(s[1], c0)), gl_add(v.c1, gl_mul(s[1], c1))};
+    return v;
+  }
 };
 
 // One proof at zeta, for an identity check: t and h are the proof's columns inside the table's and the helper's openings blocks, whose
@@ -635,6 +643,12 @@ struct ZetaView {
   __device__ __forceinline__ void selected(uint32_t j, gl2 v) { b = gl2_add(b, gl2_mul(weight(j), v)); }
   __device__ __forceinline__ void started(uint32_t j, gl2 v) { b = gl2_add(b, gl2_mul(weight(j), v)); }
   __device__ __forceinline__ void chained(uint32_t j, gl2 v) { c = gl2_add(c, gl2_mul(weight(j), v)); }
+  template <uint32_t SUMS>  // (CosetView::combined over F_p^2)
+  __device__ __forceinline__ gl2 combined(const gl2* s) const {
+    gl2 v = gl2_mul(s[0], b);
+    if (SUMS == 2) v = gl2_add(v, gl2_mul(s[1], c));
+    return gl2_add(a, v);
+  }
 };
 
 // gamma^0 .. gamma^n into LDS, the workgroup's threads striding over the powers; the caller's next barrier completes it
@@ -1894,7 +1908,8 @@ int launch_air_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_t
 // ---- constraint set 7: the round constraints of the SHA-512 table (include/tmx.h "the round constraints of the SHA-512 table") -------------
 // A sibling of set 3 on T.2: 64-bit words as lo / hi limbs, 80-row blocks.  No power-of-two subgroup fits 80 rows, so the selector and the
 // round constants are three preprocessed columns of full degree (SEL, KLO, KHI): the prover fills and extends them like helper columns, the
-// verifier evaluates them at zeta barycentrically over the N rows.  Nothing above changes.
+// verifier evaluates them at zeta barycentrically over the N rows.  The kernels that do so, the hot pass and the check are written once for
+// sets 7, 8 and 9, behind set 9's evaluator; a set's own part is its helper kernel, its evaluator and its row values.  Nothing above changes.
 // Helper column offsets inside a proof's 599, table columns inside its 18 (the low limb; the high limb is the next one), constraint indices
 // inside its 628.
 constexpr uint32_t Q_A = 0, Q_B = 64, Q_C = 128, Q_E = 192, Q_F = 256, Q_G = 320, Q_U0 = 384, Q_U1 = 448, Q_V = 512, Q_S0 = 576, Q_S1 = 578,
@@ -1906,16 +1921,6 @@ constexpr uint32_t SHA512_BLOCK = 80;
 
 // SEL at row r of N: off on the last row of every block and on the wrap row N - 1 (N is no multiple of 80, so the latter is a row of its own)
 __device__ __forceinline__ bool sha512_sel(uint32_t r, uint32_t n) { return r % SHA512_BLOCK != SHA512_BLOCK - 1 && r != n - 1; }
-
-// One lane per row: the three preprocessed columns before the LDE, planar (3 << log_rows words)
-__global__ __launch_bounds__(256) void k_air_sha512_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
-  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= N) return;
-  const uint64_t k = K_SHA512[r % SHA512_BLOCK];
-  pre[r] = sha512_sel(r, N) ? 1 : 0;
-  pre[N + r] = (uint32_t)k;
-  pre[2 * (size_t)N + r] = k >> 32;
-}
 
 // One lane per (proof, row) of the pre-LDE table, k_air_sha_helper's shape: the eighteen limbs of the row, the block's first row (LIVE)
 // and W of the next row (the carries), then 599 stores, each of them consecutive words of one column across the wave.  Operands are the
@@ -1983,43 +1988,42 @@ __global__ __launch_bounds__(256) void k_air_sha512_helper(uint32_t log_rows, ui
   }
 }
 
-// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^628, gamma^(628 first); the selector and the round constants
-// are columns, not tables
-__global__ __launch_bounds__(256) void k_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
-                                                           const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_CONSTRAINTS, tab + AIR7_TAB_ZINV, tab + AIR7_TAB_GPOW);
-}
-
-// The 628 constraints of one proof at one point; klo and khi are KLO and KHI at the point.  The bit loop is set 3's (air_round_bits) per
-// 32-bit limb, the high limb first, with the rotations of SHA-512 taken mod 64 across both limbs: per bit index the nine bit words and the
-// six rotated ones (A_(i+28), A_(i+34), A_(i+39), E_(i+14), E_(i+18), E_(i+41)), re-read through the cache; nine constraints and one Horner
-// step by 2 of the ten word sums.  The ten sums of a limb go into its word constraints before the other limb starts, so no more than ten
-// are ever live.  Behind the loops the words are read again for the two-limb updates; the thirteen selected constraints go to a gamma sum
-// of their own: SEL(x) is factored out of it, the kernel applies it once.
+// The round-bit machinery of sets 7 and 9, the 64-bit sibling of air_round_bits: six registers of a row in the roles a, b, c, e, f, g (set
+// 7: themselves; set 9: b, c, d, f, g, h).  `bits` as in RoundBits, the columns 64 per register.  The six registers' table columns are t_a
+// + 0, 2, 4, 8, 10, 12 and their word constraints j_word + 0, 2, .. 10; S0, S1, CH and MAJ are the helper columns h_s0 + 0, 2, 4, 6 with the
+// constraints j_s0 + 0, 2, 4, 6.  Everywhere the low limb's column or index; the high limb's is the next one.
+struct RoundBits512 {
+  RoundBits bits;
+  uint32_t t_a, j_word, h_s0, j_s0;
+};
+// Set 3's bit loop per 32-bit limb, the high limb first, with the rotations of SHA-512 taken mod 64 across both limbs: per bit index the
+// nine bit words and the six rotated ones (A_(i+28), A_(i+34), A_(i+39), E_(i+14), E_(i+18), E_(i+41)), re-read through the cache; nine
+// constraints and one Horner step by 2 of the ten word sums.  The ten sums of a limb go into its word constraints before the other limb
+// starts, so no more than ten are ever live.
 template <class F, class View>
-__device__ __forceinline__ void air_sha512_constraints(View& at, typename F::T klo, typename F::T khi) {
+__device__ __forceinline__ void air_round_bits512(View& at, const RoundBits512 s) {
   using A = Forms<F>;
   using T = typename F::T;
+  const RoundBits r = s.bits;
 #pragma unroll 1
   for (uint32_t l = 2; l-- > 0;) {
     RoundWords<F> w = {F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero()};
 #pragma unroll View::BITS
     for (uint32_t b = 32; b-- > 0;) {
       const uint32_t i = 32 * l + b;
-      const T A_ = at.again(Q_A + i), B = at.once(Q_B + i), C = at.once(Q_C + i), E = at.again(Q_E + i), F_ = at.once(Q_F + i), G = at.once(Q_G + i);
-      const T U0 = at.once(Q_U0 + i), U1 = at.once(Q_U1 + i), V = at.once(Q_V + i);
-      const T A28 = at.again(Q_A + ((i + 28) & 63)), A34 = at.again(Q_A + ((i + 34) & 63)), A39 = at.again(Q_A + ((i + 39) & 63));
-      const T E14 = at.again(Q_E + ((i + 14) & 63)), E18 = at.again(Q_E + ((i + 18) & 63)), E41 = at.again(Q_E + ((i + 41) & 63));
-      at.plain(Q_A + i, A::boolean(A_));
-      at.plain(Q_B + i, A::boolean(B));
-      at.plain(Q_C + i, A::boolean(C));
-      at.plain(Q_E + i, A::boolean(E));
-      at.plain(Q_F + i, A::boolean(F_));
-      at.plain(Q_G + i, A::boolean(G));
-      at.plain(JQ_U0 + i, A::sub(U0, A::exor(A28, A34)));
-      at.plain(JQ_U1 + i, A::sub(U1, A::exor(E14, E18)));
-      at.plain(JQ_V + i, A::sub(V, A::mul(A_, B)));
+      const T A_ = at.again(r.a + i), B = at.once(r.b + i), C = at.once(r.c + i), E = at.again(r.e + i), F_ = at.once(r.f + i), G = at.once(r.g + i);
+      const T U0 = at.once(r.u0 + i), U1 = at.once(r.u1 + i), V = at.once(r.v + i);
+      const T A28 = at.again(r.a + ((i + 28) & 63)), A34 = at.again(r.a + ((i + 34) & 63)), A39 = at.again(r.a + ((i + 39) & 63));
+      const T E14 = at.again(r.e + ((i + 14) & 63)), E18 = at.again(r.e + ((i + 18) & 63)), E41 = at.again(r.e + ((i + 41) & 63));
+      at.plain(r.a + i, A::boolean(A_));
+      at.plain(r.b + i, A::boolean(B));
+      at.plain(r.c + i, A::boolean(C));
+      at.plain(r.e + i, A::boolean(E));
+      at.plain(r.f + i, A::boolean(F_));
+      at.plain(r.g + i, A::boolean(G));
+      at.plain(r.j_u0 + i, A::sub(U0, A::exor(A28, A34)));
+      at.plain(r.j_u1 + i, A::sub(U1, A::exor(E14, E18)));
+      at.plain(r.j_v + i, A::sub(V, A::mul(A_, B)));
       w.a = A::dbl_add(w.a, A_);
       w.b = A::dbl_add(w.b, B);
       w.c = A::dbl_add(w.c, C);
@@ -2031,31 +2035,52 @@ __device__ __forceinline__ void air_sha512_constraints(View& at, typename F::T k
       w.ch = A::dbl_add(w.ch, A::add(G, A::mul(E, A::sub(F_, G))));
       w.maj = A::dbl_add(w.maj, A::add(V, A::mul(C, A::sub(A::add(A_, B), A::add(V, V)))));
     }
-    at.plain(JQ_WORD + 0 + l, A::sub(at.tbl(R_A + l), w.a));
-    at.plain(JQ_WORD + 2 + l, A::sub(at.tbl(R_B + l), w.b));
-    at.plain(JQ_WORD + 4 + l, A::sub(at.tbl(R_C + l), w.c));
-    at.plain(JQ_WORD + 6 + l, A::sub(at.tbl(R_E + l), w.e));
-    at.plain(JQ_WORD + 8 + l, A::sub(at.tbl(R_F + l), w.f));
-    at.plain(JQ_WORD + 10 + l, A::sub(at.tbl(R_G + l), w.g));
-    at.plain(JQ_S0 + l, A::sub(at.again(Q_S0 + l), w.s0));
-    at.plain(JQ_S1 + l, A::sub(at.again(Q_S1 + l), w.s1));
-    at.plain(JQ_CH + l, A::sub(at.again(Q_CH + l), w.ch));
-    at.plain(JQ_MAJ + l, A::sub(at.again(Q_MAJ + l), w.maj));
+    at.plain(s.j_word + 0 + l, A::sub(at.tbl(s.t_a + 0 + l), w.a));
+    at.plain(s.j_word + 2 + l, A::sub(at.tbl(s.t_a + 2 + l), w.b));
+    at.plain(s.j_word + 4 + l, A::sub(at.tbl(s.t_a + 4 + l), w.c));
+    at.plain(s.j_word + 6 + l, A::sub(at.tbl(s.t_a + 8 + l), w.e));
+    at.plain(s.j_word + 8 + l, A::sub(at.tbl(s.t_a + 10 + l), w.f));
+    at.plain(s.j_word + 10 + l, A::sub(at.tbl(s.t_a + 12 + l), w.g));
+    at.plain(s.j_s0 + 0 + l, A::sub(at.again(s.h_s0 + 0 + l), w.s0));
+    at.plain(s.j_s0 + 2 + l, A::sub(at.again(s.h_s0 + 2 + l), w.s1));
+    at.plain(s.j_s0 + 4 + l, A::sub(at.again(s.h_s0 + 4 + l), w.ch));
+    at.plain(s.j_s0 + 6 + l, A::sub(at.again(s.h_s0 + 6 + l), w.maj));
   }
+}
+// The twelve carry bits of sets 7 and 9 (CAL, CAH, CEL, CEH, three bits each from helper column h on): their X^2 - X constraints from index j
+// on and the four values.  In full under either view: carry stays in registers.
+template <class F, class View>
+__device__ __forceinline__ void air_carries512(View& at, uint32_t h, uint32_t j, typename F::T carry[4]) {
+  using A = Forms<F>;
+  using T = typename F::T;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    const T x0 = at.once(h + 3 * k), x1 = at.once(h + 3 * k + 1), x2 = at.once(h + 3 * k + 2);
+    at.plain(j + 3 * k, A::boolean(x0));
+    at.plain(j + 3 * k + 1, A::boolean(x1));
+    at.plain(j + 3 * k + 2, A::boolean(x2));
+    carry[k] = A::add(x0, A::add(A::add(x1, x1), A::scale(x2, 4)));
+  }
+}
+
+// The 628 constraints of one proof at one point; klo and khi are KLO and KHI at the point.  The bit loop on a, b, c, e, f, g; behind it the
+// words are read again for the two-limb updates; the thirteen selected constraints go to a gamma sum of their own: SEL(x) is factored out
+// of it, the kernel applies it once.
+template <class F, class View>
+__device__ __forceinline__ void air_sha512_constraints(View& at, typename F::T klo, typename F::T khi) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  static_assert(R_B == R_A + 2 && R_C == R_A + 4 && R_E == R_A + 8 && R_F == R_A + 10 && R_G == R_A + 12 && R_H == R_A + 14 && Q_S1 == Q_S0 + 2 &&
+                    Q_CH == Q_S0 + 4 && Q_MAJ == Q_S0 + 6 && JQ_S1 == JQ_S0 + 2 && JQ_CH == JQ_S0 + 4 && JQ_MAJ == JQ_S0 + 6,
+                "RoundBits512 counts on these strides");
+  air_round_bits512<F>(at, {{Q_A, Q_B, Q_C, Q_E, Q_F, Q_G, Q_U0, Q_U1, Q_V, JQ_U0, JQ_U1, JQ_V}, R_A, JQ_WORD, Q_S0, JQ_S0});
   const T LIVE = at.again(Q_LIVE);
   at.plain(JQ_LIVE, A::boolean(LIVE));
   at.plain(JQ_KL, A::sub(at.again(Q_KL), A::mul(LIVE, klo)));
   at.plain(JQ_KL + 1, A::sub(at.again(Q_KL + 1), A::mul(LIVE, khi)));
   at.selected(JQ_LIVEN, A::sub(at.next(Q_LIVE), LIVE));
-  T carry[4];  // the values CAL, CAH, CEL, CEH (both loops in full under either view: carry stays in registers)
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    const T x0 = at.once(Q_CAL + 3 * k), x1 = at.once(Q_CAL + 3 * k + 1), x2 = at.once(Q_CAL + 3 * k + 2);
-    at.plain(JQ_CARRY + 3 * k, A::boolean(x0));
-    at.plain(JQ_CARRY + 3 * k + 1, A::boolean(x1));
-    at.plain(JQ_CARRY + 3 * k + 2, A::boolean(x2));
-    carry[k] = A::add(x0, A::add(A::add(x1, x1), A::scale(x2, 4)));
-  }
+  T carry[4];  // the values CAL, CAH, CEL, CEH
+  air_carries512<F>(at, Q_CAL, JQ_CARRY, carry);
 #pragma unroll
   for (uint32_t l = 0; l < 2; l++) {
     const T ta = at.tbl(R_A + l), tb = at.tbl(R_B + l), tc = at.tbl(R_C + l), td = at.tbl(R_D + l), te = at.tbl(R_E + l), tf = at.tbl(R_F + l),
@@ -2078,206 +2103,9 @@ __device__ __forceinline__ void air_sha512_constraints(View& at, typename F::T k
   }
 }
 
-// The set-7 hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^628), the eighteen table columns and the 599 helper columns read once from HBM.  pre: the three extended preprocessed planes (SEL,
-// KLO, KHI; 3 << log_m words), one word each per lane.  Per proof  v = a + SEL(x) b; at the end 1 / (x^N - 1).  FORM as in set 3.
-template <int FORM>
-__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
-                                                                     const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
-                                                                     const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
-                                                                     uint64_t* __restrict__ out) {
-  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
-  if (i >= M) return;
-  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
-  const uint64_t* __restrict__ gp = tab + AIR7_TAB_GPOW;
-  const uint64_t sel = gl_canon(pre[i]), klo = gl_canon(pre[M + i]), khi = gl_canon(pre[2 * M + i]);
-  const uint64_t zinv = tab[AIR7_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
-  const gl2 g628 = {gp[2 * AIR_SHA512_CONSTRAINTS], gp[2 * AIR_SHA512_CONSTRAINTS + 1]};
-  gl2 t = {0, 0};
-  for (uint32_t p = n_proofs; p-- > 0;) {
-    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_HELPER_COLS) << log_m), gp, log_m, i, nx};
-    air_sha512_constraints<FieldP>(at, klo, khi);
-    const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sel, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sel, at.b1))};
-    t = gl2_add(gl2_mul(t, g628), v);
-  }
-  gl2 q = gl2_scale(t, zinv);
-  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_CONSTRAINTS + 1) + 1]});
-  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
-  out[i] = q.c0;
-  out[M + i] = q.c1;
-}
-
-// The three preprocessed columns at zeta, barycentric over the N rows: P(zeta) = (zeta^N - 1) / N  sum_r v_r omega^r / (zeta - omega^r).
-// Several workgroups; thread g of T takes the rows g, g + T, ... four at a time, inverting its four zeta - omega^r with one F_p^2 inversion
-// (prefix products, one Fermat chain, back-substitution); v_r comes from r itself (SEL, K512[r mod 80]).  A workgroup's three sums meet in
-// LDS and go to its row of `part`: [6] words of sums, then 1 if a denominator was zero (such a term is left out).  air_sha512_periodic_at
-// folds the rows.
-constexpr int AIR7_EVAL_PER = 4;
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
-                                                                                 uint64_t* __restrict__ part) {
-  __shared__ uint64_t red[6][AIR_CHECK_THREADS];
-  __shared__ uint32_t bad;
-  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
-  const uint64_t stride = gl_pow(om, T);
-  uint64_t y = gl_pow(om, g);
-  gl2 ssel = {0, 0}, sklo = {0, 0}, skhi = {0, 0};
-  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
-    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
-    uint64_t yk[AIR7_EVAL_PER];
-    gl2 run = {1, 0};
-#pragma unroll
-    for (int m = 0; m < AIR7_EVAL_PER; m++) {
-      const bool in = r0 + m * T < N;
-      yk[m] = y;
-      den[m] = {gl_sub(z.c0, y), z.c1};
-      pre[m] = run;
-      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
-        bad = 1;
-        den[m] = {1, 0};
-      }
-      if (in) run = gl2_mul(run, den[m]);
-      y = gl_mul(y, stride);
-    }
-    gl2 inv = gl2_inv(run);
-#pragma unroll
-    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
-      const uint32_t r = r0 + m * T;
-      if (r < N) {
-        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
-        inv = gl2_mul(inv, den[m]);
-        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
-        const uint64_t k = K_SHA512[r % SHA512_BLOCK];
-        if (sha512_sel(r, N)) ssel = gl2_add(ssel, term);
-        sklo = gl2_add(sklo, gl2_scale(term, (uint32_t)k));
-        skhi = gl2_add(skhi, gl2_scale(term, k >> 32));
-      }
-    }
-  }
-  const uint32_t t = threadIdx.x;
-  red[0][t] = ssel.c0, red[1][t] = ssel.c1, red[2][t] = sklo.c0, red[3][t] = sklo.c1, red[4][t] = skhi.c0, red[5][t] = skhi.c1;
-  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
-    __syncthreads();
-    if (t < h)
-      for (uint32_t k = 0; k < 6; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
-  }
-  __syncthreads();
-  if (t < 6) part[(size_t)blockIdx.x * AIR7_PART_WORDS + t] = red[t][0];
-  if (t == 6) part[(size_t)blockIdx.x * AIR7_PART_WORDS + 6] = bad;
-}
-
-// SEL(zeta), KLO(zeta), KHI(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
-__device__ __forceinline__ bool air_sha512_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2 v[3]) {
-  uint64_t s[6] = {0, 0, 0, 0, 0, 0}, bad = 0;
-  for (uint32_t k = 0; k < n_parts; k++) {
-    for (uint32_t j = 0; j < 6; j++) s[j] = gl_add(s[j], part[(size_t)k * AIR7_PART_WORDS + j]);
-    bad |= part[(size_t)k * AIR7_PART_WORDS + 6];
-  }
-  const gl2 lead = gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv);
-  for (uint32_t j = 0; j < 3; j++) v[j] = gl2_mul(lead, {s[2 * j], s[2 * j + 1]});
-  return bad == 0;
-}
-
-// One thread: the three values (six words), then 1 if a denominator was zero, at out[0 .. 7)
-__global__ void k_air_sha512_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                           const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
-  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v[3];
-  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_periodic_at(part, n_parts, zn, n_inv, v);
-  for (uint32_t j = 0; j < 3; j++) {
-    out[2 * j] = v[j].c0;
-    out[2 * j + 1] = v[j].c1;
-  }
-  out[6] = fine ? 0 : 1;
-}
-
-// The set-7 identity at zeta, one workgroup: gamma^0 .. gamma^628 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
-// their 628 constraints over F_p^2 from the table's and the helper's openings, with SEL, KLO and KHI at zeta from the barycentric kernel's
-// rows.  A proof contributes gamma^(628 p) (a + SEL(zeta) b); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero denominator in
-// the barycentric sums clears every verdict.
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
-                                                                         uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                                                         const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
-                                                                         const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
-                                                                         const uint64_t* __restrict__ gamma, uint32_t n_queries,
-                                                                         uint32_t* __restrict__ ok) {
-  __shared__ uint64_t gpw[2 * (AIR_SHA512_CONSTRAINTS + 1)];
-  const gl2 g = {gamma[0], gamma[1]};
-  air_gamma_powers(g, AIR_SHA512_CONSTRAINTS, gpw);
-  __syncthreads();
-  gl2 zn = {zeta[0], zeta[1]}, pv[3];
-  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_periodic_at(part, n_parts, zn, n_inv, pv);
-  gl2 sum = {0, 0};
-  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
-    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
-    air_sha512_constraints<FieldP2>(at, pv[1], pv[2]);
-    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_CONSTRAINTS * p), gl2_add(at.a, gl2_mul(pv[0], at.b))));
-  }
-  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
-  if (!fine)
-    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
-}
-
-int launch_air_sha512_periodic(uint32_t log_rows, void* d_pre, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows, reinterpret_cast<uint64_t*>(d_pre));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
-  const uint64_t n = (uint64_t)n_proofs << log_rows;
-  hipLaunchKernelGGL(k_air_sha512_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
-                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
-  // (three workgroups: the 630 gamma powers; 2^log_blowup <= 64 inverses)
-  hipLaunchKernelGGL(k_air_sha512_tables, dim3((AIR_SHA512_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n,
-                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
-                               const void* d_tab, int form, void* d_quot, void* stream) {
-  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
-  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
-  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
-  const uint64_t* pre = reinterpret_cast<const uint64_t*>(d_pre);
-  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
-  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
-  if (form == AIR_FORM_WHOLE)
-    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
-  else if (form == AIR_FORM_PIECE)
-    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
-  else
-    hipLaunchKernelGGL(k_air_sha512_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
-                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
-                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                            const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                            uint32_t n_queries, void* d_ok, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
-                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
-                     reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
-                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
-                     reinterpret_cast<uint32_t*>(d_ok));
-  return (int)hipGetLastError();
-}
-
 // ---- constraint set 8: the message schedule of the SHA-512 table (include/tmx.h "the message schedule of the SHA-512 table") ----------------
 // A sibling of set 4 on T.2: W as lo / hi limbs, the schedule sum as one carry-free pipeline per limb, 80-row blocks.  The selector "the
-// next row is a schedule row" has the period 80: one more preprocessed column of full degree (SCH), filled, extended and evaluated at zeta
-// as set 7's three are.  Nothing above changes.
+// next row is a schedule row" has the period 80: one preprocessed column of full degree (SCH).
 // Helper column offsets inside a proof's 230 (QL_k at Z_QL + k, QH_k at Z_QH + k), constraint indices inside its 234 (the pipelines' at
 // JZ_QL + k and JZ_QH + k).  The low limb's column or index first; the high limb's is the next one.
 constexpr uint32_t Z_WB = 0, Z_X0 = 64, Z_X1 = 128, Z_G0 = 192, Z_G1 = 194, Z_QL = 195, Z_QH = 210, Z_CL = 226, Z_CH = 228;
@@ -2291,13 +2119,6 @@ __device__ __forceinline__ uint64_t sched512_s1(uint64_t w) { return rotr64(w, 1
 __device__ __forceinline__ bool sha512_sch(uint32_t r, uint32_t n) {
   const uint32_t t = r % SHA512_BLOCK;
   return t >= 15 && t <= SHA512_BLOCK - 2 && r != n - 1;
-}
-
-// One lane per row: SCH before the LDE (1 << log_rows words)
-__global__ __launch_bounds__(256) void k_air_sha512_sched_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
-  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= N) return;
-  pre[r] = sha512_sch(r, N) ? 1 : 0;
 }
 
 // One lane per (proof, row) of the pre-LDE table, k_air_sched_helper's shape: 230 stores, each of them consecutive words of one column
@@ -2351,13 +2172,6 @@ __global__ __launch_bounds__(256) void k_air_sha512_sched_helper(uint32_t log_ro
   put(Z_CL + 1, cl >> 1);
   put(Z_CH, ch & 1);
   put(Z_CH + 1, ch >> 1);
-}
-
-// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^234, gamma^(234 first); the selector is a column, not a table
-__global__ __launch_bounds__(256) void k_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
-                                                                 const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_SCHED_CONSTRAINTS, tab + AIR8_TAB_ZINV, tab + AIR8_TAB_GPOW);
 }
 
 // The 234 constraints of one proof at one point.  The bit loop is set 4's (air_sched_constraints) per 32-bit limb, the high limb first, with
@@ -2418,202 +2232,11 @@ __device__ __forceinline__ void air_sha512_sched_constraints(View& at) {
   }
 }
 
-// The set-8 hot pass, k_air_sha512_quotient's frame: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^234), W's two columns and the 230 helper columns.  pre: the extended SCH plane (1 << log_m words), one word per lane.  Per proof
-// v = a + SCH(x) b; at the end 1 / (x^N - 1).  FORM as in set 3.
-template <int FORM>
-__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
-                                                                           const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
-                                                                           const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
-                                                                           uint64_t* __restrict__ out) {
-  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
-  if (i >= M) return;
-  const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
-  const uint64_t* __restrict__ gp = tab + AIR8_TAB_GPOW;
-  const uint64_t sch = gl_canon(pre[i]);
-  const uint64_t zinv = tab[AIR8_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
-  const gl2 g234 = {gp[2 * AIR_SHA512_SCHED_CONSTRAINTS], gp[2 * AIR_SHA512_SCHED_CONSTRAINTS + 1]};
-  gl2 t = {0, 0};
-  for (uint32_t p = n_proofs; p-- > 0;) {
-    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_SCHED_HELPER_COLS) << log_m), gp, log_m, i, nx};
-    air_sha512_sched_constraints<FieldP>(at);
-    const gl2 v = {gl_add(gl_canon(at.a0), gl_mul(sch, at.b0)), gl_add(gl_canon(at.a1), gl_mul(sch, at.b1))};
-    t = gl2_add(gl2_mul(t, g234), v);
-  }
-  gl2 q = gl2_scale(t, zinv);
-  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1) + 1]});
-  if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
-  out[i] = q.c0;
-  out[M + i] = q.c1;
-}
-
-// SCH at zeta, barycentric over the N rows: k_air_sha512_periodic_eval's batching (thread g of T takes the rows g, g + T, ... four at a
-// time, one F_p^2 inversion per four denominators; up to AIR7_MAX_PARTS workgroups) with one sum, v_r = SCH_r from r itself.  A
-// workgroup's sum meets in LDS and goes to its row of `part`: [2] words of the sum, then 1 if a denominator was zero (such a term is left
-// out).  air_sha512_sched_periodic_at folds the rows.
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
-                                                                                       uint64_t* __restrict__ part) {
-  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
-  __shared__ uint32_t bad;
-  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
-  const uint64_t stride = gl_pow(om, T);
-  uint64_t y = gl_pow(om, g);
-  gl2 ssch = {0, 0};
-  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
-    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
-    uint64_t yk[AIR7_EVAL_PER];
-    gl2 run = {1, 0};
-#pragma unroll
-    for (int m = 0; m < AIR7_EVAL_PER; m++) {
-      const bool in = r0 + m * T < N;
-      yk[m] = y;
-      den[m] = {gl_sub(z.c0, y), z.c1};
-      pre[m] = run;
-      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
-        bad = 1;
-        den[m] = {1, 0};
-      }
-      if (in) run = gl2_mul(run, den[m]);
-      y = gl_mul(y, stride);
-    }
-    gl2 inv = gl2_inv(run);
-#pragma unroll
-    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
-      const uint32_t r = r0 + m * T;
-      if (r < N) {
-        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
-        inv = gl2_mul(inv, den[m]);
-        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
-        if (sha512_sch(r, N)) ssch = gl2_add(ssch, term);
-      }
-    }
-  }
-  const uint32_t t = threadIdx.x;
-  red[0][t] = ssch.c0, red[1][t] = ssch.c1;
-  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
-    __syncthreads();
-    if (t < h)
-      for (uint32_t k = 0; k < 2; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
-  }
-  __syncthreads();
-  if (t < 2) part[(size_t)blockIdx.x * AIR8_PART_WORDS + t] = red[t][0];
-  if (t == 2) part[(size_t)blockIdx.x * AIR8_PART_WORDS + 2] = bad;
-}
-
-// SCH(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
-__device__ __forceinline__ bool air_sha512_sched_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2& v) {
-  uint64_t s0 = 0, s1 = 0, bad = 0;
-  for (uint32_t k = 0; k < n_parts; k++) {
-    s0 = gl_add(s0, part[(size_t)k * AIR8_PART_WORDS]);
-    s1 = gl_add(s1, part[(size_t)k * AIR8_PART_WORDS + 1]);
-    bad |= part[(size_t)k * AIR8_PART_WORDS + 2];
-  }
-  v = gl2_mul(gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv), {s0, s1});
-  return bad == 0;
-}
-
-// One thread: the value (two words), then 1 if a denominator was zero, at out[0 .. 3)
-__global__ void k_air_sha512_sched_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                                 const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
-  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v;
-  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_sched_periodic_at(part, n_parts, zn, n_inv, v);
-  out[0] = v.c0;
-  out[1] = v.c1;
-  out[2] = fine ? 0 : 1;
-}
-
-// The set-8 identity at zeta, one workgroup: gamma^0 .. gamma^234 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
-// their 234 constraints over F_p^2 from the table's and the helper's openings, with SCH at zeta from the barycentric kernel's rows.  A
-// proof contributes gamma^(234 p) (a + SCH(zeta) b); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero denominator in the
-// barycentric sum clears every verdict.
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
-                                                                               uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                                                               const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
-                                                                               const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
-                                                                               const uint64_t* __restrict__ gamma, uint32_t n_queries,
-                                                                               uint32_t* __restrict__ ok) {
-  __shared__ uint64_t gpw[2 * (AIR_SHA512_SCHED_CONSTRAINTS + 1)];
-  const gl2 g = {gamma[0], gamma[1]};
-  air_gamma_powers(g, AIR_SHA512_SCHED_CONSTRAINTS, gpw);
-  __syncthreads();
-  gl2 zn = {zeta[0], zeta[1]}, sch;
-  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_sched_periodic_at(part, n_parts, zn, n_inv, sch);
-  gl2 sum = {0, 0};
-  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
-    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_SCHED_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
-    air_sha512_sched_constraints<FieldP2>(at);
-    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_SCHED_CONSTRAINTS * p), gl2_add(at.a, gl2_mul(sch, at.b))));
-  }
-  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
-  if (!fine)
-    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
-}
-
-int launch_air_sha512_sched_periodic(uint32_t log_rows, void* d_pre, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_sched_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
-                     reinterpret_cast<uint64_t*>(d_pre));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
-  const uint64_t n = (uint64_t)n_proofs << log_rows;
-  hipLaunchKernelGGL(k_air_sha512_sched_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
-                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
-  // (one workgroup: the 236 gamma powers; 2^log_blowup <= 64 inverses)
-  hipLaunchKernelGGL(k_air_sha512_sched_tables, dim3((AIR_SHA512_SCHED_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof,
-                     s_n, w_n, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                                     const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream) {
-  const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
-  const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
-  const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
-  const uint64_t* pre = reinterpret_cast<const uint64_t*>(d_pre);
-  const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
-  uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
-  if (form == AIR_FORM_WHOLE)
-    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
-  else if (form == AIR_FORM_PIECE)
-    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
-  else
-    hipLaunchKernelGGL(k_air_sha512_sched_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab,
-                       out);
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_sched_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
-                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_sched_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
-                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_sched_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                                  const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                                  uint32_t n_queries, void* d_ok, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_sched_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
-                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
-                     reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
-                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
-                     reinterpret_cast<uint32_t*>(d_ok));
-  return (int)hipGetLastError();
-}
-
 // ---- constraint set 9: the block starts of the SHA-512 table (include/tmx.h "the block starts of the SHA-512 table") ------------------------
 // A sibling of set 5 on T.2: row 0 of a block is round 0 applied to the eight words the block starts from, so six of them stand in row 0
-// itself (b, c, d, f, g, h) and set 7's bit loop runs on them with the register names shifted by one.  A lane is two blocks of 80 rows:
-// the selectors "the next row starts a hash" and "the next row starts a second block" are two more preprocessed columns of full degree
-// (STA, CHN), filled, extended and evaluated at zeta as set 7's three are.  Nothing above changes.
+// itself (b, c, d, f, g, h) and the bit loop (air_round_bits512) runs on them with the register names shifted by one.  A lane is two
+// blocks of 80 rows: the selectors "the next row starts a hash" and "the next row starts a second block" are two preprocessed columns of
+// full degree (STA, CHN).
 // Helper column offsets inside a proof's 629 (a word's low limb first; PZ_j and CZ_j at + 2 j), constraint indices inside its 673.
 constexpr uint32_t Y_B = 0, Y_C = 64, Y_D = 128, Y_F = 192, Y_G = 256, Y_H = 320, Y_U0 = 384, Y_U1 = 448, Y_V = 512, Y_S0 = 576, Y_S1 = 578,
                    Y_CH = 580, Y_MAJ = 582, Y_LV = 584, Y_PZ = 585, Y_CZ = 601, Y_CAL = 617, Y_CAH = 620, Y_CEL = 623, Y_CEH = 626;
@@ -2630,14 +2253,6 @@ __host__ __device__ constexpr uint64_t limb_of(uint64_t x, uint32_t l) { return 
 // and (N - 1) mod 160 is 127, 95, 31 or 63, never 159.  CHN: on where the next row is row 0 of a second block (never the wrap row).
 __device__ __forceinline__ bool sha512_sta(uint32_t r, uint32_t n) { return r % SHA512_LANE == SHA512_LANE - 1 || r == n - 1; }
 __device__ __forceinline__ bool sha512_chn(uint32_t r) { return r % SHA512_LANE == SHA512_BLOCK - 1; }
-
-// One lane per row: STA and CHN before the LDE, planar (2 << log_rows words)
-__global__ __launch_bounds__(256) void k_air_sha512_init_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
-  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= N) return;
-  pre[r] = sha512_sta(r, N) ? 1 : 0;
-  pre[(size_t)N + r] = sha512_chn(r) ? 1 : 0;
-}
 
 // One lane per (proof, row) of the pre-LDE table, k_air_sha512_helper's shape: the eighteen limbs of the row and the block's first row
 // (LV), then 629 stores, each of them consecutive words of one column across the wave.  The next row (cyclic inside the proof) is loaded
@@ -2730,74 +2345,21 @@ __global__ __launch_bounds__(256) void k_air_sha512_init_helper(uint32_t log_row
   }
 }
 
-// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^673, gamma^(673 first); the selectors are columns, not tables
-__global__ __launch_bounds__(256) void k_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
-                                                                const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, AIR_SHA512_INIT_CONSTRAINTS, tab + AIR9_TAB_ZINV, tab + AIR9_TAB_GPOW);
-}
-
-// The 673 constraints of one proof at one point.  The bit loop is set 7's (air_sha512_constraints) on b, c, d, f, g, h in the roles a, b,
-// c, e, f, g: per 32-bit limb, the high limb first, the rotations of SHA-512 taken mod 64 across both limbs as column offsets, a limb's
-// ten word sums spent on its word constraints before the other limb starts.  Behind it LV, the twelve carry bits, and one rolled loop
-// over the eight words the next block starts from: per word and limb the CZ bit, the PZ constraint (it holds on every row: no selector)
-// and, for the six words that stand in row 0, the two selected linear forms at the next row.  The selected forms go to two gamma sums
-// of their own (started, chained): STA(x) and CHN(x) are factored out of them, the kernel applies each once.
+// The 673 constraints of one proof at one point.  The bit loop (air_round_bits512) on b, c, d, f, g, h in the roles a, b, c, e, f, g.
+// Behind it LV, the twelve carry bits, and one rolled loop over the eight words the next block starts from: per word and limb the CZ
+// bit, the PZ constraint (it holds on every row: no selector) and, for the six words that stand in row 0, the two selected linear forms
+// at the next row.  The selected forms go to two gamma sums of their own (started, chained): STA(x) and CHN(x) are factored out of them,
+// the kernel applies each once.
 template <class F, class View>
 __device__ __forceinline__ void air_sha512_init_constraints(View& at) {
   using A = Forms<F>;
   using T = typename F::T;
-#pragma unroll 1
-  for (uint32_t l = 2; l-- > 0;) {
-    RoundWords<F> w = {F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero(), F::zero()};
-#pragma unroll View::BITS
-    for (uint32_t b = 32; b-- > 0;) {
-      const uint32_t i = 32 * l + b;
-      const T B = at.again(Y_B + i), C = at.once(Y_C + i), D = at.once(Y_D + i), F_ = at.again(Y_F + i), G = at.once(Y_G + i), H = at.once(Y_H + i);
-      const T U0 = at.once(Y_U0 + i), U1 = at.once(Y_U1 + i), V = at.once(Y_V + i);
-      const T B28 = at.again(Y_B + ((i + 28) & 63)), B34 = at.again(Y_B + ((i + 34) & 63)), B39 = at.again(Y_B + ((i + 39) & 63));
-      const T F14 = at.again(Y_F + ((i + 14) & 63)), F18 = at.again(Y_F + ((i + 18) & 63)), F41 = at.again(Y_F + ((i + 41) & 63));
-      at.plain(Y_B + i, A::boolean(B));
-      at.plain(Y_C + i, A::boolean(C));
-      at.plain(Y_D + i, A::boolean(D));
-      at.plain(Y_F + i, A::boolean(F_));
-      at.plain(Y_G + i, A::boolean(G));
-      at.plain(Y_H + i, A::boolean(H));
-      at.plain(JY_U0 + i, A::sub(U0, A::exor(B28, B34)));
-      at.plain(JY_U1 + i, A::sub(U1, A::exor(F14, F18)));
-      at.plain(JY_V + i, A::sub(V, A::mul(B, C)));
-      w.a = A::dbl_add(w.a, B);
-      w.b = A::dbl_add(w.b, C);
-      w.c = A::dbl_add(w.c, D);
-      w.e = A::dbl_add(w.e, F_);
-      w.f = A::dbl_add(w.f, G);
-      w.g = A::dbl_add(w.g, H);
-      w.s0 = A::dbl_add(w.s0, A::exor(U0, B39));
-      w.s1 = A::dbl_add(w.s1, A::exor(U1, F41));
-      w.ch = A::dbl_add(w.ch, A::add(H, A::mul(F_, A::sub(G, H))));
-      w.maj = A::dbl_add(w.maj, A::add(V, A::mul(D, A::sub(A::add(B, C), A::add(V, V)))));
-    }
-    at.plain(JY_WORD + 0 + l, A::sub(at.tbl(R_B + l), w.a));
-    at.plain(JY_WORD + 2 + l, A::sub(at.tbl(R_C + l), w.b));
-    at.plain(JY_WORD + 4 + l, A::sub(at.tbl(R_D + l), w.c));
-    at.plain(JY_WORD + 6 + l, A::sub(at.tbl(R_F + l), w.e));
-    at.plain(JY_WORD + 8 + l, A::sub(at.tbl(R_G + l), w.f));
-    at.plain(JY_WORD + 10 + l, A::sub(at.tbl(R_H + l), w.g));
-    at.plain(JY_S0 + l, A::sub(at.again(Y_S0 + l), w.s0));
-    at.plain(JY_S1 + l, A::sub(at.again(Y_S1 + l), w.s1));
-    at.plain(JY_CH + l, A::sub(at.again(Y_CH + l), w.ch));
-    at.plain(JY_MAJ + l, A::sub(at.again(Y_MAJ + l), w.maj));
-  }
+  static_assert(Y_S1 == Y_S0 + 2 && Y_CH == Y_S0 + 4 && Y_MAJ == Y_S0 + 6 && JY_S1 == JY_S0 + 2 && JY_CH == JY_S0 + 4 && JY_MAJ == JY_S0 + 6,
+                "RoundBits512 counts on these strides");
+  air_round_bits512<F>(at, {{Y_B, Y_C, Y_D, Y_F, Y_G, Y_H, Y_U0, Y_U1, Y_V, JY_U0, JY_U1, JY_V}, R_B, JY_WORD, Y_S0, JY_S0});
   at.plain(JY_LV, A::boolean(at.again(Y_LV)));
-  T carry[4];  // the values CAL, CAH, CEL, CEH (this loop in full under either view: carry stays in registers)
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    const T x0 = at.once(Y_CAL + 3 * k), x1 = at.once(Y_CAL + 3 * k + 1), x2 = at.once(Y_CAL + 3 * k + 2);
-    at.plain(JY_CARRY + 3 * k, A::boolean(x0));
-    at.plain(JY_CARRY + 3 * k + 1, A::boolean(x1));
-    at.plain(JY_CARRY + 3 * k + 2, A::boolean(x2));
-    carry[k] = A::add(x0, A::add(A::add(x1, x1), A::scale(x2, 4)));
-  }
+  T carry[4];  // the values CAL, CAH, CEL, CEH
+  air_carries512<F>(at, Y_CAL, JY_CARRY, carry);
   // PZ_(j,l) - LV' (IV_(j,l) + s_(j,l) [+ CZL_j] - 2^32 CZ_(j,l)), and with each of the six words that stand in row 0 its two selected
   // linear forms per limb: the next row's limb against IV_(j,l) LV' (start rows) and against PZ_(j,l) (chain rows).  Rolled over j.
   const T LVn = at.next(Y_LV);
@@ -2843,43 +2405,109 @@ __device__ __forceinline__ void air_sha512_init_constraints(View& at) {
   }
 }
 
-// The set-9 hot pass, k_air_sha512_quotient's frame: one lane per point, a loop over the proofs from the last to the first (Horner by
-// gamma^673), the eighteen table columns and the 629 helper columns.  pre: the two extended preprocessed planes (STA, CHN; 2 << log_m
-// words), one word each per lane, read once per point.  Per proof v = a + STA(x) b + CHN(x) c; at the end 1 / (x^N - 1).  FORM as in set 3.
-template <int FORM>
-__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
-                                                                          const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
-                                                                          const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
-                                                                          uint64_t* __restrict__ out) {
+// ---- sets 7, 8 and 9: the kernels around the preprocessed columns ----------------------------------------------------------------------------
+// What a set is to them: its counts and table offsets (air.h), the values of its preprocessed planes at row r of N, and how a proof at one
+// point becomes one value given the planes at that point.  The first SELECTORS planes hold 0 / 1 and weigh the proof's selected gamma
+// sums (View::combined); set 7's other two are operands of its evaluator.  Every kernel below is written once over such a descriptor.
+struct Sha512Round {  // set 7: SEL, KLO, KHI
+  static constexpr uint32_t PLANES = 3, SELECTORS = 1, HELPER_COLS = AIR_SHA512_HELPER_COLS, CONSTRAINTS = AIR_SHA512_CONSTRAINTS;
+  static constexpr uint32_t TAB_GPOW = AIR7_TAB_GPOW, TAB_ZINV = AIR7_TAB_ZINV, PART_WORDS = AIR7_PART_WORDS;
+  static __device__ __forceinline__ void planes(uint32_t r, uint32_t n, uint64_t v[PLANES]) {
+    const uint64_t k = K_SHA512[r % SHA512_BLOCK];
+    v[0] = sha512_sel(r, n) ? 1 : 0;
+    v[1] = (uint32_t)k;
+    v[2] = k >> 32;
+  }
+  template <class F, class View>
+  static __device__ __forceinline__ gl2 proof(View& at, const typename F::T* pv) {
+    air_sha512_constraints<F>(at, pv[1], pv[2]);
+    return at.template combined<SELECTORS>(pv);
+  }
+};
+struct Sha512Sched {  // set 8: SCH
+  static constexpr uint32_t PLANES = 1, SELECTORS = 1, HELPER_COLS = AIR_SHA512_SCHED_HELPER_COLS, CONSTRAINTS = AIR_SHA512_SCHED_CONSTRAINTS;
+  static constexpr uint32_t TAB_GPOW = AIR8_TAB_GPOW, TAB_ZINV = AIR8_TAB_ZINV, PART_WORDS = AIR8_PART_WORDS;
+  static __device__ __forceinline__ void planes(uint32_t r, uint32_t n, uint64_t v[PLANES]) { v[0] = sha512_sch(r, n) ? 1 : 0; }
+  template <class F, class View>
+  static __device__ __forceinline__ gl2 proof(View& at, const typename F::T* pv) {
+    air_sha512_sched_constraints<F>(at);
+    return at.template combined<SELECTORS>(pv);
+  }
+};
+struct Sha512Init {  // set 9: STA, CHN
+  static constexpr uint32_t PLANES = 2, SELECTORS = 2, HELPER_COLS = AIR_SHA512_INIT_HELPER_COLS, CONSTRAINTS = AIR_SHA512_INIT_CONSTRAINTS;
+  static constexpr uint32_t TAB_GPOW = AIR9_TAB_GPOW, TAB_ZINV = AIR9_TAB_ZINV, PART_WORDS = AIR9_PART_WORDS;
+  static __device__ __forceinline__ void planes(uint32_t r, uint32_t n, uint64_t v[PLANES]) {
+    v[0] = sha512_sta(r, n) ? 1 : 0;
+    v[1] = sha512_chn(r) ? 1 : 0;
+  }
+  template <class F, class View>
+  static __device__ __forceinline__ gl2 proof(View& at, const typename F::T* pv) {
+    air_sha512_init_constraints<F>(at);
+    return at.template combined<SELECTORS>(pv);
+  }
+};
+
+// One lane per row: the planes before the LDE, planar (PLANES << log_rows words)
+template <class S>
+__global__ __launch_bounds__(256) void k_air_sha512_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
+  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= N) return;
+  uint64_t v[S::PLANES];
+  S::planes(r, N, v);
+#pragma unroll
+  for (uint32_t j = 0; j < S::PLANES; j++) pre[j * (size_t)N + r] = v[j];
+}
+
+// One thread per table entry: 1 / (x^N - 1) by i mod B and gamma^0 .. gamma^CONSTRAINTS, gamma^(CONSTRAINTS first); the selectors and the
+// round constants are columns, not tables
+template <class S>
+__global__ __launch_bounds__(256) void k_air_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n,
+                                                           const uint64_t* __restrict__ gamma, uint64_t* __restrict__ tab) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  air_zinv_gpow(k, log_blowup, first_proof, s_n, w_n, gamma, S::CONSTRAINTS, tab + S::TAB_ZINV, tab + S::TAB_GPOW);
+}
+
+// The hot pass, k_air_sha_quotient's shape: one lane per point, a loop over the proofs from the last to the first (Horner by
+// gamma^CONSTRAINTS), the eighteen table columns and the helper columns read once from HBM.  pre: the extended preprocessed planes
+// (PLANES << log_m words), one word each per lane, read once per point.  Per proof S::proof; at the end 1 / (x^N - 1).  FORM as in set 3.
+template <class S, int FORM>
+__global__ __launch_bounds__(AIR_THREADS) void k_air_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs,
+                                                                     const uint64_t* __restrict__ cols, const uint64_t* __restrict__ hcols,
+                                                                     const uint64_t* __restrict__ pre, const uint64_t* __restrict__ tab,
+                                                                     uint64_t* __restrict__ out) {
   const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
   if (i >= M) return;
   const uint64_t nx = (i + (1ull << log_blowup)) & (M - 1);
-  const uint64_t* __restrict__ gp = tab + AIR9_TAB_GPOW;
-  const uint64_t sta = gl_canon(pre[i]), chn = gl_canon(pre[M + i]);
-  const uint64_t zinv = tab[AIR9_TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
-  const gl2 g673 = {gp[2 * AIR_SHA512_INIT_CONSTRAINTS], gp[2 * AIR_SHA512_INIT_CONSTRAINTS + 1]};
+  const uint64_t* __restrict__ gp = tab + S::TAB_GPOW;
+  uint64_t pv[S::PLANES];
+#pragma unroll
+  for (uint32_t j = 0; j < S::PLANES; j++) pv[j] = gl_canon(pre[j * M + i]);
+  const uint64_t zinv = tab[S::TAB_ZINV + (i & ((1ull << log_blowup) - 1))];
+  const gl2 gn = {gp[2 * S::CONSTRAINTS], gp[2 * S::CONSTRAINTS + 1]};
   gl2 t = {0, 0};
   for (uint32_t p = n_proofs; p-- > 0;) {
-    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * AIR_SHA512_INIT_HELPER_COLS) << log_m), gp, log_m, i, nx};
-    air_sha512_init_constraints<FieldP>(at);
-    const gl2 v = {gl_add(gl_add(gl_canon(at.a0), gl_mul(sta, at.b0)), gl_mul(chn, at.c0)),
-                   gl_add(gl_add(gl_canon(at.a1), gl_mul(sta, at.b1)), gl_mul(chn, at.c1))};
-    t = gl2_add(gl2_mul(t, g673), v);
+    CosetView at = {cols + (((uint64_t)p * AIR_SHA512_WIDTH) << log_m), hcols + (((uint64_t)p * S::HELPER_COLS) << log_m), gp, log_m, i, nx};
+    const gl2 v = S::template proof<FieldP>(at, pv);  // (first: t gn would be live across the evaluator)
+    t = gl2_add(gl2_mul(t, gn), v);
   }
   gl2 q = gl2_scale(t, zinv);
-  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1)], gp[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1) + 1]});
+  if (FORM != AIR_FORM_WHOLE) q = gl2_mul(q, {gp[2 * (S::CONSTRAINTS + 1)], gp[2 * (S::CONSTRAINTS + 1) + 1]});
   if (FORM == AIR_FORM_PIECE_ACC) q = gl2_add(q, {gl_canon(out[i]), gl_canon(out[M + i])});
   out[i] = q.c0;
   out[M + i] = q.c1;
 }
 
-// STA and CHN at zeta, barycentric over the N rows: k_air_sha512_periodic_eval's batching (thread g of T takes the rows g, g + T, ... four
-// at a time, one F_p^2 inversion per four denominators; up to AIR7_MAX_PARTS workgroups) with two sums, v_r from r itself.  A workgroup's
-// sums meet in LDS and go to its row of `part`: [4] words of the two sums, then 1 if a denominator was zero (such a term is left out).
-// air_sha512_init_periodic_at folds the rows.
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
-                                                                                      uint64_t* __restrict__ part) {
-  __shared__ uint64_t red[4][AIR_CHECK_THREADS];
+// The planes at zeta, barycentric over the N rows: P(zeta) = (zeta^N - 1) / N  sum_r v_r omega^r / (zeta - omega^r).  Several workgroups;
+// thread g of T takes the rows g, g + T, ... four at a time, inverting its four zeta - omega^r with one F_p^2 inversion (prefix products,
+// one Fermat chain, back-substitution); v_r comes from r itself (S::planes).  A workgroup's sums meet in LDS and go to its row of `part`:
+// [2 PLANES] words of sums, then 1 if a denominator was zero (such a term is left out).  air_sha512_periodic_at folds the rows.
+constexpr int AIR_SHA512_EVAL_PER = 4;
+template <class S>
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
+                                                                                 uint64_t* __restrict__ part) {
+  static_assert(2 * S::PLANES + 1 <= S::PART_WORDS, "a row of `part` holds the sums and the flag");
+  __shared__ uint64_t red[2 * S::PLANES][AIR_CHECK_THREADS];
   __shared__ uint32_t bad;
   const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
   if (threadIdx.x == 0) bad = 0;
@@ -2887,13 +2515,13 @@ __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_periodic_
   const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
   const uint64_t stride = gl_pow(om, T);
   uint64_t y = gl_pow(om, g);
-  gl2 ssta = {0, 0}, schn = {0, 0};
-  for (uint32_t r0 = g; r0 < N; r0 += AIR7_EVAL_PER * T) {
-    gl2 pre[AIR7_EVAL_PER], den[AIR7_EVAL_PER];
-    uint64_t yk[AIR7_EVAL_PER];
+  gl2 sum[S::PLANES] = {};
+  for (uint32_t r0 = g; r0 < N; r0 += AIR_SHA512_EVAL_PER * T) {
+    gl2 pre[AIR_SHA512_EVAL_PER], den[AIR_SHA512_EVAL_PER];
+    uint64_t yk[AIR_SHA512_EVAL_PER];
     gl2 run = {1, 0};
 #pragma unroll
-    for (int m = 0; m < AIR7_EVAL_PER; m++) {
+    for (int m = 0; m < AIR_SHA512_EVAL_PER; m++) {
       const bool in = r0 + m * T < N;
       yk[m] = y;
       den[m] = {gl_sub(z.c0, y), z.c1};
@@ -2907,102 +2535,107 @@ __global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_periodic_
     }
     gl2 inv = gl2_inv(run);
 #pragma unroll
-    for (int m = AIR7_EVAL_PER - 1; m >= 0; m--) {
+    for (int m = AIR_SHA512_EVAL_PER - 1; m >= 0; m--) {
       const uint32_t r = r0 + m * T;
       if (r < N) {
         const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
         inv = gl2_mul(inv, den[m]);
         if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
-        if (sha512_sta(r, N)) ssta = gl2_add(ssta, term);
-        if (sha512_chn(r)) schn = gl2_add(schn, term);
+        uint64_t v[S::PLANES];
+        S::planes(r, N, v);
+#pragma unroll
+        for (uint32_t j = 0; j < S::PLANES; j++) {
+          if (j >= S::SELECTORS) sum[j] = gl2_add(sum[j], gl2_scale(term, v[j]));
+          else if (v[j]) sum[j] = gl2_add(sum[j], term);
+        }
       }
     }
   }
   const uint32_t t = threadIdx.x;
-  red[0][t] = ssta.c0, red[1][t] = ssta.c1, red[2][t] = schn.c0, red[3][t] = schn.c1;
+#pragma unroll
+  for (uint32_t j = 0; j < S::PLANES; j++) red[2 * j][t] = sum[j].c0, red[2 * j + 1][t] = sum[j].c1;
   for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
     __syncthreads();
     if (t < h)
-      for (uint32_t k = 0; k < 4; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
+      for (uint32_t k = 0; k < 2 * S::PLANES; k++) red[k][t] = gl_add(red[k][t], red[k][t + h]);
   }
   __syncthreads();
-  if (t < 4) part[(size_t)blockIdx.x * AIR9_PART_WORDS + t] = red[t][0];
-  if (t == 4) part[(size_t)blockIdx.x * AIR9_PART_WORDS + 4] = bad;
+  if (t < 2 * S::PLANES) part[(size_t)blockIdx.x * S::PART_WORDS + t] = red[t][0];
+  if (t == 2 * S::PLANES) part[(size_t)blockIdx.x * S::PART_WORDS + 2 * S::PLANES] = bad;
 }
 
-// STA(zeta), CHN(zeta) from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
-__device__ __forceinline__ bool air_sha512_init_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2 v[2]) {
-  uint64_t s[4] = {0, 0, 0, 0}, bad = 0;
+// The planes at zeta from the workgroups' rows of `part`; n_inv = 1 / N; returns false if a denominator was zero
+template <class S>
+__device__ __forceinline__ bool air_sha512_periodic_at(const uint64_t* __restrict__ part, uint32_t n_parts, gl2 zn, uint64_t n_inv, gl2 v[S::PLANES]) {
+  uint64_t s[2 * S::PLANES] = {}, bad = 0;
   for (uint32_t k = 0; k < n_parts; k++) {
-    for (uint32_t j = 0; j < 4; j++) s[j] = gl_add(s[j], part[(size_t)k * AIR9_PART_WORDS + j]);
-    bad |= part[(size_t)k * AIR9_PART_WORDS + 4];
+    for (uint32_t j = 0; j < 2 * S::PLANES; j++) s[j] = gl_add(s[j], part[(size_t)k * S::PART_WORDS + j]);
+    bad |= part[(size_t)k * S::PART_WORDS + 2 * S::PLANES];
   }
   const gl2 lead = gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv);
-  for (uint32_t j = 0; j < 2; j++) v[j] = gl2_mul(lead, {s[2 * j], s[2 * j + 1]});
+  for (uint32_t j = 0; j < S::PLANES; j++) v[j] = gl2_mul(lead, {s[2 * j], s[2 * j + 1]});
   return bad == 0;
 }
 
-// One thread: the two values (four words), then 1 if a denominator was zero, at out[0 .. 5)
-__global__ void k_air_sha512_init_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                                const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
-  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v[2];
+// One thread: the values (2 PLANES words), then 1 if a denominator was zero, at out[0 .. 2 PLANES]
+template <class S>
+__global__ void k_air_sha512_periodic_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                           const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
+  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, v[S::PLANES];
   for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_init_periodic_at(part, n_parts, zn, n_inv, v);
-  for (uint32_t j = 0; j < 2; j++) {
+  const bool fine = air_sha512_periodic_at<S>(part, n_parts, zn, n_inv, v);
+  for (uint32_t j = 0; j < S::PLANES; j++) {
     out[2 * j] = v[j].c0;
     out[2 * j + 1] = v[j].c1;
   }
-  out[4] = fine ? 0 : 1;
+  out[2 * S::PLANES] = fine ? 0 : 1;
 }
 
-// The set-9 identity at zeta, one workgroup: gamma^0 .. gamma^673 go to LDS first; thread t takes the proofs t, t + 256, ... and evaluates
-// their 673 constraints over F_p^2 from the table's and the helper's openings, with STA and CHN at zeta from the barycentric kernel's
-// rows.  A proof contributes gamma^(673 p) (a + STA(zeta) b + CHN(zeta) c); the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero
+// The identity at zeta, one workgroup: gamma^0 .. gamma^CONSTRAINTS go to LDS first; thread t takes the proofs t, t + 256, ... and
+// evaluates their constraints over F_p^2 from the table's and the helper's openings, with the planes at zeta from the barycentric
+// kernel's rows.  A proof contributes gamma^(CONSTRAINTS p) S::proof; the sum is compared with (u_0 + X u_1) (zeta^N - 1).  A zero
 // denominator in the barycentric sums clears every verdict.
-__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
-                                                                              uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
-                                                                              const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
-                                                                              const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
-                                                                              const uint64_t* __restrict__ gamma, uint32_t n_queries,
-                                                                              uint32_t* __restrict__ ok) {
-  __shared__ uint64_t gpw[2 * (AIR_SHA512_INIT_CONSTRAINTS + 1)];
+template <class S>
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                         uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                                         const uint64_t* __restrict__ open_t, const uint64_t* __restrict__ open_h,
+                                                                         const uint64_t* __restrict__ open_q, const uint64_t* __restrict__ zeta,
+                                                                         const uint64_t* __restrict__ gamma, uint32_t n_queries,
+                                                                         uint32_t* __restrict__ ok) {
+  __shared__ uint64_t gpw[2 * (S::CONSTRAINTS + 1)];
   const gl2 g = {gamma[0], gamma[1]};
-  air_gamma_powers(g, AIR_SHA512_INIT_CONSTRAINTS, gpw);
+  air_gamma_powers(g, S::CONSTRAINTS, gpw);
   __syncthreads();
-  gl2 zn = {zeta[0], zeta[1]}, pv[2];
+  gl2 zn = {zeta[0], zeta[1]}, pv[S::PLANES];
   for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
-  const bool fine = air_sha512_init_periodic_at(part, n_parts, zn, n_inv, pv);
+  const bool fine = air_sha512_periodic_at<S>(part, n_parts, zn, n_inv, pv);
   gl2 sum = {0, 0};
   for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
-    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * AIR_SHA512_INIT_HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
-    air_sha512_init_constraints<FieldP2>(at);
-    const gl2 v = gl2_add(at.a, gl2_add(gl2_mul(pv[0], at.b), gl2_mul(pv[1], at.c)));
-    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)AIR_SHA512_INIT_CONSTRAINTS * p), v));
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * S::HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    const gl2 v = S::template proof<FieldP2>(at, pv);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)S::CONSTRAINTS * p), v));
   }
   air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
   if (!fine)
     for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
 }
 
-int launch_air_sha512_init_periodic(uint32_t log_rows, void* d_pre, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_init_periodic, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
+template <class S>
+static int launch_sha512_periodic(uint32_t log_rows, void* d_pre, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic<S>, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
                      reinterpret_cast<uint64_t*>(d_pre));
   return (int)hipGetLastError();
 }
-int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
-  const uint64_t n = (uint64_t)n_proofs << log_rows;
-  hipLaunchKernelGGL(k_air_sha512_init_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs,
-                     reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<uint64_t*>(d_helper));
+template <class S>
+static int launch_sha512_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
+  // (one workgroup per 256 of the CONSTRAINTS + 2 gamma powers; 2^log_blowup <= 64 inverses)
+  hipLaunchKernelGGL(k_air_sha512_tables<S>, dim3((S::CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof, s_n, w_n,
+                     reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
   return (int)hipGetLastError();
 }
-int launch_air_sha512_init_tables(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream) {
-  // (three workgroups: the 675 gamma powers; 2^log_blowup <= 64 inverses)
-  hipLaunchKernelGGL(k_air_sha512_init_tables, dim3((AIR_SHA512_INIT_CONSTRAINTS + 2 + 255) / 256), dim3(256), 0, S_(stream), log_blowup, first_proof,
-                     s_n, w_n, reinterpret_cast<const uint64_t*>(d_gamma), reinterpret_cast<uint64_t*>(d_tab));
-  return (int)hipGetLastError();
-}
-int launch_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
-                                    const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream) {
+template <class S>
+static int launch_sha512_quotient(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols,
+                                  const void* d_pre, const void* d_tab, int form, void* d_quot, void* stream) {
   const dim3 grid((uint32_t)(((1ull << log_m) + AIR_THREADS - 1) / AIR_THREADS)), block(AIR_THREADS);
   const uint64_t* cols = reinterpret_cast<const uint64_t*>(d_cols);
   const uint64_t* hcols = reinterpret_cast<const uint64_t*>(d_helper_cols);
@@ -3010,33 +2643,61 @@ int launch_air_sha512_init_quotient(uint32_t log_m, uint32_t log_blowup, uint32_
   const uint64_t* tab = reinterpret_cast<const uint64_t*>(d_tab);
   uint64_t* out = reinterpret_cast<uint64_t*>(d_quot);
   if (form == AIR_FORM_WHOLE)
-    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_WHOLE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+    hipLaunchKernelGGL((k_air_sha512_quotient<S, AIR_FORM_WHOLE>), grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
   else if (form == AIR_FORM_PIECE)
-    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_PIECE>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
+    hipLaunchKernelGGL((k_air_sha512_quotient<S, AIR_FORM_PIECE>), grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab, out);
   else
-    hipLaunchKernelGGL(k_air_sha512_init_quotient<AIR_FORM_PIECE_ACC>, grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab,
+    hipLaunchKernelGGL((k_air_sha512_quotient<S, AIR_FORM_PIECE_ACC>), grid, block, 0, S_(stream), log_m, log_blowup, n_proofs, cols, hcols, pre, tab,
                        out);
   return (int)hipGetLastError();
 }
-int launch_air_sha512_init_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_init_periodic_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
+template <class S>
+static int launch_sha512_periodic_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic_eval<S>, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
                      reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_part));
   return (int)hipGetLastError();
 }
-int launch_air_sha512_init_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_init_periodic_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
+template <class S>
+static int launch_sha512_periodic_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_periodic_fold<S>, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
                      reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
   return (int)hipGetLastError();
 }
-int launch_air_sha512_init_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
-                                 const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
-                                 uint32_t n_queries, void* d_ok, void* stream) {
-  hipLaunchKernelGGL(k_air_sha512_init_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
+template <class S>
+static int launch_sha512_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                               const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma,
+                               uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_check<S>, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
                      air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_open_t),
                      reinterpret_cast<const uint64_t*>(d_open_h), reinterpret_cast<const uint64_t*>(d_open_q),
                      reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma), n_queries,
                      reinterpret_cast<uint32_t*>(d_ok));
   return (int)hipGetLastError();
+}
+// (internal, and handed out by a host function: a table of host functions must not be a constant the device pass emits too)
+template <class S>
+static constexpr AirSha512Launch AIR_SHA512_LAUNCH_OF = {launch_sha512_periodic<S>,      launch_sha512_tables<S>,        launch_sha512_quotient<S>,
+                                                         launch_sha512_periodic_eval<S>, launch_sha512_periodic_fold<S>, launch_sha512_check<S>};
+const AirSha512Launch* air_sha512_launch(uint32_t set) {
+  return set == 7 ? &AIR_SHA512_LAUNCH_OF<Sha512Round> : set == 8 ? &AIR_SHA512_LAUNCH_OF<Sha512Sched> : &AIR_SHA512_LAUNCH_OF<Sha512Init>;
+}
+
+// The three helper oracles: one lane per (proof, row)
+template <class Kernel>
+static int launch_sha512_helper(Kernel k, uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, n_proofs, reinterpret_cast<const uint64_t*>(d_table),
+                     reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  return launch_sha512_helper(k_air_sha512_helper, log_rows, n_proofs, d_table, d_helper, stream);
+}
+int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  return launch_sha512_helper(k_air_sha512_sched_helper, log_rows, n_proofs, d_table, d_helper, stream);
+}
+int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
+  return launch_sha512_helper(k_air_sha512_init_helper, log_rows, n_proofs, d_table, d_helper, stream);
 }
 
 }  // namespace tmx

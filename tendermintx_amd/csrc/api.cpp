@@ -4597,26 +4597,17 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // for the others, and does its public step at four places, each a branch on has_public: gamma observes the table's digest (sha_gamma), the
 // pass writes its tables to d_air6 and the piece that starts at proof 0 carries - PQ (sha_pass), the verifier forms V before its check
 // (sha_verify_call), and the helper kernel reads d_pub (sha_helper_launch).  Its helper is resident only: the streamed calls take sets 3 - 5 and 7 - 9.
-// Set 7 (the SHA-512 table: 18 columns per proof, 80-row blocks) is the fifth row.  Where it differs is a branch on has_periodic: the pass
-// reads the three extended preprocessed planes of d_air7 instead of period-64 tables (sha_pass; sha512_periodic fills and extends them in
-// front of it), the verifier runs the barycentric kernel in front of its check (sha_verify_call), and the set-level call takes
-// TMX_TRACE_SHA512 alone.  Rows 3 - 6 take none of these branches: they enqueue what they enqueued before the row existed.
-// Set 8 (the SHA-512 message schedule) is the sixth row and takes set 7's branches.  What the two differ in there is a ShaPeriodic the row
-// carries: how many preprocessed planes there are, the context scratch that holds them, and the launches that fill them, read them in the
-// pass and evaluate them at zeta.  Set 7's row names d_air7 and its own launches: it enqueues what it enqueued before.
-// Set 9 (the SHA-512 block starts) is the seventh row: two planes (STA, CHN) in d_air9, and the same branches.
+// Sets 7, 8 and 9 (the SHA-512 table: 18 columns per proof, 80-row blocks) are the fifth, sixth and seventh rows.  Where they differ from
+// rows 3 - 6 is a branch on has_periodic: the pass reads the extended preprocessed planes of the set's scratch instead of period-64 tables
+// (sha_pass; sha512_periodic fills and extends them in front of it), the verifier runs the barycentric kernel in front of its check
+// (sha_verify_call), and the set-level call takes TMX_TRACE_SHA512 alone.  Rows 3 - 6 take none of these branches.  What the three differ
+// in there is a ShaPeriodic the row carries: how many preprocessed planes there are (3, 1, 2), the context scratch that holds them (d_air7,
+// d_air8, d_air9), and the set's instantiations of the launches that fill them, read them in the pass and evaluate them at zeta.
 struct ShaPeriodic {
   uint32_t planes, part_words;  // the preprocessed columns; the words of one workgroup's row of the barycentric kernel
   void* tmx_ctx::*scratch;      // rows of the barycentric kernel | the planes before the LDE [planes][N] | extended [planes][M]
   size_t tmx_ctx::*bytes;
-  int (*fill)(uint32_t log_rows, void* d_pre, void* stream);
-  int (*tables)(uint32_t log_blowup, uint64_t first_proof, uint64_t s_n, uint64_t w_n, const void* d_gamma, void* d_tab, void* stream);
-  int (*quotient)(uint32_t log_m, uint32_t log_blowup, uint32_t n_proofs, const void* d_cols, const void* d_helper_cols, const void* d_pre,
-                  const void* d_tab, int form, void* d_quot, void* stream);
-  int (*eval)(uint32_t log_rows, uint64_t om, const void* d_zeta, void* d_part, void* stream);
-  int (*fold)(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
-  int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part, const void* d_open_t,
-               const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
+  const AirSha512Launch* k;  // fill, tables, quotient, eval, fold, check (air.h)
 };
 struct ShaSet {
   uint32_t id, helper_cols;
@@ -4678,18 +4669,12 @@ static int sha7_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const voi
 static int sha8_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
   return launch_air_sha512_sched_helper(log_rows, n_proofs, d_table, d_helper, stream);
 }
-static const ShaPeriodic SHA7_PERIODIC = {3, AIR7_PART_WORDS, &tmx_ctx::d_air7, &tmx_ctx::air7_bytes, launch_air_sha512_periodic,
-                                          launch_air_sha512_tables, launch_air_sha512_quotient, launch_air_sha512_periodic_eval,
-                                          launch_air_sha512_periodic_fold, launch_air_sha512_check};
 static int sha9_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const void* d_table, void* d_helper, void* stream) {
   return launch_air_sha512_init_helper(log_rows, n_proofs, d_table, d_helper, stream);
 }
-static const ShaPeriodic SHA9_PERIODIC = {2, AIR9_PART_WORDS, &tmx_ctx::d_air9, &tmx_ctx::air9_bytes, launch_air_sha512_init_periodic,
-                                          launch_air_sha512_init_tables, launch_air_sha512_init_quotient, launch_air_sha512_init_periodic_eval,
-                                          launch_air_sha512_init_periodic_fold, launch_air_sha512_init_check};
-static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, &tmx_ctx::air8_bytes, launch_air_sha512_sched_periodic,
-                                          launch_air_sha512_sched_tables, launch_air_sha512_sched_quotient, launch_air_sha512_sched_periodic_eval,
-                                          launch_air_sha512_sched_periodic_fold, launch_air_sha512_sched_check};
+static const ShaPeriodic SHA7_PERIODIC = {3, AIR7_PART_WORDS, &tmx_ctx::d_air7, &tmx_ctx::air7_bytes, air_sha512_launch(7)};
+static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, &tmx_ctx::air8_bytes, air_sha512_launch(8)};
+static const ShaPeriodic SHA9_PERIODIC = {2, AIR9_PART_WORDS, &tmx_ctx::d_air9, &tmx_ctx::air9_bytes, air_sha512_launch(9)};
 
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
 static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
@@ -4857,7 +4842,7 @@ static const uint64_t* sha512_planes(const tmx_ctx* c, const ShaSet& d, uint32_t
 static int32_t sha512_periodic(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_blowup, void* hip_stream) {
   const uint32_t log_sub = log_m - log_blowup;
   uint64_t* pre = reinterpret_cast<uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d);
-  const int rc = d.per->fill(log_sub, pre, hip_stream);
+  const int rc = d.per->k->fill(log_sub, pre, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic", rc);
   return tmx_lde_goldilocks_device(c, log_sub, log_blowup, d.per->planes, pre, pre + ((size_t)d.per->planes << log_sub), hip_stream);
 }
@@ -4904,8 +4889,8 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
                                   d_quot, s);
   } else if (d.has_periodic) {  // the extended planes (sha512_periodic, in front of this call) instead of the period-64 tables
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
-    if ((rc = d.per->tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
-    rc = d.per->quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, d, log_n - log_blowup), tab, form, d_quot, s);
+    if ((rc = d.per->k->tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
+    rc = d.per->k->quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, d, log_n - log_blowup), tab, form, d_quot, s);
   } else {
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
     if ((rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s)))
@@ -5025,10 +5010,10 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
     const uint32_t log_sub = log_n - p->log_blowup;
     const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_sub)), n_inv = gl_pow_host(1ull << log_sub, P - 2);
     void* part = c->*(d.per->scratch);
-    rc = d.per->eval(log_sub, om, V + 32 + FRI_ZETA_AT, part, s);
+    rc = d.per->k->eval(log_sub, om, V + 32 + FRI_ZETA_AT, part, s);
     if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
-    rc = d.per->check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
-                      V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+    rc = d.per->k->check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
+                         V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
   } else {
     rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
                  V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
@@ -5462,7 +5447,7 @@ static int32_t sha_periodic_call(tmx_ctx* c, const ShaSet& d, uint32_t log_rows,
   if (log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be at most 6");
   if (!d_pre || (log_blowup && !d_ext)) return fail(c, TMX_ERR_BAD_ARG, "d_pre must be set, and d_ext unless log_blowup is 0");
   HIPCK(c, hipSetDevice(c->cfg.device));
-  const int rc = d.per->fill(log_rows, d_pre, hip_stream);
+  const int rc = d.per->k->fill(log_rows, d_pre, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic", rc);
   return log_blowup ? tmx_lde_goldilocks_device(c, log_rows, log_blowup, d.per->planes, d_pre, d_ext, hip_stream) : TMX_OK;
 }
@@ -5476,9 +5461,9 @@ static int32_t sha_periodic_eval_call(tmx_ctx* c, const ShaSet& d, uint32_t log_
   if (st) return st;
   const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_rows)), n_inv = gl_pow_host(1ull << log_rows, P - 2);
   void* part = c->*(d.per->scratch);
-  int rc = d.per->eval(log_rows, om, d_zeta, part, hip_stream);
+  int rc = d.per->k->eval(log_rows, om, d_zeta, part, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
-  rc = d.per->fold(log_rows, n_inv, part, d_zeta, d_out, hip_stream);
+  rc = d.per->k->fold(log_rows, n_inv, part, d_zeta, d_out, hip_stream);
   if (rc) return sha_launch_failed(c, d, "periodic_fold", rc);
   return TMX_OK;
 }

@@ -486,7 +486,7 @@ def test_zero_quotient_for_a_table_with_a_changed_a_hi(ctx, oracle, step2):
 
 @pytest.mark.gpu
 def test_257_proofs_through_the_check_kernel(ctx, oracle, step2):
-    """N = 128, 257 proofs (one more than k_air_sha512_check has threads: thread 0 takes proofs 0 and 256) -- the live first blocks of T.2
+    """N = 128, 257 proofs (one more than k_air_sha512_check<Sha512Round> has threads: thread 0 takes proofs 0 and 256) -- the live first blocks of T.2
     of step N = 2 in turn, 48 rows of padding behind each, every seventh proof zero --, blow-up 2, two queries: the device accepts every
     query as the model's identity does; a helper opening bumped in proof 256 and a table opening in proof 255 are rejected"""
     many = 257

@@ -1,5 +1,5 @@
-"""The set-7 kernels (tendermintx_amd/csrc/air.hip k_air_sha512_helper, k_air_sha512_periodic, k_air_sha512_periodic_eval, k_air_sha512_tables,
-k_air_sha512_quotient, k_air_sha512_check) and their host paths (api.cpp sha_pass, sha_verify_call, sha_set_call under has_periodic,
+"""The set-7 kernels (tendermintx_amd/csrc/air.hip k_air_sha512_helper, k_air_sha512_periodic<Sha512Round>, k_air_sha512_periodic_eval<Sha512Round>, k_air_sha512_tables<Sha512Round>,
+k_air_sha512_quotient<Sha512Round, FORM>, k_air_sha512_check<Sha512Round>) and their host paths (api.cpp sha_pass, sha_verify_call, sha_set_call under has_periodic,
 sha512_scratch) at every shape and row value they branch on: a verifier that folds 2, 4 and 32 rows of the barycentric kernel's `part`,
 the rows-per-thread regimes of that kernel and a zero denominator in every batch slot and in workgroups other than 0, LIVE from each of the
 eighteen limbs alone, the extreme carries and the carry columns on SEL-off rows, N = 128 and blow-up 64 in the quotient, three pieces in
@@ -217,7 +217,7 @@ def _periodic(ctx, log_rows, log_blowup):
 @pytest.mark.gpu
 @pytest.mark.parametrize("log_rows,log_blowup", [(7, 6), (8, 2), (11, 1)])
 def test_preprocessed_columns_at_the_edge_sizes(ctx, oracle, log_rows, log_blowup):
-    """SEL, KLO, KHI at N = 128 under blow-up 64, N = 256 (one workgroup of k_air_sha512_periodic exactly) and N = 2048 (eight), against the
+    """SEL, KLO, KHI at N = 128 under blow-up 64, N = 256 (one workgroup of k_air_sha512_periodic<Sha512Round> exactly) and N = 2048 (eight), against the
     model and the CPU oracle's LDE"""
     pre, ext = _periodic(ctx, log_rows, log_blowup)
     want = sm.periodic(1 << log_rows)
@@ -394,7 +394,7 @@ def _model_verdicts(oracle, p, k_trace, caps, proof):
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,log_blowup,n_proofs", [(128, 6, 1), (2048, 1, 2), (4096, 2, 1)])
 def test_tiled_tables_through_the_caller_level_chain(ctx, oracle, live_blocks, N, log_blowup, n_proofs):
-    """N = 128 under blow-up 64, N = 2048 (k_air_sha512_check folds two rows of `part`) and N = 4096 (four), after an evaluation that left
+    """N = 128 under blow-up 64, N = 2048 (k_air_sha512_check<Sha512Round> folds two rows of `part`) and N = 4096 (four), after an evaluation that left
     all 64 rows nonzero: the quotient has degree <= N - 2, every verdict equals the model verifier's (all accept), the plain batch verifier
     accepts, and a proof with one bumped helper opening of the last proof is rejected on every query by the device and the model"""
     _prime(ctx)
@@ -434,7 +434,7 @@ def _chain_on_device(ctx, table, log_blowup, n_queries):
 
 @pytest.mark.gpu
 def test_full_size_table_through_the_check_kernel(ctx, oracle, live_blocks):
-    """N = 2^15, the real size of T.2 (409 full blocks; k_air_sha512_check folds 32 rows of `part`), blow-up 2, one proof, two queries; the
+    """N = 2^15, the real size of T.2 (409 full blocks; k_air_sha512_check<Sha512Round> folds 32 rows of `part`), blow-up 2, one proof, two queries; the
     extended helper (314 MB) never leaves the device.  tests/sha512_air_model.py's identity, which needs the caps and the openings alone,
     holds, the device accepts both queries and the plain batch verifier does; a bumped table opening and a bumped helper opening fail
     the identity and are rejected on both queries.  (0.4 s on the MI355X.)"""

@@ -455,6 +455,22 @@ def test_sta_chn_at_zeta_flags_and_non_canonical_words(ctx, oracle):
     assert _bary(ctx, 9, z) == _bary_model(oracle, 9, z)
 
 
+# r -> (batch slot, workgroup, STA-on, CHN-on) at N = 4096: four workgroups, T = 1024 threads, thread g takes the rows g + 1024 m as slot m
+ROOTS_12 = {159: (0, 0, True, False), 1119: (1, 0, True, False), 2079: (2, 0, True, False), 3199: (3, 0, True, False),
+            1359: (1, 1, False, True)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", list(ROOTS_12))
+def test_sta_chn_at_zeta_zero_denominator_in_every_slot_and_workgroup(ctx, oracle, r):
+    """zeta = (omega^r, 0) at N = 4096 for r = 159, 1119, 2079, 3199 (workgroup 0, slots 0, 1, 2, 3; STA-on rows, r mod 160 = 159) and
+    1359 (workgroup 1, slot 1: the flag reaches the fold through that workgroup's row of `part` alone; a CHN-on row, r mod 160 = 79):
+    the flag is raised"""
+    sta, chn = sm.periodic(4096)[:, r]
+    assert (r // 1024, r % 1024 // 256, bool(sta), bool(chn)) == ROOTS_12[r]
+    assert _bary(ctx, 12, (pow(oracle.gl_root(12), r, P), 0))[4] == 1
+
+
 def _device_quotient(ctx, log_n, log_blowup, n_proofs, d_cols, d_hcols, d_cap, d_cap_h, cap_height=CAP_H, **kw):
     return _guarded(2 << log_n, lambda out: ctx.air_sha512_init_quotient_device(log_n, log_blowup, cap_height, n_proofs, d_cols.data_ptr(),
                                                                                d_hcols.data_ptr(), d_cap.data_ptr(), d_cap_h.data_ptr(), out, 0, **kw))
@@ -634,7 +650,7 @@ def test_the_rerun_start_passes_sets_7_and_8_and_fails_set_9_on_the_device(ctx, 
 
 @pytest.mark.gpu
 def test_257_proofs_through_the_check_kernel(ctx, oracle, step2):
-    """N = 128, 257 proofs (one more than k_air_sha512_init_check has threads: thread 0 takes proofs 0 and 256) -- the first 128 rows of
+    """N = 128, 257 proofs (one more than k_air_sha512_check<Sha512Init> has threads: thread 0 takes proofs 0 and 256) -- the first 128 rows of
     the live lanes of T.2 of step N = 2 in turn (a live first block, the chain row 79, a second block cut off at the wrap row, which set 9
     alone does not mind: it looks at rows 0 and 80), every seventh proof zero --, blow-up 2, two queries, [table, H9, Q9]: the device
     accepts every query as the model's identity does; a helper opening bumped in proof 256 and a table opening in proof 255 are rejected"""

@@ -529,7 +529,7 @@ def test_the_rerun_block_passes_set_7_and_fails_set_8_on_the_device(ctx, oracle,
 
 @pytest.mark.gpu
 def test_257_proofs_through_the_check_kernel(ctx, oracle, step2):
-    """N = 128, 257 proofs (one more than k_air_sha512_sched_check has threads: thread 0 takes proofs 0 and 256) -- the live first blocks
+    """N = 128, 257 proofs (one more than k_air_sha512_check<Sha512Sched> has threads: thread 0 takes proofs 0 and 256) -- the live first blocks
     of T.2 of step N = 2 in turn, 48 rows of padding behind each, every seventh proof zero --, blow-up 2, two queries, [table, H8, Q8]:
     the device accepts every query as the model's identity does; a helper opening bumped in proof 256 and a table opening in proof 255
     are rejected"""

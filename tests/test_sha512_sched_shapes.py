@@ -1,5 +1,5 @@
-"""The set-8 kernels (tendermintx_amd/csrc/air.hip k_air_sha512_sched_helper, k_air_sha512_sched_periodic, k_air_sha512_sched_periodic_eval,
-k_air_sha512_sched_tables, k_air_sha512_sched_quotient, k_air_sha512_sched_check) and their host paths (api.cpp sha_pass, sha_verify_call,
+"""The set-8 kernels (tendermintx_amd/csrc/air.hip k_air_sha512_sched_helper, k_air_sha512_periodic<Sha512Sched>, k_air_sha512_periodic_eval<Sha512Sched>,
+k_air_sha512_tables<Sha512Sched>, k_air_sha512_quotient<Sha512Sched, FORM>, k_air_sha512_check<Sha512Sched>) and their host paths (api.cpp sha_pass, sha_verify_call,
 sha_set_call under SHA_SETS[5] and SHA8_PERIODIC, sha512_scratch on d_air8) at every shape and row value they branch on: a high-limb carry
 that exists through the low limb's carry alone (and one that needs all of CL = 3, not its low bit), all sixteen (CL, CH) pairs, the carry
 columns on SCH-off rows under operands that would carry, a verifier that folds 2, 4 and 32 rows of the barycentric kernel's `part`, the
@@ -262,7 +262,7 @@ def test_helper_at_every_grid_shape_equals_the_model(ctx, log_rows, n_proofs):
 # ---- GPU: SCH and the barycentric kernel
 @pytest.mark.gpu
 def test_sch_and_its_extension_at_2048_rows(ctx, oracle):
-    """N = 2048 (eight workgroups of k_air_sha512_sched_periodic), blow-up 2, against the model and the CPU oracle's LDE; the column sum is
+    """N = 2048 (eight workgroups of k_air_sha512_periodic<Sha512Sched>), blow-up 2, against the model and the CPU oracle's LDE; the column sum is
     the number of SCH-on rows counted from r mod 80 alone"""
     pre, ext = _periodic(ctx, 11, 1)
     want = sm.periodic(2048)
@@ -399,7 +399,7 @@ def _open_at(p):
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,log_blowup,n_proofs", [(2048, 1, 2), (4096, 2, 1)])
 def test_tiled_tables_through_the_caller_level_chain(ctx, oracle, N, log_blowup, n_proofs):
-    """[table, H8, Q8] at N = 2048 (k_air_sha512_sched_check folds two rows of `part`) and N = 4096 (four), the edge blocks inside, after
+    """[table, H8, Q8] at N = 2048 (k_air_sha512_check<Sha512Sched> folds two rows of `part`) and N = 4096 (four), the edge blocks inside, after
     an evaluation that left all 64 rows nonzero: helper, gamma and quotient equal the model's, the quotient has degree <= N - 2, every
     verdict equals the model verifier's (all accept), and a proof with one bumped opening -- the last proof's W_lo at zeta, an X1 bit at
     zeta, QH_9 at zeta omega, the quotient's u_1 -- is rejected on every query by the device and the model"""
@@ -448,7 +448,7 @@ def _chain_on_device(ctx, table, log_blowup, n_queries):
 
 @pytest.mark.gpu
 def test_full_size_table_through_the_check_kernel(ctx, oracle):
-    """N = 2^15, the real size of T.2 (409 full blocks; k_air_sha512_sched_check folds 32 rows of `part`, primed by a 2^18 evaluation),
+    """N = 2^15, the real size of T.2 (409 full blocks; k_air_sha512_check<Sha512Sched> folds 32 rows of `part`, primed by a 2^18 evaluation),
     blow-up 2, one proof, two queries; the extended helper (121 MB) never leaves the device.  The model's identity, which needs the caps
     and the openings alone, holds and the device accepts both queries; a bumped table opening and a bumped helper opening fail the identity
     and are rejected on both queries"""

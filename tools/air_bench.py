@@ -48,19 +48,19 @@
            (tmx_trace_commit_set_air_sha256_link_device) on the HEADER member of a set SHA256 | HEADER of the same P proofs beside set 5's
            call on the same set, alternating, with the prove over table, H5, Q5, H6, Q6 and both verifiers.
   sha512   constraint set 7 (tmx_air_sha512_*) beside set 3, its yardstick: k_air_sha512_helper over S512_PROOFS proofs (16) x 18 random table
-           columns, then the quotient call of set 7 (the preprocessed columns filled and extended, gamma, the tables, k_air_sha512_quotient)
+           columns, then the quotient call of set 7 (the preprocessed columns filled and extended, gamma, the tables, k_air_sha512_quotient<Sha512Round, FORM>)
            and of set 3 (SHA_PROOFS proofs, 32) over random extended columns at M = 2^LOG_M (16), and a plain FRI prove over set 7's table
            columns, alternating; ns_per_helper_word_set7 / _set3 and their ratio.  Under `rocprofv3 --kernel-trace --stats` (MODE=sha512) the
            helper kernel, both hot passes and k_fri_combine show in ONE trace.  Then the set-level call on the SHA512 member of a set
            SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove over table, helper, quotient and HEADER, and the verifier.
   sha512_sched   constraint set 8 (tmx_air_sha512_sched_*) beside set 4, its yardstick: k_air_sha512_sched_helper over S512_PROOFS proofs (16)
            x 18 random table columns, then the quotient call of set 8 (SCH filled and extended, gamma, the tables,
-           k_air_sha512_sched_quotient; 248 columns per proof) and of set 4 (SCHED_PROOFS proofs, 32; 124 columns per proof) over random
+           k_air_sha512_quotient<Sha512Sched, FORM>; 248 columns per proof) and of set 4 (SCHED_PROOFS proofs, 32; 124 columns per proof) over random
            extended columns at M = 2^LOG_M (16), alternating; ps_per_helper_word_set8 / _set4 and their ratio.  Then the set-level call of
            set 8 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the verifier.
   sha512_init    constraint set 9 (tmx_air_sha512_init_*) beside set 7, its yardstick: k_air_sha512_init_helper over S512_PROOFS proofs (16)
            x 18 random table columns of 2^(LOG_M - BLOWUP) rows, then the quotient call of set 9 (STA and CHN filled and extended, gamma, the
-           tables, k_air_sha512_init_quotient; 647 columns per proof) and of set 7 (617 columns per proof) over random extended columns at
+           tables, k_air_sha512_quotient<Sha512Init, FORM>; 647 columns per proof) and of set 7 (617 columns per proof) over random extended columns at
            M = 2^LOG_M (16) and the SAME table, alternating in one process; ps_per_helper_word_set9 / _set7 and their ratio.  Then the
            set-level call of set 9 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the
            verifier.
@@ -753,7 +753,7 @@ if "link" in modes:
 if "sha512" in modes:
     # constraint set 7 beside set 3, its yardstick: the helper kernel, the caller-level quotient call of each set over random extended columns
     # (S512_PROOFS proofs of 18 + 599 columns against SHA_PROOFS proofs of 9 + 300, M = 2^LOG_M each) and a plain FRI prove over set 7's table
-    # columns, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512) k_air_sha512_helper, k_air_sha512_quotient,
+    # columns, alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512) k_air_sha512_helper, k_air_sha512_quotient<Sha512Round, FORM>,
     # k_air_sha_quotient and k_fri_combine show in ONE trace.  ns_per_helper_word: the call's time per helper word read, the figure the two
     # passes are compared on.  Then the set-level call on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
     log_m, cp, cp3 = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16")), int(os.environ.get("SHA_PROOFS", "32"))
@@ -839,7 +839,7 @@ if "sha512" in modes:
 if "sha512_sched" in modes:
     # constraint set 8 beside set 4, its yardstick: the helper kernel, then the caller-level quotient call of each set over random extended
     # columns (S512_PROOFS proofs of 18 + 230 columns against SCHED_PROOFS proofs of 9 + 115, M = 2^LOG_M each: an equal count of words read),
-    # alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512_sched) k_air_sha512_sched_helper, k_air_sha512_sched_quotient and
+    # alternating -- under `rocprofv3 --kernel-trace --stats` (MODE=sha512_sched) k_air_sha512_sched_helper, k_air_sha512_quotient<Sha512Sched, FORM> and
     # k_air_sched_quotient show in ONE trace.  ps_per_helper_word: the call's time per helper word read, the figure the two passes are
     # compared on.  Then the set-level call of set 8 on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
     log_m, cp, cp4 = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16")), int(os.environ.get("SCHED_PROOFS", "32"))
@@ -921,8 +921,8 @@ if "sha512_sched" in modes:
 if "sha512_init" in modes:
     # constraint set 9 beside set 7, its yardstick: the helper kernel, then the caller-level quotient call of each set over random extended
     # columns (S512_PROOFS proofs of the SAME 18 table columns, 629 against 599 helper columns, M = 2^LOG_M), alternating in one process --
-    # under `rocprofv3 --kernel-trace --stats` (MODE=sha512_init) k_air_sha512_init_helper, k_air_sha512_init_quotient and
-    # k_air_sha512_quotient show in ONE trace.  ps_per_helper_word: the call's time per helper word read, the figure the two passes are
+    # under `rocprofv3 --kernel-trace --stats` (MODE=sha512_init) k_air_sha512_init_helper, k_air_sha512_quotient<Sha512Init, FORM> and
+    # k_air_sha512_quotient<Sha512Round, FORM> show in ONE trace.  ps_per_helper_word: the call's time per helper word read, the figure the two passes are
     # compared on.  Then the set-level call of set 9 on SHA512 of a set SHA512 | HEADER of S512_SET_P proofs at N = n.
     log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16"))
     log_rows = log_m - log_blowup
