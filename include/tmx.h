@@ -1785,7 +1785,8 @@ int32_t tmx_air_sha512_sched_periodic_eval_device(tmx_ctx* ctx, uint32_t log_row
  * Scratch: per section set 3's formula with 629 columns, and once per context (2 (N + M) + 512) 8 bytes of its own for STA, CHN and the
  * barycentric kernel's rows (the context scratch of sets 7 and 8 is not touched).  The streamed call keeps refusing every constraint_set
  * but 3, 4 and 5.  Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream; tmx_air_last_gamma covers
- * the quotient calls and the set-level call.  Follow-up: the link of T.2 to Level-1.  At 629 columns the full 256-proof T.2 cannot be
+ * the quotient calls and the set-level call.  The link of T.2 to Level-1 is constraint set 10 ("the SHA-512 table's link to Level-1"
+ * below).  At 629 columns the full 256-proof T.2 cannot be
  * resident: the streamed form of the helpers of sets 7 - 9 is the block "streamed helpers of the SHA-512 sets" below. */
 #define TMX_AIR_SHA512_INIT_HELPER_COLS 629
 #define TMX_AIR_SHA512_INIT_CONSTRAINTS 673
@@ -1849,6 +1850,126 @@ int32_t tmx_trace_commit_set_air_sha512_streamed_device(tmx_ctx* ctx, uint32_t c
  * TMX_TRACE_SHA512, as the last resident or streamed set-level call left it (a streamed call leaves exactly what _streamed_bytes returns);
  * 0 if there is none, for a constraint_set outside 7 .. 9 and for any other section. */
 uint64_t tmx_trace_commit_set_air_sha512_scratch_bytes(const tmx_ctx* ctx, uint32_t constraint_set, uint32_t section);
+
+/* ---- the SHA-512 table's link to Level-1 (constraint set 10) ------------------------------------------------------------------------------
+ * Sets 7 + 8 + 9 prove that every live block of T.2 is a SHA-512 compression that starts from the IV or from the first block's
+ * feed-forward; they do not say WHICH message was hashed nor that the result is the digest Level-1 returns.  Set 10 is set 6's sibling for
+ * T.2, built from set 6's public table gathered from the element rows and the preprocessed planes of full degree of sets 7 - 9 (an
+ * 80-row block fits no subgroup, so set 6's seventeen coset polynomials have no counterpart and are not needed).  Resident only.
+ *   PROVED     together with sets 7 + 8 + 9: for every lane of T.2 the sixteen W words of each live block are the padded message R | A | M
+ *              that Level-1's element row carries (the dummy triple where the lane did not sign), the blocks that are live are exactly those
+ *              the message length calls for, a first block starts from the IV and a second one from the first block's feed-forward, and
+ *              the last live block's feed-forward is the digest of D.1a.  Range argument, set 6's: every constraint below is an integer
+ *              identity between values far below p once CD is boolean, the public words are below 2^32 and s_j is range-checked by set
+ *              7's bits; the digest rows pin DG to public words below 2^32 and the chain carries that to CV of the next block; the limbs
+ *              of DG on the rows between are NOT range-checked by this set (they are in no selected constraint).
+ *   slots      T.2 of N = 2^log_rows rows is cut into block slots k = r / 80: lane k / 2, block k mod 2 of its hash.  Every slot with a row
+ *              below N counts, the partial last slot too: ceil(N / 80) slots, padded with zero rows to K = 2^log_k, a power of two, so that
+ *              set 2's Poseidon digest rule applies to the table as a column-major oracle.
+ *   pub        column-major, 49 n_proofs columns of K words, every word < 2^32; per proof (a 64-bit word's LOW limb first, T.2's order):
+ *              0 .. 31    w[k][t] as 2 t (low limb), 2 t + 1 (high limb): the sixteen message words of the block
+ *              32 .. 47   dig[k][j] as 32 + 2 j, 33 + 2 j: the eight digest words on the LAST LIVE block of a lane, zero elsewhere
+ *              48         lv[k]: 1 where the block is live
+ *              gathered from H.2 (pubkey, signature.r, message, message_byte_length, signed; a byte is eight big-endian bit elements)
+ *              and the 512 digest elements of D.1a ALONE -- neither the trace rows nor the context's Level-1 scratch are read -- by the
+ *              rules T.2 is generated by: the message is R | A | M[0 .. min(message_byte_length, 124)); a lane that did not sign is
+ *              hashed on the dummy triple (dummy key, dummy R, 32 zero bytes: ONE block, lv = 0 on its second slot); SHA-512 padding
+ *              (80, zeros, the 128-bit bit length at the end of the last block; two blocks from message_byte_length = 48 on); lanes >= n_max,
+ *              the partial last slot and the padding are zero with lv = 0.
+ *   helper     65 columns per proof of N words, all < 2^32, defined for any input (operands are the low 32 bits of the words, lv is set
+ *              when its low 32 bits are not zero):
+ *              0 .. 15    CV_j as 2 j, 2 j + 1: the state the row's block starts from, constant inside a block -- IV_j in a live first
+ *                         block; in a live second block lv[k - 1] IV_j + s_j of the row in front of it, mod 2^64; 0 where lv[k] = 0
+ *              16 .. 31   DG_j = (CV_j + s_j) mod 2^64 on every row, s_j the row's state word j (a .. h)
+ *              32 .. 47   CDL_j, CDH_j as 32 + 2 j, 33 + 2 j: the carry bits out of the low and the high limb of that sum
+ *              48         LN: lv of the NEXT slot -- the slot of the next row, cyclic: behind the last slot stands slot 0
+ *              49 .. 64   CH_j = LN DG_j
+ *   planes     five preprocessed columns of full degree, filled and extended by the prover like helper columns and evaluated at zeta by the
+ *              verifier barycentrically over the N rows: STA (r mod 160 = 159, and the wrap row N - 1 switched on explicitly) and CHN
+ *              (r mod 160 = 79), set 9's; SEL, set 7's; E79 (r mod 80 = 79); MSG (r mod 80 < 16).
+ *   constraints 115 per proof, x' the value at the next row, c = 2 j + limb:
+ *              0 .. 15    CD_c (CD_c - 1)
+ *              16 .. 31   DG_c + 2^32 CD_c - CV_c - s_c [- CDL_j in the high limb]
+ *              32 .. 47   CH_c - LN DG_c
+ *              48 .. 63   SEL (CV_c' - CV_c)
+ *              64 .. 79   CHN (CV_c' - CH_c): the second block starts from this block's DG, or from 0
+ *              80 .. 95   STA (CV_c' - IV_c LN)
+ *              96         (CHN + STA) LN - lv of the next slot
+ *              97 .. 112  E79 DG_c - CHN CH_c - dig_c of the row's slot
+ *              113, 114   MSG W_limb - w[k][t]_limb on row 80 k + t
+ *              Every nonlinear one has degree 2 and no selector, every selected one is a plane times a linear form: ONE two-column
+ *              quotient over x^N - 1 suffices, of honest degree N - 2.  The public terms (96 .. 114) enter linearly: under gamma they are ONE
+ *              F_p^2 value per row, V_r = sum_p sum_j gamma^(115 p + j) (the term of constraint j of proof p on row r), and Pub_gamma is
+ *              the polynomial of degree < N through V_r on the trace domain.
+ *   challenge  set 6's rule with the set id 10: a fresh duplex observes 2^33, then 10, log_n, log_blowup, cap_height, n_proofs, the table
+ *              cap, THIS helper's cap, then the Poseidon Merkle root (cap height 0) of pub as a column-major oracle of K rows; gamma drawn
+ *              again while gamma.c1 == 0.
+ *   quotient   q(x_i) = (sum_p sum_(j < 115) gamma^(115 p + j) C_(p,j)(x_i) - Pub_gamma(x_i)) / (x_i^N - 1), C the column parts, planar and
+ *              canonical.  In pieces, Pub_gamma is subtracted by the piece that starts at proof 0 (set 6's rule).
+ *   identity   sum_p gamma^(115 p) (A_p + STA(zeta) S_p + CHN(zeta) C_p) - Pub_gamma(zeta) == (u_0 + X u_1) (zeta^N - 1).  The verifier hashes
+ *              d_pub itself, forms its own V_r and evaluates Pub_gamma(zeta) barycentrically over the N rows; it trusts nothing the prover
+ *              extended.  A zero denominator in either barycentric sum or a failed identity clears every verdict.
+ *   tmx_air_sha512_public_shape          host only: log2 K and the column count 49 n_proofs of pub for (kind, n_max, n_proofs), from
+ *                                        tmx_trace_commit_shape's rows of TMX_TRACE_SHA512.  TMX_ERR_BAD_ARG: a bad kind or n_max,
+ *                                        n_proofs = 0, 65 n_proofs > 2^24, a table outside 2^7 .. 2^18 rows.
+ *   tmx_air_sha512_public_device         gathers pub from the element rows at d_elems as tmx_witness_batch_device leaves them (n_proofs rows
+ *                                        of the context's n_max): one lane per (proof, slot).  Also refused: a null pointer.
+ *   tmx_air_sha512_link_helper_device    the helper (65 n_proofs columns at d_helper) from PRE-LDE table columns (18 n_proofs at d_table) and
+ *                                        pub (49 n_proofs columns of 2^log_k words, log_k = ceil(log2(ceil(2^log_rows / 80)))): one lane per
+ *                                        (proof, row).  TMX_ERR_BAD_ARG: log_rows outside 7 .. 18, n_proofs = 0, 65 n_proofs > 2^24, a null
+ *                                        pointer.
+ *   tmx_air_sha512_link_quotient_device  fills and extends the five planes under the context's CURRENT NTT domain, draws gamma from d_cap,
+ *                                        d_cap_helper and the digest of d_pub, then the quotient of the EXTENDED columns into d_quot (2 <<
+ *                                        log_n words), V_r, its extension and the subtraction.  TMX_ERR_BAD_ARG: FRI's rules on log_n and
+ *                                        log_blowup, log_n - log_blowup outside 7 .. 18, n_proofs = 0, 65 n_proofs > 2^24, a null pointer.
+ *   tmx_air_sha512_link_quotient_range_device   set 3's range call: the piece [proof_lo, proof_hi), d_helper_cols that piece's own columns,
+ *                                        written or (accumulate = 1) added; also refused: an empty or overhanging range, accumulate > 1.
+ *   tmx_air_sha512_link_verify_device    tmx_batch_verify_device, gamma from the caps and the verifier's own digest of d_pub, the two
+ *                                        barycentric kernels, then the identity for the oracles k_trace (18 k columns), k_helper (65 k) and
+ *                                        k_helper + 1 (2).  TMX_ERR_BAD_ARG unless the column counts are these, the three log_n equal,
+ *                                        k_helper > k_trace, k_helper + 1 < n_oracles, d_pub set (and the rules above).
+ *   tmx_trace_commit_set_air_sha512_link_device   the set-level call: `section` = TMX_TRACE_SHA512 alone, a RESIDENT member only; the pair
+ *                                        (TMX_TRACE_SHA512_LINK_HELPER, _LINK_QUOTIENT) goes behind every pair of sets 7 - 9 that follows
+ *                                        the table, and their calls insert in front of it.  Refused before anything is enqueued: any other
+ *                                        section, an absent or streamed section, a second call on the section, a null pointer, a set with
+ *                                        no room for two more oracles.  TMX_BATCH_MAX_ORACLES stays 8: [table, H7, Q7, H8, Q8, H9, Q9]
+ *                                        refuses this pair, so sets 7 - 9 combine with set 10 at most two at a time on one section.
+ *   tmx_air_sha512_link_periodic_device, _periodic_eval_device   the five planes on their own (5 << log_rows words, extended 5 << (log_rows +
+ *                                        log_blowup)), and at zeta: d_out[0 .. 10), d_out[10] = 1 if a denominator was zero.
+ *   tmx_air_sha512_link_public_side_device, _public_eval_device   the public side on its own, for tests: V (2 << log_rows words) under a given
+ *                                        gamma and its extension; Pub_gamma(zeta) from a V: d_out[0 .. 2), d_out[2] the flag.
+ * Scratch: per section set 3's formula with 65 columns, and once per context (7 (N + M) + 66816) 8 bytes of its own (the planes,
+ * V and the extended Pub_gamma, the rows of the two barycentric kernels, the levels of the public digest; the scratch of sets 6 - 9 is not
+ * touched).  Every refusal comes before anything is enqueued; everything is asynchronous on hip_stream apart from a domain change;
+ * tmx_air_last_gamma covers the quotient calls and the set-level call.  The streamed SHA-512 call keeps refusing constraint_set 10.  Still
+ * open: the reduction h = digest mod L against D.1b; LIVE / LV of sets 7 and 9 against this lv; a streamed form of the helper (65 columns
+ * per proof at 256 proofs, N = 2^15 and blow-up 8 are about 39 GB extended: resident only); a wider oracle cap. */
+#define TMX_AIR_SHA512_PUBLIC_WIDTH 49
+#define TMX_AIR_SHA512_LINK_HELPER_COLS 65
+#define TMX_AIR_SHA512_LINK_CONSTRAINTS 115
+#define TMX_TRACE_SHA512_LINK_HELPER 2097152u
+#define TMX_TRACE_SHA512_LINK_QUOTIENT 4194304u
+int32_t tmx_air_sha512_public_shape(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols);
+int32_t tmx_air_sha512_public_device(tmx_ctx* ctx, int32_t kind, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub, void* hip_stream);
+int32_t tmx_air_sha512_link_helper_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, const uint64_t* d_pub,
+                                          uint64_t* d_helper, void* hip_stream);
+int32_t tmx_air_sha512_link_quotient_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_link_quotient_range_device(tmx_ctx* ctx, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream);
+int32_t tmx_air_sha512_link_verify_device(tmx_ctx* ctx, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream);
+int32_t tmx_trace_commit_set_air_sha512_link_device(tmx_ctx* ctx, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
+                                                    void* hip_stream);
+int32_t tmx_air_sha512_link_periodic_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream);
+int32_t tmx_air_sha512_link_periodic_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream);
+int32_t tmx_air_sha512_link_public_side_device(tmx_ctx* ctx, uint32_t log_rows, uint32_t log_blowup, uint32_t n_proofs, const uint64_t* d_pub,
+                                               const uint64_t* d_gamma, uint64_t* d_v, uint64_t* d_ext, void* hip_stream);
+int32_t tmx_air_sha512_link_public_eval_device(tmx_ctx* ctx, uint32_t log_rows, const uint64_t* d_v, const uint64_t* d_zeta, uint64_t* d_out,
+                                               void* hip_stream);
 
 /* Self-test hook: k_ed_fin inverts with Bernstein-Yang division steps (inv25519.hpp); this runs that inversion and the Fermat chain
  * on n caller-provided values (eight little-endian words each, taken mod 2^255 - 19) and returns both results per value:

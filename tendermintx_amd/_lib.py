@@ -32,6 +32,8 @@ TRACE_SHA512_SCHED_HELPER, TRACE_SHA512_SCHED_QUOTIENT = 131072, 262144   # TMX_
 AIR_SHA512_INIT_HELPER_COLS, AIR_SHA512_INIT_CONSTRAINTS = 629, 673   # TMX_AIR_SHA512_INIT_*: constraint set 9, the SHA-512 block starts
 TRACE_SHA512_INIT_HELPER, TRACE_SHA512_INIT_QUOTIENT = 524288, 1048576   # TMX_TRACE_SHA512_INIT_*: the helper and the quotient of set 9
 AIR_SHA256_PUBLIC_WIDTH, AIR_SHA256_LINK_HELPER_COLS, AIR_SHA256_LINK_CONSTRAINTS = 26, 33, 50   # constraint set 6, the link to Level-1
+AIR_SHA512_PUBLIC_WIDTH, AIR_SHA512_LINK_HELPER_COLS, AIR_SHA512_LINK_CONSTRAINTS = 49, 65, 115   # constraint set 10, the SHA-512 table's link to Level-1
+TRACE_SHA512_LINK_HELPER, TRACE_SHA512_LINK_QUOTIENT = 2097152, 4194304   # TMX_TRACE_SHA512_LINK_*: the helper and the quotient of set 10
 
 
 class ValidatorRec(C.Structure):
@@ -457,6 +459,23 @@ def lib():
         L.tmx_trace_commit_set_air_sha512_streamed_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tmx_trace_commit_set_air_sha512_scratch_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.tmx_trace_commit_set_air_sha512_scratch_bytes.restype = C.c_uint64
+    except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
+        if not os.environ.get("TMX_LIB"):
+            raise
+    try:   # constraint set 10: the public table and the helper of the SHA-512 table's link to Level-1
+        L.tmx_air_sha512_public_shape.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.tmx_air_sha512_public_device.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_helper_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_quotient_device.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p] * 7
+        L.tmx_air_sha512_link_quotient_range_device.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 7
+        L.tmx_air_sha512_link_verify_device.argtypes = [C.c_void_p, C.POINTER(BatchParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_trace_commit_set_air_sha512_link_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_periodic_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_periodic_eval_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_public_side_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p]
+        L.tmx_air_sha512_link_public_eval_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:   # only an older build named by $TMX_LIB: the in-tree library has them
         if not os.environ.get("TMX_LIB"):
             raise

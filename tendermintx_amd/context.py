@@ -590,6 +590,65 @@ class Context:
         the flags of the public table (26 n_proofs columns of 2^(log_rows - 6) words) at d_pub"""
         check(self._L.tmx_air_sha256_link_helper_device(self._h, log_rows, n_proofs, d_table, d_pub, d_helper, self._stream(stream)), self._h)
 
+    # ---- constraint set 10: the SHA-512 table's link to Level-1 (include/tmx.h): the public table and the helper
+    def air_sha512_public_shape(self, kind, n_proofs):
+        """(log2 K, columns) of the public table of T.2 of n_proofs proofs at this context's n_max"""
+        return air_sha512_public_shape(kind, self.n_max, n_proofs)
+
+    def air_sha512_public_device(self, kind, n_proofs, d_elems, d_pub, stream=None):
+        """the public table of T.2 (column-major, 49 n_proofs columns of K words at d_pub: per block slot the sixteen message words and the
+        digest in low / high limbs, lv) from the element rows witness_batch_device wrote"""
+        check(self._L.tmx_air_sha512_public_device(self._h, kind, n_proofs, d_elems, d_pub, self._stream(stream)), self._h)
+
+    def air_sha512_link_helper_device(self, log_rows, n_proofs, d_table, d_pub, d_helper, stream=None):
+        """the link helper (65 n_proofs columns of 2^log_rows words at d_helper) from the pre-LDE table columns (18 n_proofs) at d_table and
+        lv of the public table (49 n_proofs columns, one row per 80-row block slot, padded to a power of two) at d_pub"""
+        check(self._L.tmx_air_sha512_link_helper_device(self._h, log_rows, n_proofs, d_table, d_pub, d_helper, self._stream(stream)), self._h)
+
+    def air_sha512_link_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot,
+                                        stream=None, proof_range=None, accumulate=0):
+        """the five planes filled and extended, gamma from the table cap, the helper cap and the digest of d_pub, then the quotient of the 115
+        constraints per proof over the extended table and helper columns into d_quot (planar, 2 << log_n words); proof_range and accumulate
+        as in air_sha256_quotient_device: the piece that starts at proof 0 carries the public polynomial"""
+        if proof_range is not None or accumulate:
+            lo, hi = proof_range if proof_range is not None else (0, n_proofs)
+            check(self._L.tmx_air_sha512_link_quotient_range_device(self._h, log_n, log_blowup, cap_height, n_proofs, lo, hi, int(accumulate), d_cols,
+                                                                    d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot, self._stream(stream)), self._h)
+            return
+        check(self._L.tmx_air_sha512_link_quotient_device(self._h, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper,
+                                                          d_pub, d_quot, self._stream(stream)), self._h)
+
+    def air_sha512_link_verify_device(self, params, k_trace, k_helper, d_caps, d_proof, d_pub, d_ok, stream=None):
+        """batch_verify_device, then the set-10 identity at zeta for the oracles k_trace (table), k_helper (helper), k_helper + 1 (quotient)
+        against the public table at d_pub, which the verifier hashes, combines and evaluates at zeta itself"""
+        check(self._L.tmx_air_sha512_link_verify_device(self._h, C.byref(self._batch_params(params)), k_trace, k_helper, d_caps, d_proof, d_pub,
+                                                        d_ok, self._stream(stream)), self._h)
+
+    def trace_commit_set_air_sha512_link_device(self, section, d_pub, d_cap_h, d_cap_q, stream=None):
+        """adds the SHA-512 link helper and quotient of the resident member `section` (SHA512 only) against the public table at d_pub to the
+        commit set, behind the pairs of sets 7 - 9 that already follow the table"""
+        check(self._L.tmx_trace_commit_set_air_sha512_link_device(self._h, section, d_pub, d_cap_h, d_cap_q, self._stream(stream)), self._h)
+
+    def air_sha512_link_periodic_device(self, log_rows, log_blowup, d_pre, d_ext, stream=None):
+        """STA, CHN, SEL, E79, MSG (planar, 5 << log_rows words at d_pre) and, unless log_blowup is 0, their extension under the current NTT
+        domain at d_ext"""
+        check(self._L.tmx_air_sha512_link_periodic_device(self._h, log_rows, log_blowup, d_pre, d_ext, self._stream(stream)), self._h)
+
+    def air_sha512_link_periodic_eval_device(self, log_rows, d_zeta, d_out, stream=None):
+        """d_out[0 .. 10) = the five planes at the F_p^2 point at d_zeta, barycentric over the 2^log_rows rows; d_out[10] = 1 on a zero
+        denominator"""
+        check(self._L.tmx_air_sha512_link_periodic_eval_device(self._h, log_rows, d_zeta, d_out, self._stream(stream)), self._h)
+
+    def air_sha512_link_public_side_device(self, log_rows, log_blowup, n_proofs, d_pub, d_gamma, d_v, d_ext, stream=None):
+        """V_r under the gamma at d_gamma (planar, 2 << log_rows words at d_v) and, unless log_blowup is 0, Pub_gamma on the coset at d_ext"""
+        check(self._L.tmx_air_sha512_link_public_side_device(self._h, log_rows, log_blowup, n_proofs, d_pub, d_gamma, d_v, d_ext,
+                                                             self._stream(stream)), self._h)
+
+    def air_sha512_link_public_eval_device(self, log_rows, d_v, d_zeta, d_out, stream=None):
+        """d_out[0 .. 2) = Pub_gamma at the F_p^2 point at d_zeta, barycentric over the 2^log_rows rows of V at d_v; d_out[2] = 1 on a zero
+        denominator"""
+        check(self._L.tmx_air_sha512_link_public_eval_device(self._h, log_rows, d_v, d_zeta, d_out, self._stream(stream)), self._h)
+
     def air_sha256_link_quotient_device(self, log_n, log_blowup, cap_height, n_proofs, d_cols, d_helper_cols, d_cap, d_cap_helper, d_pub, d_quot,
                                         stream=None, proof_range=None, accumulate=0):
         """gamma from the table cap, the helper cap and the digest of d_pub, the seventeen public polynomials, then the quotient of the 50
@@ -912,6 +971,14 @@ def air_sha256_public_shape(kind, section, n_max, n_proofs, L=None):
     L = L or _lib.lib()
     log_k, n_cols = C.c_uint32(), C.c_uint32()
     check(L.tmx_air_sha256_public_shape(kind, section, n_max, n_proofs, C.byref(log_k), C.byref(n_cols)))
+    return int(log_k.value), int(n_cols.value)
+
+
+def air_sha512_public_shape(kind, n_max, n_proofs, L=None):
+    """tmx_air_sha512_public_shape (no context, no device): (log2 K, columns) of the public table of constraint set 10"""
+    L = L or _lib.lib()
+    log_k, n_cols = C.c_uint32(), C.c_uint32()
+    check(L.tmx_air_sha512_public_shape(kind, n_max, n_proofs, C.byref(log_k), C.byref(n_cols)))
     return int(log_k.value), int(n_cols.value)
 
 

@@ -263,6 +263,56 @@ struct AirSha512Launch {
   int (*check)(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part, const void* d_open_t,
                const void* d_open_h, const void* d_open_q, const void* d_zeta, const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
 };
-const AirSha512Launch* air_sha512_launch(uint32_t set);  // set = 7, 8 or 9
+const AirSha512Launch* air_sha512_launch(uint32_t set);  // set = 7, 8, 9 or 10
+
+// ---- constraint set 10: the SHA-512 table's link to Level-1 (include/tmx.h "the SHA-512 table's link to Level-1").  The same table, a public
+// table of 49 columns per proof on the table's block slots (slot k = rows 80 k .. 80 k + 79, the partial last slot included), a helper
+// oracle of 65 columns per proof, 115 constraints per proof, five preprocessed planes (STA, CHN, SEL, E79, MSG) behind the descriptor of sets
+// 7 - 9 (air_sha512_launch(10): fill, tables, quotient, eval and fold; its check is the one below, which knows the public side).  gamma is set
+// 6's rule with the set id 10 (launch_air_link_gamma).  All public terms enter linearly: under gamma they are ONE F_p^2 value V_r per row.
+constexpr uint32_t AIR_SHA512_PUBLIC_WIDTH = 49, AIR_SHA512_LINK_HELPER_COLS = 65, AIR_SHA512_LINK_CONSTRAINTS = 115;
+// The tables of a quotient launch (sets 7 - 9's layout) and the rows of the two barycentric kernels: the planes' (five sums and a flag) and
+// the public side's (one sum and a flag)
+constexpr uint32_t AIR10_TAB_GPOW = 0, AIR10_TAB_ZINV = 256, AIR10_PART_WORDS = 16, AIR10_PUB_PART_WORDS = 4;
+constexpr uint64_t AIR10_TAB_WORDS = AIR10_TAB_ZINV + 64;
+static_assert(2 * (AIR_SHA512_LINK_CONSTRAINTS + 2) <= AIR10_TAB_ZINV && AIR10_TAB_WORDS <= AIR_TAB_SEL + (256ull << 6),
+              "the set-10 tables live in the table part of set 1's scratch");
+// log2 of the public table's rows for a table of 2^log_rows rows: the slots ceil(2^log_rows / 80), padded to a power of two
+inline uint32_t air_sha512_public_log_k(uint32_t log_rows) {
+  const uint64_t slots = ((1ull << log_rows) + 79) / 80;
+  uint32_t lg = 0;
+  while ((1ull << lg) < slots) lg++;
+  return lg;
+}
+// Where the gather reads in an element row, recorded by build_program (api.cpp) beside AirShaPublicGeom and for the same reason.  A struct
+// of its own: set 6's gather takes AirShaPublicGeom by value, so a field added there would change that kernel's arguments.
+//   h2, h2_lane, d1a, d1a_lane   as in AirShaPublicGeom
+//   h2_pk, h2_r, h2_msg          inside a ValidatorVariable: the bits of pubkey, signature.r and message[124]
+//   h2_mlen, h2_signed           message_byte_length and signed
+//   d1a_digest                   inside a D.1a lane: the 512 bits of the SHA-512 digest
+struct AirSha512PublicGeom {
+  uint64_t elem_stride;
+  uint32_t n;
+  uint32_t h2, h2_lane, h2_pk, h2_r, h2_msg, h2_mlen, h2_signed;
+  uint32_t d1a, d1a_lane, d1a_digest;
+};
+// The public table from element rows: one lane per (proof, block slot); d_pub 49 n_proofs columns of 2^log_k words
+int launch_air_sha512_public_gather(const void* d_rows, const AirSha512PublicGeom& G, uint32_t log_k, uint32_t n_proofs, void* d_pub, void* stream);
+// The helper oracle from pre-LDE columns and the public lv: one lane per (proof, row); d_table 18 n_proofs columns of 2^log_rows words, d_pub
+// 49 n_proofs columns of 2^air_sha512_public_log_k(log_rows), d_helper 65 n_proofs columns of 2^log_rows
+int launch_air_sha512_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, const void* d_pub, void* d_helper, void* stream);
+// d_v (planar, 2 << log_rows canonical words) = V_r from pub and gamma (2 words at d_gamma): one lane per row, Horner over the proofs
+int launch_air_sha512_link_combine(uint32_t log_rows, uint32_t n_proofs, const void* d_pub, const void* d_gamma, void* d_v, void* stream);
+// d_quot (planar, 2 << log_m) -= Pub_gamma / (x^N - 1): d_ext the extended V, d_tab the quotient launch's tables.  The piece that starts at
+// proof 0 is followed by it (set 6's rule)
+int launch_air_sha512_link_public_sub(uint32_t log_m, uint32_t log_blowup, const void* d_ext, const void* d_tab, void* d_quot, void* stream);
+// The barycentric sums of Pub_gamma at zeta over the N rows from d_v: air_sha512_eval_parts(log_rows) rows of AIR10_PUB_PART_WORDS at d_part
+int launch_air_sha512_link_public_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, const void* d_v, void* d_part, void* stream);
+// d_out[0 .. 2) = Pub_gamma(zeta) from those rows, d_out[2] = 1 if a denominator was zero; n_inv = 1 / N
+int launch_air_sha512_link_public_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream);
+// The identity at zeta: AirSha512Launch::check with the public side's rows at d_pub_part
+int launch_air_sha512_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                 const void* d_pub_part, const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta,
+                                 const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream);
 
 }  // namespace tmx

@@ -2448,6 +2448,65 @@ struct Sha512Init {  // set 9: STA, CHN
   }
 };
 
+// Set 10, the link to Level-1 (its public table and helper kernels stand at the end of this file; the block "constraint set 10" there says
+// what the columns are).  Helper column offsets inside a proof's 65, public columns inside its 49 (a word's low limb first: word j at
+// + 2 j, + 2 j + 1), constraint indices inside its 115 (a family's member 2 j + limb).
+constexpr uint32_t L_CV = 0, L_DG = 16, L_CD = 32, L_LN = 48, L_CH = 49;
+constexpr uint32_t U_W = 0, U_DIG = 32, U_LV = 48;
+constexpr uint32_t JL_CD = 0, JL_SUM = 16, JL_CH = 32, JL_SEL = 48, JL_CHN = 64, JL_STA = 80, JL_LVN = 96, JL_DIG = 97, JL_MSG = 113;
+
+// The 115 constraints of one proof at one point: the column parts -- what the public polynomial Pub_gamma is subtracted from (the families
+// from JL_LVN on carry a public term).  Every nonlinear one has degree 2 and no selector; a selected one is a plane times a linear form.
+// STA(x) and CHN(x) are factored out into the started and the chained sum (the kernel applies each once); SEL, E79 and MSG are operands.
+template <class F, class View>
+__device__ __forceinline__ void air_sha512_link_constraints(View& at, typename F::T SEL, typename F::T E79, typename F::T MSG) {
+  using A = Forms<F>;
+  using T = typename F::T;
+  const T LN = at.again(L_LN);
+#pragma unroll 1
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t iv = IV_SHA512[j];  // (j is uniform: a scalar load)
+    T cdl = F::zero();
+#pragma unroll
+    for (uint32_t l = 0; l < 2; l++) {
+      const uint32_t c = 2 * j + l;
+      const T CV = at.once(L_CV + c), DG = at.once(L_DG + c), CD = at.once(L_CD + c), CH = at.once(L_CH + c), CVn = at.next(L_CV + c);
+      at.plain(JL_CD + c, A::boolean(CD));
+      T s = A::sub(A::add(DG, A::scale(CD, 1ull << 32)), A::add(CV, at.tbl(R_A + c)));
+      if (l) s = A::sub(s, cdl);  // the carry out of the low limb comes in
+      else cdl = CD;
+      at.plain(JL_SUM + c, s);
+      at.plain(JL_CH + c, A::sub(CH, A::mul(LN, DG)));
+      at.plain(JL_SEL + c, A::mul(SEL, A::sub(CVn, CV)));
+      at.chained(JL_CHN + c, A::sub(CVn, CH));
+      at.started(JL_STA + c, A::sub(CVn, A::scale(LN, limb_of(iv, l))));
+      at.plain(JL_DIG + c, A::mul(E79, DG));  // E79 DG - CHN CH
+      at.chained(JL_DIG + c, A::sub(F::zero(), CH));
+    }
+  }
+  at.started(JL_LVN, LN);  // (CHN + STA) LN
+  at.chained(JL_LVN, LN);
+  at.plain(JL_MSG, A::mul(MSG, at.tbl(R_W)));
+  at.plain(JL_MSG + 1, A::mul(MSG, at.tbl(R_W + 1)));
+}
+
+struct Sha512Link {  // set 10: STA, CHN (set 9's), then SEL (set 7's), E79 "the last row of a block", MSG "a message row"
+  static constexpr uint32_t PLANES = 5, SELECTORS = 2, HELPER_COLS = AIR_SHA512_LINK_HELPER_COLS, CONSTRAINTS = AIR_SHA512_LINK_CONSTRAINTS;
+  static constexpr uint32_t TAB_GPOW = AIR10_TAB_GPOW, TAB_ZINV = AIR10_TAB_ZINV, PART_WORDS = AIR10_PART_WORDS;
+  static __device__ __forceinline__ void planes(uint32_t r, uint32_t n, uint64_t v[PLANES]) {
+    v[0] = sha512_sta(r, n) ? 1 : 0;
+    v[1] = sha512_chn(r) ? 1 : 0;
+    v[2] = sha512_sel(r, n) ? 1 : 0;
+    v[3] = r % SHA512_BLOCK == SHA512_BLOCK - 1 ? 1 : 0;
+    v[4] = r % SHA512_BLOCK < 16 ? 1 : 0;
+  }
+  template <class F, class View>
+  static __device__ __forceinline__ gl2 proof(View& at, const typename F::T* pv) {
+    air_sha512_link_constraints<F>(at, pv[2], pv[3], pv[4]);
+    return at.template combined<SELECTORS>(pv);
+  }
+};
+
 // One lane per row: the planes before the LDE, planar (PLANES << log_rows words)
 template <class S>
 __global__ __launch_bounds__(256) void k_air_sha512_periodic(uint32_t log_rows, uint64_t* __restrict__ pre) {
@@ -2679,7 +2738,10 @@ template <class S>
 static constexpr AirSha512Launch AIR_SHA512_LAUNCH_OF = {launch_sha512_periodic<S>,      launch_sha512_tables<S>,        launch_sha512_quotient<S>,
                                                          launch_sha512_periodic_eval<S>, launch_sha512_periodic_fold<S>, launch_sha512_check<S>};
 const AirSha512Launch* air_sha512_launch(uint32_t set) {
-  return set == 7 ? &AIR_SHA512_LAUNCH_OF<Sha512Round> : set == 8 ? &AIR_SHA512_LAUNCH_OF<Sha512Sched> : &AIR_SHA512_LAUNCH_OF<Sha512Init>;
+  return set == 7    ? &AIR_SHA512_LAUNCH_OF<Sha512Round>
+         : set == 8  ? &AIR_SHA512_LAUNCH_OF<Sha512Sched>
+         : set == 10 ? &AIR_SHA512_LAUNCH_OF<Sha512Link>
+                     : &AIR_SHA512_LAUNCH_OF<Sha512Init>;
 }
 
 // The three helper oracles: one lane per (proof, row)
@@ -2698,6 +2760,300 @@ int launch_air_sha512_sched_helper(uint32_t log_rows, uint32_t n_proofs, const v
 }
 int launch_air_sha512_init_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, void* d_helper, void* stream) {
   return launch_sha512_helper(k_air_sha512_init_helper, log_rows, n_proofs, d_table, d_helper, stream);
+}
+
+// ---- constraint set 10: the SHA-512 table's link to Level-1 (include/tmx.h "the SHA-512 table's link to Level-1") ----------------------------
+// The public table and the helper oracle; sets 7 - 9 above stay as they are.
+
+// plonky2x DUMMY_PUBLIC_KEY and the R half of DUMMY_SIGNATURE, little-endian words (trace.hip and kernels.hip have the same words; pinned
+// by tests/test_oracle_kat.py::test_dummy_constants and, here, by the gather test on a lane that did not sign)
+__device__ __constant__ const uint32_t LINK512_DUMMY_PK[8] = {0xdde3888au, 0x95f10974u, 0x2ddb52fdu, 0x725dba3cu, 0xbf0967cau, 0x1b12941du, 0x018874f3u, 0x5c6f0fb4u};
+__device__ __constant__ const uint32_t LINK512_DUMMY_R[8] = {0x9e681437u, 0x11c27854u, 0xa49ded06u, 0x899e5855u, 0xf0bb77bbu, 0x3f50499fu, 0x5b4aa285u, 0x8a063530u};
+
+// Byte `pos` of the padded message R | A | M of a lane (v: its ValidatorVariable): `total` message bytes, 80, zeros, the bit length at the
+// end of the last block (8 total < 2^16: the other fourteen length bytes are zero).  A lane that did not sign hashes the dummy triple.
+__device__ __forceinline__ uint32_t link512_padded_byte(const AirSha512PublicGeom& G, const uint64_t* __restrict__ v, bool is_signed, uint32_t total,
+                                                        uint32_t n_blocks, uint32_t pos) {
+  if (pos >= total) {
+    if (pos == total) return 0x80u;
+    const uint32_t tail = 128u * n_blocks - 1u - pos;
+    return tail < 2u ? ((8u * total) >> (8u * tail)) & 0xffu : 0u;
+  }
+  if (pos < 32u) return is_signed ? link_byte(v + G.h2_r + 8u * pos) : (LINK512_DUMMY_R[pos >> 2] >> (8u * (pos & 3u))) & 0xffu;
+  if (pos < 64u) return is_signed ? link_byte(v + G.h2_pk + 8u * (pos - 32u)) : (LINK512_DUMMY_PK[(pos - 32u) >> 2] >> (8u * (pos & 3u))) & 0xffu;
+  return is_signed ? link_byte(v + G.h2_msg + 8u * (pos - 64u)) : 0u;
+}
+
+// One lane per (proof, block slot k): lane i = k / 2 of the validators, block b = k mod 2 of its hash.  The sixteen message words of the
+// block, the digest where the block is the last live one of its lane, and lv, from H.2 and D.1a of the proof's element row alone, by the
+// rules of k_trace_sha512 (trace.hip): the dummy triple for a lane that did not sign, the message length clamped to 124.  Slots of lanes
+// >= n -- the partial last slot and the padding are among them -- and unused second blocks are all zero.  Lanes run over the slots, so each
+// of the 49 stores of a wave covers consecutive words of one column.
+__global__ __launch_bounds__(256) void k_air_sha512_public_gather(const uint64_t* __restrict__ rows, AirSha512PublicGeom G, uint32_t log_k,
+                                                                  uint32_t n_proofs, uint64_t* __restrict__ pub) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_k)) return;
+  const uint32_t p = (uint32_t)(idx >> log_k), k = (uint32_t)(idx & ((1u << log_k) - 1));
+  const uint64_t* __restrict__ row = rows + (uint64_t)p * G.elem_stride;
+  const uint32_t i = k >> 1, b = k & 1u;
+  const bool inside = i < G.n;
+  const uint64_t* __restrict__ v = row + G.h2 + (uint64_t)G.h2_lane * (inside ? i : 0u);
+  const uint64_t* __restrict__ dig = row + G.d1a + (uint64_t)G.d1a_lane * (inside ? i : 0u) + G.d1a_digest;
+  const bool is_signed = (uint32_t)v[G.h2_signed] != 0;
+  const uint64_t len = v[G.h2_mlen];
+  const uint32_t total = 64u + (is_signed ? (len > 124u ? 124u : (uint32_t)len) : 32u), n_blocks = total + 17u > 128u ? 2u : 1u;
+  const bool live = inside && b < n_blocks, last = live && b + 1u == n_blocks;
+  uint64_t* __restrict__ dst = pub + (((uint64_t)p * AIR_SHA512_PUBLIC_WIDTH) << log_k) + k;
+#pragma unroll 1
+  for (uint32_t t = 0; t < 32; t++) {  // limb t & 1 of word t / 2: the low limb is the word's last four bytes
+    uint32_t limb = 0;
+    if (live) {
+#pragma unroll 1
+      for (uint32_t c = 0; c < 4; c++) limb = (limb << 8) | link512_padded_byte(G, v, is_signed, total, n_blocks, 128u * b + 4u * (t ^ 1u) + c);
+    }
+    dst[(uint64_t)(U_W + t) << log_k] = limb;
+  }
+#pragma unroll 1
+  for (uint32_t t = 0; t < 16; t++) {
+    uint32_t limb = 0;
+    if (last) {
+#pragma unroll
+      for (uint32_t c = 0; c < 4; c++) limb = (limb << 8) | link_byte(dig + 8u * (4u * (t ^ 1u) + c));
+    }
+    dst[(uint64_t)(U_DIG + t) << log_k] = limb;
+  }
+  dst[(uint64_t)U_LV << log_k] = live ? 1 : 0;
+}
+
+// One lane per (proof, row) of the pre-LDE table: the row's eight state words, lv of its slot and of the next one (the slot of the next
+// row, cyclic inside the proof: behind the partial last slot stands slot 0), and in a second block the eight state words of the row in
+// front of it; then 65 stores, each of them consecutive words of one column across the wave.  CV, the state a block starts from, is the
+// IV in a live first block, the first block's feed-forward in a live second block and 0 in a block that is not live; DG = CV + s mod 2^64
+// with its two carry bits; LN and CH = LN DG.  Operands are the low 32 bits of the words; lv is set when its low 32 bits are not zero.
+__global__ __launch_bounds__(256) void k_air_sha512_link_helper(uint32_t log_rows, uint32_t log_k, uint32_t n_proofs, const uint64_t* __restrict__ table,
+                                                                const uint64_t* __restrict__ pub, uint64_t* __restrict__ helper) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ((uint64_t)n_proofs << log_rows)) return;
+  const uint32_t p = (uint32_t)(idx >> log_rows), N = 1u << log_rows;
+  const uint32_t r = (uint32_t)(idx & (N - 1)), k = r / SHA512_BLOCK, kn = SHA512_BLOCK * (k + 1) < N ? k + 1 : 0;
+  const uint64_t* __restrict__ t = table + (((uint64_t)p * AIR_SHA512_WIDTH) << log_rows);
+  const uint64_t* __restrict__ lv = pub + (((uint64_t)p * AIR_SHA512_PUBLIC_WIDTH + U_LV) << log_k);
+  const bool live = (uint32_t)lv[k] != 0, second = k & 1u, live_front = second && (uint32_t)lv[k - 1] != 0;
+  const uint64_t ln = (uint32_t)lv[kn] != 0 ? 1 : 0;
+  const uint32_t front = second ? SHA512_BLOCK * k - 1 : r;  // (the last row of the first block)
+  uint64_t* __restrict__ o = helper + (((uint64_t)p * AIR_SHA512_LINK_HELPER_COLS) << log_rows) + r;
+  auto put = [&](uint32_t col, uint64_t x) { o[(uint64_t)col << log_rows] = x; };
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    const uint64_t* __restrict__ lo_col = t + ((uint64_t)(R_A + 2 * j) << log_rows);
+    const uint64_t* __restrict__ hi_col = t + ((uint64_t)(R_A + 2 * j + 1) << log_rows);
+    uint64_t cv = 0;
+    if (live) cv = second ? (live_front ? IV_SHA512[j] : 0) + ((uint64_t)(uint32_t)lo_col[front] | (uint64_t)(uint32_t)hi_col[front] << 32) : IV_SHA512[j];
+    const uint64_t lo = limb_of(cv, 0) + (uint32_t)lo_col[r], cdl = lo >> 32;
+    const uint64_t hi = limb_of(cv, 1) + (uint32_t)hi_col[r] + cdl, cdh = hi >> 32;
+    put(L_CV + 2 * j, limb_of(cv, 0));
+    put(L_CV + 2 * j + 1, limb_of(cv, 1));
+    put(L_DG + 2 * j, (uint32_t)lo);
+    put(L_DG + 2 * j + 1, (uint32_t)hi);
+    put(L_CD + 2 * j, cdl);
+    put(L_CD + 2 * j + 1, cdh);
+    put(L_CH + 2 * j, ln ? (uint32_t)lo : 0u);
+    put(L_CH + 2 * j + 1, ln ? (uint32_t)hi : 0u);
+  }
+  put(L_LN, ln);
+}
+
+// The public side under gamma, one lane per row r: V_r = sum_p gamma^(115 p) sum_j gamma^j (the public term of constraint j of proof p on
+// row r), Horner over the proofs from the last to the first.  The public terms: lv of the next slot where STA or CHN is on (JL_LVN), dig
+// of the row's slot on the last row of a block (JL_DIG ..), w[k][t] on row 80 k + t, t < 16 (JL_MSG, + 1); most rows have none.  v: two
+// planes of N canonical words.
+__global__ __launch_bounds__(256) void k_air_sha512_link_combine(uint32_t log_rows, uint32_t log_k, uint32_t n_proofs, const uint64_t* __restrict__ pub,
+                                                                 const uint64_t* __restrict__ gamma, uint64_t* __restrict__ v) {
+  const uint32_t N = 1u << log_rows, r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= N) return;
+  const uint32_t k = r / SHA512_BLOCK, t = r % SHA512_BLOCK, kn = SHA512_BLOCK * (k + 1) < N ? k + 1 : 0;
+  const bool edge = sha512_sta(r, N) || sha512_chn(r), e79 = t == SHA512_BLOCK - 1, msg = t < 16;
+  gl2 acc = {0, 0};
+  if (edge || e79 || msg) {
+    const gl2 g = {gamma[0], gamma[1]};
+    const gl2 g_lvn = gl2_pow(g, JL_LVN), g_msg = gl2_pow(g, JL_MSG), g_all = gl2_pow(g, AIR_SHA512_LINK_CONSTRAINTS);
+    for (uint32_t p = n_proofs; p-- > 0;) {
+      const uint64_t* __restrict__ u = pub + (((uint64_t)p * AIR_SHA512_PUBLIC_WIDTH) << log_k);
+      gl2 s = {0, 0};
+      if (edge) s = gl2_scale(g_lvn, gl_canon(u[((uint64_t)U_LV << log_k) + kn]));
+      if (e79) {
+        gl2 w = gl2_mul(g_lvn, g);  // gamma^JL_DIG
+#pragma unroll 1
+        for (uint32_t c = 0; c < 16; c++, w = gl2_mul(w, g)) s = gl2_add(s, gl2_scale(w, gl_canon(u[((uint64_t)(U_DIG + c) << log_k) + k])));
+      }
+      if (msg) {
+        s = gl2_add(s, gl2_scale(g_msg, gl_canon(u[((uint64_t)(U_W + 2 * t) << log_k) + k])));
+        s = gl2_add(s, gl2_scale(gl2_mul(g_msg, g), gl_canon(u[((uint64_t)(U_W + 2 * t + 1) << log_k) + k])));
+      }
+      acc = gl2_add(gl2_mul(acc, g_all), s);
+    }
+  }
+  v[r] = acc.c0;
+  v[(size_t)N + r] = acc.c1;
+}
+
+// One lane per point: quot -= Pub_gamma / (x^N - 1), both planes; ext the extended V (2 << log_m words), zinv the quotient tables' (by i mod B)
+__global__ __launch_bounds__(256) void k_air_sha512_link_public_sub(uint32_t log_m, uint32_t log_blowup, const uint64_t* __restrict__ ext,
+                                                                    const uint64_t* __restrict__ zinv, uint64_t* __restrict__ quot) {
+  const uint64_t M = 1ull << log_m, i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const uint64_t z = zinv[i & ((1ull << log_blowup) - 1)];
+  quot[i] = gl_sub(gl_canon(quot[i]), gl_mul(gl_canon(ext[i]), z));
+  quot[M + i] = gl_sub(gl_canon(quot[M + i]), gl_mul(gl_canon(ext[M + i]), z));
+}
+
+// Pub_gamma at zeta, barycentric over the N rows from the verifier's own V: k_air_sha512_periodic_eval's walk with ONE F_p^2 value per
+// row, read from v.  A workgroup's sum goes to its row of `part`: two words of sum, then 1 if a denominator was zero.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_link_public_eval(uint32_t log_rows, uint64_t om, const uint64_t* __restrict__ zeta,
+                                                                                   const uint64_t* __restrict__ v, uint64_t* __restrict__ part) {
+  __shared__ uint64_t red[2][AIR_CHECK_THREADS];
+  __shared__ uint32_t bad;
+  const uint32_t N = 1u << log_rows, T = gridDim.x * AIR_CHECK_THREADS, g = blockIdx.x * AIR_CHECK_THREADS + threadIdx.x;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const gl2 z = {gl_canon(zeta[0]), gl_canon(zeta[1])};
+  const uint64_t stride = gl_pow(om, T);
+  uint64_t y = gl_pow(om, g);
+  gl2 sum = {0, 0};
+  for (uint32_t r0 = g; r0 < N; r0 += AIR_SHA512_EVAL_PER * T) {
+    gl2 pre[AIR_SHA512_EVAL_PER], den[AIR_SHA512_EVAL_PER];
+    uint64_t yk[AIR_SHA512_EVAL_PER];
+    gl2 run = {1, 0};
+#pragma unroll
+    for (int m = 0; m < AIR_SHA512_EVAL_PER; m++) {
+      const bool in = r0 + m * T < N;
+      yk[m] = y;
+      den[m] = {gl_sub(z.c0, y), z.c1};
+      pre[m] = run;
+      if (in && den[m].c0 == 0 && den[m].c1 == 0) {
+        bad = 1;
+        den[m] = {1, 0};
+      }
+      if (in) run = gl2_mul(run, den[m]);
+      y = gl_mul(y, stride);
+    }
+    gl2 inv = gl2_inv(run);
+#pragma unroll
+    for (int m = AIR_SHA512_EVAL_PER - 1; m >= 0; m--) {
+      const uint32_t r = r0 + m * T;
+      if (r < N) {
+        const gl2 term = gl2_scale(gl2_mul(inv, pre[m]), yk[m]);  // omega^r / (zeta - omega^r)
+        inv = gl2_mul(inv, den[m]);
+        if (gl_sub(z.c0, yk[m]) == 0 && z.c1 == 0) continue;
+        sum = gl2_add(sum, gl2_mul(term, {gl_canon(v[r]), gl_canon(v[(size_t)N + r])}));
+      }
+    }
+  }
+  const uint32_t t = threadIdx.x;
+  red[0][t] = sum.c0, red[1][t] = sum.c1;
+  for (uint32_t h = AIR_CHECK_THREADS / 2; h; h >>= 1) {
+    __syncthreads();
+    if (t < h) red[0][t] = gl_add(red[0][t], red[0][t + h]), red[1][t] = gl_add(red[1][t], red[1][t + h]);
+  }
+  __syncthreads();
+  if (t < 2) part[(size_t)blockIdx.x * AIR10_PUB_PART_WORDS + t] = red[t][0];
+  if (t == 2) part[(size_t)blockIdx.x * AIR10_PUB_PART_WORDS + 2] = bad;
+}
+
+// The set-10 identity at zeta, one workgroup: k_air_sha512_check over Sha512Link with the public side -- the sum over the proofs less
+// Pub_gamma(zeta), folded from the rows of pub_part, against (u_0 + X u_1) (zeta^N - 1).  A zero denominator in either barycentric sum
+// clears every verdict.
+__global__ __launch_bounds__(AIR_CHECK_THREADS) void k_air_sha512_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub,
+                                                                             uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                                                             const uint64_t* __restrict__ pub_part, const uint64_t* __restrict__ open_t,
+                                                                             const uint64_t* __restrict__ open_h, const uint64_t* __restrict__ open_q,
+                                                                             const uint64_t* __restrict__ zeta, const uint64_t* __restrict__ gamma,
+                                                                             uint32_t n_queries, uint32_t* __restrict__ ok) {
+  using S = Sha512Link;
+  __shared__ uint64_t gpw[2 * (S::CONSTRAINTS + 1)];
+  const gl2 g = {gamma[0], gamma[1]};
+  air_gamma_powers(g, S::CONSTRAINTS, gpw);
+  __syncthreads();
+  gl2 zn = {zeta[0], zeta[1]}, pv[S::PLANES];
+  for (uint32_t k = 0; k < log_sub; k++) zn = gl2_mul(zn, zn);
+  bool fine = air_sha512_periodic_at<S>(part, n_parts, zn, n_inv, pv);
+  gl2 sum = {0, 0};
+  for (uint32_t p = threadIdx.x; p < n_proofs; p += AIR_CHECK_THREADS) {
+    ZetaView at = {open_t + (uint64_t)p * AIR_SHA512_WIDTH, open_h + (uint64_t)p * S::HELPER_COLS, 1ull << log_r_t, 1ull << log_r_h, gpw};
+    const gl2 v = S::template proof<FieldP2>(at, pv);
+    sum = gl2_add(sum, gl2_mul(gl2_pow(g, (uint64_t)S::CONSTRAINTS * p), v));
+  }
+  gl2 ps = {0, 0};
+  for (uint32_t k = 0; k < n_parts; k++) {
+    ps = gl2_add(ps, {pub_part[(size_t)k * AIR10_PUB_PART_WORDS], pub_part[(size_t)k * AIR10_PUB_PART_WORDS + 1]});
+    if (pub_part[(size_t)k * AIR10_PUB_PART_WORDS + 2]) fine = false;
+  }
+  if (threadIdx.x == 0) sum = gl2_sub(sum, gl2_mul(gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv), ps));
+  air_check_verdict(sum, open_q, {gl_sub(zn.c0, 1), zn.c1}, n_queries, ok);
+  if (!fine)
+    for (uint32_t q = threadIdx.x; q < n_queries; q += AIR_CHECK_THREADS) ok[q] = 0;
+}
+
+// One thread: Pub_gamma(zeta) from the rows of `part` (2 words), then 1 if a denominator was zero, at out[0 .. 2]
+__global__ void k_air_sha512_link_public_fold(uint32_t log_rows, uint32_t n_parts, uint64_t n_inv, const uint64_t* __restrict__ part,
+                                              const uint64_t* __restrict__ zeta, uint64_t* __restrict__ out) {
+  gl2 zn = {gl_canon(zeta[0]), gl_canon(zeta[1])}, ps = {0, 0};
+  for (uint32_t k = 0; k < log_rows; k++) zn = gl2_mul(zn, zn);
+  uint64_t bad = 0;
+  for (uint32_t k = 0; k < n_parts; k++) {
+    ps = gl2_add(ps, {part[(size_t)k * AIR10_PUB_PART_WORDS], part[(size_t)k * AIR10_PUB_PART_WORDS + 1]});
+    bad |= part[(size_t)k * AIR10_PUB_PART_WORDS + 2];
+  }
+  const gl2 v = gl2_mul(gl2_scale({gl_sub(zn.c0, 1), zn.c1}, n_inv), ps);
+  out[0] = v.c0;
+  out[1] = v.c1;
+  out[2] = bad ? 1 : 0;
+}
+
+int launch_air_sha512_link_public_fold(uint32_t log_rows, uint64_t n_inv, const void* d_part, const void* d_zeta, void* d_out, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_link_public_fold, dim3(1), dim3(1), 0, S_(stream), log_rows, air_sha512_eval_parts(log_rows), n_inv,
+                     reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<uint64_t*>(d_out));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_link_combine(uint32_t log_rows, uint32_t n_proofs, const void* d_pub, const void* d_gamma, void* d_v, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_link_combine, dim3(((1u << log_rows) + 255) / 256), dim3(256), 0, S_(stream), log_rows,
+                     air_sha512_public_log_k(log_rows), n_proofs, reinterpret_cast<const uint64_t*>(d_pub), reinterpret_cast<const uint64_t*>(d_gamma),
+                     reinterpret_cast<uint64_t*>(d_v));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_link_public_sub(uint32_t log_m, uint32_t log_blowup, const void* d_ext, const void* d_tab, void* d_quot, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_link_public_sub, dim3((uint32_t)(((1ull << log_m) + 255) / 256)), dim3(256), 0, S_(stream), log_m, log_blowup,
+                     reinterpret_cast<const uint64_t*>(d_ext), reinterpret_cast<const uint64_t*>(d_tab) + AIR10_TAB_ZINV,
+                     reinterpret_cast<uint64_t*>(d_quot));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_link_public_eval(uint32_t log_rows, uint64_t om, const void* d_zeta, const void* d_v, void* d_part, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_link_public_eval, dim3(air_sha512_eval_parts(log_rows)), dim3(AIR_CHECK_THREADS), 0, S_(stream), log_rows, om,
+                     reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_v), reinterpret_cast<uint64_t*>(d_part));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_link_check(uint32_t n_proofs, uint32_t log_r_t, uint32_t log_r_h, uint32_t log_sub, uint64_t n_inv, const void* d_part,
+                                 const void* d_pub_part, const void* d_open_t, const void* d_open_h, const void* d_open_q, const void* d_zeta,
+                                 const void* d_gamma, uint32_t n_queries, void* d_ok, void* stream) {
+  hipLaunchKernelGGL(k_air_sha512_link_check, dim3(1), dim3(AIR_CHECK_THREADS), 0, S_(stream), n_proofs, log_r_t, log_r_h, log_sub,
+                     air_sha512_eval_parts(log_sub), n_inv, reinterpret_cast<const uint64_t*>(d_part), reinterpret_cast<const uint64_t*>(d_pub_part),
+                     reinterpret_cast<const uint64_t*>(d_open_t), reinterpret_cast<const uint64_t*>(d_open_h),
+                     reinterpret_cast<const uint64_t*>(d_open_q), reinterpret_cast<const uint64_t*>(d_zeta), reinterpret_cast<const uint64_t*>(d_gamma),
+                     n_queries, reinterpret_cast<uint32_t*>(d_ok));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_public_gather(const void* d_rows, const AirSha512PublicGeom& G, uint32_t log_k, uint32_t n_proofs, void* d_pub, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_k;
+  hipLaunchKernelGGL(k_air_sha512_public_gather, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), reinterpret_cast<const uint64_t*>(d_rows),
+                     G, log_k, n_proofs, reinterpret_cast<uint64_t*>(d_pub));
+  return (int)hipGetLastError();
+}
+int launch_air_sha512_link_helper(uint32_t log_rows, uint32_t n_proofs, const void* d_table, const void* d_pub, void* d_helper, void* stream) {
+  const uint64_t n = (uint64_t)n_proofs << log_rows;
+  hipLaunchKernelGGL(k_air_sha512_link_helper, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S_(stream), log_rows, air_sha512_public_log_k(log_rows),
+                     n_proofs, reinterpret_cast<const uint64_t*>(d_table), reinterpret_cast<const uint64_t*>(d_pub),
+                     reinterpret_cast<uint64_t*>(d_helper));
+  return (int)hipGetLastError();
 }
 
 }  // namespace tmx

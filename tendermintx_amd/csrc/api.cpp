@@ -106,6 +106,7 @@ struct Program {
   uint32_t d1b_start = 0;  // first element of D.1b in a row (the EdDSA finish writes that section directly: RowOut)
   uint32_t mask_hint = 0, mask_derived = 0;  // sections of H / of D (tmx_witness_batch_opts: a caller may ask for one of them only)
   AirShaPublicGeom pub = {};  // where tmx_air_sha256_public_device reads in a row: recorded while the table is emitted (air.h)
+  AirSha512PublicGeom pub512 = {};  // likewise for tmx_air_sha512_public_device: H.2 and the digest of D.1a
   uint32_t tail_dep_elem = 0;  // first element of a row whose value is written by the final checks (verdicts, check words, all_ok): the small-launch tail
 };
 
@@ -137,16 +138,22 @@ Program build_program(int kind, uint32_t n) {
   // H.2 validators[N] : ValidatorVariable (variables.rs:69-79) = pubkey, signature{r, s}, message[124],
   //     message_byte_length, voting_power, validator_byte_length, signed
   mark = (uint32_t)L.v.size();
+  P.pub512.h2_pk = (uint32_t)L.v.size() - mark;
   L.bytes(VR_OFF_PK, 32);
+  P.pub512.h2_r = (uint32_t)L.v.size() - mark;
   L.bytes(VR_OFF_SIG, 32);
   L.u256(VR_OFF_SIG + 32);
+  P.pub512.h2_msg = (uint32_t)L.v.size() - mark;
   L.bytes(VR_OFF_MSG, 124);
+  P.pub512.h2_mlen = (uint32_t)L.v.size() - mark;
   L.u16(VR_OFF_MLEN);
   L.u64(VR_OFF_POWER);
   P.pub.h2_vlen = (uint32_t)L.v.size() - mark;
   L.u8(VR_OFF_VLEN);
+  P.pub512.h2_signed = (uint32_t)L.v.size() - mark;
   L.flag0(VR_OFF_FLAGS);
   P.pub.h2 = elem; P.pub.h2_lane = (uint32_t)L.v.size() - mark;
+  P.pub512.h2 = P.pub.h2; P.pub512.h2_lane = P.pub.h2_lane;
   add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_TARGET, 0);
 
   // H.3 nb_validators, round, ChainIdProofVariable, HeightProofVariable, validators-hash proof, then
@@ -200,8 +207,10 @@ Program build_program(int kind, uint32_t n) {
   L.bytes(TL_OFF_LT + LN_OFF_MARSHAL, 46);
   P.pub.lane_leaf = (uint32_t)L.v.size() - mark;  // (the marshalled validator first, then the leaf hash: D.2a the same)
   L.bytes(TL_OFF_LT + LN_OFF_LEAF, 32);
+  P.pub512.d1a_digest = (uint32_t)L.v.size() - mark;
   L.bytes(TL_OFF_ED + ED_OFF_DIGEST, 64);
   P.pub.d1a = elem; P.pub.d1a_lane = (uint32_t)L.v.size() - mark;
+  P.pub512.d1a = P.pub.d1a; P.pub512.d1a_lane = P.pub.d1a_lane;
   add_section((uint32_t)L.v.size() - mark, n, mark, SEC_LUT, SRC_TL, 4);
   // D.1b per target lane: h, the ten coordinates, the EdDSA verdict, the six flags, the two prefix sums
   mark = (uint32_t)L.v.size();
@@ -468,8 +477,8 @@ struct tmx_ctx {
   // and its quotient member -- extended columns | tree levels (Oracle.buf names it).  With a streamed helper
   // (tmx_trace_commit_set_air_sha256_streamed_device, _sha512_streamed_device) the helper's extended columns are absent and behind the quotient's levels sit the
   // sponge states [12][M] and the helper's chunk buffer [chunk_proofs helper_cols][M]
-  void* d_set_sha[7][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4 .. 6: sets 7, 8 and 9, whose one section uses slot 0)
-  size_t set_sha_bytes[7][3] = {};
+  void* d_set_sha[8][3] = {};  // (rows 0 .. 2: constraint sets 3 .. 5; row 3: set 6; rows 4 .. 7: sets 7, 8, 9 and 10, whose one section uses slot 0)
+  size_t set_sha_bytes[8][3] = {};
   // constraint set 2 (tmx_air_ladder_boundary_*): the set-2 tables | the size-K twiddles | V (prover) | V (verifier) | the coefficients of
   // Pub_gamma | the public tree's levels (prover) | (verifier) | Pub_gamma on the coset (2 << log_m words: the part that grows)
   void* d_air2 = nullptr;
@@ -488,6 +497,8 @@ struct tmx_ctx {
   // the two extended planes (2 M: the part that grows)
   void* d_air9 = nullptr;
   size_t air9_bytes = 0;
+  void* d_air10 = nullptr;  // set 10's own: its planes as sets 7 - 9 keep theirs, and the public side (link512_* below)
+  size_t air10_bytes = 0;
   // the DEEP verifier's scratch: the openings tree of the proof it checks (grows on demand)
   void* d_deepv = nullptr;
   size_t deepv_bytes = 0;
@@ -1489,6 +1500,7 @@ void tmx_ctx_destroy(tmx_ctx* c) {
   if (c->d_air7) (void)hipFree(c->d_air7);
   if (c->d_air8) (void)hipFree(c->d_air8);
   if (c->d_air9) (void)hipFree(c->d_air9);
+  if (c->d_air10) (void)hipFree(c->d_air10);
   if (c->ev_air) (void)hipEventDestroy(c->ev_air);
   for (auto& sl : c->idx_ring) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev), (void)hipEventDestroy(sl.ev);
@@ -4603,11 +4615,17 @@ int32_t tmx_trace_commit_set_air_boundary_device(tmx_ctx* c, const uint64_t* d_p
 // (sha_verify_call), and the set-level call takes TMX_TRACE_SHA512 alone.  Rows 3 - 6 take none of these branches.  What the three differ
 // in there is a ShaPeriodic the row carries: how many preprocessed planes there are (3, 1, 2), the context scratch that holds them (d_air7,
 // d_air8, d_air9), and the set's instantiations of the launches that fill them, read them in the pass and evaluate them at zeta.
+// Set 10 (the SHA-512 table's link to Level-1) is the eighth row and has BOTH has_public and has_periodic.  Set 6's public step is taken
+// under has_public && !has_periodic; set 10 takes the periodic branch and, inside it, a public step of its own at the same four places:
+// gamma observes the digest of its 49-column table (sha_gamma), the piece that starts at proof 0 is followed by - Pub_gamma / (x^N - 1)
+// (sha_pass: link512_public), the verifier forms V and evaluates Pub_gamma(zeta) before a check that knows it (sha_verify_call), and the
+// helper kernel reads d_pub (sha_helper_launch).  Rows 3 - 9 enqueue what they enqueued.  Resident only.
 struct ShaPeriodic {
   uint32_t planes, part_words;  // the preprocessed columns; the words of one workgroup's row of the barycentric kernel
   void* tmx_ctx::*scratch;      // rows of the barycentric kernel | the planes before the LDE [planes][N] | extended [planes][M]
   size_t tmx_ctx::*bytes;
   const AirSha512Launch* k;  // fill, tables, quotient, eval, fold, check (air.h)
+  uint32_t fixed_words = 0;  // set 10: words of its public side between the rows and the planes (LINK512_*); its V and extended Pub follow the planes
 };
 struct ShaSet {
   uint32_t id, helper_cols;
@@ -4675,11 +4693,18 @@ static int sha9_helper(uint32_t log_rows, uint32_t n_proofs, uint32_t, const voi
 static const ShaPeriodic SHA7_PERIODIC = {3, AIR7_PART_WORDS, &tmx_ctx::d_air7, &tmx_ctx::air7_bytes, air_sha512_launch(7)};
 static const ShaPeriodic SHA8_PERIODIC = {1, AIR8_PART_WORDS, &tmx_ctx::d_air8, &tmx_ctx::air8_bytes, air_sha512_launch(8)};
 static const ShaPeriodic SHA9_PERIODIC = {2, AIR9_PART_WORDS, &tmx_ctx::d_air9, &tmx_ctx::air9_bytes, air_sha512_launch(9)};
+// Set 10's fixed words behind the rows of the planes' barycentric kernel: the rows of the public side's | the levels of the public digest,
+// prover | verifier (a table of at most 2^12 slots)
+constexpr uint64_t LINK512_LEV_WORDS = 8ull << 12, LINK512_OFF_PUB_PART = (uint64_t)AIR7_MAX_PARTS * AIR10_PART_WORDS,
+                   LINK512_OFF_LEVP = LINK512_OFF_PUB_PART + (uint64_t)AIR7_MAX_PARTS * AIR10_PUB_PART_WORDS,
+                   LINK512_OFF_LEVV = LINK512_OFF_LEVP + LINK512_LEV_WORDS;
+static const ShaPeriodic SHA10_PERIODIC = {5, AIR10_PART_WORDS, &tmx_ctx::d_air10, &tmx_ctx::air10_bytes, air_sha512_launch(10),
+                                           (uint32_t)(LINK512_OFF_LEVV + LINK512_LEV_WORDS - LINK512_OFF_PUB_PART)};
 
 // by ascending id: a set-level call places its pair behind the pairs of the sets in front of it
 static const char SHA_BAD_SUB[] = "log_n - log_blowup must be at least 6: a SHA-256 block is 64 rows";
 static const char SHA_BAD_ROWS[] = "log_rows must be 6 .. 27: a SHA-256 block is 64 rows";
-static const ShaSet SHA_SETS[7] = {
+static const ShaSet SHA_SETS[8] = {
     {3, AIR_SHA_HELPER_COLS, false, false, 6, 27, TMX_TRACE_SHA256_HELPER, TMX_TRACE_SHA256_QUOTIENT, 0, SHA_BAD_SUB, SHA_BAD_ROWS, "sha", "helper",
      "the commit set already holds the helper and the quotient of that section", "k_trace + 1", "k_trace + 2",
      "k_trace, k_trace + 1 and k_trace + 2 must all be oracles of the proof", sha3_helper, sha3_tables, sha3_quotient, sha3_check, AIR_SHA_WIDTH, false, nullptr},
@@ -4715,6 +4740,13 @@ static const ShaSet SHA_SETS[7] = {
      "SHA-512 block-start helper", "the commit set already holds the SHA-512 block-start helper and quotient of that section", "k_helper",
      "k_helper + 1", "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", sha9_helper, nullptr, nullptr, nullptr,
      AIR_SHA512_WIDTH, true, &SHA9_PERIODIC},
+    // (set 10: BOTH a public table and preprocessed planes; its helper reads d_pub, its pass and its check know the public side)
+    {10, AIR_SHA512_LINK_HELPER_COLS, false, true, 7, 18, TMX_TRACE_SHA512_LINK_HELPER, TMX_TRACE_SHA512_LINK_QUOTIENT, 7,
+     "log_n - log_blowup must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them",
+     "log_rows must be 7 .. 18: a SHA-512 block is 80 rows and the verifier evaluates the preprocessed columns over all of them", "sha512_link",
+     "SHA-512 link helper", "the commit set already holds the SHA-512 link helper and quotient of that section", "k_helper", "k_helper + 1",
+     "k_trace < k_helper, and k_helper and k_helper + 1 must be oracles of the proof", nullptr, nullptr, nullptr, nullptr, AIR_SHA512_WIDTH, true,
+     &SHA10_PERIODIC},
 };
 
 static int32_t sha_launch_failed(tmx_ctx* c, const ShaSet& d, const char* kernel, int rc) {
@@ -4750,11 +4782,12 @@ static void link_geo(uint32_t log_n, uint32_t log_blowup, uint64_t root_2_32, ui
 
 // s_n = s^N, w_n = w^N; the selector's period is 64 << chain rows: s_sel = s^(N/64), w_sel = w^(N/64), rho = omega_64^-1 under chain = 0,
 // s^(N/128), w^(N/128), omega_128^-1 under chain = 1; link: filled for a set with a public table
-struct ShaGeo { uint64_t s_n, w_n, s_sel, w_sel, rho; LinkGeo link; };
+struct ShaGeo { uint64_t s_n, w_n, s_sel, w_sel, rho; LinkGeo link; uint64_t root, shift; /* the domain they were taken under */ };
 
 static int32_t sha_geo(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t log_blowup, uint32_t chain, uint64_t root_2_32, uint64_t shift, ShaGeo& A) {
   const uint64_t P = 0xffffffff00000001ull;
-  if (d.has_public) link_geo(log_n, log_blowup, root_2_32, shift, A.link);
+  if (d.has_public && !d.has_periodic) link_geo(log_n, log_blowup, root_2_32, shift, A.link);
+  A.root = root_2_32; A.shift = shift;
   const uint64_t s = shift % P, w = gl_pow_host(root_2_32, 1ull << (32 - log_n)), n = 1ull << (log_n - log_blowup);
   const uint32_t log_per = 6 + chain;
   A.s_n = gl_pow_host(s, n); A.w_n = gl_pow_host(w, n);
@@ -4818,12 +4851,14 @@ static int32_t link_public(tmx_ctx* c, uint32_t log_m, uint32_t log_blowup, cons
 // What set 7 has of its own inside that path: the preprocessed columns.  A scratch of its own (words at d_air7): the barycentric kernel's
 // rows | SEL, KLO, KHI before the LDE [3][N] | the three extended planes [3][M].  One per context, not per section.
 // Set 8 has the same of its own (words at d_air8) with one plane, SCH: d_air7 does not grow for it.  Set 9 likewise (d_air9; STA, CHN).
-static uint64_t sha512_off_pre(const ShaSet& d) { return (uint64_t)AIR7_MAX_PARTS * d.per->part_words; }
+static uint64_t sha512_off_pre(const ShaSet& d) { return (uint64_t)AIR7_MAX_PARTS * d.per->part_words + d.per->fixed_words; }
 static_assert(AIR7_MAX_PARTS * AIR7_PART_WORDS == 512, "set 7's scratch layout stays as it is");
 
 // the scratch of set 7, 8 or 9, for a coset of 2^log_m points over 2^log_sub rows (log_m = 0: the verifier, which fills and extends nothing)
 static int32_t sha512_scratch(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_sub) {
-  const size_t planes = d.per->planes, want = (sha512_off_pre(d) + (log_m ? (planes << log_sub) + (planes << log_m) : 0)) * 8;
+  // (a set with a public table, set 10: behind the planes the extended Pub_gamma [2][M], then V [2][N]; the verifier passes its log_sub for V)
+  const size_t planes = d.per->planes, pub = d.has_public ? 2 : 0;
+  const size_t want = (sha512_off_pre(d) + (log_m ? (planes << log_sub) + ((planes + pub) << log_m) : 0) + (pub << log_sub)) * 8;
   void*& buf = c->*(d.per->scratch);
   size_t& bytes = c->*(d.per->bytes);
   if (bytes < want) {
@@ -4835,6 +4870,38 @@ static int32_t sha512_scratch(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint3
 }
 static const uint64_t* sha512_planes(const tmx_ctx* c, const ShaSet& d, uint32_t log_sub) {
   return reinterpret_cast<const uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d) + ((size_t)d.per->planes << log_sub);
+}
+
+// set 10's extended Pub_gamma and its V inside that scratch (log_m = 0: the verifier's layout, V alone)
+static uint64_t* link512_pubext(const tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_sub) {
+  return reinterpret_cast<uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d) + ((size_t)d.per->planes << log_sub) + ((size_t)d.per->planes << log_m);
+}
+static uint64_t* link512_v(const tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_sub) {
+  return log_m ? link512_pubext(c, d, log_m, log_sub) + ((size_t)2 << log_m) : reinterpret_cast<uint64_t*>(c->*(d.per->scratch)) + sha512_off_pre(d);
+}
+
+// The public side of set 10's pass: V_r from d_pub under the prover's gamma, extended like two helper columns under the domain the geometry
+// was taken under (put there for the extension if the context's has moved), and subtracted from the quotient over x^N - 1
+static int32_t link512_public(tmx_ctx* c, const ShaSet& d, uint32_t log_m, uint32_t log_blowup, const ShaGeo& A, uint32_t n_proofs,
+                              const uint64_t* d_pub, const uint64_t* tab, uint64_t* d_quot, hipStream_t s) {
+  const uint32_t log_sub = log_m - log_blowup;
+  uint64_t* v = link512_v(c, d, log_m, log_sub);
+  uint64_t* ext = link512_pubext(c, d, log_m, log_sub);
+  int rc = launch_air_sha512_link_combine(log_sub, n_proofs, d_pub, reinterpret_cast<const uint64_t*>(c->d_air) + 32 + FRI_GAMMA_AT, v, s);
+  if (rc) return sha_launch_failed(c, d, "combine", rc);
+  const uint64_t root = c->ntt_root, shift = c->ntt_shift;
+  const bool moved = root != A.root || shift != A.shift;
+  int32_t st;
+  if (moved && (st = tmx_ntt_set_domain(c, A.root, A.shift))) return st;
+  st = tmx_lde_goldilocks_device(c, log_sub, log_blowup, 2, v, ext, s);
+  if (moved) {
+    const int32_t back = tmx_ntt_set_domain(c, root, shift);
+    if (!st) st = back;
+  }
+  if (st) return st;
+  rc = launch_air_sha512_link_public_sub(log_m, log_blowup, ext, tab, d_quot, s);
+  if (rc) return sha_launch_failed(c, d, "public_sub", rc);
+  return TMX_OK;
 }
 
 // The preprocessed columns (SEL, KLO and KHI; SCH) filled and extended exactly as helper columns are: under the context's current NTT
@@ -4859,9 +4926,11 @@ static int32_t sha_gamma(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t l
     if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha_gamma launch: ") + hipGetErrorString((hipError_t)rc));
     return TMX_OK;
   }
-  const uint32_t log_k = log_n - log_blowup - 6;
-  uint64_t* lev = reinterpret_cast<uint64_t*>(c->d_air6) + (verifier ? AIR6_OFF_LEVV : AIR6_OFF_LEVP);
-  const int32_t st = tmx_poseidon_merkle_device(c, log_k, AIR_SHA_PUBLIC_WIDTH * n_proofs, d_pub, 0, lev, s);
+  // (set 10: the slots of its 80-row blocks, 49 columns per proof, the levels in its own scratch; the lone-lane kernel is set 6's)
+  const uint32_t log_k = d.has_periodic ? air_sha512_public_log_k(log_n - log_blowup) : log_n - log_blowup - 6;
+  uint64_t* lev = d.has_periodic ? reinterpret_cast<uint64_t*>(c->d_air10) + (verifier ? LINK512_OFF_LEVV : LINK512_OFF_LEVP)
+                                 : reinterpret_cast<uint64_t*>(c->d_air6) + (verifier ? AIR6_OFF_LEVV : AIR6_OFF_LEVP);
+  const int32_t st = tmx_poseidon_merkle_device(c, log_k, (d.has_periodic ? AIR_SHA512_PUBLIC_WIDTH : AIR_SHA_PUBLIC_WIDTH) * n_proofs, d_pub, 0, lev, s);
   if (st) return st;
   const int rc = launch_air_link_gamma(c->d_pos_consts, c->pos_mode, obs, cap_words, d_cap, d_cap_helper,
                                        lev + 4 * (tmx_poseidon_merkle_digests(log_k, 0) - 1), W, W + 32, s);
@@ -4877,7 +4946,7 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
                         uint64_t* d_quot, hipStream_t s) {
   uint64_t* W = reinterpret_cast<uint64_t*>(c->d_air);
   int rc;
-  if (d.has_public) {
+  if (d.has_public && !d.has_periodic) {
     uint64_t* X = reinterpret_cast<uint64_t*>(c->d_air6);
     if (first == 0) {
       const int32_t st = link_public(c, log_n, log_blowup, A, n_all, d_pub, s);
@@ -4891,6 +4960,8 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
     if ((rc = d.per->k->tables(log_blowup, first, A.s_n, A.w_n, W + 32 + FRI_GAMMA_AT, tab, s))) return sha_launch_failed(c, d, "tables", rc);
     rc = d.per->k->quotient(log_n, log_blowup, n_proofs, cols, hcols, sha512_planes(c, d, log_n - log_blowup), tab, form, d_quot, s);
+    // (set 10: the piece that starts at proof 0 carries - Pub_gamma / (x^N - 1), set 6's rule)
+    if (!rc && d.has_public && first == 0) return link512_public(c, d, log_n, log_blowup, A, n_all, d_pub, tab, d_quot, s);
   } else {
     uint64_t* tab = W + 2 * (32 + AIR_CHAL_WORDS);
     if ((rc = d.tables(log_blowup, chain, first, A.s_n, A.w_n, A.s_sel, A.w_sel, A.rho, W + 32 + FRI_GAMMA_AT, tab, s)))
@@ -4903,7 +4974,8 @@ static int32_t sha_pass(tmx_ctx* c, const ShaSet& d, uint32_t log_n, uint32_t lo
 
 static int sha_helper_launch(const ShaSet& d, uint32_t log_rows, uint32_t n_proofs, uint32_t chain, const void* d_table, const void* d_pub,
                              void* d_helper, void* stream) {
-  return d.has_public ? launch_air_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, stream)
+  return d.has_public ? (d.has_periodic ? launch_air_sha512_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, stream)
+                                        : launch_air_link_helper(log_rows, n_proofs, d_table, d_pub, d_helper, stream))
                       : d.helper(log_rows, n_proofs, chain, d_table, d_helper, stream);
 }
 
@@ -4943,7 +5015,7 @@ static int32_t sha_quotient_call(tmx_ctx* c, const ShaSet& d, uint32_t log_n, ui
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, log_blowup))) return st;
-  if (d.has_public && (st = link_scratch(c, log_n))) return st;
+  if (d.has_public && !d.has_periodic && (st = link_scratch(c, log_n))) return st;
   if (d.has_periodic && ((st = sha512_scratch(c, d, log_n, log_n - log_blowup)) || (st = sha512_periodic(c, d, log_n, log_blowup, hip_stream)))) return st;
   if ((st = sha_gamma(c, d, log_n, log_blowup, cap_height, n_proofs, chain, d_cap, d_cap_helper, d_pub, false, s))) return st;
   if ((st = sha_pass(c, d, log_n, log_blowup, chain, A, proof_lo, proof_hi - proof_lo, d_cols + (((uint64_t)proof_lo * d.width) << log_n),
@@ -4985,8 +5057,8 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
   if ((st = tmx_batch_verify_device(c, p, d_caps, d_proof, d_ok, hip_stream))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   if ((st = air_scratch(c, p->log_blowup))) return st;
-  if (d.has_public && (st = link_scratch(c, 0))) return st;
-  if (d.has_periodic && (st = sha512_scratch(c, d, 0, 0))) return st;
+  if (d.has_public && !d.has_periodic && (st = link_scratch(c, 0))) return st;
+  if (d.has_periodic && (st = sha512_scratch(c, d, 0, d.has_public ? log_n - p->log_blowup : 0))) return st;
   tmx_batch_layout L;
   batch_layout(*p, L);
   const FriGeom G = batch_geom(*p, L, c->ntt_root, c->ntt_shift);
@@ -4999,7 +5071,7 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
                       true, s)))
     return st;
   const uint64_t *open_t = d_proof + L.off_open[k_trace], *open_h = d_proof + L.off_open[k_helper], *open_q = d_proof + L.off_open[k_helper + 1];
-  if (d.has_public) {
+  if (d.has_public && !d.has_periodic) {
     const LinkGeo& B = A.link;
     uint64_t* vv = reinterpret_cast<uint64_t*>(c->d_air6) + AIR6_OFF_VV;
     rc = launch_air_link_combine(B.log_k, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, vv, s);
@@ -5012,8 +5084,16 @@ static int32_t sha_verify_call(tmx_ctx* c, const ShaSet& d, const tmx_batch_para
     void* part = c->*(d.per->scratch);
     rc = d.per->k->eval(log_sub, om, V + 32 + FRI_ZETA_AT, part, s);
     if (rc) return sha_launch_failed(c, d, "periodic_eval", rc);
-    rc = d.per->k->check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
-                         V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+    if (d.has_public) {  // set 10: the verifier's own V from d_pub and its gamma, Pub_gamma(zeta) over the N rows, then the check that knows it
+      uint64_t* vv = link512_v(c, d, 0, log_sub);
+      uint64_t* pub_part = reinterpret_cast<uint64_t*>(part) + LINK512_OFF_PUB_PART;
+      if ((rc = launch_air_sha512_link_combine(log_sub, n_proofs, d_pub, V + 32 + FRI_GAMMA_AT, vv, s))) return sha_launch_failed(c, d, "combine", rc);
+      if ((rc = launch_air_sha512_link_public_eval(log_sub, om, V + 32 + FRI_ZETA_AT, vv, pub_part, s))) return sha_launch_failed(c, d, "public_eval", rc);
+      rc = launch_air_sha512_link_check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, pub_part, open_t, open_h, open_q,
+                                        V + 32 + FRI_ZETA_AT, V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
+    } else
+      rc = d.per->k->check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_sub, n_inv, part, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
+                           V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
   } else {
     rc = d.check(n_proofs, G.o_log_r[k_trace], G.o_log_r[k_helper], log_n - p->log_blowup, chain, A.rho, open_t, open_h, open_q, V + 32 + FRI_ZETA_AT,
                  V + 32 + FRI_GAMMA_AT, p->n_queries, d_ok, s);
@@ -5091,7 +5171,7 @@ static int32_t sha_set_call(tmx_ctx* c, const ShaSet& d, uint32_t section, uint3
   if ((st = poseidon_ready(c, s))) return st;
   c->air_valid = false;
   if ((st = air_scratch(c, r.log_blowup))) return st;
-  if (d.has_public && (st = link_scratch(c, log_m))) return st;
+  if (d.has_public && !d.has_periodic && (st = link_scratch(c, log_m))) return st;
   if (d.has_periodic && (st = sha512_scratch(c, d, log_m, log_sub))) return st;
   // the scratch of this set and section (ShaScratch)
   const bool streamed = by_chunks && chunk_proofs < n_proofs;
@@ -5360,6 +5440,99 @@ int32_t tmx_air_sha256_link_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_
   return sha_helper_call(c, SHA_SETS[3], log_rows, n_proofs, 0, d_table, d_pub, d_helper, hip_stream);
 }
 
+// ---- the public table of the SHA-512 table from element rows, and the helper oracle over it (constraint set 10)
+int32_t tmx_air_sha512_public_shape(int32_t kind, uint32_t n_max, uint32_t n_proofs, uint32_t* log_k, uint32_t* n_cols) {
+  uint32_t log_rows = 0, width = 0;
+  if (n_proofs < 1 || tmx_trace_commit_shape(kind, n_max, TMX_TRACE_SHA512, &log_rows, &width) != TMX_OK) return TMX_ERR_BAD_ARG;
+  if (log_rows < 7 || log_rows > 18) return TMX_ERR_BAD_ARG;
+  if ((uint64_t)n_proofs * AIR_SHA512_LINK_HELPER_COLS > TMX_DEEP_MAX_COLS) return TMX_ERR_BAD_ARG;
+  if (log_k) *log_k = air_sha512_public_log_k(log_rows);
+  if (n_cols) *n_cols = AIR_SHA512_PUBLIC_WIDTH * n_proofs;
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha512_public_device(tmx_ctx* c, int32_t kind, uint32_t n_proofs, const void* d_elems, uint64_t* d_pub, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  if (kind != TMX_KIND_SKIP && kind != TMX_KIND_STEP) return fail(c, TMX_ERR_BAD_ARG, "kind must be TMX_KIND_SKIP or TMX_KIND_STEP");
+  uint32_t log_k = 0;
+  if (tmx_air_sha512_public_shape(kind, c->cfg.n_max, n_proofs, &log_k, nullptr))
+    return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1 (65 n_proofs at most 2^24) and the table 2^7 .. 2^18 rows");
+  if (!d_elems || !d_pub) return fail(c, TMX_ERR_BAD_ARG, "d_elems and d_pub must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const Program& prog = c->prog[kind];
+  AirSha512PublicGeom G = prog.pub512;  // (every offset as build_program recorded it)
+  G.elem_stride = prog.sp.elem_stride; G.n = c->cfg.n_max;
+  const int rc = launch_air_sha512_public_gather(d_elems, G, log_k, n_proofs, d_pub, hip_stream);
+  if (rc) return fail(c, TMX_ERR_HIP, std::string("k_air_sha512_public_gather launch: ") + hipGetErrorString((hipError_t)rc));
+  return TMX_OK;
+}
+
+int32_t tmx_air_sha512_link_helper_device(tmx_ctx* c, uint32_t log_rows, uint32_t n_proofs, const uint64_t* d_table, const uint64_t* d_pub,
+                                          uint64_t* d_helper, void* hip_stream) {
+  return sha_helper_call(c, SHA_SETS[7], log_rows, n_proofs, 0, d_table, d_pub, d_helper, hip_stream);
+}
+
+// ---- constraint set 10 through row 7 of the host path above
+int32_t tmx_air_sha512_link_quotient_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                            const uint64_t* d_cols, const uint64_t* d_helper_cols, const uint64_t* d_cap,
+                                            const uint64_t* d_cap_helper, const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_call(c, SHA_SETS[7], log_n, log_blowup, cap_height, n_proofs, 0, 0, n_proofs, AIR_FORM_WHOLE, d_cols, d_helper_cols, d_cap,
+                           d_cap_helper, d_pub, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_link_quotient_range_device(tmx_ctx* c, uint32_t log_n, uint32_t log_blowup, uint32_t cap_height, uint32_t n_proofs,
+                                                  uint32_t proof_lo, uint32_t proof_hi, uint32_t accumulate, const uint64_t* d_cols,
+                                                  const uint64_t* d_helper_cols, const uint64_t* d_cap, const uint64_t* d_cap_helper,
+                                                  const uint64_t* d_pub, uint64_t* d_quot, void* hip_stream) {
+  return sha_quotient_range_call(c, SHA_SETS[7], log_n, log_blowup, cap_height, n_proofs, 0, proof_lo, proof_hi, accumulate, d_cols, d_helper_cols, d_cap,
+                                 d_cap_helper, d_pub, d_quot, hip_stream);
+}
+
+int32_t tmx_air_sha512_link_verify_device(tmx_ctx* c, const tmx_batch_params* p, uint32_t k_trace, uint32_t k_helper, const uint64_t* d_caps,
+                                          const uint64_t* d_proof, const uint64_t* d_pub, uint32_t* d_ok, void* hip_stream) {
+  return sha_verify_call(c, SHA_SETS[7], p, k_trace, k_helper, 0, d_caps, d_proof, d_pub, d_ok, hip_stream);
+}
+
+int32_t tmx_trace_commit_set_air_sha512_link_device(tmx_ctx* c, uint32_t section, const uint64_t* d_pub, uint64_t* d_cap_h, uint64_t* d_cap_q,
+                                                    void* hip_stream) {
+  return sha_set_call(c, SHA_SETS[7], section, 0, false, d_pub, d_cap_h, d_cap_q, hip_stream);
+}
+
+// The public side on its own, for tests: V (planar, 2 << log_rows words at d_v) from d_pub and the two words at d_gamma, and, extended
+// under the current NTT domain, Pub_gamma on the coset (2 << (log_rows + log_blowup) words at d_ext; log_blowup = 0: d_v alone)
+int32_t tmx_air_sha512_link_public_side_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint32_t n_proofs, const uint64_t* d_pub,
+                                               const uint64_t* d_gamma, uint64_t* d_v, uint64_t* d_ext, void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  const ShaSet& d = SHA_SETS[7];
+  if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
+  if (log_blowup > 6) return fail(c, TMX_ERR_BAD_ARG, "log_blowup must be at most 6");
+  if (n_proofs < 1 || (uint64_t)n_proofs * d.helper_cols > TMX_DEEP_MAX_COLS) return fail(c, TMX_ERR_BAD_ARG, "n_proofs must be at least 1 and " + sha_too_many_cols(d));
+  if (!d_pub || !d_gamma || !d_v || (log_blowup && !d_ext)) return fail(c, TMX_ERR_BAD_ARG, "d_pub, d_gamma and d_v must be set, and d_ext unless log_blowup is 0");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  const int rc = launch_air_sha512_link_combine(log_rows, n_proofs, d_pub, d_gamma, d_v, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "combine", rc);
+  return log_blowup ? tmx_lde_goldilocks_device(c, log_rows, log_blowup, 2, d_v, d_ext, hip_stream) : TMX_OK;
+}
+
+// d_out[0 .. 2) = Pub_gamma(zeta) from V at d_v (2 << log_rows words) and the two words at d_zeta, d_out[2] = 1 if a denominator was zero
+int32_t tmx_air_sha512_link_public_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_v, const uint64_t* d_zeta, uint64_t* d_out,
+                                               void* hip_stream) {
+  if (!c) return TMX_ERR_BAD_ARG;
+  const ShaSet& d = SHA_SETS[7];
+  if (log_rows < d.rows_lo || log_rows > d.rows_hi) return fail(c, TMX_ERR_BAD_ARG, d.bad_rows);
+  if (!d_v || !d_zeta || !d_out) return fail(c, TMX_ERR_BAD_ARG, "d_v, d_zeta and d_out must be set");
+  HIPCK(c, hipSetDevice(c->cfg.device));
+  int32_t st = sha512_scratch(c, d, 0, 0);
+  if (st) return st;
+  const uint64_t P = 0xffffffff00000001ull, om = gl_pow_host(c->ntt_root, 1ull << (32 - log_rows)), n_inv = gl_pow_host(1ull << log_rows, P - 2);
+  uint64_t* pub_part = reinterpret_cast<uint64_t*>(c->d_air10) + LINK512_OFF_PUB_PART;
+  int rc = launch_air_sha512_link_public_eval(log_rows, om, d_zeta, d_v, pub_part, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "public_eval", rc);
+  rc = launch_air_sha512_link_public_fold(log_rows, n_inv, pub_part, d_zeta, d_out, hip_stream);
+  if (rc) return sha_launch_failed(c, d, "public_fold", rc);
+  return TMX_OK;
+}
+
 uint64_t tmx_trace_commit_set_air_sha256_streamed_bytes(uint32_t constraint_set, uint32_t log_m, uint32_t log_blowup, uint32_t cap_height,
                                                         uint32_t n_proofs, uint32_t chunk_proofs, uint64_t* lde_scratch_bytes) {
   if (lde_scratch_bytes) *lde_scratch_bytes = 0;
@@ -5476,6 +5649,15 @@ int32_t tmx_air_sha512_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t l
 
 int32_t tmx_air_sha512_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
   return sha_periodic_eval_call(c, SHA_SETS[4], log_rows, d_zeta, d_out, hip_stream);
+}
+
+// (set 10's planes STA, CHN, SEL, E79, MSG on their own; the rest of set 10 stands with its public table further up)
+int32_t tmx_air_sha512_link_periodic_device(tmx_ctx* c, uint32_t log_rows, uint32_t log_blowup, uint64_t* d_pre, uint64_t* d_ext, void* hip_stream) {
+  return sha_periodic_call(c, SHA_SETS[7], log_rows, log_blowup, d_pre, d_ext, hip_stream);
+}
+
+int32_t tmx_air_sha512_link_periodic_eval_device(tmx_ctx* c, uint32_t log_rows, const uint64_t* d_zeta, uint64_t* d_out, void* hip_stream) {
+  return sha_periodic_eval_call(c, SHA_SETS[7], log_rows, d_zeta, d_out, hip_stream);
 }
 
 // ---- constraint set 8: the message schedule of the SHA-512 table, through row 5 of the host path above

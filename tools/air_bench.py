@@ -64,6 +64,13 @@
            M = 2^LOG_M (16) and the SAME table, alternating in one process; ps_per_helper_word_set9 / _set7 and their ratio.  Then the
            set-level call of set 9 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n, the prove and the
            verifier.
+  sha512_link    constraint set 10 (tmx_air_sha512_link_*), the SHA-512 table's link to Level-1, beside set 6 and set 8: the gather
+           (k_air_sha512_public_gather over S512_SET_P proofs at N = n) and the helper kernel (S512_PROOFS proofs, 16, of 2^(LOG_M - BLOWUP)
+           rows), then the quotient call of set 10 (five planes filled and extended, gamma with the public digest, the tables,
+           k_air_sha512_quotient<Sha512Link, FORM>, V, its extension and the subtraction; 83 columns per proof), of set 8 (248) and of set 6
+           (42, 9 table columns) over random extended columns at M = 2^LOG_M (16), alternating in one process; ps per word read of each and
+           the ratios.  Then the set-level call of set 10 on the SHA512 member of a set SHA512 | HEADER of S512_SET_P proofs (16) at N = n,
+           the prove over the four oracles and the verifier.
   sha512_streamed  the streamed helpers of constraint sets 7 - 9 (tmx_trace_commit_set_air_sha512_streamed_device), sha_streamed's sibling, on
            a set SHA512 | HEADER of SHA_SET_P proofs (16) at N = n, the sets named in SETS (7 by default; 7,8,9), CHUNK_PROOFS proofs per
            chunk (8).  The resident and the streamed set-level calls, alternating in one process after a warm call, every round listed,
@@ -997,6 +1004,101 @@ if "sha512_init" in modes:
     print(json.dumps(res), flush=True)
     ctx.close()
     del tr  # (given back so that a mode chained behind this one, such as sha512_streamed, starts from the memory it reports as free)
+    torch.cuda.empty_cache()
+
+if "sha512_link" in modes:
+    # constraint set 10 beside its two siblings: set 6 (the same kind of statement on the SHA-256 tables) and set 8 (the lightest pass of
+    # the shared k_air_sha512_quotient frame), caller-level calls over random extended columns at the same M, alternating in one process.
+    # ps_per_word: the call's time per column word read (table + helper), the figure the passes are compared on.
+    log_m, cp = int(os.environ.get("LOG_M", "16")), int(os.environ.get("S512_PROOFS", "16"))
+    log_rows = log_m - log_blowup
+    torch.manual_seed(seed)
+    ctx = Context(4, b"celestia", device=0)
+
+    def capped(words, k_):
+        c_ = torch.randint(0, 2**62, (words,), dtype=torch.int64, device=dev)
+        lv = torch.empty(4 * ctx.poseidon_merkle_digests(log_m, cap_h), dtype=torch.int64, device=dev)
+        ctx.poseidon_merkle_device(log_m, k_, c_.data_ptr(), cap_h, lv.data_ptr(), 0)
+        return c_, lv[-(4 << cap_h):]
+
+    log_k10 = (-(-(1 << log_rows) // 80) - 1).bit_length()
+    cols, cap_t = capped((18 * cp) << log_m, 18 * cp)
+    cols6, cap_t6 = capped((9 * cp) << log_m, 9 * cp)
+    hcols10, cap10 = capped((65 * cp) << log_m, 65 * cp)
+    hcols8, cap8 = capped((230 * cp) << log_m, 230 * cp)
+    hcols6, cap6 = capped((33 * cp) << log_m, 33 * cp)
+    pub10 = torch.randint(0, 2**32, ((49 * cp) << log_k10,), dtype=torch.int64, device=dev)
+    pub6 = torch.randint(0, 2**32, ((26 * cp) << (log_rows - 6),), dtype=torch.int64, device=dev)
+    table = torch.randint(0, 2**62, ((18 * cp) << log_rows,), dtype=torch.int64, device=dev)
+    pre = torch.empty((65 * cp) << log_rows, dtype=torch.int64, device=dev)
+    quot = torch.empty(2 << log_m, dtype=torch.int64, device=dev)
+    q10 = lambda: ctx.air_sha512_link_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols10.data_ptr(), cap_t.data_ptr(),
+                                                      cap10.data_ptr(), pub10.data_ptr(), quot.data_ptr(), 0)
+    q8 = lambda: ctx.air_sha512_sched_quotient_device(log_m, log_blowup, cap_h, cp, cols.data_ptr(), hcols8.data_ptr(), cap_t.data_ptr(),
+                                                      cap8.data_ptr(), quot.data_ptr(), 0)
+    q6 = lambda: ctx.air_sha256_link_quotient_device(log_m, log_blowup, cap_h, cp, cols6.data_ptr(), hcols6.data_ptr(), cap_t6.data_ptr(),
+                                                     cap6.data_ptr(), pub6.data_ptr(), quot.data_ptr(), 0)
+    res = {"mode": "sha512_link", "log_m": log_m, "proofs": cp, "reps": reps, "helper_kernel_ms": [], "sha512_link_quotient_call_ms": [],
+           "sha512_sched_quotient_call_ms": [], "sha256_link_quotient_call_ms": []}
+    for _ in range(rounds):
+        res["helper_kernel_ms"].append(r4(timed(lambda: ctx.air_sha512_link_helper_device(log_rows, cp, table.data_ptr(), pub10.data_ptr(),
+                                                                                         pre.data_ptr(), 0), reps)))
+        res["sha512_link_quotient_call_ms"].append(r4(timed(q10, reps)))
+        res["sha512_sched_quotient_call_ms"].append(r4(timed(q8, reps)))
+        res["sha256_link_quotient_call_ms"].append(r4(timed(q6, reps)))
+    res["quotient_sha256"] = words_digest(q10, quot)
+    ps10 = min(res["sha512_link_quotient_call_ms"]) * 1e9 / ((83 * cp) << log_m)
+    ps8 = min(res["sha512_sched_quotient_call_ms"]) * 1e9 / ((248 * cp) << log_m)
+    ps6 = min(res["sha256_link_quotient_call_ms"]) * 1e9 / ((42 * cp) << log_m)
+    res.update(ps_per_word_set10=round(ps10, 2), ps_per_word_set8=round(ps8, 2), ps_per_word_set6=round(ps6, 2),
+               ratio_set10_over_set8=round(ps10 / ps8, 3), ratio_set10_over_set6=round(ps10 / ps6, 3), helper_rows=1 << log_rows,
+               helper_store_tb_per_s=round(((65 * cp) << log_rows) * 8 / min(res["helper_kernel_ms"]) / 1e9, 3))
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del cols, cap_t, cols6, cap_t6, hcols10, cap10, hcols8, cap8, hcols6, cap6, pub10, pub6, table, pre, quot
+    torch.cuda.empty_cache()
+    # the gather, the set-level call of set 10 on SHA512, the prove over the four oracles and the verifier
+    from tendermintx_amd.synth import bench_workload
+    sp = int(os.environ.get("S512_SET_P", "16"))
+    w = bench_workload("survey8d", n, sp, seed=0x544D58)
+    d = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in (w.proofs, w.targets, w.trusteds)]
+    ctx = Context(n, b"celestia", 100800, device=0, max_batch=sp)
+    out = torch.empty(sp * ctx.elem_stride(KIND_SKIP), dtype=torch.int64, device=dev)
+    rep = torch.empty(sp * 64, dtype=torch.uint8, device=dev)
+    tr = torch.empty(sp * ctx.trace_elem_count(KIND_SKIP), dtype=torch.int64, device=dev)
+    ctx.witness_batch_device(KIND_SKIP, sp, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), out.data_ptr(), rep.data_ptr(), 0)
+    ctx.trace_rows_device(KIND_SKIP, sp, d[1].data_ptr(), d[2].data_ptr(), tr.data_ptr(), _lib.TRACE_ALL, 0)
+    torch.cuda.synchronize(dev)
+    SHA512, HEADER = 2, 32
+    cw = 4 << cap_h
+    log_k, pub_cols = ctx.air_sha512_public_shape(KIND_SKIP, sp)
+    pub = torch.empty(pub_cols << log_k, dtype=torch.int64, device=dev)
+    gather = lambda: ctx.air_sha512_public_device(KIND_SKIP, sp, out.data_ptr(), pub.data_ptr(), 0)
+    scaps, cap_h_, cap_q = (torch.zeros(k * cw, dtype=torch.int64, device=dev) for k in (2, 1, 1))
+    ok = torch.zeros(nq, dtype=torch.int32, device=dev)
+    commit = lambda: ctx.trace_commit_set_device(KIND_SKIP, sp, SHA512 | HEADER, log_blowup, cap_h, tr.data_ptr(), scaps.data_ptr(), 0)
+    res = {"mode": "sha512_link_set", "proofs": sp, "n": n, "reps": reps, "gather_ms": [], "commit_ms": r4(timed(commit, 2)), "air_sha512_link_ms": [],
+           "prove_with_ms": []}
+    for _ in range(rounds):
+        res["gather_ms"].append(r4(timed(gather, reps)))
+        res["air_sha512_link_ms"].append(r4(timed(lambda: ctx.trace_commit_set_air_sha512_link_device(SHA512, pub.data_ptr(), cap_h_.data_ptr(),
+                                                                                                      cap_q.data_ptr(), 0), reps, before=commit)))
+        shape, order = ctx.trace_commit_set_shape()
+        bp = dict(shape, arity_bits=arity, final_log_max=final_max, n_queries=nq, pow_bits=0)
+        proof = torch.empty(ctx.batch_layout(bp)["words"], dtype=torch.int64, device=dev)
+        res["prove_with_ms"].append(r4(timed(lambda: ctx.trace_commit_set_prove_device(bp, proof.data_ptr(), 0), reps)))
+        res["degree_ok"] = ctx.fri_last_degree_ok()
+        kt = order.index(SHA512)
+        all_caps = torch.cat([scaps[:(kt + 1) * cw], cap_h_, cap_q, scaps[(kt + 1) * cw:]])
+        res["verify_ms"] = r4(timed(lambda: ctx.air_sha512_link_verify_device(bp, kt, kt + 1, all_caps.data_ptr(), proof.data_ptr(), pub.data_ptr(),
+                                                                              ok.data_ptr(), 0), 3))
+        res["all_ok"] = bool((ok.cpu().numpy() == 1).all())
+        res.update(order=order, log_n=bp["log_n"], columns=bp["n_cols"], cap_h_sha256=hashlib.sha256(cap_h_.cpu().numpy().tobytes()).hexdigest()[:16],
+                   cap_q_sha256=hashlib.sha256(cap_q.cpu().numpy().tobytes()).hexdigest()[:16])
+        del proof
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    del tr, out
     torch.cuda.empty_cache()
 
 if "sha512_streamed" in modes:
